@@ -31,8 +31,17 @@ its own chunks.
 
 rank 0 prints ONE JSON line with "roofline" (k_solve, HBM-bound by the
 algorithmic-bytes model of SURVEY.md §8d D3, HIP-event kernel times from the
-timed region) and "cpu_baseline" (the oracle -- CPU restatement of OSQP 0.6 --
-timed on this host on a bounded sample of the same instances, N=1 only).
+timed region).
+
+A plain run does what the headline figure needs and no more: it builds the
+batches, solves the base batch, warms up, times the steps and prints the line.
+--full adds everything that takes runs of its own, after the timed region and
+never in `value`: "cpu_baseline" (the oracle -- CPU restatement of OSQP 0.6 --
+timed on this host on a bounded sample of the same instances, N=1 only), the
+identity-dispatch rate, "pcie_inclusive", "latency", the copy-kernel HBM peak
+and the PMC traffic record of the roofline (null in a plain line).
+--dump-outputs DIR writes the last timed step's outputs (x, y, status, iters
+of its batch) as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -77,6 +86,14 @@ def parse(argv=None):
                     help="lateral layouts (cfg 2/3/4): each step builds q, l, u on the device from the instances' "
                          "(x0, xr, bound regime) (SURVEY.md §8f F1) and solves with one shared P, A -- timed "
                          "from x0 alone; a separate metric, not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs that are not the headline: the CPU baseline and "
+                         "its parity figures, the identity-dispatch rate, the PCIe-inclusive rate, the per-call "
+                         "latency, the copy-kernel HBM peak and the roofline's PMC traffic record (each can still "
+                         "be switched off with its --no-... option); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (x, y, status, iters) as DIR/<name>.npy, float64; "
+                         "past 64 MB in all a fixed seeded sample of the instances (rows.npy names them)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--separate-setup", action="store_true",
@@ -96,7 +113,10 @@ def parse(argv=None):
                     help="skip the PCIe-inclusive diagnostic (host buffers in, host buffers out)")
     ap.add_argument("--no-latency", action="store_true",
                     help="skip the per-call latency diagnostic (one cfg-5 QP through the osqp shim)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_cpu = args.no_dispatch_ab = args.no_pcie = args.no_latency = True
+    return args
 
 
 def dist_env():
@@ -430,6 +450,31 @@ def pcie_leg(solver, dev, local, bufs, host_in, outs, pin, steps, mode, warmup=8
             gc.enable()
 
 
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(path, outs, rank=0, world=1, max_bytes=DUMP_MAX_BYTES):
+    """Write the arrays of `outs` (name -> (B, ...) numpy array or torch tensor, one row per
+    instance) as float64 <path>/<name>.npy (rank r > 0: <name>.rank<r>.npy).  Where the rank's
+    share of `max_bytes` does not hold all B instances, the same fixed sample of them in every
+    array (seed 0, sorted; rows.npy holds their indices, taken on the tensor's device before
+    the copy to the host), so two runs with the same arguments write the same instances."""
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(outs.values())).shape[0]
+    outs = dict(outs, rows=np.arange(B))
+    per_row = 8 * sum(int(np.prod(v.shape[1:])) for v in outs.values())
+    keep = max(1, (max_bytes // world - 128 * len(outs)) // per_row)  # (128: the .npy header)
+    rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False)) if keep < B else None
+    suffix = f".rank{rank}" if rank else ""
+    for k, v in outs.items():
+        if isinstance(v, np.ndarray):
+            v = v if rows is None else v[rows]
+        else:
+            import torch
+            v = (v if rows is None else v[torch.as_tensor(rows, device=v.device)]).cpu().numpy()
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 LATENCY_WORKLOAD = {
     5: "incremental-dynamic-N50, ONE QP (n 508, m 916), fresh OSQP()+setup()+solve() per call, cold "
        "(mpc_dynamics.py:392-396)",
@@ -648,6 +693,8 @@ def main(argv=None, solver_cls=None, device=None):
         if kt:
             kt["method"] = "a HIP event pair around every solve launch in the timed region"
     iters_last = dit.cpu().numpy()  # the last timed step's batch (the flop model's iteration count)
+    if args.dump_outputs:  # what the last timed step returned, before any later leg reuses the buffers
+        dump_outputs(args.dump_outputs, {"x": dx, "y": dy, "status": dst, "iters": dit}, rank, world)
     solver.timing(False)
     if args.no_kernel_timing:  # diagnostic: kernel times from a few untimed steps
         solver.timing(True, setup=not fused)
@@ -742,7 +789,7 @@ def main(argv=None, solver_cls=None, device=None):
     flop_iter = 2 * (3 * info["nb"] * S * S + 2 * nnzA) + 12 * (n + m)
     fp64_tflops = flop_iter * float(iters_last.astype(np.float64).sum()) / (solve_ms * 1e-3) / 1e12
 
-    traffic = pmc_traffic(spec["name"], B, solve_kernel_name(info, fused=fused), one_shot)
+    traffic = pmc_traffic(spec["name"], B, solve_kernel_name(info, fused=fused), one_shot) if args.full else {}
     copy_gbs = copy_peak(local) if (on_gpu and rank == 0 and not args.no_cpu) else None
 
     cpu = None

@@ -110,13 +110,13 @@ def test_cfg4_shards_tile_one_global_batch(monkeypatch):
 
 
 def test_bench_main_one_rank_cpu_baseline(tmp_path):
-    """`bench.py` at N = 1 on CPU with the oracle stand-in: the cpu_baseline object -- the
+    """`bench.py --full` at N = 1 on CPU with the oracle stand-in: the cpu_baseline object -- the
     oracle timed on a bounded sample, its statuses / iterations / control blocks against the
     base-batch solve (parity_max_du; exactly 0 here, the stand-in being the oracle)."""
     out = tmp_path / "line.json"
     with open(out, "w") as f:
-        rc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--config", "2",
-                             "--batch", "16", "--steps", "2", "--warmup", "1", "--no-dispatch-ab",
+        rc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--full",
+                             "--config", "2", "--batch", "16", "--steps", "2", "--warmup", "1", "--no-dispatch-ab",
                              "--cpu-seconds", "0.2"], stdout=f, timeout=240,
                             env=dict(os.environ, OMP_NUM_THREADS="2")).returncode
     assert rc == 0
@@ -125,3 +125,55 @@ def test_bench_main_one_rank_cpu_baseline(tmp_path):
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
     assert cb["status_match_gpu"] == 1.0 and cb["iter_match_gpu"] == 1.0
     assert cb["parity_max_du"] == 0.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) on CPU with the oracle stand-in: the line carries the
+    headline fields and none of the legs of --full, --steps sets the number of timed steps, and
+    --dump-outputs writes the last timed step's x, y, status, iters as float64 .npy files --
+    the same arrays from a second run with the same arguments."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"line{k}.json"
+        with open(out, "w") as f:
+            rc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--gpus", "1",
+                                 "--batch", "16", "--steps", "3", "--warmup", "1",
+                                 "--dump-outputs", str(tmp_path / f"dump{k}")], stdout=f, timeout=240).returncode
+        assert rc == 0
+        d = json.loads([ln for ln in open(out).read().splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["unit"] == "QP solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 16 * 3 / (d["ms_per_step"] * 3 / 1e3)) < 1e-6 * d["value"]
+        assert d["cpu_baseline"] is None and d["pcie_inclusive"] is None and d["latency"] is None
+        assert d["config"]["value_identity_dispatch_rank0"] is None
+        assert d["roofline"]["traffic"] is None and d["roofline"]["peak_copy_measured"] is None
+        dumps.append({p.stem: np.load(p) for p in sorted((tmp_path / f"dump{k}").iterdir())})
+    a, b = dumps
+    assert set(a) == set(b) == {"x", "y", "status", "iters", "rows"}
+    assert a["x"].shape == (16, 104) and a["y"].shape == (16, 188) and a["status"].shape == (16,)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k])
+    assert np.all(a["status"] == 1) and np.all(a["iters"] > 0) and np.any(a["x"] != 0)
+
+
+def test_dump_outputs_samples_past_the_size_limit(tmp_path):
+    """bench.dump_outputs past its byte limit: one fixed sorted sample of the instances in every
+    array, rows.npy naming them, the files together within the limit; a rank above 0 writes
+    under its own names."""
+    import bench
+    rng = np.random.default_rng(1)
+    outs = {"x": rng.standard_normal((1000, 7)), "status": np.arange(1000, dtype=np.int32)}
+    import torch
+    for k in range(2):  # (numpy arrays, then the torch tensors the bench passes)
+        bench.dump_outputs(str(tmp_path / f"d{k}"), {n: torch.from_numpy(v) if k else v for n, v in outs.items()},
+                           max_bytes=16384)
+    assert np.array_equal(np.load(tmp_path / "d0" / "x.npy"), np.load(tmp_path / "d1" / "x.npy"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "d0").iterdir()}
+    rows = got["rows"].astype(int)
+    assert 100 < rows.size < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["x"], outs["x"][rows]) and np.array_equal(got["status"], rows)
+    assert sum(p.stat().st_size for p in (tmp_path / "d0").iterdir()) <= 16384
+    assert np.array_equal(rows, np.load(tmp_path / "d1" / "rows.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), outs, rank=1, world=2, max_bytes=16384)
+    assert sorted(p.name for p in (tmp_path / "r").iterdir()) == ["rows.rank1.npy", "status.rank1.npy", "x.rank1.npy"]
+    assert np.load(tmp_path / "r" / "rows.rank1.npy").size < rows.size

@@ -12,7 +12,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 b() {  # b <name> <limit> <bench args...>
     local name=$1 lim=$2; shift 2
-    timeout -k 10 "$lim" python3 bench.py "$@" > $out/$name.json 2> $out/$name.err || { echo "$name failed ($?)"; exit 1; }
+    timeout -k 10 "$lim" python3 bench.py --full "$@" > $out/$name.json 2> $out/$name.err || { echo "$name failed ($?)"; exit 1; }
 }
 bash tools/gpu_profile.sh $tag/cfg2 || exit 1
 bash tools/gpu_profile.sh $tag/cfg3 --config 3 --batch 65536 --steps 3 --warmup 1 || exit 1

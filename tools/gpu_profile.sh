@@ -1,6 +1,6 @@
 #!/bin/bash
 # One measurement pass on the GPU box (run through gpurun, from the repo root):
-#   the bench line (with its CPU baseline)                         -> bench.json
+#   the bench line (--full: with its CPU baseline)                 -> bench.json
 #   rocprofv3 --kernel-trace --stats of the same workload          -> kt/
 #   --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes         -> pmc_f/, pmc_w/, traffic.json
 #   two SQ passes: where the waves' cycles go, the LDS counters    -> sq1/, sq2/, sq.json
@@ -19,7 +19,7 @@ step() {  # step <name> <timeout> <cmd...>: stdout+stderr to $out/<name>.log
     local rc=$?
     if [ $rc -ne 0 ]; then echo "$name failed ($rc)" | tee -a "$out/failed"; exit $rc; fi
 }
-timeout -k 10 300 python3 bench.py "${args[@]}" > $out/bench.json 2> $out/bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 300 python3 bench.py --full "${args[@]}" > $out/bench.json 2> $out/bench.err || { echo "bench failed"; exit 1; }
 short=(--no-cpu --no-dispatch-ab --no-pcie --steps 4 --warmup 1 "${args[@]}")
 step kt 240 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python3 bench.py --no-cpu --no-dispatch-ab --no-pcie --steps 10 --warmup 2 "${args[@]}"
 step pmc_f 120 rocprofv3 --pmc FETCH_SIZE -d $out/pmc_f -o f --output-format csv -- python3 bench.py "${short[@]}"
