@@ -114,8 +114,23 @@ __device__ __forceinline__ void st_row16(double* __restrict__ dst, const int i, 
 #undef MPCQP_XOR_PERM8
 #undef MPCQP_CSW
 
+// Where element (i, c) of an S x S tile lives.  SWZ (the one-shot four-wave kernel's
+// S_k^{-1} tiles, one_shot_form 2 without eliminated columns and amax <= 5): the column pair
+// (c & 15) / 2 within its 16-column half is XORed with i & 7.  Column pairs stay adjacent,
+// the halves stay apart and every row is a permutation of itself, so a lane that keeps row i,
+// columns [16 h, 16 h + 16) reads pair s of its half at position s ^ (i & 7) with one
+// ds_read_b128: the values arrive in column order (no swap network, ld_row16's cost) and a
+// 16-lane group of one read spreads over the eight bank quads (2-way instead of 16-way:
+// 64 instead of 512 LDS cycles per wave and tile, tools/lds_banks.py --swizzle).  The layout
+// changes no value and no order of a sum.  !SWZ: row-major, today's code exactly.
+template <bool SWZ>
+__device__ __forceinline__ int tile_at(const int i, const int c) {
+    if constexpr (SWZ) return i * S + (c & 16) + 2 * (((c & 15) >> 1) ^ (i & 7)) + (c & 1);
+    else return i * S + c;
+}
+
 // Gauss-Jordan inverse of the SPD tile T (32 x 32 in LDS) by ONE wave, in place, with a
-// copy to Sgk.  Lane (i, h) = (lane % 32, lane / 32) keeps row i, columns [16 h, 16 h + 16)
+// copy to Sgk. Lane (i, h) = (lane % 32, lane / 32) keeps row i, columns [16 h, 16 h + 16)
 // in registers.  The in-place Gauss-Jordan matrix of a symmetric input stays symmetric up
 // to sign -- M_ij = -M_ji exactly when one of i, j is already pivoted -- so row p is
 // published by the lanes that hold column p (one ds_write_b64 per lane and pivot) and the
@@ -262,12 +277,22 @@ __device__ __forceinline__ bool gj_wave(double* __restrict__ T, double* __restri
 // T (LDS or the workspace) holds true values between the segments (sc = 1 on entry).
 // buf: 2 S doubles of LDS.  a <= 16 (a <= 8 for the unrolled SEG 2).
 // Rot (unrolled form only): the tile rows are read and written in ld_row16's rotated order.
-template <int SEG, bool Compact = false, bool Rot = false>
+// Swz (unrolled form only): T has tile_at<true>'s layout -- the lane's column pair s is at
+// position s ^ (i & 7) of its half, read into and stored from v[2 s], v[2 s + 1] directly.
+template <int SEG, bool Compact = false, bool Rot = false, bool Swz = false>
 __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restrict__ buf, const int a, const int npiv,
                                        const double* __restrict__ dl) {
+    static_assert(!Swz || (!Rot && !Compact), "the swizzled tiles: the unrolled form, reads in place order");
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     double v[16];
-    if constexpr (!Rot || Compact) {
+    if constexpr (Swz) {
+#pragma unroll
+        for (int jj = 0; jj < 16; jj += 2) {
+            const double2 t2 = *(const double2*)(T + tile_at<true>(i, 16 * h + jj));
+            v[jj] = t2.x;
+            v[jj + 1] = t2.y;
+        }
+    } else if constexpr (!Rot || Compact) {
 #pragma unroll
         for (int jj = 0; jj < 16; jj += 2) {
             const double2 t2 = *(const double2*)(T + i * S + 16 * h + jj);
@@ -346,7 +371,11 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
         for (int p = 0; p < 8; ++p)
             if (p < a) step(p, p, done || i < p);
     }
-    if constexpr (!Rot || Compact) {
+    if constexpr (Swz) {
+#pragma unroll
+        for (int jj = 0; jj < 16; jj += 2)
+            *(double2*)(T + tile_at<true>(i, 16 * h + jj)) = make_double2(sc * v[jj], sc * v[jj + 1]);
+    } else if constexpr (!Rot || Compact) {
 #pragma unroll
         for (int jj = 0; jj < 16; jj += 2) *(double2*)(T + i * S + 16 * h + jj) = make_double2(sc * v[jj], sc * v[jj + 1]);
     } else {
@@ -357,12 +386,13 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
 
 // Assembly of block k's D_k (sigma I + the plan's terms) and E_k (rows < amax) by the
 // threads t0, t0 + nt, ...; sync() orders the zeroing before the targets' sums.
-// POL: the polish system's row weights (factorize's comment).
-template <bool POL, bool DEEP, bool STORE, class KP>
+// POL: the polish system's row weights (factorize's comment).  SWZ: D has tile_at<true>'s
+// layout (E is no tile of that kind and stays row-major).
+template <bool POL, bool DEEP, bool STORE, bool SWZ = false, class KP>
 __device__ __forceinline__ void assemble_targets(const KP& p, const SLds& L, const double rho, const int k,
                                                  double* __restrict__ D, double* __restrict__ E, const int t0,
                                                  const int nt);
-template <bool POL, bool DEEP, class KP, class Sync>
+template <bool POL, bool DEEP, bool SWZ = false, class KP, class Sync>
 __device__ __forceinline__ void assemble_block(const KP& p, const SLds& L, const double rho, const int k,
                                                double* __restrict__ D, double* __restrict__ E, const int t0,
                                                const int nt, Sync sync) {
@@ -370,18 +400,19 @@ __device__ __forceinline__ void assemble_block(const KP& p, const SLds& L, const
     for (int e = 2 * t0; e < SS; e += 2 * nt) *(double2*)(D + e) = make_double2(0.0, 0.0);
     for (int e = 2 * t0; e < amax * S; e += 2 * nt) *(double2*)(E + e) = make_double2(0.0, 0.0);
     sync();
-    if (t0 < S) D[t0 * S + t0] = p.pad_var[k * S + t0] >= 0 ? (POL ? p.delta : p.sigma) : 1.0;
+    if (t0 < S) D[tile_at<SWZ>(t0, t0)] = p.pad_var[k * S + t0] >= 0 ? (POL ? p.delta : p.sigma) : 1.0;
     sync();
-    assemble_targets<POL, DEEP, false>(p, L, rho, k, D, E, t0, nt);
+    assemble_targets<POL, DEEP, false, SWZ>(p, L, rho, k, D, E, t0, nt);
 }
 
 // The targets' sums (assemble_block).  STORE: the tiles hold zeros and the diagonal
 // (sigma, or 1 on padding rows) already, and every target is written once as that
 // base value plus its sum (no read: the workspace tiles of factorize_g).
-template <bool POL, bool DEEP, bool STORE, class KP>
+template <bool POL, bool DEEP, bool STORE, bool SWZ, class KP>
 __device__ __forceinline__ void assemble_targets(const KP& p, const SLds& L, const double rho, const int k,
                                                  double* __restrict__ D, double* __restrict__ E, const int t0,
                                                  const int nt) {
+    static_assert(!(SWZ && STORE), "the swizzled tiles are the LDS ones, summed in place");
     const int ntgt = p.ntgt;
     const int2* __restrict__ tt = (const int2*)p.tterm;
     // every target has one owner: its terms are summed in plan order.  The wave's first
@@ -398,7 +429,7 @@ __device__ __forceinline__ void assemble_targets(const KP& p, const SLds& L, con
             if (tg < SS) D[tg] = ((tg >> 5) == (tg & (S - 1)) ? (POL ? p.delta : p.sigma) : 0.0) + acc;
             else E[tg - SS] = 0.0 + acc;
         } else {
-            if (tg < SS) D[tg] += acc;
+            if (tg < SS) D[SWZ ? tile_at<SWZ>(tg >> 5, tg & (S - 1)) : tg] += acc;
             else E[tg - SS] += acc;
         }
     };
@@ -572,10 +603,14 @@ __device__ __forceinline__ bool factorize_w2(const KP& p, SLds& L, const double 
 // TT = 512 (solve_heavy.hip, the one-instance-per-CU kernel): waves 0-3 run stage 1 and the
 // chain exactly as with 256 threads, waves 4-7 join the F / G products (the same sums per
 // output element: the factor is bit-identical to the 256-thread one).
-template <bool ROT = false, int TT = 256, class KP>
+// SWZ (the one-shot kernel, solve_w4_body): the S_k^{-1} tiles in Sg have tile_at<true>'s layout
+// -- D_k's assembly, the Gauss-Jordan's load and store-back and the F_k product go through the
+// map; the E tiles, the G blocks, dl and the wave buffers are as they were.
+template <bool ROT = false, int TT = 256, bool SWZ = false, class KP>
 __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double rho, double* __restrict__ Hg,
                                              double* __restrict__ Sg, double* __restrict__ Fo) {
     static_assert(TT == 256 || TT == 512, "four or eight waves");
+    static_assert(!(ROT && SWZ), "the swizzled tiles are read in place order");
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int amax = p.amax, as = amax * S;
     const long gstride = (long)amax * S;
@@ -603,7 +638,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
     // quasi-definite matrix would find, even though the reduced blocks may still factor
     bool oke = true;
     if (sw) {
-    assemble_block<false, true>(p, L, rho, w, Sg + (long)w * SS, Ek(w), lane, 64, wave_sync);
+    assemble_block<false, true, SWZ>(p, L, rho, w, Sg + (long)w * SS, Ek(w), lane, 64, wave_sync);
     wave_sync();
     if (p.ne && lane < S) {
         // eliminated columns (plan.h Plan::eown): the owner lane of block column w S + lane
@@ -622,7 +657,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
             }
             const double ed = 1.0 / kjj, ec = kpj * ed;
             oke = kjj > 0.0 && ed < __builtin_huge_val();
-            Sg[(long)w * SS + lane * S + lane] -= kpj * ec;
+            Sg[(long)w * SS + tile_at<SWZ>(lane, lane)] -= kpj * ec;
             Fo[2 * e] = ec;
             Fo[2 * e + 1] = ed;
         }
@@ -632,7 +667,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
     FPH(8)
     bool okw = true;
     if (sw) {
-        okw = gj_seg<1, false, ROT>(Sg + (long)w * SS, bufw, w ? amax : 0, p.bsize[w], nullptr);
+        okw = gj_seg<1, false, ROT, SWZ>(Sg + (long)w * SS, bufw, w ? amax : 0, p.bsize[w], nullptr);
         okw = okw && __builtin_amdgcn_ballot_w64(!oke) == 0;
     }
     FPH(10)
@@ -647,8 +682,9 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
         for (int o = tid; o < as; o += TT) {
             const int r = o >> 5, j = o & (S - 1);
             double sacc = 0.0;
+            // (SWZ: lane j reads row l through the map -- a permutation within the row)
 #pragma unroll 4
-            for (int l = l0; l < l0 + bmax; ++l) sacc += E[r * S + l] * Sp[l * S + j];
+            for (int l = l0; l < l0 + bmax; ++l) sacc += E[r * S + l] * Sp[tile_at<SWZ>(l, j)];
             F[o] = sacc;
             Hg[(long)(k * (k - 1) / 2 + k - 1) * gstride + o] = -sacc;
         }
@@ -665,7 +701,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
                 dl[r * 16 + c] = -sacc;
             }
             wave_sync();
-            okw = gj_seg<2, false, ROT>(Sg + (long)k * SS, bufw, amax, p.bsize[k], dl) && okw;
+            okw = gj_seg<2, false, ROT, SWZ>(Sg + (long)k * SS, bufw, amax, p.bsize[k], dl) && okw;
         } else {
             // waves 1-3 meanwhile: G_kj = -F_k G_{k-1,j} (j < k-1), off the chain's path
 #pragma unroll 1
@@ -996,9 +1032,12 @@ __device__ __forceinline__ bool factorize_g(const KP& p, SLds& L, const double r
 // POL: the polish system P + delta I + A' diag(w) A instead (solve.hip::k_polish): row
 // weights w_i = (number of active copies of row i, from ct bits 0/1) * rho with
 // rho = 1 / delta, diagonal delta, factor stored as in mode 1.
-template <int TT, class KP, bool POL = false, bool ROT = false>
+// SWZ: factorize_w4's tiles in tile_at<true>'s layout (no other form takes it).
+template <int TT, class KP, bool POL = false, bool ROT = false, bool SWZ = false>
 __device__ __forceinline__ bool factorize(const KP& p, SLds& L, double rho, double* __restrict__ Fg,
                                           double* __restrict__ Hg, double* __restrict__ Sg) {
+    static_assert(!SWZ || (TT == 256 && !POL), "the four-wave kernel's factorisation");
+    if constexpr (SWZ) return factorize_w4<ROT, TT, true>(p, L, rho, Hg, Sg, Fg);  // (launched for variant 17 only)
     if constexpr (TT == 128 && !POL) {  // the two-wave kernel (variant 10: nb = 4, amax <= 8)
         if (p.mode == 2 && p.nb == 4 && p.amax <= 8) return factorize_w2<ROT>(p, L, rho, Hg, Sg);
     }
@@ -1727,12 +1766,13 @@ __device__ __noinline__ bool factorize_gl_nl(const KParams* gp, long b, double r
 }
 // the same with the G blocks to the LDS region after the tiles (the one-shot fused kernel's GL
 // form, one_shot_form 2: no workspace round trip) instead of the instance's H tiles
-template <int TT, bool ROT = false>
+// SWZ: the tiles in tile_at<true>'s layout
+template <int TT, bool ROT = false, bool SWZ = false>
 __device__ __noinline__ bool factorize_g_nl(const KParams* gp, long b, double rho) {
     KPc& p = kconst(gp);
     SL2 c = carve(p);
     double* const sg = w4_tiles(p, c);
-    return factorize<TT, KPc, false, ROT>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
+    return factorize<TT, KPc, false, ROT, SWZ>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
 }
 
 

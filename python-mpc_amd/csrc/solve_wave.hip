@@ -1197,6 +1197,10 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     const double* Hg = GL == 1 ? C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16) + (long)NB * SS
                            : p.H + b * (long)p.nb * SS;
     double* const Sg = C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16);  // S_k^{-1} tiles in LDS (lds_w2_bytes)
+    // SWZ: the tiles in tile_at<true>'s layout (solve_phases.h) -- the one-shot form 2 without
+    // eliminated columns and amax <= 5, the headline's instantiation.  Its tiles never leave LDS
+    // (no RU / factor_only copy, no dense rows); the other instantiations' stay row-major
+    constexpr bool SWZ = ONE && GL == 1 && !EL && !DK && QR <= 5;
 
     if (p.err[b]) {
         for (int j = tid; j < n; j += T4) if (xo) xo[b * n + j] = __builtin_nan("");
@@ -1320,7 +1324,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 __syncthreads();
                 if (tid == 0) p.ffresh[b] = 0;
             } else if constexpr (GL == 1) {
-                ok = factorize_g_nl<T4, EL>(p.self, b, rho);
+                ok = factorize_g_nl<T4, EL, SWZ>(p.self, b, rho);
             } else if constexpr (GL == 2) {
                 ok = factorize_gl_nl<T4, EL>(p.self, b, rho);
             } else if constexpr (EL) {
@@ -1405,7 +1409,15 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             }
         }
         double SB[16];
-        if constexpr (!DK) {
+        if constexpr (SWZ) {
+            // (the row through an empty asm: the eight swizzled positions are formed here, at the
+            // run start, instead of once per kernel and then held across the solve -- 2 spilled
+            // VGPRs that way)
+            const double* src = Sg + (long)w * SS;
+            const int rs = opaque_v(r);
+#pragma unroll
+            for (int c = 0; c < 16; c += 2) ld2(src + tile_at<true>(rs, 16 * h + c), SB[c], SB[c + 1]);
+        } else if constexpr (!DK) {
             const double* src = Sg + (long)w * SS + r * S + 16 * h;
 #pragma unroll
             for (int c = 0; c < 16; c += 2) ld2(src + c, SB[c], SB[c + 1]);
