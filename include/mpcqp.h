@@ -382,6 +382,54 @@ int mpcqp_incr_shift_device(const mpcqp_incr_layout *L, const mpcqp_vehicle *veh
 int mpcqp_incr_warm_shift_device(int64_t B, int32_t N, int32_t nxa, int32_t nu, const double *dx, const double *dy,
                                  double *dxs, double *dys, int32_t device, void *stream);
 
+/* ======================================================================
+ * The same loop on the kinematic bicycle: Control/MPC/mpc_incre_kine_func.py
+ * simulate (:223-436), batched.  State (x, y, v, yaw), input (steer, accel);
+ * the QP is mpcqp_incr_layout with nx 4, nu 2 (mpcqp_incr_assemble_device).
+ * ====================================================================== */
+
+/* Vehicle_Kinematics(...) constructor arguments (vehicle_models.py:829-833) */
+typedef struct {
+    double l_f, l_r, dt;
+} mpcqp_kin_vehicle;
+
+/* Vehicle_Kinematics.get_kinematics_model (vehicle_models.py:835-863), batched.
+ * For b < B, k < N: x = dx[b*x_sb + k*x_sk + 0..4), u = du[b*u_sb + k*u_sk + 0..2)
+ * -> Ad[(b*N + k)*16] (4x4), Bd[(b*N + k)*8] (4x2), gd[(b*N + k)*4], row-major.
+ * Inputs are never written. */
+int mpcqp_kin_linearise_device(const mpcqp_kin_vehicle *veh, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                               int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, double *dAd, double *dBd,
+                               double *dgd, int32_t device, void *stream);
+
+/* reference_search (mpc_incre_kine_func.py:42-81, nearest_point :28-40, look_ind 1) for
+ * every vehicle: pred[b*(N+1)*nxa + k*nxa + 0..nxa) (speed in state 2), path_x / path_y /
+ * path_yaw[npath], set_speed[B] -> Xr[b*4*(N+1)] (4 rows: path x, path y, set_speed[b],
+ * path_yaw at the same index).  Near the path's end the index holds the start of the last
+ * segment (where the reference raises IndexError), as mpcqp_reference_search_device does. */
+int mpcqp_kin_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double *dpath_x,
+                                      const double *dpath_y, const double *dpath_yaw, const double *dset_speed,
+                                      const double *dpred, double dt, double *dXr, int32_t device, void *stream);
+
+/* The tail of simulate's loop (:382-428) for a layout with nx 4, nu 2 (any other:
+ * MPCQP_EUNSUPPORTED).  Per vehicle b with done[b] == 0, in the reference's order:
+ *   1. unpack sol[b*n] as mpc_increment does (:194-217);
+ *   2. while traj_len[b] < traj_cap, append (x, y, yaw, du_0[steer]) of the state the step
+ *      started from to traj[(b*traj_cap + traj_len[b])*4] and count it (:389-393);
+ *   3. stop rule (:395-401): if the distance from that state to Xr[:, 0] is below 0.5,
+ *      finish_cnt[b] goes up; once it exceeds 15, done[b] = 1, pred / pred_du hold the
+ *      unpacked solution (the reference breaks right after mpc_increment wrote them) and
+ *      nothing below runs;
+ *   4. plant step u = u_prev + du_0, x+ = Ad_0 x + Bd_0 u + gd_0 into xt[b*6];
+ *   5. horizon shift (:407-428) into pred[b*(N+1)*6], pred_du[b*(N+1)*2].  The reference
+ *      shifts in place, so its terminal Euler step (update_kinematics_model) takes the
+ *      solution's stage-N state AND stage-N control, and advances v before yaw uses it.
+ * A vehicle with done[b] != 0 is left untouched (xt, pred, pred_du, finish_cnt, traj).
+ * traj / traj_len may be NULL when traj_cap is 0.  finish_cnt, done, traj_len: int32[B]. */
+int mpcqp_kin_shift_device(const mpcqp_incr_layout *L, const mpcqp_kin_vehicle *veh, int64_t B, const double *dsol,
+                           const double *dAd, const double *dBd, const double *dgd, const double *dXr, double *dxt,
+                           double *dpred, double *dpdu, int32_t *dfinish_cnt, int32_t *ddone, double *dtraj,
+                           int32_t traj_cap, int32_t *dtraj_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,10 @@
 //   F3  k_reference      reference_search / nearest_point       mpc_dynamics.py:30-90
 //       k_incr_shift     plant step + horizon shift              mpc_dynamics.py:578-617
 //                        (terminal state: update_dynamics_model  vehicle_models.py:343-477)
+// and the same loop of Control/MPC/mpc_incre_kine_func.py:simulate on the kinematic bicycle:
+//       k_kin_linearise  Vehicle_Kinematics.get_kinematics_model vehicle_models.py:835-863
+//       k_kin_reference  reference_search / nearest_point        mpc_incre_kine_func.py:28-81
+//       k_kin_shift      record, stop rule, plant step, shift    mpc_incre_kine_func.py:382-428
 //
 // One thread per (vehicle, stage) for the linearisation and per vehicle for the
 // sequential parts (reference search walks the path, the shift reorders the
@@ -182,6 +186,42 @@ __device__ void euler_step(const VehicleK& k, const double* xin, const double* u
     double f[6];
     dynamics(k, x, u, t, f);
     for (int i = 0; i < 6; ++i) xn[i] = x[i] + f[i] * k.dt;
+}
+
+// ---------------------------------------------------------- kinematic bicycle --
+// Vehicle_Kinematics.get_kinematics_model (vehicle_models.py:835-863) for one (x, u):
+// x = (X, Y, v, yaw), u = (steer, accel); the model is already discrete (Ad = A, Bd = B,
+// gd = C of the reference).  Every entry of the 4x4 / 4x2 / 4 outputs is written.
+__device__ void kin_linearise_one(const mpcqp_kin_vehicle& k, const double* x, const double* u,
+                                  double* __restrict__ Ad, double* __restrict__ Bd, double* __restrict__ gd) {
+    const double v = x[2], yaw = x[3], st = u[0];
+    const double dt = k.dt, wb = k.l_f + k.l_r;
+    const double cy = cos(yaw), sy = sin(yaw), cs = cos(st);
+    for (int i = 0; i < 16; ++i) Ad[i] = 0.0;
+    for (int i = 0; i < 8; ++i) Bd[i] = 0.0;
+    Ad[0 * 4 + 0] = 1.0; Ad[1 * 4 + 1] = 1.0; Ad[2 * 4 + 2] = 1.0; Ad[3 * 4 + 3] = 1.0;
+    Ad[0 * 4 + 2] = dt * cy;
+    Ad[0 * 4 + 3] = -dt * v * sy;
+    Ad[1 * 4 + 2] = dt * sy;
+    Ad[1 * 4 + 3] = dt * v * cy;
+    Ad[3 * 4 + 2] = dt * tan(st) / wb;
+    Bd[2 * 2 + 1] = dt;
+    Bd[3 * 2 + 0] = dt * v / (wb * (cs * cs));
+    gd[0] = dt * v * sy * yaw;
+    gd[1] = -dt * v * cy * yaw;
+    gd[2] = 0.0;
+    gd[3] = -dt * v * st / (wb * (cs * cs));
+}
+
+__global__ __launch_bounds__(256) void k_kin_linearise(mpcqp_kin_vehicle k, long B, int N,
+                                                       const double* __restrict__ x, long x_sb, long x_sk,
+                                                       const double* __restrict__ u, long u_sb, long u_sk,
+                                                       double* __restrict__ Ad, double* __restrict__ Bd,
+                                                       double* __restrict__ gd) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * N) return;
+    const long b = t / N, s = t - b * N;
+    kin_linearise_one(k, x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * 16, Bd + t * 8, gd + t * 4);
 }
 
 // ------------------------------------------------------- incremental QP layout --
@@ -372,6 +412,128 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
     for (int i = 0; i < nx; ++i) pb[N * nxa + i] = xe[i];
     for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = pb[(N - 1) * nxa + nx + j];
     for (int j = 0; j < nu; ++j) db[N * nu + j] = db[(N - 1) * nu + j];
+}
+
+// reference_search of mpc_incre_kine_func.py (:42-81, nearest_point :28-40, look_ind = 1):
+// the walk of k_reference with the speed in state 2 and the reference rows
+// (path x, path y, set_speed[b], path_yaw[ind]);  Xr: (B, 4, N+1).
+__global__ __launch_bounds__(128) void k_kin_reference(long B, int N, int nxa, int np, const double* __restrict__ px,
+                                                       const double* __restrict__ py, const double* __restrict__ pyaw,
+                                                       const double* __restrict__ set_speed,
+                                                       const double* __restrict__ pred, double dt,
+                                                       double* __restrict__ Xr) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double* pb = pred + b * (long)(N + 1) * nxa;
+    const double X0 = pb[0], Y0 = pb[1];
+    double min_d = INFINITY;
+    int ind = -1;
+    for (int i = np - 1; i >= 0; --i) {  // reversed(range(len(path_x))), strict <
+        const double d = sqrt((px[i] - X0) * (px[i] - X0) + (py[i] - Y0) * (py[i] - Y0));
+        if (d < min_d) { min_d = d; ind = i; }
+    }
+    // look_ind = 1; the index holds the start of the last segment where the reference
+    // raises IndexError (as k_reference does).  A NaN position leaves ind = -1: 0 below.
+    ind = max(min(ind + 1, np - 2), 0);
+    auto seg = [&](int i) {
+        return sqrt((px[i + 1] - px[i]) * (px[i + 1] - px[i]) + (py[i + 1] - py[i]) * (py[i + 1] - py[i]));
+    };
+    double path_d = seg(ind), cumul = 0.0;
+    const double vref = set_speed[b];
+    double* Xb = Xr + b * 4L * (N + 1);
+    for (int i = 0; i <= N; ++i) {
+        cumul += fabs(pb[i * nxa + 2]) * dt;
+        while (cumul >= path_d && ind + 1 < np - 1) {
+            ind += 1;
+            path_d += seg(ind);
+        }
+        Xb[0 * (N + 1) + i] = px[ind];
+        Xb[1 * (N + 1) + i] = py[ind];
+        Xb[2 * (N + 1) + i] = vref;
+        Xb[3 * (N + 1) + i] = pyaw[ind];
+    }
+}
+
+// Tail of mpc_incre_kine_func.simulate's loop (:382-428), per vehicle, in the reference's
+// order: unpack the solution (mpc_increment :194-217), record the trajectory point
+// (:389-393), stop rule (:395-401), plant step (:385-387, :403-405), horizon shift
+// (:407-428).  The reference shifts pred_x~ in place (temp_pred_x_tilda IS pred_x_tilda),
+// so by the time the terminal state is formed column N-1 already holds column N: the
+// control of the terminal Euler step is the solution's stage-N control, not stage N-1's;
+// update_kinematics_model (vehicle_models.py:877-880) then advances v before yaw uses it.
+// A vehicle whose done flag is set is skipped whole.
+__global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L, long B,
+                                                   const double* __restrict__ sol, const double* __restrict__ Ad,
+                                                   const double* __restrict__ Bd, const double* __restrict__ gd,
+                                                   const double* __restrict__ Xr, double* __restrict__ xt,
+                                                   double* __restrict__ pred, double* __restrict__ pdu,
+                                                   int* __restrict__ finish_cnt, int* __restrict__ done,
+                                                   double* __restrict__ traj, int traj_cap,
+                                                   int* __restrict__ traj_len) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (done[b]) return;
+    constexpr int nx = 4, nu = 2, nxa = 6;
+    const int N = L.N, n = L.n;
+    const double* s = sol + b * n;
+    const double* D = s + (N + 1) * nxa;  // du_0 .. du_{N-1}
+    double* pb = pred + b * (long)(N + 1) * nxa;
+    double* db = pdu + b * (long)(N + 1) * nu;
+    double* xb = xt + b * nxa;
+    // trajectory point: the state the step started from and the first steer increment
+    if (traj_cap > 0) {
+        const int len = traj_len[b];
+        if (len >= 0 && len < traj_cap) {
+            double* tr = traj + (b * (long)traj_cap + len) * 4;
+            tr[0] = xb[0]; tr[1] = xb[1]; tr[2] = xb[3]; tr[3] = D[0];
+            traj_len[b] = len + 1;
+        }
+    }
+    // stop rule: the reference breaks here, leaving pred_x~ / pred_du as mpc_increment unpacked them
+    const double ex = Xr[b * (long)nx * (N + 1)] - xb[0], ey = Xr[b * (long)nx * (N + 1) + (N + 1)] - xb[1];
+    if (sqrt(ex * ex + ey * ey) < 0.5) {
+        const int c = finish_cnt[b] + 1;
+        finish_cnt[b] = c;
+        if (c > 15) {
+            for (int i = 0; i < (N + 1) * nxa; ++i) pb[i] = s[i];
+            for (int i = 0; i < N * nu; ++i) db[i] = D[i];
+            for (int j = 0; j < nu; ++j) db[N * nu + j] = D[(N - 1) * nu + j];
+            done[b] = 1;
+            return;
+        }
+    }
+    // plant step
+    const double* A0 = Ad + b * (long)N * nx * nx;  // stage 0
+    const double* B0 = Bd + b * (long)N * nx * nu;
+    const double* g0 = gd + b * (long)N * nx;
+    double xnext[nx], uu[nu];
+    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + D[j];
+    for (int i = 0; i < nx; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * xb[j];
+        double bu = 0.0;
+        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * uu[j];
+        xnext[i] = (acc + bu) + g0[i];
+    }
+    for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
+    for (int j = 0; j < nu; ++j) xb[nx + j] = uu[j];
+    // shift, from the solution
+    for (int i = 0; i < nxa; ++i) pb[i] = xb[i];
+    for (int k = 1; k <= N - 1; ++k)
+        for (int i = 0; i < nxa; ++i) pb[k * nxa + i] = s[(k + 1) * nxa + i];
+    for (int k = 0; k <= N - 2; ++k)
+        for (int j = 0; j < nu; ++j) db[k * nu + j] = D[(k + 1) * nu + j];
+    for (int j = 0; j < nu; ++j) db[(N - 1) * nu + j] = db[N * nu + j] = D[(N - 1) * nu + j];
+    // terminal state: update_kinematics_model on (x_N, u_N) of the solution, v first
+    const double* sN = s + N * nxa;
+    const double wb = vk.l_f + vk.l_r;
+    const double v1 = sN[2] + sN[5] * vk.dt;
+    pb[N * nxa + 0] = sN[0] + sN[2] * cos(sN[3]) * vk.dt;
+    pb[N * nxa + 1] = sN[1] + sN[2] * sin(sN[3]) * vk.dt;
+    pb[N * nxa + 2] = v1;
+    pb[N * nxa + 3] = sN[3] + v1 / wb * tan(sN[4]) * vk.dt;
+    pb[N * nxa + 4] = sN[4];
+    pb[N * nxa + 5] = sN[5];
 }
 
 // ---- F1 for the LTI (lateral) layouts: affine vector assembly ----
@@ -639,6 +801,51 @@ int mpcqp_incr_shift_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh
     const VehicleK vk = vehicle_constants(*veh);
     hipLaunchKernelGGL(k_incr_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, vk, incr_k(*L),
                        (long)B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mpcqp_kin_linearise_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                               int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
+                               double* dgd, int32_t device, void* stream) {
+    if (!veh || !dx || !du || !dAd || !dBd || !dgd || B < 0 || N < 1)
+        return set_error(MPCQP_EINVAL, "kin_linearise: bad arguments");
+    if (B == 0) return 0;
+    MHIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_kin_linearise, dim3(grid_of(B * N, 256)), dim3(256), 0, (hipStream_t)stream, *veh, (long)B,
+                       (int)N, dx, (long)x_sb, (long)x_sk, du, (long)u_sb, (long)u_sk, dAd, dBd, dgd);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mpcqp_kin_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
+                                      const double* dpath_y, const double* dpath_yaw, const double* dset_speed,
+                                      const double* dpred, double dt, double* dXr, int32_t device, void* stream) {
+    if (!dpath_x || !dpath_y || !dpath_yaw || !dset_speed || !dpred || !dXr || B < 0 || N < 1 || nxa < 4 || npath < 2)
+        return set_error(MPCQP_EINVAL, "kin_reference_search: bad arguments");
+    if (B == 0) return 0;
+    MHIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_kin_reference, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, (long)B, (int)N,
+                       (int)nxa, (int)npath, dpath_x, dpath_y, dpath_yaw, dset_speed, dpred, dt, dXr);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
+                           const double* dAd, const double* dBd, const double* dgd, const double* dXr, double* dxt,
+                           double* dpred, double* dpdu, int32_t* dfinish_cnt, int32_t* ddone, double* dtraj,
+                           int32_t traj_cap, int32_t* dtraj_len, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dXr || !dxt || !dpred || !dpdu || !dfinish_cnt || !ddone ||
+        B < 0 || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_shift: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED, "kin_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    MHIPCHK(hipSetDevice(L->dev));
+    hipLaunchKernelGGL(k_kin_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, incr_k(*L),
+                       (long)B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu, dfinish_cnt, ddone, dtraj, (int)traj_cap,
+                       dtraj_len);
     MHIPCHK(hipGetLastError());
     return 0;
 }

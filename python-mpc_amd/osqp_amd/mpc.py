@@ -234,6 +234,32 @@ def linearise_dynamics(veh: VehicleParams, x, u):
     return Ad, Bc * veh.dt, gc * veh.dt
 
 
+# ---------------------------------------------- kinematic bicycle linearisation --
+def linearise_kinematics(l_f, l_r, dt, x, u):
+    """Batched Vehicle_Kinematics.get_kinematics_model (vehicle_models.py:835-863):
+    x (B,4) = [X, Y, v, yaw], u (B,2) = [steer, accel] -> Ad (B,4,4), Bd (B,4,2), gd (B,4)
+    (the reference's A, B, C: the model is already discrete)."""
+    x = np.atleast_2d(np.asarray(x, float)); u = np.atleast_2d(np.asarray(u, float))
+    wb = l_f + l_r
+    v, yaw, st = x[:, 2], x[:, 3], u[:, 0]
+    cy, sy, cs = np.cos(yaw), np.sin(yaw), np.cos(st)
+    B = x.shape[0]
+    Ad = np.tile(np.eye(4), (B, 1, 1))
+    Ad[:, 0, 2] = dt * cy
+    Ad[:, 0, 3] = -dt * v * sy
+    Ad[:, 1, 2] = dt * sy
+    Ad[:, 1, 3] = dt * v * cy
+    Ad[:, 3, 2] = dt * np.tan(st) / wb
+    Bd = np.zeros((B, 4, 2))
+    Bd[:, 2, 1] = dt
+    Bd[:, 3, 0] = dt * v / (wb * cs ** 2)
+    gd = np.zeros((B, 4))
+    gd[:, 0] = dt * v * sy * yaw
+    gd[:, 1] = -dt * v * cy * yaw
+    gd[:, 3] = -dt * v * st / (wb * cs ** 2)
+    return Ad, Bd, gd
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),
@@ -254,6 +280,19 @@ DYN_R = np.diag([50., 50.])
 DYN_DUMIN = np.array([-np.deg2rad(2.0), -0.5])                   # :461-464
 DYN_XMIN_T = np.array([-np.inf, -np.inf, -2 * np.pi, -100., -30., -0.5 * np.pi, -np.deg2rad(15), -3.])
 DYN_XMAX_T = np.array([np.inf, np.inf, 2 * np.pi, 100., 30., 0.5 * np.pi, np.deg2rad(15), 1.])
+
+KIN_Q = np.diag([100.0, 100.0, 10.0, 100.0])                     # mpc_incre_kine_func.py:264-267
+KIN_QN = np.diag([1000.0, 1000.0, 100.0, 1000.0])
+KIN_R = np.diag([100., 100.])
+KIN_DUMIN = np.array([-np.deg2rad(0.5), -0.5])                   # :257-260
+KIN_XMIN_T = np.array([-np.inf, -np.inf, -100., -2 * np.pi, -np.deg2rad(15), -3.])
+KIN_XMAX_T = np.array([np.inf, np.inf, 100., 2 * np.pi, np.deg2rad(15), 1.])
+# structural nonzeros of get_kinematics_model's A and B (vehicle_models.py:843-856)
+KIN_MASK_A = np.eye(4, dtype=np.uint8)
+for _i, _j in [(0, 2), (0, 3), (1, 2), (1, 3), (3, 2)]:
+    KIN_MASK_A[_i, _j] = 1
+KIN_MASK_B = np.zeros((4, 2), np.uint8)
+KIN_MASK_B[2, 1] = KIN_MASK_B[3, 0] = 1
 
 
 def _lateral_x0(rng, B):

@@ -12,6 +12,10 @@ This module runs the same steps for B vehicles at once on the MI355X through the
 C ABI of include/mpcqp.h (mpcqp_linearise_device, mpcqp_incr_*,
 mpcqp_reference_search_device) and the batched solver (DeviceBatch).  Arrays are
 torch tensors on the device; nothing is copied to the host inside a step.
+
+KinematicMPC is the same loop on the kinematic bicycle, Control/MPC/mpc_incre_kine_func.py:
+simulate (:223-436), with its trajectory record and stop rule (mpcqp_kin_linearise_device,
+mpcqp_kin_reference_search_device, mpcqp_kin_shift_device).
 """
 from __future__ import annotations
 
@@ -33,6 +37,15 @@ class Vehicle(C.Structure):
     def __init__(self, m=1300, l_f=1.25, l_r=1.40, width=1.78, length=4.25, C_d=0.34, A_f=2.0, C_roll=0.015,
                  dt=0.05):
         super().__init__(m, l_f, l_r, width, length, C_d, A_f, C_roll, dt)
+
+
+class KinVehicle(C.Structure):
+    """Vehicle_Kinematics.__init__ arguments (vehicle_models.py:829-833); dt as in
+    mpc_incre_kine_func.simulate (0.02)."""
+    _fields_ = [(k, C.c_double) for k in ("l_f", "l_r", "dt")]
+
+    def __init__(self, l_f=1.25, l_r=1.40, dt=0.02):
+        super().__init__(l_f, l_r, dt)
 
 
 # structural nonzeros of get_dynamics_model's Ad = I + dt Ac and Bd = dt Bc (vehicle_models.py:273-292)
@@ -63,6 +76,10 @@ def _bind():
     L.mpcqp_affine_apply_device.argtypes = [vp, i64, vp, i32, vp, vp, vp, vp, vp]
     L.mpcqp_affine_free.argtypes = [vp]
     L.mpcqp_affine_free.restype = None
+    L.mpcqp_kin_linearise_device.argtypes = [_P(KinVehicle), i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, i32,
+                                             vp]
+    L.mpcqp_kin_reference_search_device.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, vp, d, vp, i32, vp]
+    L.mpcqp_kin_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 11 + [i32, vp, vp]
     L._mpc_bound = True
     return L
 
@@ -435,3 +452,196 @@ class DynamicMPC:
                                          _stream(torch, self.dev)), "incr_shift")
         self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
         return self.status, self.iters
+
+
+# ------------------------------------------------------------ kinematic bicycle --
+def linearise_kinematics(veh: KinVehicle, x, u, device=0):
+    """Batched Vehicle_Kinematics.get_kinematics_model (vehicle_models.py:835-863).
+
+    x: (B, N, 4) or (B, 4) float64 device tensor (X, Y, v, yaw), u: (B, N, 2) or (B, 2)
+    (steer, accel), any strides with a contiguous last dimension -> Ad (B, N, 4, 4),
+    Bd (B, N, 4, 2), gd (B, N, 4) (N axis dropped for 2-D inputs).  Inputs are not modified."""
+    import torch
+    L = _bind()
+    squeeze = x.dim() == 2
+    if squeeze:
+        x, u = x[:, None, :], u[:, None, :]
+    B, N = x.shape[0], x.shape[1]
+    if x.shape[2] != 4 or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
+        raise ValueError("x must be (B, N, 4) and u (B, N, 2)")
+    if x.stride(2) != 1 or u.stride(2) != 1:
+        raise ValueError("the state / input axis must be contiguous")
+    kw = dict(dtype=torch.float64, device=x.device)
+    Ad = torch.empty((B, N, 4, 4), **kw); Bd = torch.empty((B, N, 4, 2), **kw); gd = torch.empty((B, N, 4), **kw)
+    _check(L.mpcqp_kin_linearise_device(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0),
+                                        u.stride(1), _p(Ad), _p(Bd), _p(gd), x.device.index or 0,
+                                        _stream(torch, x.device)), "kin_linearise")
+    if squeeze:
+        return Ad[:, 0], Bd[:, 0], gd[:, 0]
+    return Ad, Bd, gd
+
+
+def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):
+    """reference_search of mpc_incre_kine_func.py (:42-81) per vehicle: pred (B, N+1, nxa)
+    device tensor of predicted augmented states (speed in state 2), set_speed (B,)
+    -> Xr (B, 4, N+1) with rows path x, path y, set_speed, path yaw."""
+    import torch
+    L = _bind()
+    B, N1, nxa = pred.shape
+    if path_y.numel() != path_x.numel() or path_yaw.numel() != path_x.numel() or set_speed.numel() != B:
+        raise ValueError("path_x, path_y, path_yaw must have one length and set_speed B entries")
+    for t in (path_x, path_y, path_yaw, set_speed, pred):
+        if not t.is_contiguous() or t.dtype != torch.float64:
+            raise ValueError("reference_search_kin inputs must be contiguous float64 tensors")
+    Xr = torch.empty((B, 4, N1), dtype=torch.float64, device=pred.device)
+    _check(L.mpcqp_kin_reference_search_device(B, N1 - 1, nxa, path_x.numel(), _p(path_x), _p(path_y), _p(path_yaw),
+                                               _p(set_speed), _p(pred), float(dt), _p(Xr), pred.device.index or 0,
+                                               _stream(torch, pred.device)), "kin_reference_search")
+    return Xr
+
+
+class KinematicMPC:
+    """B copies of mpc_incre_kine_func.simulate(init_state, path_x, path_y, path_yaw)
+    (:223-436), every step on the device.
+
+    State per vehicle: x~ = (X, Y, v, yaw, steer, accel), the predicted horizon pred_x~
+    (N+1 stages) and pred_du.  x0 is (B, 4), u0 (B, 2) (simulate's own u0 is (0, 0.01));
+    set_speed is each vehicle's initial v (:279).  ``step()`` = reference search ->
+    linearisation of every predicted stage -> mpc_increment's QP -> batched OSQP solve
+    (settings of :180: polish off, warm_start off) -> trajectory record, stop rule, plant
+    step and shift (mpcqp_kin_shift_device).
+
+    Stop rule (:395-401): a vehicle within 0.5 of its first reference point counts up
+    ``finish_cnt``; once the count exceeds 15 it is ``done`` and frozen -- its xt, pred,
+    pdu, count and trajectory no longer change.
+
+    ``trajectories()`` gives simulate's four lists as (traj (B, traj_cap, 4), traj_len):
+    columns x, y, yaw and the step's first steer increment, one row per step a vehicle
+    took while not done, rows beyond traj_cap dropped.  Row 0 is the initial state; its
+    last column reproduces the reference, whose traj_steer starts with u0[1, 0] -- the
+    initial ACCELERATION (:323), not a steer value.
+
+    ``warm_start=True`` (an extension; the reference solves every step cold) starts
+    each solve from the previous step's solution shifted one stage (warm_shift)."""
+
+    def __init__(self, x0, u0, path_x, path_y, path_yaw, N=40, veh: KinVehicle | None = None, device=0, traj_cap=0,
+                 **solver_settings):
+        import torch
+        from . import mpc
+        self.torch = torch
+        self.dev = torch.device("cuda", device)
+        self.veh = veh or KinVehicle()
+        self.N = int(N)
+        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
+        if x0.shape[1] != 4 or u0.shape != (x0.shape[0], 2):
+            raise ValueError("x0 must be (B, 4) and u0 (B, 2)")
+        self.B = x0.shape[0]
+        self.traj_cap = int(traj_cap)
+        self.layout = IncrementalLayout(self.N, mpc.KIN_Q, mpc.KIN_QN, mpc.KIN_R, mpc.KIN_XMIN_T, mpc.KIN_XMAX_T,
+                                        mpc.KIN_DUMIN, -mpc.KIN_DUMIN, maskA=mpc.KIN_MASK_A, maskB=mpc.KIN_MASK_B,
+                                        device=device)
+        P, A, _, _ = self.layout.pattern()
+        settings = dict(verbose=False, polish=False, warm_start=False)   # mpc_incre_kine_func.py:180
+        settings.update(solver_settings)
+        settings.pop("verbose", None)
+        self.warm = bool(settings.pop("warm_start"))
+        self.have_sol = False
+        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
+        self.path_x, self.path_y, self.path_yaw = (
+            torch.as_tensor(np.ascontiguousarray(np.asarray(p, np.float64)), **kw).contiguous()
+            for p in (path_x, path_y, path_yaw))
+        if not (self.path_x.numel() == self.path_y.numel() == self.path_yaw.numel() >= 2):
+            raise ValueError("path_x, path_y, path_yaw must have one length, at least 2")
+        self.xt = torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
+        self.set_speed = torch.from_numpy(np.ascontiguousarray(x0[:, 2])).to(**kw).contiguous()
+        n, m = self.layout.n, self.layout.m
+        self.sol = torch.empty((self.B, n), **kw)
+        self.y = torch.empty((self.B, m), **kw)
+        self.status = torch.empty(self.B, **ikw)
+        self.iters = torch.empty(self.B, **ikw)
+        self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)             # del_u0 = 0 (:276, :293-296)
+        self.finish_cnt = torch.zeros(self.B, **ikw)
+        self.done = torch.zeros(self.B, **ikw)
+        # the lists' first entries (:320-323): x0, y0, yaw0 and u0[1] (see the class docstring)
+        traj0 = np.zeros((self.B, max(self.traj_cap, 1), 4))
+        traj0[:, 0] = np.stack([x0[:, 0], x0[:, 1], x0[:, 3], u0[:, 1]], axis=1)
+        self.traj = torch.from_numpy(traj0).to(**kw).contiguous()
+        self.traj_len = torch.full((self.B,), 1 if self.traj_cap > 0 else 0, **ikw)
+        # every kernel of a step runs on this stream, in order (see DynamicMPC)
+        self.stream = torch.cuda.Stream(self.dev)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            self.pred = self._initial_rollout()
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+
+    def _initial_rollout(self):
+        """Initial guess (:289-308): roll the linearised model forward with zero increments."""
+        torch = self.torch
+        pred = torch.empty((self.B, self.N + 1, 6), dtype=torch.float64, device=self.dev)
+        pred[:, 0] = self.xt
+        xk = self.xt.clone()
+        for i in range(self.N):
+            Ad, Bd, gd = linearise_kinematics(self.veh, xk[:, :4].contiguous(), xk[:, 4:].contiguous(),
+                                              self.dev.index or 0)
+            x1 = torch.einsum("bij,bj->bi", Ad, xk[:, :4]) + torch.einsum("bij,bj->bi", Bd, xk[:, 4:]) + gd
+            xk = torch.cat([x1, xk[:, 4:] + self.pdu[:, i]], dim=1)
+            pred[:, i + 1] = xk
+        return pred
+
+    def step(self):
+        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
+        Asynchronous: ordered after the caller's current stream, and the caller's stream
+        is ordered after the step."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            out = self._step()
+        caller.wait_stream(self.stream)
+        return out
+
+    def _step(self):
+        L = _bind()
+        torch = self.torch
+        N = self.N
+        Xr = reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred, self.veh.dt)
+        Ad, Bd, gd = linearise_kinematics(self.veh, self.pred[:, :N, :4], self.pred[:, :N, 4:], self.dev.index or 0)
+        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, self.xt, Xr)
+        st = _stream(torch, self.dev)  # self.stream
+        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
+        if self.warm and self.have_sol:
+            xs, ys = warm_shift(N, 6, 2, self.sol, self.y)
+            self.solver.warm_start(xs, ys, stream=st)
+        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
+        self.have_sol = True
+        _check(L.mpcqp_kin_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
+                                        _p(gd), _p(Xr), _p(self.xt), _p(self.pred), _p(self.pdu),
+                                        _p(self.finish_cnt), _p(self.done), _p(self.traj), self.traj_cap,
+                                        _p(self.traj_len), st), "kin_shift")
+        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
+        return self.status, self.iters
+
+    def trajectories(self):
+        """(traj, traj_len) as host arrays: traj (B, traj_cap, 4) = x, y, yaw, steer increment;
+        traj_len[b] rows of traj[b] are filled (row 0: the initial state and u0[1], as the
+        reference's lists start)."""
+        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
+
+    def run(self, max_steps, check_every=16):
+        """step() until every vehicle is done or max_steps steps were taken; returns the number
+        of steps taken.  ``done`` is read back (one host synchronisation) only every
+        `check_every` steps, so up to check_every - 1 steps may run after the last vehicle
+        stopped.  A done vehicle is still solved with the rest of the batch: its state no
+        longer moves, so its QP repeats from one step to the next and its solution is
+        discarded."""
+        check_every = max(int(check_every), 1)
+        steps = 0
+        while steps < max_steps:
+            self.step()
+            steps += 1
+            if steps % check_every == 0 and bool(self.done.all().item()):
+                break
+        return steps
