@@ -430,6 +430,67 @@ int mpcqp_kin_shift_device(const mpcqp_incr_layout *L, const mpcqp_kin_vehicle *
                            double *dpred, double *dpdu, int32_t *dfinish_cnt, int32_t *ddone, double *dtraj,
                            int32_t traj_cap, int32_t *dtraj_len, void *stream);
 
+/* ======================================================================
+ * The LTV MPC in the inputs themselves (no u_prev augmentation): the layout of
+ * Control/MPC/mpc_kinematics_pred_matrix.py:268-352 mpc__, mpc_dynamics.py:160-279 mpc and
+ * mpc_kinematics.py:202-265 mpc_ (per-stage state bounds), and the closed loop of
+ * mpc_kinematics_pred_matrix.main (:355-563).
+ * ====================================================================== */
+
+/* Variables (x_0..x_N, u_0..u_{N-1}): n = (N+1) nx + N nu; rows [A_eq; I]: (N+1) nx dynamics
+ * equalities, then the identity box on every variable, m = 2 (N+1) nx + N nu.
+ * P = blockdiag(Q x N, QN, R x N) (upper-triangular CSC, constant); A_eq = -I on the diagonal,
+ * Ad_k on the sub-diagonal, Bd_k one block down, its pattern from maskA[nx*nx] / maskB[nx*nu]
+ * as in mpcqp_incr_layout.  Q, QN (nx x nx), R (nu x nu) dense row-major; xmin / xmax nx
+ * entries, umin / umax nu (+-inf allowed, clipped to +-1e30).  N >= 2, 1 <= nx <= 6,
+ * 1 <= nu <= 2, else MPCQP_EUNSUPPORTED. */
+typedef struct mpcqp_ltv_layout mpcqp_ltv_layout;
+int mpcqp_ltv_layout_create(int32_t N, int32_t nx, int32_t nu, const double *Q, const double *QN, const double *R,
+                            const double *xmin, const double *xmax, const double *umin, const double *umax,
+                            const uint8_t *maskA, const uint8_t *maskB, int32_t device, mpcqp_ltv_layout **out);
+int mpcqp_ltv_layout_dims(const mpcqp_ltv_layout *L, int32_t *n, int32_t *m, int32_t *nnzP, int32_t *nnzA);
+/* As mpcqp_incr_layout_pattern; any pointer may be NULL. */
+int mpcqp_ltv_layout_pattern(const mpcqp_ltv_layout *L, int32_t *Pp, int32_t *Pi, double *Px, int32_t *Ap,
+                             int32_t *Ai, double *Ax_template, double *l_template, double *u_template);
+/* Per instance b: Ad[b*N*nx*nx], Bd[b*N*nx*nu], gd[b*N*nx] for stages 0..N-1, x0[b*nx],
+ * Xr[b*nx*(N+1)] (nx rows, N+1 columns) -> Ax[b*nnzA], q[b*n] = (-Q Xr_k (k < N); -QN Xr_N; 0),
+ * l[b*m], u[b*m] with l = u = (-x0; -gd_k) on the equality rows.  xlo / xhi[b*(N+1)*nx]
+ * (stage-major) are optional per-instance, per-stage state bounds (the corridor of mpc_):
+ * NULL = the layout's xmin / xmax on every stage; given, they replace the state rows of the
+ * box, clipped to +-1e30.  The input rows of the box always come from the layout. */
+int mpcqp_ltv_assemble_device(const mpcqp_ltv_layout *L, int64_t B, const double *dAd, const double *dBd,
+                              const double *dgd, const double *dx0, const double *dXr, const double *dxlo,
+                              const double *dxhi, double *dAx, double *dq, double *dl, double *du, void *stream);
+void mpcqp_ltv_layout_free(mpcqp_ltv_layout *L);
+
+/* Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): pred_u[b*(N+1)*2] = u0[b*2]
+ * in all N+1 stages, pred_x[b*(N+1)*4]: stage 0 = x0[b*4], stage k+1 =
+ * update_kinematics_model(stage k, u0) (vehicle_models.py:866-883: the nonlinear Euler step,
+ * v advanced before yaw reads it). */
+int mpcqp_kin_rollout_device(const mpcqp_kin_vehicle *veh, int64_t B, int32_t N, const double *dx0,
+                             const double *du0, double *dpred_x, double *dpred_u, int32_t device, void *stream);
+
+/* The tail of mpc_kinematics_pred_matrix.main's loop (:479-563) for a layout with nx 4, nu 2
+ * (any other: MPCQP_EUNSUPPORTED).  sol[b*n] = (S_0..S_N, U_0..U_{N-1}).  status[b] is the
+ * solver's code (NULL: all solved).  A vehicle whose status is not 1 (solved) is skipped as
+ * the reference's `continue` skips it: x, u, pred_x, pred_u, traj, traj_len and steps_taken
+ * stay bit for bit and skipped[b] goes up.  Otherwise:
+ *   1. while traj_len[b] < traj_cap, append (x, y, v, yaw, U_0[steer], U_0[accel]) -- the
+ *      state the step started from and the control applied -- to
+ *      traj[(b*traj_cap + traj_len[b])*6] and count it;
+ *   2. plant step x <- Ad_0 x + Bd_0 U_0 + gd_0 (x[b*4]), u <- U_0 (u[b*2]);
+ *   3. pred_x: stage 0 = x, stage k = S_{k+1} (1 <= k <= N-1), stage N =
+ *      update_kinematics_model(S_N, U_{N-1});
+ *   4. pred_u: stage k = U_{k+1} (k <= N-2), stages N-1 and N = U_{N-1};
+ *   5. steps_taken[b] goes up.
+ * skipped, steps_taken, traj_len: int32[B]; steps_taken may be NULL, traj / traj_len when
+ * traj_cap is 0. */
+int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout *L, const mpcqp_kin_vehicle *veh, int64_t B,
+                               const double *dsol, const int32_t *dstatus, const double *dAd, const double *dBd,
+                               const double *dgd, double *dx, double *du, double *dpred_x, double *dpred_u,
+                               int32_t *dskipped, int32_t *dsteps_taken, double *dtraj, int32_t traj_cap,
+                               int32_t *dtraj_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

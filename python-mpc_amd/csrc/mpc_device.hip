@@ -11,6 +11,11 @@
 //       k_kin_linearise  Vehicle_Kinematics.get_kinematics_model vehicle_models.py:835-863
 //       k_kin_reference  reference_search / nearest_point        mpc_incre_kine_func.py:28-81
 //       k_kin_shift      record, stop rule, plant step, shift    mpc_incre_kine_func.py:382-428
+// and the LTV MPC in the inputs themselves (mpcqp_ltv_layout), with the closed loop of
+// Control/MPC/mpc_kinematics_pred_matrix.py:main:
+//       k_ltv_assemble_vec  mpc__ / mpc / mpc_'s q, l, u           mpc_kinematics_pred_matrix.py:268-352
+//       k_kin_rollout       initial horizon (nonlinear Euler)      :405-419
+//       k_kin_ltv_shift     skip rule, record, plant step, shift   :479-563
 //
 // One thread per (vehicle, stage) for the linearisation and per vehicle for the
 // sequential parts (reference search walks the path, the shift reorders the
@@ -536,6 +541,142 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
     pb[N * nxa + 5] = sN[5];
 }
 
+// ------------------------------------------------------ direct-input LTV layout --
+// The QP of mpc__ (mpc_kinematics_pred_matrix.py:268-352), mpc (mpc_dynamics.py:160-279) and
+// mpc_ (mpc_kinematics.py:202-265): variables (x_0 .. x_N, u_0 .. u_{N-1}), no augmentation,
+//   A = [ Aeq ; I ],  Aeq = [ -I + subdiag(Ad_k) | Bd_k shifted one block down ].
+// Held as an IncrLayout with nxa = nx, so the A values go through k_incr_assemble_A; Qt holds
+// Q and QN themselves (q = -Q Xr_k).  q, l, u of one vehicle per thread; xlo / xhi (may be
+// null) are the per-stage state bounds of mpc_'s corridor, (B, N+1, nx).
+__global__ __launch_bounds__(128) void k_ltv_assemble_vec(IncrK L, long B, const double* __restrict__ gd,
+                                                          const double* __restrict__ x0,
+                                                          const double* __restrict__ Xr,
+                                                          const double* __restrict__ xlo,
+                                                          const double* __restrict__ xhi, double* __restrict__ q,
+                                                          double* __restrict__ l, double* __restrict__ u) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int N = L.N, nx = L.nx, n = L.n, m = L.m;
+    const double INF = 1e30;
+    double* qb = q + b * n;
+    const double* Xb = Xr + b * (long)nx * (N + 1);  // Xr[j][k] at j*(N+1)+k
+    for (int k = 0; k <= N; ++k) {
+        const double* W = L.Qt + (k == N ? nx * nx : 0);
+        for (int i = 0; i < nx; ++i) {
+            double acc = 0.0;
+            for (int j = 0; j < nx; ++j) acc += W[i * nx + j] * Xb[j * (N + 1) + k];
+            qb[k * nx + i] = -acc;
+        }
+    }
+    for (int i = (N + 1) * nx; i < n; ++i) qb[i] = 0.0;
+    double* lb = l + b * m;
+    double* ub = u + b * m;
+    for (int i = 0; i < nx; ++i) lb[i] = ub[i] = -x0[b * nx + i];
+    const double* gb = gd + b * (long)N * nx;
+    for (int i = 0; i < N * nx; ++i) lb[nx + i] = ub[nx + i] = -gb[i];
+    const int ns = (N + 1) * nx;  // state rows of the box start at ns, input rows at 2 ns
+    for (int i = 0; i < ns; ++i) {
+        lb[ns + i] = xlo ? fmin(fmax(xlo[b * (long)ns + i], -INF), INF) : L.ltpl[ns + i];
+        ub[ns + i] = xhi ? fmin(fmax(xhi[b * (long)ns + i], -INF), INF) : L.utpl[ns + i];
+    }
+    for (int r = 2 * ns; r < m; ++r) {
+        lb[r] = L.ltpl[r];
+        ub[r] = L.utpl[r];
+    }
+}
+
+// update_kinematics_model (vehicle_models.py:866-883): the reference updates in place, so v
+// advances before yaw reads it.  xn may alias x.
+__device__ __forceinline__ void kin_update(const mpcqp_kin_vehicle& k, const double* x, const double* u,
+                                           double* xn) {
+    const double X = x[0], Y = x[1], v = x[2], yaw = x[3];
+    const double v1 = v + u[1] * k.dt;
+    xn[0] = X + v * cos(yaw) * k.dt;
+    xn[1] = Y + v * sin(yaw) * k.dt;
+    xn[2] = v1;
+    xn[3] = yaw + v1 / (k.l_f + k.l_r) * tan(u[0]) * k.dt;
+}
+
+// Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): u0 in every stage, the
+// nonlinear model rolled forward from x0.  pred_x (B, N+1, 4), pred_u (B, N+1, 2).
+__global__ __launch_bounds__(128) void k_kin_rollout(mpcqp_kin_vehicle vk, long B, int N,
+                                                     const double* __restrict__ x0, const double* __restrict__ u0,
+                                                     double* __restrict__ pred_x, double* __restrict__ pred_u) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double* px = pred_x + b * (long)(N + 1) * 4;
+    double* pu = pred_u + b * (long)(N + 1) * 2;
+    const double uu[2] = {u0[b * 2], u0[b * 2 + 1]};
+    double xk[4];
+    for (int i = 0; i < 4; ++i) xk[i] = px[i] = x0[b * 4 + i];
+    for (int k = 0; k <= N; ++k) { pu[k * 2] = uu[0]; pu[k * 2 + 1] = uu[1]; }
+    for (int k = 0; k < N; ++k) {
+        kin_update(vk, xk, uu, xk);
+        for (int i = 0; i < 4; ++i) px[(k + 1) * 4 + i] = xk[i];
+    }
+}
+
+// Tail of mpc_kinematics_pred_matrix.main's loop (:479-563), per vehicle.  The reference
+// shifts pred_x / pred_u in place through aliases; read from the solution (S_0..S_N,
+// U_0..U_{N-1}) the result is: pred_x = (x_next, S_2..S_N, update(S_N, U_{N-1})),
+// pred_u = (U_1..U_{N-1}, U_{N-1}, U_{N-1}) -- the terminal control is stage N-1, unlike
+// k_kin_shift.  A vehicle whose status is not `solved` is skipped whole (:480-484).
+__global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int N, int n, long B,
+                                                       const double* __restrict__ sol,
+                                                       const int* __restrict__ status,
+                                                       const double* __restrict__ Ad, const double* __restrict__ Bd,
+                                                       const double* __restrict__ gd, double* __restrict__ x,
+                                                       double* __restrict__ u, double* __restrict__ pred_x,
+                                                       double* __restrict__ pred_u, int* __restrict__ skipped,
+                                                       int* __restrict__ steps_taken, double* __restrict__ traj,
+                                                       int traj_cap, int* __restrict__ traj_len) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (status && status[b] != 1) {
+        skipped[b] += 1;
+        return;
+    }
+    constexpr int nx = 4, nu = 2;
+    const double* S = sol + b * n;
+    const double* U = S + (N + 1) * nx;
+    double* xb = x + b * nx;
+    double* ub = u + b * nu;
+    double* px = pred_x + b * (long)(N + 1) * nx;
+    double* pu = pred_u + b * (long)(N + 1) * nu;
+    // plt_states[:, i], plt_actions[:, i]: the state the step started from, the control applied
+    if (traj_cap > 0) {
+        const int len = traj_len[b];
+        if (len >= 0 && len < traj_cap) {
+            double* tr = traj + (b * (long)traj_cap + len) * 6;
+            for (int i = 0; i < nx; ++i) tr[i] = xb[i];
+            tr[4] = U[0]; tr[5] = U[1];
+            traj_len[b] = len + 1;
+        }
+    }
+    // plant step (:534-541)
+    const double* A0 = Ad + b * (long)N * nx * nx;  // stage 0
+    const double* B0 = Bd + b * (long)N * nx * nu;
+    const double* g0 = gd + b * (long)N * nx;
+    double xnext[nx];
+    for (int i = 0; i < nx; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * xb[j];
+        double bu = 0.0;
+        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * U[j];
+        xnext[i] = (acc + bu) + g0[i];
+    }
+    for (int i = 0; i < nx; ++i) xb[i] = px[i] = xnext[i];
+    for (int j = 0; j < nu; ++j) ub[j] = U[j];
+    // shift (:543-563), from the solution
+    for (int k = 1; k <= N - 1; ++k)
+        for (int i = 0; i < nx; ++i) px[k * nx + i] = S[(k + 1) * nx + i];
+    kin_update(vk, S + N * nx, U + (N - 1) * nu, px + N * nx);
+    for (int k = 0; k <= N - 2; ++k)
+        for (int j = 0; j < nu; ++j) pu[k * nu + j] = U[(k + 1) * nu + j];
+    for (int j = 0; j < nu; ++j) pu[(N - 1) * nu + j] = pu[N * nu + j] = U[(N - 1) * nu + j];
+    if (steps_taken) steps_taken[b] += 1;
+}
+
 // ---- F1 for the LTI (lateral) layouts: affine vector assembly ----
 // vehicle_lateral_mpc_slack_increment.py:32-121 / its loop :201-229 and
 // Control/MPC/mpc_kinematics.py:148-191 rebuild P, q, A, l, u every step although with the
@@ -583,6 +724,7 @@ __global__ __launch_bounds__(256) void k_affine(AffineK a, long B, const double*
 using namespace mpcqp;
 
 struct mpcqp_incr_layout : IncrLayout {};
+struct mpcqp_ltv_layout : IncrLayout {};  // nxa = nx: no augmentation
 
 struct mpcqp_affine {
     int dev = 0, L = 0, R = 0, T = 0, seg0 = 0, seg1 = 0, nparam = 0;
@@ -624,6 +766,58 @@ IncrK incr_k(const IncrLayout& L) {
     return k;
 }
 
+// P = blockdiag(kron(I_N, C'QC), C'QN C, kron(I_N, R)), upper triangle, zeros dropped
+// (mpc_dynamics.py:304-307); with nxa = nx, C = I: blockdiag(Q x N, QN, R x N)
+void build_P(IncrLayout& L, const double* Q, const double* QN, const double* R) {
+    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, n = L.n;
+    L.Pp.assign(n + 1, 0);
+    for (int c = 0; c < n; ++c) {
+        if (c < (N + 1) * nxa) {
+            const int k = c / nxa, j = c % nxa;
+            const double* W = k == N ? QN : Q;
+            if (j < nx)
+                for (int i = 0; i <= j; ++i) {
+                    const double v = W[i * nx + j];
+                    if (v != 0.0) { L.Pi.push_back(k * nxa + i); L.Px.push_back(v); }
+                }
+        } else {
+            const int c0 = c - (N + 1) * nxa, k = c0 / nu, j = c0 % nu;
+            for (int i = 0; i <= j; ++i) {
+                const double v = R[i * nu + j];
+                if (v != 0.0) { L.Pi.push_back((N + 1) * nxa + k * nu + i); L.Px.push_back(v); }
+            }
+        }
+        L.Pp[c + 1] = (int)L.Pi.size();
+    }
+}
+
+// dims / pattern / free of either layout (mpcqp_incr_layout, mpcqp_ltv_layout)
+int layout_dims(const IncrLayout* L, const char* what, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA) {
+    if (!L || !n || !m || !nnzP || !nnzA) return set_error(MPCQP_EINVAL, "%s: NULL argument", what);
+    *n = L->n; *m = L->m; *nnzP = (int32_t)L->Pi.size(); *nnzA = (int32_t)L->Ai.size();
+    return 0;
+}
+
+int layout_pattern(const IncrLayout* L, const char* what, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
+                   int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
+    if (!L) return set_error(MPCQP_EINVAL, "%s: NULL layout", what);
+    if (Pp) std::memcpy(Pp, L->Pp.data(), sizeof(int32_t) * L->Pp.size());
+    if (Pi) std::memcpy(Pi, L->Pi.data(), sizeof(int32_t) * L->Pi.size());
+    if (Px) std::memcpy(Px, L->Px.data(), sizeof(double) * L->Px.size());
+    if (Ap) std::memcpy(Ap, L->Ap.data(), sizeof(int32_t) * L->Ap.size());
+    if (Ai) std::memcpy(Ai, L->Ai.data(), sizeof(int32_t) * L->Ai.size());
+    if (Ax_template) std::memcpy(Ax_template, L->Atpl.data(), sizeof(double) * L->Atpl.size());
+    if (l_template) std::memcpy(l_template, L->ltpl.data(), sizeof(double) * L->ltpl.size());
+    if (u_template) std::memcpy(u_template, L->utpl.data(), sizeof(double) * L->utpl.size());
+    return 0;
+}
+
+void layout_free_device(IncrLayout* L) {
+    if (L->d_asrc) (void)hipSetDevice(L->dev);
+    for (void* p : {(void*)L->d_asrc, (void*)L->d_Atpl, (void*)L->d_ltpl, (void*)L->d_utpl, (void*)L->d_Qt})
+        if (p) (void)hipFree(p);
+}
+
 unsigned grid_of(long count, int block) { return (unsigned)((count + block - 1) / block); }
 
 }  // namespace
@@ -660,26 +854,7 @@ int mpcqp_incr_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q,
     const int nxa = nx + nu, n = (N + 1) * nxa + N * nu, m = (N + 1) * nxa + n;
     L->N = N; L->nx = nx; L->nu = nu; L->nxa = nxa; L->n = n; L->m = m; L->dev = device;
     const double INF = 1e30;  // the osqp wrapper clips +-inf to +-OSQP_INFTY
-    // P = blockdiag(kron(I_N, C'QC), C'QN C, kron(I_N, R)), upper triangle, zeros dropped (:304-307)
-    L->Pp.assign(n + 1, 0);
-    for (int c = 0; c < n; ++c) {
-        if (c < (N + 1) * nxa) {
-            const int k = c / nxa, j = c % nxa;
-            const double* W = k == N ? QN : Q;
-            if (j < nx)
-                for (int i = 0; i <= j; ++i) {
-                    const double v = W[i * nx + j];
-                    if (v != 0.0) { L->Pi.push_back(k * nxa + i); L->Px.push_back(v); }
-                }
-        } else {
-            const int c0 = c - (N + 1) * nxa, k = c0 / nu, j = c0 % nu;
-            for (int i = 0; i <= j; ++i) {
-                const double v = R[i * nu + j];
-                if (v != 0.0) { L->Pi.push_back((N + 1) * nxa + k * nu + i); L->Px.push_back(v); }
-            }
-        }
-        L->Pp[c + 1] = (int)L->Pi.size();
-    }
+    build_P(*L, Q, QN, R);
     // A by column (:336-369, :381-382)
     L->Ap.assign(n + 1, 0);
     auto push = [&](int row, int src, double tpl) {
@@ -738,23 +913,12 @@ int mpcqp_incr_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q,
 }
 
 int mpcqp_incr_layout_dims(const mpcqp_incr_layout* L, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA) {
-    if (!L || !n || !m || !nnzP || !nnzA) return set_error(MPCQP_EINVAL, "incr_layout_dims: NULL argument");
-    *n = L->n; *m = L->m; *nnzP = (int32_t)L->Pi.size(); *nnzA = (int32_t)L->Ai.size();
-    return 0;
+    return layout_dims(L, "incr_layout_dims", n, m, nnzP, nnzA);
 }
 
 int mpcqp_incr_layout_pattern(const mpcqp_incr_layout* L, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
                               int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
-    if (!L) return set_error(MPCQP_EINVAL, "incr_layout_pattern: NULL layout");
-    if (Pp) std::memcpy(Pp, L->Pp.data(), sizeof(int32_t) * L->Pp.size());
-    if (Pi) std::memcpy(Pi, L->Pi.data(), sizeof(int32_t) * L->Pi.size());
-    if (Px) std::memcpy(Px, L->Px.data(), sizeof(double) * L->Px.size());
-    if (Ap) std::memcpy(Ap, L->Ap.data(), sizeof(int32_t) * L->Ap.size());
-    if (Ai) std::memcpy(Ai, L->Ai.data(), sizeof(int32_t) * L->Ai.size());
-    if (Ax_template) std::memcpy(Ax_template, L->Atpl.data(), sizeof(double) * L->Atpl.size());
-    if (l_template) std::memcpy(l_template, L->ltpl.data(), sizeof(double) * L->ltpl.size());
-    if (u_template) std::memcpy(u_template, L->utpl.data(), sizeof(double) * L->utpl.size());
-    return 0;
+    return layout_pattern(L, "incr_layout_pattern", Pp, Pi, Px, Ap, Ai, Ax_template, l_template, u_template);
 }
 
 int mpcqp_incr_assemble_device(const mpcqp_incr_layout* L, int64_t B, const double* dAd, const double* dBd,
@@ -931,10 +1095,133 @@ void mpcqp_affine_free(mpcqp_affine* a) {
 
 void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {
     if (!L) return;
-    if (L->d_asrc) (void)hipSetDevice(L->dev);
-    for (void* p : {(void*)L->d_asrc, (void*)L->d_Atpl, (void*)L->d_ltpl, (void*)L->d_utpl, (void*)L->d_Qt})
-        if (p) (void)hipFree(p);
+    layout_free_device(L);
     delete L;
+}
+
+// ------------------------------------------------------ direct-input LTV layout --
+int mpcqp_ltv_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q, const double* QN, const double* R,
+                            const double* xmin, const double* xmax, const double* umin, const double* umax,
+                            const uint8_t* maskA, const uint8_t* maskB, int32_t device, mpcqp_ltv_layout** out) {
+    if (!out || !Q || !QN || !R || !xmin || !xmax || !umin || !umax || !maskA || !maskB)
+        return set_error(MPCQP_EINVAL, "ltv_layout_create: NULL argument");
+    if (N < 2 || nx < 1 || nu < 1 || nx > 6 || nu > 2)
+        return set_error(MPCQP_EUNSUPPORTED, "ltv_layout_create: need N >= 2, 1 <= nx <= 6, 1 <= nu <= 2");
+    for (int i = 0; i < nx; ++i)
+        if (!(xmin[i] <= xmax[i])) return set_error(MPCQP_EINVAL, "ltv_layout_create: xmin > xmax");
+    for (int j = 0; j < nu; ++j)
+        if (!(umin[j] <= umax[j])) return set_error(MPCQP_EINVAL, "ltv_layout_create: umin > umax");
+    *out = nullptr;
+    auto L = std::make_unique<mpcqp_ltv_layout>();
+    const int ns = (N + 1) * nx, n = ns + N * nu, m = ns + n;
+    L->N = N; L->nx = nx; L->nu = nu; L->nxa = nx; L->n = n; L->m = m; L->dev = device;
+    const double INF = 1e30;  // the osqp wrapper clips +-inf to +-OSQP_INFTY
+    build_P(*L, Q, QN, R);
+    // A by column (mpc_kinematics_pred_matrix.py:293-309, :326, :341)
+    L->Ap.assign(n + 1, 0);
+    auto push = [&](int row, int src, double tpl) {
+        L->Ai.push_back(row); L->asrc.push_back(src); L->Atpl.push_back(tpl);
+    };
+    for (int c = 0; c < n; ++c) {
+        if (c < ns) {
+            const int k = c / nx, j = c % nx;
+            push(c, kConstSrc, -1.0);  // -I
+            if (k < N)                 // Ad_k in rows of stage k+1
+                for (int i = 0; i < nx; ++i)
+                    if (maskA[i * nx + j]) push((k + 1) * nx + i, k * nx * nx + i * nx + j, 0.0);
+        } else {
+            const int c0 = c - ns, k = c0 / nu, j = c0 % nu;  // u_k: Bd_k in rows of stage k+1
+            for (int i = 0; i < nx; ++i)
+                if (maskB[i * nu + j]) push((k + 1) * nx + i, -1 - (k * nx * nu + i * nu + j), 0.0);
+        }
+        push(ns + c, kConstSrc, 1.0);  // A_ineq = I
+        L->Ap[c + 1] = (int)L->Ai.size();
+    }
+    // box bounds (:327-328), clipped like the osqp wrapper; equality rows 0
+    L->ltpl.assign(m, 0.0); L->utpl.assign(m, 0.0);
+    for (int k = 0; k <= N; ++k)
+        for (int i = 0; i < nx; ++i) {
+            L->ltpl[ns + k * nx + i] = std::min(std::max(xmin[i], -INF), INF);
+            L->utpl[ns + k * nx + i] = std::min(std::max(xmax[i], -INF), INF);
+        }
+    for (int k = 0; k < N; ++k)
+        for (int j = 0; j < nu; ++j) {
+            L->ltpl[2 * ns + k * nu + j] = std::min(std::max(umin[j], -INF), INF);
+            L->utpl[2 * ns + k * nu + j] = std::min(std::max(umax[j], -INF), INF);
+        }
+    // q = -Q Xr_k: the weights themselves, stage and terminal
+    L->Qt.assign(2 * nx * nx, 0.0);
+    for (int i = 0; i < nx * nx; ++i) {
+        L->Qt[i] = Q[i];
+        L->Qt[nx * nx + i] = QN[i];
+    }
+    *out = L.release();  // device copies are made by the first assemble (host-only use needs no GPU)
+    return 0;
+}
+
+int mpcqp_ltv_layout_dims(const mpcqp_ltv_layout* L, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA) {
+    return layout_dims(L, "ltv_layout_dims", n, m, nnzP, nnzA);
+}
+
+int mpcqp_ltv_layout_pattern(const mpcqp_ltv_layout* L, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
+                             int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
+    return layout_pattern(L, "ltv_layout_pattern", Pp, Pi, Px, Ap, Ai, Ax_template, l_template, u_template);
+}
+
+int mpcqp_ltv_assemble_device(const mpcqp_ltv_layout* L, int64_t B, const double* dAd, const double* dBd,
+                              const double* dgd, const double* dx0, const double* dXr, const double* dxlo,
+                              const double* dxhi, double* dAx, double* dq, double* dl, double* du, void* stream) {
+    if (!L || !dAd || !dBd || !dgd || !dx0 || !dXr || !dAx || !dq || !dl || !du || B < 0)
+        return set_error(MPCQP_EINVAL, "ltv_assemble: bad arguments");
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_ltv_layout*>(L))) return e;
+    MHIPCHK(hipSetDevice(L->dev));
+    const IncrK k = incr_k(*L);
+    const long nA = (long)B * k.nnzA;
+    hipLaunchKernelGGL(k_incr_assemble_A, dim3(grid_of(nA, 256)), dim3(256), 0, (hipStream_t)stream, k, (long)B,
+                       dAd, dBd, dAx);
+    hipLaunchKernelGGL(k_ltv_assemble_vec, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, k, (long)B,
+                       dgd, dx0, dXr, dxlo, dxhi, dq, dl, du);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+void mpcqp_ltv_layout_free(mpcqp_ltv_layout* L) {
+    if (!L) return;
+    layout_free_device(L);
+    delete L;
+}
+
+int mpcqp_kin_rollout_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx0,
+                             const double* du0, double* dpred_x, double* dpred_u, int32_t device, void* stream) {
+    if (!veh || !dx0 || !du0 || !dpred_x || !dpred_u || B < 0 || N < 1)
+        return set_error(MPCQP_EINVAL, "kin_rollout: bad arguments");
+    if (B == 0) return 0;
+    MHIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_kin_rollout, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, (long)B, (int)N,
+                       dx0, du0, dpred_x, dpred_u);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
+                               const double* dsol, const int32_t* dstatus, const double* dAd, const double* dBd,
+                               const double* dgd, double* dx, double* du, double* dpred_x, double* dpred_u,
+                               int32_t* dskipped, int32_t* dsteps_taken, double* dtraj, int32_t traj_cap,
+                               int32_t* dtraj_len, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dpred_u || !dskipped || B < 0 ||
+        traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_ltv_shift: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_ltv_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0) return 0;
+    MHIPCHK(hipSetDevice(L->dev));
+    hipLaunchKernelGGL(k_kin_ltv_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, (int)L->N,
+                       (int)L->n, (long)B, dsol, dstatus, dAd, dBd, dgd, dx, du, dpred_x, dpred_u, dskipped,
+                       dsteps_taken, dtraj, (int)traj_cap, dtraj_len);
+    MHIPCHK(hipGetLastError());
+    return 0;
 }
 
 }  // extern "C"

@@ -79,6 +79,32 @@ def vanilla_qp(Ad, Bd, gd, x0, Xr, Q, QN, R, N, xmin, xmax, umin, umax):
     return _csc(P), q, _csc(A), np.concatenate([leq, lineq]), np.concatenate([leq, uineq])
 
 
+# ------------------------------------------------- LTV in the inputs themselves --
+def ltv_qp(Ad_list, Bd_list, gd_list, x0, Xr, Q, QN, R, N, xmin, xmax, umin, umax, xlo=None, xhi=None):
+    """The LTV MPC in (x_0..x_N, u_0..u_{N-1}) with per-stage Ad_k, Bd_k, gd_k:
+    Control/MPC/mpc_kinematics_pred_matrix.py:268-352 (`mpc__`), Control/MPC/mpc_dynamics.py:160-279
+    (`mpc`) and, with the per-stage state bounds xlo / xhi ((N+1, nx), replacing xmin / xmax),
+    Control/MPC/mpc_kinematics.py:202-265 (`mpc_`, the x/y corridor).  Returns P, q, A, l, u."""
+    Ad_list = [np.asarray(a, float) for a in Ad_list]
+    Bd_list = [np.asarray(b, float) for b in Bd_list]
+    nx, nu = Bd_list[0].shape
+    if len(Ad_list) != N or len(Bd_list) != N or len(gd_list) != N:
+        raise ValueError("Ad_list, Bd_list, gd_list must have N entries")
+    Q = np.asarray(sparse.csr_matrix(Q).todense()); QN = np.asarray(sparse.csr_matrix(QN).todense())
+    R = np.asarray(sparse.csr_matrix(R).todense())
+    P = sparse.block_diag([sparse.kron(sparse.eye(N), Q), QN, sparse.kron(sparse.eye(N), R)])
+    q = np.concatenate([-(Q @ Xr[:, k]) for k in range(N)] + [-(QN @ Xr[:, N]), np.zeros(N * nu)])
+    Aeq = _dyn_eq(Ad_list, Bd_list, N)
+    leq = np.concatenate([-np.asarray(x0, float).ravel()] + [-np.asarray(g, float).ravel() for g in gd_list])
+    Aineq = sparse.eye((N + 1) * nx + N * nu)
+    xl = np.tile(xmin, N + 1) if xlo is None else np.asarray(xlo, float).reshape((N + 1) * nx)
+    xh = np.tile(xmax, N + 1) if xhi is None else np.asarray(xhi, float).reshape((N + 1) * nx)
+    lineq = np.concatenate([xl, np.tile(umin, N)])
+    uineq = np.concatenate([xh, np.tile(umax, N)])
+    A = sparse.vstack([Aeq, Aineq])
+    return _csc(P), q, _csc(A), np.concatenate([leq, lineq]), np.concatenate([leq, uineq])
+
+
 # ---------------------------------------------------------- slack (cfg 1/3/4) --
 SLACK_Q = np.diag([5., 5., 10., 10.])                        # :66
 SLACK_R = 10.0                                               # :71
@@ -293,6 +319,22 @@ for _i, _j in [(0, 2), (0, 3), (1, 2), (1, 3), (3, 2)]:
     KIN_MASK_A[_i, _j] = 1
 KIN_MASK_B = np.zeros((4, 2), np.uint8)
 KIN_MASK_B[2, 1] = KIN_MASK_B[3, 0] = 1
+
+KINLTV_Q = np.diag([10.0, 10.0, 100.0, 10.0])                    # mpc_kinematics_pred_matrix.py:425-435
+KINLTV_QN = np.diag([100.0, 100.0, 1000.0, 100.0])
+KINLTV_R = np.diag([1000., 100.])
+KINLTV_UMIN = np.array([-np.deg2rad(15), -3.])
+KINLTV_UMAX = np.array([np.deg2rad(15), 1.])
+KINLTV_XMIN = np.array([-np.inf, -np.inf, -100., -2 * np.pi])
+KINLTV_XMAX = np.array([np.inf, np.inf, 100., 2 * np.pi])
+
+# structural nonzeros of get_dynamics_model's Ad = I + dt Ac and Bd = dt Bc (vehicle_models.py:273-292)
+DYN_MASK_A = np.eye(6, dtype=np.uint8)
+for _i, _j in [(0, 2), (0, 3), (0, 4), (1, 2), (1, 3), (1, 4), (2, 5), (3, 3), (3, 4), (3, 5), (4, 3), (4, 4),
+               (4, 5), (5, 3), (5, 4), (5, 5)]:
+    DYN_MASK_A[_i, _j] = 1
+DYN_MASK_B = np.zeros((6, 2), np.uint8)
+DYN_MASK_B[3:, :] = 1
 
 
 def _lateral_x0(rng, B):

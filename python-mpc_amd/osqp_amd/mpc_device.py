@@ -16,6 +16,10 @@ torch tensors on the device; nothing is copied to the host inside a step.
 KinematicMPC is the same loop on the kinematic bicycle, Control/MPC/mpc_incre_kine_func.py:
 simulate (:223-436), with its trajectory record and stop rule (mpcqp_kin_linearise_device,
 mpcqp_kin_reference_search_device, mpcqp_kin_shift_device).
+
+LTVLayout is the LTV MPC in the inputs themselves (mpc__, mpc_dynamics.mpc, mpc_'s corridor;
+mpcqp_ltv_*), and KinematicLTVMPC the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:
+main (:355-563) on it (mpcqp_kin_rollout_device, mpcqp_kin_ltv_shift_device).
 """
 from __future__ import annotations
 
@@ -48,13 +52,8 @@ class KinVehicle(C.Structure):
         super().__init__(l_f, l_r, dt)
 
 
-# structural nonzeros of get_dynamics_model's Ad = I + dt Ac and Bd = dt Bc (vehicle_models.py:273-292)
-DYN_MASK_A = np.eye(6, dtype=np.uint8)
-for _i, _j in [(0, 2), (0, 3), (0, 4), (1, 2), (1, 3), (1, 4), (2, 5), (3, 3), (3, 4), (3, 5), (4, 3), (4, 4),
-               (4, 5), (5, 3), (5, 4), (5, 5)]:
-    DYN_MASK_A[_i, _j] = 1
-DYN_MASK_B = np.zeros((6, 2), np.uint8)
-DYN_MASK_B[3:, :] = 1
+# structural nonzeros of get_dynamics_model's Ad and Bd (kept under these names here too)
+from .mpc import DYN_MASK_A, DYN_MASK_B  # noqa: E402
 
 
 def _bind():
@@ -80,6 +79,14 @@ def _bind():
                                              vp]
     L.mpcqp_kin_reference_search_device.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, vp, d, vp, i32, vp]
     L.mpcqp_kin_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 11 + [i32, vp, vp]
+    L.mpcqp_ltv_layout_create.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, _P(vp)]
+    L.mpcqp_ltv_layout_dims.argtypes = [vp, _P(i32), _P(i32), _P(i32), _P(i32)]
+    L.mpcqp_ltv_layout_pattern.argtypes = [vp] * 9
+    L.mpcqp_ltv_assemble_device.argtypes = [vp, i64] + [vp] * 12
+    L.mpcqp_ltv_layout_free.argtypes = [vp]
+    L.mpcqp_ltv_layout_free.restype = None
+    L.mpcqp_kin_rollout_device.argtypes = [_P(KinVehicle), i64, i32, vp, vp, vp, vp, i32, vp]
+    L.mpcqp_kin_ltv_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 12 + [i32, vp, vp]
     L._mpc_bound = True
     return L
 
@@ -645,3 +652,219 @@ class KinematicMPC:
             if steps % check_every == 0 and bool(self.done.all().item()):
                 break
         return steps
+
+
+# ------------------------------------------------- LTV in the inputs themselves --
+class LTVLayout:
+    """The QP of mpc__ (Control/MPC/mpc_kinematics_pred_matrix.py:268-352), mpc
+    (mpc_dynamics.py:160-279) and mpc_ (mpc_kinematics.py:202-265) -- osqp_amd.mpc.ltv_qp --
+    for a batch sharing N, weights, bounds and the structural nonzeros of Ad / Bd: variables
+    (x_0..x_N, u_0..u_{N-1}), no u_prev augmentation.  ``pattern()`` gives the CSC templates,
+    ``assemble()`` the per-instance values on the device (mpcqp_ltv_*)."""
+
+    def __init__(self, N, Q, QN, R, xmin, xmax, umin, umax, maskA, maskB, device=0):
+        L = _bind()
+        Q = np.ascontiguousarray(np.asarray(sparse.csr_matrix(Q).todense(), np.float64))
+        QN = np.ascontiguousarray(np.asarray(sparse.csr_matrix(QN).todense(), np.float64))
+        R = np.ascontiguousarray(np.asarray(sparse.csr_matrix(R).todense(), np.float64))
+        self.N, self.nx, self.nu = int(N), Q.shape[0], R.shape[0]
+        arrs = [np.ascontiguousarray(np.asarray(a, np.float64).ravel()) for a in (xmin, xmax, umin, umax)]
+        mA = np.ascontiguousarray(np.asarray(maskA, np.uint8))
+        mB = np.ascontiguousarray(np.asarray(maskB, np.uint8))
+        if QN.shape != Q.shape or mA.shape != Q.shape or mB.shape != (self.nx, self.nu) or \
+                [a.size for a in arrs] != [self.nx, self.nx, self.nu, self.nu]:
+            raise ValueError("LTVLayout: Q, QN, maskA must be nx x nx, R nu x nu, maskB nx x nu, bounds nx / nu long")
+        h = C.c_void_p()
+        _check(L.mpcqp_ltv_layout_create(self.N, self.nx, self.nu, _np_ptr(Q), _np_ptr(QN), _np_ptr(R),
+                                         *(_np_ptr(a) for a in arrs), _np_ptr(mA), _np_ptr(mB), int(device),
+                                         C.byref(h)), "ltv_layout_create")
+        self._h = h.value
+        self._free = L.mpcqp_ltv_layout_free  # held: module globals may be gone at interpreter exit
+        n, m, nP, nA = (C.c_int32() for _ in range(4))
+        _check(L.mpcqp_ltv_layout_dims(self._h, C.byref(n), C.byref(m), C.byref(nP), C.byref(nA)), "dims")
+        self.n, self.m, self.nnzP, self.nnzA = n.value, m.value, nP.value, nA.value
+        self.device = int(device)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._free(h)
+
+    def pattern(self):
+        """(P, A, l_template, u_template): scipy CSC templates (P upper triangle with its
+        constant values; A with the constant entries and zeros at the stage entries) and
+        the box rows' bounds (clipped to +-1e30; equality rows 0)."""
+        n, m = self.n, self.m
+        Pp = np.zeros(n + 1, np.int32); Pi = np.zeros(self.nnzP, np.int32); Px = np.zeros(self.nnzP)
+        Ap = np.zeros(n + 1, np.int32); Ai = np.zeros(self.nnzA, np.int32); At = np.zeros(self.nnzA)
+        lt = np.zeros(m); ut = np.zeros(m)
+        _check(lib().mpcqp_ltv_layout_pattern(self._h, *(_np_ptr(a) for a in (Pp, Pi, Px, Ap, Ai, At, lt, ut))),
+               "pattern")
+        P = sparse.csc_matrix((Px, Pi, Pp), shape=(n, n))
+        A = sparse.csc_matrix((At, Ai, Ap), shape=(m, n))
+        return P, A, lt, ut
+
+    def assemble(self, Ad, Bd, gd, x0, Xr, xlo=None, xhi=None, out=None):
+        """Ad (B,N,nx,nx), Bd (B,N,nx,nu), gd (B,N,nx), x0 (B,nx), Xr (B,nx,N+1) and the optional
+        per-stage state bounds xlo / xhi (B,N+1,nx), all contiguous float64 device tensors
+        -> (Ax, q, l, u) in the layout's pattern order."""
+        import torch
+        B, N, nx, nu = Ad.shape[0], self.N, self.nx, self.nu
+        shapes = [(Ad, (B, N, nx, nx)), (Bd, (B, N, nx, nu)), (gd, (B, N, nx)), (x0, (B, nx)), (Xr, (B, nx, N + 1))]
+        shapes += [(t, (B, N + 1, nx)) for t in (xlo, xhi) if t is not None]
+        for t, shape in shapes:
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float64:
+                raise ValueError(f"assemble inputs must be contiguous float64 tensors; expected shape {shape}, "
+                                 f"got {tuple(t.shape)}")
+        if out is None:
+            kw = dict(dtype=torch.float64, device=Ad.device)
+            out = (torch.empty((B, self.nnzA), **kw), torch.empty((B, self.n), **kw),
+                   torch.empty((B, self.m), **kw), torch.empty((B, self.m), **kw))
+        Ax, q, l, u = out
+        for t, w in ((Ax, self.nnzA), (q, self.n), (l, self.m), (u, self.m)):
+            if tuple(t.shape) != (B, w) or not t.is_contiguous() or t.dtype != torch.float64:
+                raise ValueError("assemble outputs must be contiguous float64 (B, nnzA / n / m / m) tensors")
+        _check(lib().mpcqp_ltv_assemble_device(self._h, B, _p(Ad), _p(Bd), _p(gd), _p(x0), _p(Xr),
+                                               None if xlo is None else _p(xlo), None if xhi is None else _p(xhi),
+                                               _p(Ax), _p(q), _p(l), _p(u), _stream(torch, Ad.device)),
+               "ltv_assemble")
+        return out
+
+
+def rollout_kin(veh: KinVehicle, x0, u0, N):
+    """Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): x0 (B, 4), u0 (B, 2)
+    contiguous float64 device tensors -> pred_x (B, N+1, 4) by update_kinematics_model under
+    u0, pred_u (B, N+1, 2) = u0 in every stage (mpcqp_kin_rollout_device)."""
+    import torch
+    L = _bind()
+    B = x0.shape[0]
+    for t, w in ((x0, 4), (u0, 2)):
+        if tuple(t.shape) != (B, w) or not t.is_contiguous() or t.dtype != torch.float64:
+            raise ValueError("x0 must be (B, 4) and u0 (B, 2), contiguous float64")
+    kw = dict(dtype=torch.float64, device=x0.device)
+    pred_x = torch.empty((B, N + 1, 4), **kw); pred_u = torch.empty((B, N + 1, 2), **kw)
+    _check(L.mpcqp_kin_rollout_device(C.byref(veh), B, int(N), _p(x0), _p(u0), _p(pred_x), _p(pred_u),
+                                      x0.device.index or 0, _stream(torch, x0.device)), "kin_rollout")
+    return pred_x, pred_u
+
+
+class KinematicLTVMPC:
+    """B copies of mpc_kinematics_pred_matrix.main's closed loop (:355-563), every step on
+    the device.
+
+    State per vehicle: x = (X, Y, v, yaw), u = (steer, accel), the predicted horizon pred_x
+    (B, N+1, 4) and pred_u (B, N+1, 2).  x0 is (B, 4), u0 (B, 2) (main's own are (0, 0, 20, 0)
+    and (0, 0.01)).  ``step()`` = reference search (set speed 10, path yaw 0, :40-82) ->
+    linearisation of every predicted stage -> mpc__'s QP (LTVLayout) -> batched OSQP solve
+    -> skip rule, trajectory record, plant step and shift (mpcqp_kin_ltv_shift_device).
+
+    Skip rule (:480-484): a vehicle whose solve did not end `solved` (`solved inaccurate`
+    included) keeps x, u, pred_x, pred_u and its trajectory as they are, and its ``skipped``
+    count goes up; ``steps_taken`` counts the steps a vehicle executed.  A skipped vehicle of
+    a cold-solving loop meets the same QP again and stays skipped, as in the reference.
+
+    ``trajectories()`` gives (traj (B, traj_cap, 6), traj_len): columns x, y, v, yaw of the
+    state a step started from and the steer, accel it applied (plt_states / plt_actions),
+    one row per EXECUTED step, rows beyond traj_cap dropped.
+
+    Settings are the reference's (:347, warm_start=True, polish off).  The reference builds a
+    fresh solver object per step, so its warm_start never has anything to start from: every
+    solve here is cold.  ``shift_warm=True`` (an extension) starts each solve from the previous
+    step's solution shifted one stage (warm_shift)."""
+
+    SET_SPEED = 10.0  # reference_search's x_ref[2] (:62)
+
+    def __init__(self, x0, u0, path_x, path_y, N=100, veh: KinVehicle | None = None, device=0, traj_cap=0,
+                 shift_warm=False, **solver_settings):
+        import torch
+        from . import mpc
+        self.torch = torch
+        self.dev = torch.device("cuda", device)
+        self.veh = veh or KinVehicle()
+        self.N = int(N)
+        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
+        if x0.shape[1] != 4 or u0.shape != (x0.shape[0], 2):
+            raise ValueError("x0 must be (B, 4) and u0 (B, 2)")
+        self.B = x0.shape[0]
+        self.traj_cap = int(traj_cap)
+        self.layout = LTVLayout(self.N, mpc.KINLTV_Q, mpc.KINLTV_QN, mpc.KINLTV_R, mpc.KINLTV_XMIN, mpc.KINLTV_XMAX,
+                                mpc.KINLTV_UMIN, mpc.KINLTV_UMAX, mpc.KIN_MASK_A, mpc.KIN_MASK_B, device=device)
+        P, A, _, _ = self.layout.pattern()
+        settings = dict(verbose=False, polish=False, warm_start=True)   # mpc_kinematics_pred_matrix.py:347
+        settings.update(solver_settings)
+        settings.pop("verbose", None)
+        self.shift_warm = bool(shift_warm)
+        self.have_sol = False
+        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
+        self.path_x, self.path_y = (torch.as_tensor(np.ascontiguousarray(np.asarray(p, np.float64)), **kw).contiguous()
+                                    for p in (path_x, path_y))
+        if not (self.path_x.numel() == self.path_y.numel() >= 2):
+            raise ValueError("path_x, path_y must have one length, at least 2")
+        self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:63)
+        self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
+        self.x = torch.from_numpy(x0).to(**kw).contiguous()
+        self.u = torch.from_numpy(u0).to(**kw).contiguous()
+        n, m = self.layout.n, self.layout.m
+        self.sol = torch.empty((self.B, n), **kw)
+        self.y = torch.empty((self.B, m), **kw)
+        self.status = torch.empty(self.B, **ikw)
+        self.iters = torch.empty(self.B, **ikw)
+        self.skipped = torch.zeros(self.B, **ikw)
+        self.steps_taken = torch.zeros(self.B, **ikw)
+        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
+        self.traj_len = torch.zeros(self.B, **ikw)
+        self.last = None
+        # every kernel of a step runs on this stream, in order (see DynamicMPC)
+        self.stream = torch.cuda.Stream(self.dev)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            self.pred_x, self.pred_u = rollout_kin(self.veh, self.x, self.u, self.N)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+
+    def step(self):
+        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
+        Asynchronous: ordered after the caller's current stream, and the caller's stream
+        is ordered after the step."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            out = self._step()
+        caller.wait_stream(self.stream)
+        return out
+
+    def _step(self):
+        L = _bind()
+        torch = self.torch
+        N = self.N
+        Xr = reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred_x, self.veh.dt)
+        Ad, Bd, gd = linearise_kinematics(self.veh, self.pred_x[:, :N], self.pred_u[:, :N], self.dev.index or 0)
+        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, self.x, Xr)
+        st = _stream(torch, self.dev)  # self.stream
+        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
+        if self.shift_warm and self.have_sol:
+            xs, ys = warm_shift(N, 4, 2, self.sol, self.y)
+            self.solver.warm_start(xs, ys, stream=st)
+        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
+        self.have_sol = True
+        _check(L.mpcqp_kin_ltv_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(self.status),
+                                            _p(Ad), _p(Bd), _p(gd), _p(self.x), _p(self.u), _p(self.pred_x),
+                                            _p(self.pred_u), _p(self.skipped), _p(self.steps_taken), _p(self.traj),
+                                            self.traj_cap, _p(self.traj_len), st), "kin_ltv_shift")
+        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
+        return self.status, self.iters
+
+    def run(self, steps):
+        """`steps` calls of step(); returns the last (status, iters)."""
+        out = None
+        for _ in range(int(steps)):
+            out = self.step()
+        return out
+
+    def trajectories(self):
+        """(traj, traj_len) as host arrays: traj (B, traj_cap, 6) = x, y, v, yaw, steer, accel;
+        traj_len[b] rows of traj[b] are filled, one per executed step."""
+        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
