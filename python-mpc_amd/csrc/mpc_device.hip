@@ -2,20 +2,22 @@
 // (SURVEY.md §8f rows F1-F3): everything the reference does in Python between two
 // osqp solves of Control/MPC/mpc_dynamics.py:main, batched over B vehicles.
 //
-//   F2  k_linearise      Vehicle_Dynamics.get_dynamics_model   vehicle_models.py:52-340
-//   F1  k_incr_assemble  mpc_increment's QP values             mpc_dynamics.py:281-389
-//   F3  k_reference      reference_search / nearest_point       mpc_dynamics.py:30-90
-//       k_incr_shift     plant step + horizon shift              mpc_dynamics.py:578-617
-//                        (terminal state: update_dynamics_model  vehicle_models.py:343-477)
+//   F2  k_linearise<DynamicBicycle>   Vehicle_Dynamics.get_dynamics_model  vehicle_models.py:52-340
+//   F1  k_incr_assemble_A / _vec      mpc_increment's QP values            mpc_dynamics.py:281-389
+//   F3  k_reference<DynamicBicycle>   reference_search / nearest_point      mpc_dynamics.py:30-90
+//       k_incr_shift                  plant step + horizon shift             mpc_dynamics.py:578-617
+//                                     (terminal state: update_dynamics_model vehicle_models.py:343-477)
 // and the same loop of Control/MPC/mpc_incre_kine_func.py:simulate on the kinematic bicycle:
-//       k_kin_linearise  Vehicle_Kinematics.get_kinematics_model vehicle_models.py:835-863
-//       k_kin_reference  reference_search / nearest_point        mpc_incre_kine_func.py:28-81
-//       k_kin_shift      record, stop rule, plant step, shift    mpc_incre_kine_func.py:382-428
-// and the LTV MPC in the inputs themselves (mpcqp_ltv_layout), with the closed loop of
-// Control/MPC/mpc_kinematics_pred_matrix.py:main:
-//       k_ltv_assemble_vec  mpc__ / mpc / mpc_'s q, l, u           mpc_kinematics_pred_matrix.py:268-352
-//       k_kin_rollout       initial horizon (nonlinear Euler)      :405-419
-//       k_kin_ltv_shift     skip rule, record, plant step, shift   :479-563
+//       k_linearise<KinematicBicycle> Vehicle_Kinematics.get_kinematics_model vehicle_models.py:835-863
+//       k_reference<KinematicBicycle> reference_search / nearest_point        mpc_incre_kine_func.py:28-81
+//       k_kin_shift                   record, stop rule, plant step, shift    mpc_incre_kine_func.py:382-428
+// and the LTV MPC in the inputs themselves (mpcqp_ltv_layout: the same layout with nxa = nx, the
+// same two assembly kernels), with the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:main:
+//       k_kin_rollout                 initial horizon (nonlinear Euler)       :405-419
+//       k_kin_ltv_shift               skip rule, record, plant step, shift    :479-563
+// The two bicycles are model structs (DynamicBicycle, KinematicBicycle) over which the
+// linearisation and the reference walk are written once; the three shift kernels share the plant
+// step, the trajectory append and kin_update, and keep their own shift and terminal-state rules.
 //
 // One thread per (vehicle, stage) for the linearisation and per vehicle for the
 // sequential parts (reference search walks the path, the shift reorders the
@@ -65,6 +67,7 @@ static VehicleK vehicle_constants(const mpcqp_vehicle& v) {
     }
     return k;
 }
+static const mpcqp_kin_vehicle& vehicle_constants(const mpcqp_kin_vehicle& v) { return v; }  // nothing derived
 
 __device__ __forceinline__ double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
 
@@ -170,16 +173,6 @@ __device__ void linearise_one(const VehicleK& k, const double* xin, const double
     }
 }
 
-__global__ __launch_bounds__(256) void k_linearise(VehicleK k, long B, int N, const double* __restrict__ x, long x_sb,
-                                                   long x_sk, const double* __restrict__ u, long u_sb, long u_sk,
-                                                   double* __restrict__ Ad, double* __restrict__ Bd,
-                                                   double* __restrict__ gd) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * N) return;
-    const long b = t / N, s = t - b * N;
-    linearise_one(k, x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * 36, Bd + t * 12, gd + t * 6);
-}
-
 // update_dynamics_model (vehicle_models.py:343-477): one explicit-Euler step of the
 // nonlinear model from the guarded state
 __device__ void euler_step(const VehicleK& k, const double* xin, const double* uin, double* xn) {
@@ -197,8 +190,8 @@ __device__ void euler_step(const VehicleK& k, const double* xin, const double* u
 // Vehicle_Kinematics.get_kinematics_model (vehicle_models.py:835-863) for one (x, u):
 // x = (X, Y, v, yaw), u = (steer, accel); the model is already discrete (Ad = A, Bd = B,
 // gd = C of the reference).  Every entry of the 4x4 / 4x2 / 4 outputs is written.
-__device__ void kin_linearise_one(const mpcqp_kin_vehicle& k, const double* x, const double* u,
-                                  double* __restrict__ Ad, double* __restrict__ Bd, double* __restrict__ gd) {
+__device__ void linearise_one(const mpcqp_kin_vehicle& k, const double* x, const double* u,
+                              double* __restrict__ Ad, double* __restrict__ Bd, double* __restrict__ gd) {
     const double v = x[2], yaw = x[3], st = u[0];
     const double dt = k.dt, wb = k.l_f + k.l_r;
     const double cy = cos(yaw), sy = sin(yaw), cs = cos(st);
@@ -218,15 +211,64 @@ __device__ void kin_linearise_one(const mpcqp_kin_vehicle& k, const double* x, c
     gd[3] = -dt * v * st / (wb * (cs * cs));
 }
 
-__global__ __launch_bounds__(256) void k_kin_linearise(mpcqp_kin_vehicle k, long B, int N,
-                                                       const double* __restrict__ x, long x_sb, long x_sk,
-                                                       const double* __restrict__ u, long u_sb, long u_sk,
-                                                       double* __restrict__ Ad, double* __restrict__ Bd,
-                                                       double* __restrict__ gd) {
+// update_kinematics_model (vehicle_models.py:866-883): the reference updates in place, so v
+// advances before yaw reads it.  xn may alias x.
+__device__ __forceinline__ void kin_update(const mpcqp_kin_vehicle& k, const double* x, const double* u,
+                                           double* xn) {
+    const double X = x[0], Y = x[1], v = x[2], yaw = x[3];
+    const double v1 = v + u[1] * k.dt;
+    xn[0] = X + v * cos(yaw) * k.dt;
+    xn[1] = Y + v * sin(yaw) * k.dt;
+    xn[2] = v1;
+    xn[3] = yaw + v1 / (k.l_f + k.l_r) * tan(u[0]) * k.dt;
+}
+
+// -------------------------------------------------------------------- models --
+// What differs between the two bicycles where a kernel is written once over the model: the
+// state width, the constants (which select the linearise_one overload), the state that holds
+// the speed, and one column of the reference Xr (rows at `stride` = N+1) for the path index
+// `ind`.  path_yaw and set_speed are the kinematic reference's own inputs (null for the
+// dynamic one).
+struct DynamicBicycle {  // x = (X, Y, yaw, vx, vy, r)
+    static constexpr int NX = 6, SPEED = 3;
+    using K = VehicleK;
+    // (path point, yaw 0, vx 10, vy 0, r 0)   (mpc_dynamics.py:44-90)
+    static __device__ void reference_column(double* Xc, int stride, double px, double py, const double*, int,
+                                            const double*, long) {
+        Xc[0 * stride] = px;
+        Xc[1 * stride] = py;
+        Xc[2 * stride] = 0.0;
+        Xc[3 * stride] = 10.0;
+        Xc[4 * stride] = 0.0;
+        Xc[5 * stride] = 0.0;
+    }
+};
+
+struct KinematicBicycle {  // x = (X, Y, v, yaw)
+    static constexpr int NX = 4, SPEED = 2;
+    using K = mpcqp_kin_vehicle;  // its constants are the C ABI's struct itself
+    // (path x, path y, set_speed[b], path_yaw[ind])   (mpc_incre_kine_func.py:42-81)
+    static __device__ void reference_column(double* Xc, int stride, double px, double py, const double* path_yaw,
+                                            int ind, const double* set_speed, long b) {
+        Xc[0 * stride] = px;
+        Xc[1 * stride] = py;
+        Xc[2 * stride] = set_speed[b];
+        Xc[3 * stride] = path_yaw[ind];
+    }
+};
+
+// one thread per (vehicle, stage); x, u: any strides with a contiguous last axis
+template <class M>
+__global__ __launch_bounds__(256) void k_linearise(typename M::K k, long B, int N, const double* __restrict__ x,
+                                                   long x_sb, long x_sk, const double* __restrict__ u, long u_sb,
+                                                   long u_sk, double* __restrict__ Ad, double* __restrict__ Bd,
+                                                   double* __restrict__ gd) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * N) return;
     const long b = t / N, s = t - b * N;
-    kin_linearise_one(k, x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * 16, Bd + t * 8, gd + t * 4);
+    constexpr int nx = M::NX, nu = 2;
+    linearise_one(k, x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * (nx * nx), Bd + t * (nx * nu),
+                  gd + t * nx);  // the overload of M::K
 }
 
 // ------------------------------------------------------- incremental QP layout --
@@ -239,12 +281,19 @@ __global__ __launch_bounds__(256) void k_kin_linearise(mpcqp_kin_vehicle k, long
 // QP is the same -- an explicit zero contributes nothing to OSQP's arithmetic).
 // Ax source codes: >= 0 -> Ad entry (stage * nx*nx + i*nx + j); -1 - c -> Bd entry
 // c = stage * nx*nu + i*nu + j; kConst -> the template value.
+//
+// With nxa = nx the same layout is the direct-input LTV QP of mpc__
+// (mpc_kinematics_pred_matrix.py:268-352), mpc (mpc_dynamics.py:160-279) and mpc_
+// (mpc_kinematics.py:202-265): variables (x_0 .. x_N, u_0 .. u_{N-1}), no augmentation,
+//   A = [ Aeq ; I ],  Aeq = [ -I + subdiag(Ad_k) | Bd_k shifted one block down ].
 constexpr int kConstSrc = INT32_MIN;
 
 struct IncrLayout {
     int N = 0, nx = 0, nu = 0, nxa = 0, n = 0, m = 0, dev = 0;
     std::vector<int> Pp, Pi, Ap, Ai, asrc;
-    std::vector<double> Px, Atpl, ltpl, utpl, Qt, QNt;  // Qt / QNt: (Q C)' rows i < nx (nx x nx, [i][j] = Q[j][i])
+    // Qt: [2][nx*nx], stage then terminal: the rows i < nx of (Q C)' ([i][j] = Q[j][i]) for the
+    // augmented layout, Q itself for nxa = nx (q = -Q Xr_k)
+    std::vector<double> Px, Atpl, ltpl, utpl, Qt;
     int* d_asrc = nullptr;
     double *d_Atpl = nullptr, *d_ltpl = nullptr, *d_utpl = nullptr, *d_Qt = nullptr;
 };
@@ -269,84 +318,132 @@ __global__ __launch_bounds__(256) void k_incr_assemble_A(IncrK L, long B, const 
     Ax[t] = v;
 }
 
-// q, l, u of one vehicle per thread
+// q, l, u of one vehicle per thread, for either layout (nxa >= nx):
+//   q = [ -W Xr_k (k < N) ; -WN Xr_N ; 0 ],  W = L.Qt rows i < nx, augmented rows -0.0   (:313-319)
+//   leq = ueq = [ -x~_0 ; -g~_k ],  g~_k = [gd_k; 0]   (:371-378); inequality rows: the template,
+//   but for the state rows where xlo / xhi (may be null; (B, N+1, nxa)) give per-stage bounds
+//   (mpc_'s corridor), clipped like the template.
 __global__ __launch_bounds__(128) void k_incr_assemble_vec(IncrK L, long B, const double* __restrict__ gd,
                                                            const double* __restrict__ xt0,
-                                                           const double* __restrict__ Xr, double* __restrict__ q,
+                                                           const double* __restrict__ Xr,
+                                                           const double* __restrict__ xlo,
+                                                           const double* __restrict__ xhi, double* __restrict__ q,
                                                            double* __restrict__ l, double* __restrict__ u) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int N = L.N, nx = L.nx, nxa = L.nxa, n = L.n, m = L.m;
-    // q = [ -(Q C)' Xr_k  (k < N) ; -(QN C)' Xr_N ; 0 ]   (:313-319)
+    const double INF = 1e30;
     double* qb = q + b * n;
     const double* Xb = Xr + b * (long)nx * (N + 1);  // Xr[j][k] at j*(N+1)+k
     for (int k = 0; k <= N; ++k) {
         const double* W = L.Qt + (k == N ? nx * nx : 0);
-        for (int i = 0; i < nxa; ++i) {
+        for (int i = 0; i < nx; ++i) {
             double acc = 0.0;
-            if (i < nx)
-                for (int j = 0; j < nx; ++j) acc += W[i * nx + j] * Xb[j * (N + 1) + k];
+            for (int j = 0; j < nx; ++j) acc += W[i * nx + j] * Xb[j * (N + 1) + k];
             qb[k * nxa + i] = -acc;
         }
+        for (int i = nx; i < nxa; ++i) qb[k * nxa + i] = -0.0;  // the empty sum, negated
     }
-    for (int i = (N + 1) * nxa; i < n; ++i) qb[i] = 0.0;
-    // leq = ueq = [ -x~_0 ; -g~_k ],  g~_k = [gd_k; 0]   (:371-378); inequality rows: template
+    const int ns = (N + 1) * nxa;  // state rows of the box start at ns, input rows at 2 ns
+    for (int i = ns; i < n; ++i) qb[i] = 0.0;
     double* lb = l + b * m;
     double* ub = u + b * m;
     for (int i = 0; i < nxa; ++i) lb[i] = ub[i] = -xt0[b * nxa + i];
     const double* gb = gd + b * (long)N * nx;
-    for (int k = 0; k < N; ++k)
-        for (int i = 0; i < nxa; ++i) {
-            const double v = i < nx ? -gb[k * nx + i] : -0.0;
-            lb[(k + 1) * nxa + i] = ub[(k + 1) * nxa + i] = v;
-        }
-    for (int r = (N + 1) * nxa; r < m; ++r) {
+    for (int k = 0; k < N; ++k) {
+        for (int i = 0; i < nx; ++i) lb[(k + 1) * nxa + i] = ub[(k + 1) * nxa + i] = -gb[k * nx + i];
+        for (int i = nx; i < nxa; ++i) lb[(k + 1) * nxa + i] = ub[(k + 1) * nxa + i] = -0.0;
+    }
+    for (int r = ns; r < m; ++r) {
         lb[r] = L.ltpl[r];
         ub[r] = L.utpl[r];
     }
+    // per-stage state bounds over the template's (one plain copy loop above: the closed loops,
+    // which give none, spend half their data-path time in this kernel)
+    if (xlo)
+        for (int i = 0; i < ns; ++i) lb[ns + i] = fmin(fmax(xlo[b * (long)ns + i], -INF), INF);
+    if (xhi)
+        for (int i = 0; i < ns; ++i) ub[ns + i] = fmin(fmax(xhi[b * (long)ns + i], -INF), INF);
 }
 
 // ---------------------------------------------------------- receding horizon --
-// reference_search (mpc_dynamics.py:44-90) with nearest_point (:30-41, look_ind = 1):
-// Xr[:, i] = (path point, yaw 0, vx 10, vy 0, r 0) where the path index walks forward
-// while the travelled distance sum |vx_i| dt exceeds the path length covered.
-// pred: (B, N+1, nxa) stage-major;  Xr: (B, 6, N+1).
-__global__ __launch_bounds__(128) void k_reference(long B, int N, int nxa, int np, const double* __restrict__ px,
-                                                   const double* __restrict__ py, const double* __restrict__ pred,
-                                                   double dt, double* __restrict__ Xr) {
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const double* pb = pred + b * (long)(N + 1) * nxa;
-    const double X0 = pb[0], Y0 = pb[1];
-    double min_d = INFINITY;
-    int ind = -1;
-    for (int i = np - 1; i >= 0; --i) {  // reversed(range(len(path_x))), strict <
-        const double d = sqrt((px[i] - X0) * (px[i] - X0) + (py[i] - Y0) * (py[i] - Y0));
-        if (d < min_d) { min_d = d; ind = i; }
-    }
-    // look_ind = 1.  The reference reads path[ind + 1] from here on and raises
-    // IndexError once ind reaches the last point; the kernel holds the start of the
-    // last segment (np - 2) instead.
-    ind = min(ind + 1, np - 2);
-    auto seg = [&](int i) {
+// nearest_point (look_ind = 1) and the walk of reference_search along the path, as both
+// scripts have them (mpc_dynamics.py:30-90, mpc_incre_kine_func.py:28-81): the path index
+// steps forward while the travelled distance sum |v_i| dt exceeds the path length covered.
+struct PathWalk {
+    const double *px, *py;
+    int np, ind;
+    double path_d, cumul = 0.0;
+
+    __device__ double seg(int i) const {
         return sqrt((px[i + 1] - px[i]) * (px[i + 1] - px[i]) + (py[i + 1] - py[i]) * (py[i + 1] - py[i]));
-    };
-    double path_d = seg(ind), cumul = 0.0;
-    double* Xb = Xr + b * 6L * (N + 1);
-    for (int i = 0; i <= N; ++i) {
-        cumul += fabs(pb[i * nxa + 3]) * dt;
+    }
+    __device__ PathWalk(const double* px_, const double* py_, int np_, double X0, double Y0)
+        : px(px_), py(py_), np(np_), ind(-1) {
+        double min_d = INFINITY;
+        for (int i = np - 1; i >= 0; --i) {  // reversed(range(len(path_x))), strict <
+            const double d = sqrt((px[i] - X0) * (px[i] - X0) + (py[i] - Y0) * (py[i] - Y0));
+            if (d < min_d) { min_d = d; ind = i; }
+        }
+        // look_ind = 1.  The reference reads path[ind + 1] from here on and raises
+        // IndexError once ind reaches the last point; the walk holds the start of the
+        // last segment (np - 2) instead.  A NaN position leaves ind = -1: 0 here (np >= 2).
+        ind = min(ind + 1, np - 2);
+        path_d = seg(ind);
+    }
+    // the path index after travelling at `speed` for dt more
+    __device__ int advance(double speed, double dt) {
+        cumul += fabs(speed) * dt;
         while (cumul >= path_d && ind + 1 < np - 1) {
             ind += 1;
             path_d += seg(ind);
         }
-        const int ic = ind;
-        Xb[0 * (N + 1) + i] = px[ic];
-        Xb[1 * (N + 1) + i] = py[ic];
-        Xb[2 * (N + 1) + i] = 0.0;
-        Xb[3 * (N + 1) + i] = 10.0;
-        Xb[4 * (N + 1) + i] = 0.0;
-        Xb[5 * (N + 1) + i] = 0.0;
+        return ind;
     }
+};
+
+// reference_search per vehicle: pred (B, N+1, nxa) stage-major with the speed in state
+// M::SPEED;  Xr (B, M::NX, N+1), its columns by M::reference_column.
+template <class M>
+__global__ __launch_bounds__(128) void k_reference(long B, int N, int nxa, int np, const double* __restrict__ px,
+                                                   const double* __restrict__ py, const double* __restrict__ pyaw,
+                                                   const double* __restrict__ set_speed,
+                                                   const double* __restrict__ pred, double dt,
+                                                   double* __restrict__ Xr) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double* pb = pred + b * (long)(N + 1) * nxa;
+    PathWalk walk(px, py, np, pb[0], pb[1]);
+    double* Xb = Xr + b * (long)M::NX * (N + 1);
+    for (int i = 0; i <= N; ++i) {
+        const int ind = walk.advance(pb[i * nxa + M::SPEED], dt);
+        M::reference_column(Xb + i, N + 1, px[ind], py[ind], pyaw, ind, set_speed, b);
+    }
+}
+
+// x_next = (A0 x + B0 u) + g0 of the linearised stage-0 model, in the reference's association.
+// Inlined, so nx / nu are compile-time where the caller's are (the kinematic kernels) and run-time
+// where they come from the layout (k_incr_shift; unrolled for nx = 6 the compiler orders the fma
+// operands differently, and a state that is already NaN comes out with another NaN's sign).
+__device__ __forceinline__ void plant_step(int nx, int nu, const double* A0, const double* B0, const double* g0,
+                                           const double* x, const double* u, double* xnext) {
+    for (int i = 0; i < nx; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * x[j];
+        double bu = 0.0;
+        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * u[j];
+        xnext[i] = (acc + bu) + g0[i];
+    }
+}
+
+// The next free row (`width` doubles) of vehicle b's trajectory record, counted in
+// traj_len[b]; null when recording is off (traj_cap 0) or the record is full.
+__device__ __forceinline__ double* traj_append(double* traj, int traj_cap, int* traj_len, long b, int width) {
+    if (traj_cap <= 0) return nullptr;
+    const int len = traj_len[b];
+    if (len < 0 || len >= traj_cap) return nullptr;
+    traj_len[b] = len + 1;
+    return traj + (b * (long)traj_cap + len) * width;
 }
 
 // One-stage shift of a vector made of `groups` blocks of N+1 stages of width nxa followed
@@ -380,24 +477,15 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
                                                     double* __restrict__ pred, double* __restrict__ pdu) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, n = L.n;
+    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, n = L.n;  // nx 6, nu 2: the entry point's check
     const double* s = sol + b * n;
     double* pb = pred + b * (long)(N + 1) * nxa;
     double* db = pdu + b * (long)(N + 1) * nu;
-    const double* A0 = Ad + b * (long)N * nx * nx;  // stage 0
-    const double* B0 = Bd + b * (long)N * nx * nu;
-    const double* g0 = gd + b * (long)N * nx;
     double* xb = xt + b * nxa;
-    // plant step (:581-586)
+    // plant step (:581-586), stage 0 of the linearisation
     double xnext[8], uu[8];
     for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + s[(N + 1) * nxa + j];
-    for (int i = 0; i < nx; ++i) {
-        double acc = 0.0;
-        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * xb[j];
-        double bu = 0.0;
-        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * uu[j];
-        xnext[i] = (acc + bu) + g0[i];
-    }
+    plant_step(nx, nu, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, uu, xnext);
     for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
     for (int j = 0; j < nu; ++j) xb[nx + j] = uu[j];
     // shift (:589-610) from the solution (the reference's temp copies are the solution)
@@ -417,46 +505,6 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
     for (int i = 0; i < nx; ++i) pb[N * nxa + i] = xe[i];
     for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = pb[(N - 1) * nxa + nx + j];
     for (int j = 0; j < nu; ++j) db[N * nu + j] = db[(N - 1) * nu + j];
-}
-
-// reference_search of mpc_incre_kine_func.py (:42-81, nearest_point :28-40, look_ind = 1):
-// the walk of k_reference with the speed in state 2 and the reference rows
-// (path x, path y, set_speed[b], path_yaw[ind]);  Xr: (B, 4, N+1).
-__global__ __launch_bounds__(128) void k_kin_reference(long B, int N, int nxa, int np, const double* __restrict__ px,
-                                                       const double* __restrict__ py, const double* __restrict__ pyaw,
-                                                       const double* __restrict__ set_speed,
-                                                       const double* __restrict__ pred, double dt,
-                                                       double* __restrict__ Xr) {
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const double* pb = pred + b * (long)(N + 1) * nxa;
-    const double X0 = pb[0], Y0 = pb[1];
-    double min_d = INFINITY;
-    int ind = -1;
-    for (int i = np - 1; i >= 0; --i) {  // reversed(range(len(path_x))), strict <
-        const double d = sqrt((px[i] - X0) * (px[i] - X0) + (py[i] - Y0) * (py[i] - Y0));
-        if (d < min_d) { min_d = d; ind = i; }
-    }
-    // look_ind = 1; the index holds the start of the last segment where the reference
-    // raises IndexError (as k_reference does).  A NaN position leaves ind = -1: 0 below.
-    ind = max(min(ind + 1, np - 2), 0);
-    auto seg = [&](int i) {
-        return sqrt((px[i + 1] - px[i]) * (px[i + 1] - px[i]) + (py[i + 1] - py[i]) * (py[i + 1] - py[i]));
-    };
-    double path_d = seg(ind), cumul = 0.0;
-    const double vref = set_speed[b];
-    double* Xb = Xr + b * 4L * (N + 1);
-    for (int i = 0; i <= N; ++i) {
-        cumul += fabs(pb[i * nxa + 2]) * dt;
-        while (cumul >= path_d && ind + 1 < np - 1) {
-            ind += 1;
-            path_d += seg(ind);
-        }
-        Xb[0 * (N + 1) + i] = px[ind];
-        Xb[1 * (N + 1) + i] = py[ind];
-        Xb[2 * (N + 1) + i] = vref;
-        Xb[3 * (N + 1) + i] = pyaw[ind];
-    }
 }
 
 // Tail of mpc_incre_kine_func.simulate's loop (:382-428), per vehicle, in the reference's
@@ -486,13 +534,8 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
     double* db = pdu + b * (long)(N + 1) * nu;
     double* xb = xt + b * nxa;
     // trajectory point: the state the step started from and the first steer increment
-    if (traj_cap > 0) {
-        const int len = traj_len[b];
-        if (len >= 0 && len < traj_cap) {
-            double* tr = traj + (b * (long)traj_cap + len) * 4;
-            tr[0] = xb[0]; tr[1] = xb[1]; tr[2] = xb[3]; tr[3] = D[0];
-            traj_len[b] = len + 1;
-        }
+    if (double* tr = traj_append(traj, traj_cap, traj_len, b, 4)) {
+        tr[0] = xb[0]; tr[1] = xb[1]; tr[2] = xb[3]; tr[3] = D[0];
     }
     // stop rule: the reference breaks here, leaving pred_x~ / pred_du as mpc_increment unpacked them
     const double ex = Xr[b * (long)nx * (N + 1)] - xb[0], ey = Xr[b * (long)nx * (N + 1) + (N + 1)] - xb[1];
@@ -507,19 +550,10 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
             return;
         }
     }
-    // plant step
-    const double* A0 = Ad + b * (long)N * nx * nx;  // stage 0
-    const double* B0 = Bd + b * (long)N * nx * nu;
-    const double* g0 = gd + b * (long)N * nx;
+    // plant step, stage 0 of the linearisation
     double xnext[nx], uu[nu];
     for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + D[j];
-    for (int i = 0; i < nx; ++i) {
-        double acc = 0.0;
-        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * xb[j];
-        double bu = 0.0;
-        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * uu[j];
-        xnext[i] = (acc + bu) + g0[i];
-    }
+    plant_step(nx, nu, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, uu, xnext);
     for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
     for (int j = 0; j < nu; ++j) xb[nx + j] = uu[j];
     // shift, from the solution
@@ -531,70 +565,8 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
     for (int j = 0; j < nu; ++j) db[(N - 1) * nu + j] = db[N * nu + j] = D[(N - 1) * nu + j];
     // terminal state: update_kinematics_model on (x_N, u_N) of the solution, v first
     const double* sN = s + N * nxa;
-    const double wb = vk.l_f + vk.l_r;
-    const double v1 = sN[2] + sN[5] * vk.dt;
-    pb[N * nxa + 0] = sN[0] + sN[2] * cos(sN[3]) * vk.dt;
-    pb[N * nxa + 1] = sN[1] + sN[2] * sin(sN[3]) * vk.dt;
-    pb[N * nxa + 2] = v1;
-    pb[N * nxa + 3] = sN[3] + v1 / wb * tan(sN[4]) * vk.dt;
-    pb[N * nxa + 4] = sN[4];
-    pb[N * nxa + 5] = sN[5];
-}
-
-// ------------------------------------------------------ direct-input LTV layout --
-// The QP of mpc__ (mpc_kinematics_pred_matrix.py:268-352), mpc (mpc_dynamics.py:160-279) and
-// mpc_ (mpc_kinematics.py:202-265): variables (x_0 .. x_N, u_0 .. u_{N-1}), no augmentation,
-//   A = [ Aeq ; I ],  Aeq = [ -I + subdiag(Ad_k) | Bd_k shifted one block down ].
-// Held as an IncrLayout with nxa = nx, so the A values go through k_incr_assemble_A; Qt holds
-// Q and QN themselves (q = -Q Xr_k).  q, l, u of one vehicle per thread; xlo / xhi (may be
-// null) are the per-stage state bounds of mpc_'s corridor, (B, N+1, nx).
-__global__ __launch_bounds__(128) void k_ltv_assemble_vec(IncrK L, long B, const double* __restrict__ gd,
-                                                          const double* __restrict__ x0,
-                                                          const double* __restrict__ Xr,
-                                                          const double* __restrict__ xlo,
-                                                          const double* __restrict__ xhi, double* __restrict__ q,
-                                                          double* __restrict__ l, double* __restrict__ u) {
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int N = L.N, nx = L.nx, n = L.n, m = L.m;
-    const double INF = 1e30;
-    double* qb = q + b * n;
-    const double* Xb = Xr + b * (long)nx * (N + 1);  // Xr[j][k] at j*(N+1)+k
-    for (int k = 0; k <= N; ++k) {
-        const double* W = L.Qt + (k == N ? nx * nx : 0);
-        for (int i = 0; i < nx; ++i) {
-            double acc = 0.0;
-            for (int j = 0; j < nx; ++j) acc += W[i * nx + j] * Xb[j * (N + 1) + k];
-            qb[k * nx + i] = -acc;
-        }
-    }
-    for (int i = (N + 1) * nx; i < n; ++i) qb[i] = 0.0;
-    double* lb = l + b * m;
-    double* ub = u + b * m;
-    for (int i = 0; i < nx; ++i) lb[i] = ub[i] = -x0[b * nx + i];
-    const double* gb = gd + b * (long)N * nx;
-    for (int i = 0; i < N * nx; ++i) lb[nx + i] = ub[nx + i] = -gb[i];
-    const int ns = (N + 1) * nx;  // state rows of the box start at ns, input rows at 2 ns
-    for (int i = 0; i < ns; ++i) {
-        lb[ns + i] = xlo ? fmin(fmax(xlo[b * (long)ns + i], -INF), INF) : L.ltpl[ns + i];
-        ub[ns + i] = xhi ? fmin(fmax(xhi[b * (long)ns + i], -INF), INF) : L.utpl[ns + i];
-    }
-    for (int r = 2 * ns; r < m; ++r) {
-        lb[r] = L.ltpl[r];
-        ub[r] = L.utpl[r];
-    }
-}
-
-// update_kinematics_model (vehicle_models.py:866-883): the reference updates in place, so v
-// advances before yaw reads it.  xn may alias x.
-__device__ __forceinline__ void kin_update(const mpcqp_kin_vehicle& k, const double* x, const double* u,
-                                           double* xn) {
-    const double X = x[0], Y = x[1], v = x[2], yaw = x[3];
-    const double v1 = v + u[1] * k.dt;
-    xn[0] = X + v * cos(yaw) * k.dt;
-    xn[1] = Y + v * sin(yaw) * k.dt;
-    xn[2] = v1;
-    xn[3] = yaw + v1 / (k.l_f + k.l_r) * tan(u[0]) * k.dt;
+    kin_update(vk, sN, sN + nx, pb + N * nxa);
+    for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = sN[nx + j];
 }
 
 // Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): u0 in every stage, the
@@ -644,27 +616,13 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     double* px = pred_x + b * (long)(N + 1) * nx;
     double* pu = pred_u + b * (long)(N + 1) * nu;
     // plt_states[:, i], plt_actions[:, i]: the state the step started from, the control applied
-    if (traj_cap > 0) {
-        const int len = traj_len[b];
-        if (len >= 0 && len < traj_cap) {
-            double* tr = traj + (b * (long)traj_cap + len) * 6;
-            for (int i = 0; i < nx; ++i) tr[i] = xb[i];
-            tr[4] = U[0]; tr[5] = U[1];
-            traj_len[b] = len + 1;
-        }
+    if (double* tr = traj_append(traj, traj_cap, traj_len, b, 6)) {
+        for (int i = 0; i < nx; ++i) tr[i] = xb[i];
+        tr[4] = U[0]; tr[5] = U[1];
     }
-    // plant step (:534-541)
-    const double* A0 = Ad + b * (long)N * nx * nx;  // stage 0
-    const double* B0 = Bd + b * (long)N * nx * nu;
-    const double* g0 = gd + b * (long)N * nx;
+    // plant step (:534-541), stage 0 of the linearisation
     double xnext[nx];
-    for (int i = 0; i < nx; ++i) {
-        double acc = 0.0;
-        for (int j = 0; j < nx; ++j) acc += A0[i * nx + j] * xb[j];
-        double bu = 0.0;
-        for (int j = 0; j < nu; ++j) bu += B0[i * nu + j] * U[j];
-        xnext[i] = (acc + bu) + g0[i];
-    }
+    plant_step(nx, nu, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, U, xnext);
     for (int i = 0; i < nx; ++i) xb[i] = px[i] = xnext[i];
     for (int j = 0; j < nu; ++j) ub[j] = U[j];
     // shift (:543-563), from the solution
@@ -818,7 +776,122 @@ void layout_free_device(IncrLayout* L) {
         if (p) (void)hipFree(p);
 }
 
+// P, the A pattern with its source codes, and Qt of a layout with nxa >= nx state columns per
+// stage (:336-369, :381-382; mpc_kinematics_pred_matrix.py:293-309, :326, :341 for nxa = nx).
+// The bounds (set_box) are the caller's.
+void build_layout(IncrLayout& L, int N, int nx, int nu, int nxa, int device, const double* Q, const double* QN,
+                  const double* R, const uint8_t* maskA, const uint8_t* maskB, bool transpose_Q) {
+    const int ns = (N + 1) * nxa, n = ns + N * nu, m = ns + n;
+    L.N = N; L.nx = nx; L.nu = nu; L.nxa = nxa; L.n = n; L.m = m; L.dev = device;
+    build_P(L, Q, QN, R);
+    L.Ap.assign(n + 1, 0);
+    auto push = [&](int row, int src, double tpl) {
+        L.Ai.push_back(row); L.asrc.push_back(src); L.Atpl.push_back(tpl);
+    };
+    for (int c = 0; c < n; ++c) {
+        if (c < ns) {
+            const int k = c / nxa, j = c % nxa;
+            push(c, kConstSrc, -1.0);  // -I
+            if (k < N)                 // A~_k in rows of stage k+1
+                for (int i = 0; i < nxa; ++i) {
+                    const int row = (k + 1) * nxa + i;
+                    if (i < nx && j < nx) {
+                        if (maskA[i * nx + j]) push(row, k * nx * nx + i * nx + j, 0.0);
+                    } else if (i < nx) {
+                        if (maskB[i * nu + (j - nx)]) push(row, -1 - (k * nx * nu + i * nu + (j - nx)), 0.0);
+                    } else if (i == j) {
+                        push(row, kConstSrc, 1.0);
+                    }
+                }
+        } else {
+            const int c0 = c - ns, k = c0 / nu, j = c0 % nu;  // du_k / u_k: B~_k in rows of stage k+1
+            for (int i = 0; i < nxa; ++i) {
+                const int row = (k + 1) * nxa + i;
+                if (i < nx) {
+                    if (maskB[i * nu + j]) push(row, -1 - (k * nx * nu + i * nu + j), 0.0);
+                } else if (i - nx == j) {
+                    push(row, kConstSrc, 1.0);
+                }
+            }
+        }
+        push(ns + c, kConstSrc, 1.0);  // A_ineq = I
+        L.Ap[c + 1] = (int)L.Ai.size();
+    }
+    L.Qt.assign(2 * nx * nx, 0.0);
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < nx; ++j) {
+            const int src = transpose_Q ? j * nx + i : i * nx + j;
+            L.Qt[i * nx + j] = Q[src];
+            L.Qt[nx * nx + i * nx + j] = QN[src];
+        }
+}
+
+// Inequality-row bounds: xlo / xhi (nxa long) in every stage, ulo / uhi in every input stage,
+// each through the caller's clipping (the osqp wrapper clips +-inf to +-OSQP_INFTY); equality rows 0.
+constexpr double kInf = 1e30;
+template <class ClipLo, class ClipHi>
+void set_box(IncrLayout& L, const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+             ClipLo clip_lo, ClipHi clip_hi) {
+    const int N = L.N, nu = L.nu, nxa = L.nxa, ns = (N + 1) * nxa;
+    L.ltpl.assign(L.m, 0.0); L.utpl.assign(L.m, 0.0);
+    for (int k = 0; k <= N; ++k)
+        for (int i = 0; i < nxa; ++i) {
+            L.ltpl[ns + k * nxa + i] = clip_lo(xlo[i]);
+            L.utpl[ns + k * nxa + i] = clip_hi(xhi[i]);
+        }
+    for (int k = 0; k < N; ++k)
+        for (int j = 0; j < nu; ++j) {
+            L.ltpl[2 * ns + k * nu + j] = clip_lo(ulo[j]);
+            L.utpl[2 * ns + k * nu + j] = clip_hi(uhi[j]);
+        }
+}
+
 unsigned grid_of(long count, int block) { return (unsigned)((count + block - 1) / block); }
+
+// hipSetDevice, one launch of `count` threads in blocks of `block`, hipGetLastError
+template <class... P, class... A>
+int launch(int device, void* stream, long count, int block, void (*kernel)(P...), A... args) {
+    MHIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(kernel, dim3(grid_of(count, block)), dim3(block), 0, (hipStream_t)stream, (P)args...);
+    MHIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <class M, class V>
+int linearise_device(const char* what, const V* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                     int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
+                     double* dgd, int32_t device, void* stream) {
+    if (!veh || !dx || !du || !dAd || !dBd || !dgd || B < 0 || N < 1)
+        return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (B == 0) return 0;
+    return launch(device, stream, B * N, 256, k_linearise<M>, vehicle_constants(*veh), B, N, dx, x_sb, x_sk, du, u_sb,
+                  u_sk, dAd, dBd, dgd);
+}
+
+// dpath_yaw, dset_speed: the kinematic reference's (its entry point checks them), else null
+template <class M>
+int reference_device(const char* what, int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
+                     const double* dpath_y, const double* dpath_yaw, const double* dset_speed, const double* dpred,
+                     double dt, double* dXr, int32_t device, void* stream) {
+    if (!dpath_x || !dpath_y || !dpred || !dXr || B < 0 || N < 1 || nxa < 4 || npath < 2)
+        return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (B == 0) return 0;
+    return launch(device, stream, B, 128, k_reference<M>, B, N, nxa, npath, dpath_x, dpath_y, dpath_yaw, dset_speed,
+                  dpred, dt, dXr);
+}
+
+// dxlo, dxhi: per-stage state bounds (B, N+1, nxa), either may be null
+int assemble_device(const char* what, const IncrLayout* L, int64_t B, const double* dAd, const double* dBd,
+                    const double* dgd, const double* dx0, const double* dXr, const double* dxlo, const double* dxhi,
+                    double* dAx, double* dq, double* dl, double* du, void* stream) {
+    if (!L || !dAd || !dBd || !dgd || !dx0 || !dXr || !dAx || !dq || !dl || !du || B < 0)
+        return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<IncrLayout*>(L))) return e;
+    const IncrK k = incr_k(*L);
+    if (int e = launch(L->dev, stream, B * k.nnzA, 256, k_incr_assemble_A, k, B, dAd, dBd, dAx)) return e;
+    return launch(L->dev, stream, B, 128, k_incr_assemble_vec, k, B, dgd, dx0, dXr, dxlo, dxhi, dq, dl, du);
+}
 
 }  // namespace
 
@@ -827,15 +900,30 @@ extern "C" {
 int mpcqp_linearise_device(const mpcqp_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
                            int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
                            double* dgd, int32_t device, void* stream) {
-    if (!veh || !dx || !du || !dAd || !dBd || !dgd || B < 0 || N < 1)
-        return set_error(MPCQP_EINVAL, "linearise: bad arguments");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
-    const VehicleK k = vehicle_constants(*veh);
-    hipLaunchKernelGGL(k_linearise, dim3(grid_of(B * N, 256)), dim3(256), 0, (hipStream_t)stream, k, (long)B, (int)N,
-                       dx, (long)x_sb, (long)x_sk, du, (long)u_sb, (long)u_sk, dAd, dBd, dgd);
-    MHIPCHK(hipGetLastError());
-    return 0;
+    return linearise_device<DynamicBicycle>("linearise", veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dAd, dBd, dgd,
+                                            device, stream);
+}
+
+int mpcqp_kin_linearise_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                               int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
+                               double* dgd, int32_t device, void* stream) {
+    return linearise_device<KinematicBicycle>("kin_linearise", veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dAd, dBd,
+                                              dgd, device, stream);
+}
+
+int mpcqp_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
+                                  const double* dpath_y, const double* dpred, double dt, double* dXr, int32_t device,
+                                  void* stream) {
+    return reference_device<DynamicBicycle>("reference_search", B, N, nxa, npath, dpath_x, dpath_y, nullptr, nullptr,
+                                            dpred, dt, dXr, device, stream);
+}
+
+int mpcqp_kin_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
+                                      const double* dpath_y, const double* dpath_yaw, const double* dset_speed,
+                                      const double* dpred, double dt, double* dXr, int32_t device, void* stream) {
+    if (!dpath_yaw || !dset_speed) return set_error(MPCQP_EINVAL, "kin_reference_search: bad arguments");
+    return reference_device<KinematicBicycle>("kin_reference_search", B, N, nxa, npath, dpath_x, dpath_y, dpath_yaw,
+                                              dset_speed, dpred, dt, dXr, device, stream);
 }
 
 int mpcqp_incr_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q, const double* QN, const double* R,
@@ -851,64 +939,34 @@ int mpcqp_incr_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q,
         if (!(dumin[j] <= dumax[j])) return set_error(MPCQP_EINVAL, "incr_layout_create: dumin > dumax");
     *out = nullptr;
     auto L = std::make_unique<mpcqp_incr_layout>();
-    const int nxa = nx + nu, n = (N + 1) * nxa + N * nu, m = (N + 1) * nxa + n;
-    L->N = N; L->nx = nx; L->nu = nu; L->nxa = nxa; L->n = n; L->m = m; L->dev = device;
-    const double INF = 1e30;  // the osqp wrapper clips +-inf to +-OSQP_INFTY
-    build_P(*L, Q, QN, R);
-    // A by column (:336-369, :381-382)
-    L->Ap.assign(n + 1, 0);
-    auto push = [&](int row, int src, double tpl) {
-        L->Ai.push_back(row); L->asrc.push_back(src); L->Atpl.push_back(tpl);
-    };
-    for (int c = 0; c < n; ++c) {
-        if (c < (N + 1) * nxa) {
-            const int k = c / nxa, j = c % nxa;
-            push(k * nxa + j, kConstSrc, -1.0);  // -I
-            if (k < N)                           // A~_k in rows of stage k+1
-                for (int i = 0; i < nxa; ++i) {
-                    const int row = (k + 1) * nxa + i;
-                    if (i < nx && j < nx) {
-                        if (maskA[i * nx + j]) push(row, k * nx * nx + i * nx + j, 0.0);
-                    } else if (i < nx) {
-                        if (maskB[i * nu + (j - nx)]) push(row, -1 - (k * nx * nu + i * nu + (j - nx)), 0.0);
-                    } else if (i == j) {
-                        push(row, kConstSrc, 1.0);
-                    }
-                }
-        } else {
-            const int c0 = c - (N + 1) * nxa, k = c0 / nu, j = c0 % nu;  // du_k: B~_k in rows of stage k+1
-            for (int i = 0; i < nxa; ++i) {
-                const int row = (k + 1) * nxa + i;
-                if (i < nx) {
-                    if (maskB[i * nu + j]) push(row, -1 - (k * nx * nu + i * nu + j), 0.0);
-                } else if (i - nx == j) {
-                    push(row, kConstSrc, 1.0);
-                }
-            }
-        }
-        push((N + 1) * nxa + c, kConstSrc, 1.0);  // A_ineq = I
-        L->Ap[c + 1] = (int)L->Ai.size();
-    }
-    // inequality bounds (:383-384), clipped like the osqp wrapper
-    L->ltpl.assign(m, 0.0); L->utpl.assign(m, 0.0);
-    for (int k = 0; k <= N; ++k)
-        for (int i = 0; i < nxa; ++i) {
-            L->ltpl[(N + 1) * nxa + k * nxa + i] = std::max(xmin_t[i], -INF);
-            L->utpl[(N + 1) * nxa + k * nxa + i] = std::min(xmax_t[i], INF);
-        }
-    for (int k = 0; k < N; ++k)
-        for (int j = 0; j < nu; ++j) {
-            L->ltpl[(N + 1) * nxa + (N + 1) * nxa + k * nu + j] = std::max(dumin[j], -INF);
-            L->utpl[(N + 1) * nxa + (N + 1) * nxa + k * nu + j] = std::min(dumax[j], INF);
-        }
-    // (Q C)' restricted to its nx x nx nonzero block: [i][j] = W[j][i], stage and terminal
-    L->Qt.assign(2 * nx * nx, 0.0);
-    for (int i = 0; i < nx; ++i)
-        for (int j = 0; j < nx; ++j) {
-            L->Qt[i * nx + j] = Q[j * nx + i];
-            L->Qt[nx * nx + i * nx + j] = QN[j * nx + i];
-        }
+    // (Q C)' restricted to its nx x nx nonzero block: Q transposed
+    build_layout(*L, N, nx, nu, nx + nu, device, Q, QN, R, maskA, maskB, true);
+    // inequality bounds (:383-384): lower bounds clipped from below, upper from above
+    set_box(*L, xmin_t, xmax_t, dumin, dumax, [](double v) { return std::max(v, -kInf); },
+            [](double v) { return std::min(v, kInf); });
     *out = L.release();  // device copies are made by the first assemble / shift (host-only use needs no GPU)
+    return 0;
+}
+
+int mpcqp_ltv_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q, const double* QN, const double* R,
+                            const double* xmin, const double* xmax, const double* umin, const double* umax,
+                            const uint8_t* maskA, const uint8_t* maskB, int32_t device, mpcqp_ltv_layout** out) {
+    if (!out || !Q || !QN || !R || !xmin || !xmax || !umin || !umax || !maskA || !maskB)
+        return set_error(MPCQP_EINVAL, "ltv_layout_create: NULL argument");
+    if (N < 2 || nx < 1 || nu < 1 || nx > 6 || nu > 2)
+        return set_error(MPCQP_EUNSUPPORTED, "ltv_layout_create: need N >= 2, 1 <= nx <= 6, 1 <= nu <= 2");
+    for (int i = 0; i < nx; ++i)
+        if (!(xmin[i] <= xmax[i])) return set_error(MPCQP_EINVAL, "ltv_layout_create: xmin > xmax");
+    for (int j = 0; j < nu; ++j)
+        if (!(umin[j] <= umax[j])) return set_error(MPCQP_EINVAL, "ltv_layout_create: umin > umax");
+    *out = nullptr;
+    auto L = std::make_unique<mpcqp_ltv_layout>();
+    // q = -Q Xr_k: the weights themselves
+    build_layout(*L, N, nx, nu, nx, device, Q, QN, R, maskA, maskB, false);
+    // box bounds (:327-328): every bound clipped on both sides
+    const auto clip = [](double v) { return std::min(std::max(v, -kInf), kInf); };
+    set_box(*L, xmin, xmax, umin, umax, clip, clip);
+    *out = L.release();  // device copies are made by the first assemble (host-only use needs no GPU)
     return 0;
 }
 
@@ -916,40 +974,42 @@ int mpcqp_incr_layout_dims(const mpcqp_incr_layout* L, int32_t* n, int32_t* m, i
     return layout_dims(L, "incr_layout_dims", n, m, nnzP, nnzA);
 }
 
+int mpcqp_ltv_layout_dims(const mpcqp_ltv_layout* L, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA) {
+    return layout_dims(L, "ltv_layout_dims", n, m, nnzP, nnzA);
+}
+
 int mpcqp_incr_layout_pattern(const mpcqp_incr_layout* L, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
                               int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
     return layout_pattern(L, "incr_layout_pattern", Pp, Pi, Px, Ap, Ai, Ax_template, l_template, u_template);
 }
 
+int mpcqp_ltv_layout_pattern(const mpcqp_ltv_layout* L, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
+                             int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
+    return layout_pattern(L, "ltv_layout_pattern", Pp, Pi, Px, Ap, Ai, Ax_template, l_template, u_template);
+}
+
 int mpcqp_incr_assemble_device(const mpcqp_incr_layout* L, int64_t B, const double* dAd, const double* dBd,
                                const double* dgd, const double* dxt0, const double* dXr, double* dAx, double* dq,
                                double* dl, double* du, void* stream) {
-    if (!L || !dAd || !dBd || !dgd || !dxt0 || !dXr || !dAx || !dq || !dl || !du || B < 0)
-        return set_error(MPCQP_EINVAL, "incr_assemble: bad arguments");
-    if (B == 0) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    MHIPCHK(hipSetDevice(L->dev));
-    const IncrK k = incr_k(*L);
-    const long nA = (long)B * k.nnzA;
-    hipLaunchKernelGGL(k_incr_assemble_A, dim3(grid_of(nA, 256)), dim3(256), 0, (hipStream_t)stream, k, (long)B,
-                       dAd, dBd, dAx);
-    hipLaunchKernelGGL(k_incr_assemble_vec, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, k, (long)B,
-                       dgd, dxt0, dXr, dq, dl, du);
-    MHIPCHK(hipGetLastError());
-    return 0;
+    return assemble_device("incr_assemble", L, B, dAd, dBd, dgd, dxt0, dXr, nullptr, nullptr, dAx, dq, dl, du, stream);
 }
 
-int mpcqp_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
-                                  const double* dpath_y, const double* dpred, double dt, double* dXr, int32_t device,
-                                  void* stream) {
-    if (!dpath_x || !dpath_y || !dpred || !dXr || B < 0 || N < 1 || nxa < 4 || npath < 2)
-        return set_error(MPCQP_EINVAL, "reference_search: bad arguments");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_reference, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, (long)B, (int)N,
-                       (int)nxa, (int)npath, dpath_x, dpath_y, dpred, dt, dXr);
-    MHIPCHK(hipGetLastError());
-    return 0;
+int mpcqp_ltv_assemble_device(const mpcqp_ltv_layout* L, int64_t B, const double* dAd, const double* dBd,
+                              const double* dgd, const double* dx0, const double* dXr, const double* dxlo,
+                              const double* dxhi, double* dAx, double* dq, double* dl, double* du, void* stream) {
+    return assemble_device("ltv_assemble", L, B, dAd, dBd, dgd, dx0, dXr, dxlo, dxhi, dAx, dq, dl, du, stream);
+}
+
+void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {
+    if (!L) return;
+    layout_free_device(L);
+    delete L;
+}
+
+void mpcqp_ltv_layout_free(mpcqp_ltv_layout* L) {
+    if (!L) return;
+    layout_free_device(L);
+    delete L;
 }
 
 int mpcqp_incr_shift_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh, int64_t B, const double* dsol,
@@ -961,38 +1021,8 @@ int mpcqp_incr_shift_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh
         return set_error(MPCQP_EUNSUPPORTED, "incr_shift: the plant model is the 6-state dynamic bicycle (nx 6, nu 2)");
     if (B == 0) return 0;
     if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    MHIPCHK(hipSetDevice(L->dev));
-    const VehicleK vk = vehicle_constants(*veh);
-    hipLaunchKernelGGL(k_incr_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, vk, incr_k(*L),
-                       (long)B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu);
-    MHIPCHK(hipGetLastError());
-    return 0;
-}
-
-int mpcqp_kin_linearise_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
-                               int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
-                               double* dgd, int32_t device, void* stream) {
-    if (!veh || !dx || !du || !dAd || !dBd || !dgd || B < 0 || N < 1)
-        return set_error(MPCQP_EINVAL, "kin_linearise: bad arguments");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_kin_linearise, dim3(grid_of(B * N, 256)), dim3(256), 0, (hipStream_t)stream, *veh, (long)B,
-                       (int)N, dx, (long)x_sb, (long)x_sk, du, (long)u_sb, (long)u_sk, dAd, dBd, dgd);
-    MHIPCHK(hipGetLastError());
-    return 0;
-}
-
-int mpcqp_kin_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
-                                      const double* dpath_y, const double* dpath_yaw, const double* dset_speed,
-                                      const double* dpred, double dt, double* dXr, int32_t device, void* stream) {
-    if (!dpath_x || !dpath_y || !dpath_yaw || !dset_speed || !dpred || !dXr || B < 0 || N < 1 || nxa < 4 || npath < 2)
-        return set_error(MPCQP_EINVAL, "kin_reference_search: bad arguments");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_kin_reference, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, (long)B, (int)N,
-                       (int)nxa, (int)npath, dpath_x, dpath_y, dpath_yaw, dset_speed, dpred, dt, dXr);
-    MHIPCHK(hipGetLastError());
-    return 0;
+    return launch(L->dev, stream, B, 128, k_incr_shift, vehicle_constants(*veh), incr_k(*L), B, dsol, dAd, dBd, dgd,
+                  dxt, dpred, dpdu);
 }
 
 int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
@@ -1006,12 +1036,32 @@ int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* 
         return set_error(MPCQP_EUNSUPPORTED, "kin_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
     if (B == 0) return 0;
     if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    MHIPCHK(hipSetDevice(L->dev));
-    hipLaunchKernelGGL(k_kin_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, incr_k(*L),
-                       (long)B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu, dfinish_cnt, ddone, dtraj, (int)traj_cap,
-                       dtraj_len);
-    MHIPCHK(hipGetLastError());
-    return 0;
+    return launch(L->dev, stream, B, 128, k_kin_shift, *veh, incr_k(*L), B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu,
+                  dfinish_cnt, ddone, dtraj, traj_cap, dtraj_len);
+}
+
+int mpcqp_kin_rollout_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx0,
+                             const double* du0, double* dpred_x, double* dpred_u, int32_t device, void* stream) {
+    if (!veh || !dx0 || !du0 || !dpred_x || !dpred_u || B < 0 || N < 1)
+        return set_error(MPCQP_EINVAL, "kin_rollout: bad arguments");
+    if (B == 0) return 0;
+    return launch(device, stream, B, 128, k_kin_rollout, *veh, B, N, dx0, du0, dpred_x, dpred_u);
+}
+
+int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
+                               const double* dsol, const int32_t* dstatus, const double* dAd, const double* dBd,
+                               const double* dgd, double* dx, double* du, double* dpred_x, double* dpred_u,
+                               int32_t* dskipped, int32_t* dsteps_taken, double* dtraj, int32_t traj_cap,
+                               int32_t* dtraj_len, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dpred_u || !dskipped || B < 0 ||
+        traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_ltv_shift: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_ltv_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0) return 0;
+    return launch(L->dev, stream, B, 128, k_kin_ltv_shift, *veh, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
+                  dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
 }
 
 int mpcqp_incr_warm_shift_device(int64_t B, int32_t N, int32_t nxa, int32_t nu, const double* dx, const double* dy,
@@ -1019,17 +1069,9 @@ int mpcqp_incr_warm_shift_device(int64_t B, int32_t N, int32_t nxa, int32_t nu, 
     if (!dx || !dxs || B < 0 || N < 1 || nxa < 1 || nu < 1 || (!dy) != (!dys) || dx == dxs || (dy && dy == dys))
         return set_error(MPCQP_EINVAL, "incr_warm_shift: bad arguments");
     if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
     const int n = (N + 1) * nxa + N * nu, m = 2 * (N + 1) * nxa + N * nu;
-    const long tx = B * (long)n;
-    hipLaunchKernelGGL(k_stage_shift, dim3(grid_of(tx, 256)), dim3(256), 0, (hipStream_t)stream, tx, n, N, nxa, nu, 1,
-                       dx, dxs);
-    if (dy) {
-        const long ty = B * (long)m;
-        hipLaunchKernelGGL(k_stage_shift, dim3(grid_of(ty, 256)), dim3(256), 0, (hipStream_t)stream, ty, m, N, nxa,
-                           nu, 2, dy, dys);
-    }
-    MHIPCHK(hipGetLastError());
+    if (int e = launch(device, stream, B * n, 256, k_stage_shift, B * n, n, N, nxa, nu, 1, dx, dxs)) return e;
+    if (dy) return launch(device, stream, B * m, 256, k_stage_shift, B * m, m, N, nxa, nu, 2, dy, dys);
     return 0;
 }
 
@@ -1091,137 +1133,6 @@ void mpcqp_affine_free(mpcqp_affine* a) {
     for (void* p : {(void*)a->d_base, (void*)a->d_coef, (void*)a->d_idx})
         if (p) (void)hipFree(p);
     delete a;
-}
-
-void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {
-    if (!L) return;
-    layout_free_device(L);
-    delete L;
-}
-
-// ------------------------------------------------------ direct-input LTV layout --
-int mpcqp_ltv_layout_create(int32_t N, int32_t nx, int32_t nu, const double* Q, const double* QN, const double* R,
-                            const double* xmin, const double* xmax, const double* umin, const double* umax,
-                            const uint8_t* maskA, const uint8_t* maskB, int32_t device, mpcqp_ltv_layout** out) {
-    if (!out || !Q || !QN || !R || !xmin || !xmax || !umin || !umax || !maskA || !maskB)
-        return set_error(MPCQP_EINVAL, "ltv_layout_create: NULL argument");
-    if (N < 2 || nx < 1 || nu < 1 || nx > 6 || nu > 2)
-        return set_error(MPCQP_EUNSUPPORTED, "ltv_layout_create: need N >= 2, 1 <= nx <= 6, 1 <= nu <= 2");
-    for (int i = 0; i < nx; ++i)
-        if (!(xmin[i] <= xmax[i])) return set_error(MPCQP_EINVAL, "ltv_layout_create: xmin > xmax");
-    for (int j = 0; j < nu; ++j)
-        if (!(umin[j] <= umax[j])) return set_error(MPCQP_EINVAL, "ltv_layout_create: umin > umax");
-    *out = nullptr;
-    auto L = std::make_unique<mpcqp_ltv_layout>();
-    const int ns = (N + 1) * nx, n = ns + N * nu, m = ns + n;
-    L->N = N; L->nx = nx; L->nu = nu; L->nxa = nx; L->n = n; L->m = m; L->dev = device;
-    const double INF = 1e30;  // the osqp wrapper clips +-inf to +-OSQP_INFTY
-    build_P(*L, Q, QN, R);
-    // A by column (mpc_kinematics_pred_matrix.py:293-309, :326, :341)
-    L->Ap.assign(n + 1, 0);
-    auto push = [&](int row, int src, double tpl) {
-        L->Ai.push_back(row); L->asrc.push_back(src); L->Atpl.push_back(tpl);
-    };
-    for (int c = 0; c < n; ++c) {
-        if (c < ns) {
-            const int k = c / nx, j = c % nx;
-            push(c, kConstSrc, -1.0);  // -I
-            if (k < N)                 // Ad_k in rows of stage k+1
-                for (int i = 0; i < nx; ++i)
-                    if (maskA[i * nx + j]) push((k + 1) * nx + i, k * nx * nx + i * nx + j, 0.0);
-        } else {
-            const int c0 = c - ns, k = c0 / nu, j = c0 % nu;  // u_k: Bd_k in rows of stage k+1
-            for (int i = 0; i < nx; ++i)
-                if (maskB[i * nu + j]) push((k + 1) * nx + i, -1 - (k * nx * nu + i * nu + j), 0.0);
-        }
-        push(ns + c, kConstSrc, 1.0);  // A_ineq = I
-        L->Ap[c + 1] = (int)L->Ai.size();
-    }
-    // box bounds (:327-328), clipped like the osqp wrapper; equality rows 0
-    L->ltpl.assign(m, 0.0); L->utpl.assign(m, 0.0);
-    for (int k = 0; k <= N; ++k)
-        for (int i = 0; i < nx; ++i) {
-            L->ltpl[ns + k * nx + i] = std::min(std::max(xmin[i], -INF), INF);
-            L->utpl[ns + k * nx + i] = std::min(std::max(xmax[i], -INF), INF);
-        }
-    for (int k = 0; k < N; ++k)
-        for (int j = 0; j < nu; ++j) {
-            L->ltpl[2 * ns + k * nu + j] = std::min(std::max(umin[j], -INF), INF);
-            L->utpl[2 * ns + k * nu + j] = std::min(std::max(umax[j], -INF), INF);
-        }
-    // q = -Q Xr_k: the weights themselves, stage and terminal
-    L->Qt.assign(2 * nx * nx, 0.0);
-    for (int i = 0; i < nx * nx; ++i) {
-        L->Qt[i] = Q[i];
-        L->Qt[nx * nx + i] = QN[i];
-    }
-    *out = L.release();  // device copies are made by the first assemble (host-only use needs no GPU)
-    return 0;
-}
-
-int mpcqp_ltv_layout_dims(const mpcqp_ltv_layout* L, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA) {
-    return layout_dims(L, "ltv_layout_dims", n, m, nnzP, nnzA);
-}
-
-int mpcqp_ltv_layout_pattern(const mpcqp_ltv_layout* L, int32_t* Pp, int32_t* Pi, double* Px, int32_t* Ap,
-                             int32_t* Ai, double* Ax_template, double* l_template, double* u_template) {
-    return layout_pattern(L, "ltv_layout_pattern", Pp, Pi, Px, Ap, Ai, Ax_template, l_template, u_template);
-}
-
-int mpcqp_ltv_assemble_device(const mpcqp_ltv_layout* L, int64_t B, const double* dAd, const double* dBd,
-                              const double* dgd, const double* dx0, const double* dXr, const double* dxlo,
-                              const double* dxhi, double* dAx, double* dq, double* dl, double* du, void* stream) {
-    if (!L || !dAd || !dBd || !dgd || !dx0 || !dXr || !dAx || !dq || !dl || !du || B < 0)
-        return set_error(MPCQP_EINVAL, "ltv_assemble: bad arguments");
-    if (B == 0) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_ltv_layout*>(L))) return e;
-    MHIPCHK(hipSetDevice(L->dev));
-    const IncrK k = incr_k(*L);
-    const long nA = (long)B * k.nnzA;
-    hipLaunchKernelGGL(k_incr_assemble_A, dim3(grid_of(nA, 256)), dim3(256), 0, (hipStream_t)stream, k, (long)B,
-                       dAd, dBd, dAx);
-    hipLaunchKernelGGL(k_ltv_assemble_vec, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, k, (long)B,
-                       dgd, dx0, dXr, dxlo, dxhi, dq, dl, du);
-    MHIPCHK(hipGetLastError());
-    return 0;
-}
-
-void mpcqp_ltv_layout_free(mpcqp_ltv_layout* L) {
-    if (!L) return;
-    layout_free_device(L);
-    delete L;
-}
-
-int mpcqp_kin_rollout_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx0,
-                             const double* du0, double* dpred_x, double* dpred_u, int32_t device, void* stream) {
-    if (!veh || !dx0 || !du0 || !dpred_x || !dpred_u || B < 0 || N < 1)
-        return set_error(MPCQP_EINVAL, "kin_rollout: bad arguments");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_kin_rollout, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, (long)B, (int)N,
-                       dx0, du0, dpred_x, dpred_u);
-    MHIPCHK(hipGetLastError());
-    return 0;
-}
-
-int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
-                               const double* dsol, const int32_t* dstatus, const double* dAd, const double* dBd,
-                               const double* dgd, double* dx, double* du, double* dpred_x, double* dpred_u,
-                               int32_t* dskipped, int32_t* dsteps_taken, double* dtraj, int32_t traj_cap,
-                               int32_t* dtraj_len, void* stream) {
-    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dpred_u || !dskipped || B < 0 ||
-        traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
-        return set_error(MPCQP_EINVAL, "kin_ltv_shift: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "kin_ltv_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0) return 0;
-    MHIPCHK(hipSetDevice(L->dev));
-    hipLaunchKernelGGL(k_kin_ltv_shift, dim3(grid_of(B, 128)), dim3(128), 0, (hipStream_t)stream, *veh, (int)L->N,
-                       (int)L->n, (long)B, dsol, dstatus, dAd, dBd, dgd, dx, du, dpred_x, dpred_u, dskipped,
-                       dsteps_taken, dtraj, (int)traj_cap, dtraj_len);
-    MHIPCHK(hipGetLastError());
-    return 0;
 }
 
 }  // extern "C"

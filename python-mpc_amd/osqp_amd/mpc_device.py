@@ -103,6 +103,28 @@ def _stream(torch, device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _linearise(symbol, veh, x, u, nx):
+    """linearise / linearise_kinematics: the model's C entry point on (B, N, nx) states."""
+    import torch
+    L = _bind()
+    squeeze = x.dim() == 2
+    if squeeze:
+        x, u = x[:, None, :], u[:, None, :]
+    B, N = x.shape[0], x.shape[1]
+    if x.shape[2] != nx or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
+        raise ValueError(f"x must be (B, N, {nx}) and u (B, N, 2)")
+    if x.stride(2) != 1 or u.stride(2) != 1:
+        raise ValueError("the state / input axis must be contiguous")
+    kw = dict(dtype=torch.float64, device=x.device)
+    Ad = torch.empty((B, N, nx, nx), **kw); Bd = torch.empty((B, N, nx, 2), **kw); gd = torch.empty((B, N, nx), **kw)
+    _check(getattr(L, f"mpcqp_{symbol}_device")(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u),
+                                                u.stride(0), u.stride(1), _p(Ad), _p(Bd), _p(gd), x.device.index or 0,
+                                                _stream(torch, x.device)), symbol)
+    if squeeze:
+        return Ad[:, 0], Bd[:, 0], gd[:, 0]
+    return Ad, Bd, gd
+
+
 def linearise(veh: Vehicle, x, u, device=0):
     """Batched Vehicle_Dynamics.get_dynamics_model (F2).
 
@@ -110,52 +132,40 @@ def linearise(veh: Vehicle, x, u, device=0):
     with a contiguous last dimension) -> Ad (B, N, 6, 6), Bd (B, N, 6, 2), gd (B, N, 6)
     (N axis dropped for 2-D inputs).  Inputs are not modified (the reference's
     low-speed guard writes into the caller's view; here it acts on copies)."""
-    import torch
-    L = _bind()
-    squeeze = x.dim() == 2
-    if squeeze:
-        x, u = x[:, None, :], u[:, None, :]
-    B, N = x.shape[0], x.shape[1]
-    if x.shape[2] != 6 or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
-        raise ValueError("x must be (B, N, 6) and u (B, N, 2)")
-    if x.stride(2) != 1 or u.stride(2) != 1:
-        raise ValueError("the state / input axis must be contiguous")
-    kw = dict(dtype=torch.float64, device=x.device)
-    Ad = torch.empty((B, N, 6, 6), **kw); Bd = torch.empty((B, N, 6, 2), **kw); gd = torch.empty((B, N, 6), **kw)
-    _check(L.mpcqp_linearise_device(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0),
-                                    u.stride(1), _p(Ad), _p(Bd), _p(gd), x.device.index or 0,
-                                    _stream(torch, x.device)), "linearise")
-    if squeeze:
-        return Ad[:, 0], Bd[:, 0], gd[:, 0]
-    return Ad, Bd, gd
+    return _linearise("linearise", veh, x, u, 6)
 
 
-class IncrementalLayout:
-    """The QP of mpc_increment (mpc_dynamics.py:281-389) for a batch sharing N, weights,
-    bounds and the structural nonzeros of Ad / Bd (F1).  ``pattern()`` gives the CSC
-    templates (P with its values, A), ``assemble()`` the per-instance values on the device."""
+class _Layout:
+    """What IncrementalLayout and LTVLayout share: the marshalling of the weights, bounds and
+    masks into mpcqp_<kind>_layout_create, the dimensions, the handle's lifetime, pattern()."""
 
-    def __init__(self, N, Q, QN, R, xmin_t, xmax_t, dumin, dumax, maskA=DYN_MASK_A, maskB=DYN_MASK_B, device=0):
+    _kind = None  # "incr" / "ltv": the C ABI's prefix
+
+    def __init__(self, N, Q, QN, R, bounds, maskA, maskB, device):
         L = _bind()
         Q = np.ascontiguousarray(np.asarray(sparse.csr_matrix(Q).todense(), np.float64))
         QN = np.ascontiguousarray(np.asarray(sparse.csr_matrix(QN).todense(), np.float64))
         R = np.ascontiguousarray(np.asarray(sparse.csr_matrix(R).todense(), np.float64))
         self.N, self.nx, self.nu = int(N), Q.shape[0], R.shape[0]
-        self.nxa = self.nx + self.nu
-        arrs = [np.ascontiguousarray(np.asarray(a, np.float64).ravel()) for a in (xmin_t, xmax_t, dumin, dumax)]
+        arrs = [np.ascontiguousarray(np.asarray(a, np.float64).ravel()) for a in bounds]
         mA = np.ascontiguousarray(np.asarray(maskA, np.uint8))
         mB = np.ascontiguousarray(np.asarray(maskB, np.uint8))
+        self._validate(Q, QN, R, arrs, mA, mB)
         h = C.c_void_p()
-        _check(L.mpcqp_incr_layout_create(self.N, self.nx, self.nu, _np_ptr(Q), _np_ptr(QN), _np_ptr(R),
-                                          *(_np_ptr(a) for a in arrs), _np_ptr(mA), _np_ptr(mB), int(device),
-                                          C.byref(h)), "incr_layout_create")
+        _check(getattr(L, f"mpcqp_{self._kind}_layout_create")(
+            self.N, self.nx, self.nu, _np_ptr(Q), _np_ptr(QN), _np_ptr(R), *(_np_ptr(a) for a in arrs), _np_ptr(mA),
+            _np_ptr(mB), int(device), C.byref(h)), f"{self._kind}_layout_create")
         self._h = h.value
-        self._free = L.mpcqp_incr_layout_free  # held: module globals may be gone at interpreter exit
-        self._keep = (Q, QN, R, arrs, mA, mB)
+        # held: module globals may be gone at interpreter exit
+        self._free = getattr(L, f"mpcqp_{self._kind}_layout_free")
         n, m, nP, nA = (C.c_int32() for _ in range(4))
-        _check(L.mpcqp_incr_layout_dims(self._h, C.byref(n), C.byref(m), C.byref(nP), C.byref(nA)), "dims")
+        _check(getattr(L, f"mpcqp_{self._kind}_layout_dims")(self._h, C.byref(n), C.byref(m), C.byref(nP),
+                                                             C.byref(nA)), "dims")
         self.n, self.m, self.nnzP, self.nnzA = n.value, m.value, nP.value, nA.value
         self.device = int(device)
+
+    def _validate(self, Q, QN, R, arrs, mA, mB):
+        pass
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -170,11 +180,29 @@ class IncrementalLayout:
         Pp = np.zeros(n + 1, np.int32); Pi = np.zeros(self.nnzP, np.int32); Px = np.zeros(self.nnzP)
         Ap = np.zeros(n + 1, np.int32); Ai = np.zeros(self.nnzA, np.int32); At = np.zeros(self.nnzA)
         lt = np.zeros(m); ut = np.zeros(m)
-        _check(lib().mpcqp_incr_layout_pattern(self._h, *(_np_ptr(a) for a in (Pp, Pi, Px, Ap, Ai, At, lt, ut))),
-               "pattern")
+        _check(getattr(lib(), f"mpcqp_{self._kind}_layout_pattern")(
+            self._h, *(_np_ptr(a) for a in (Pp, Pi, Px, Ap, Ai, At, lt, ut))), "pattern")
         P = sparse.csc_matrix((Px, Pi, Pp), shape=(n, n))
         A = sparse.csc_matrix((At, Ai, Ap), shape=(m, n))
         return P, A, lt, ut
+
+    def _empty_out(self, B, device):
+        import torch
+        kw = dict(dtype=torch.float64, device=device)
+        return (torch.empty((B, self.nnzA), **kw), torch.empty((B, self.n), **kw),
+                torch.empty((B, self.m), **kw), torch.empty((B, self.m), **kw))
+
+
+class IncrementalLayout(_Layout):
+    """The QP of mpc_increment (mpc_dynamics.py:281-389) for a batch sharing N, weights,
+    bounds and the structural nonzeros of Ad / Bd (F1).  ``pattern()`` gives the CSC
+    templates (P with its values, A), ``assemble()`` the per-instance values on the device."""
+
+    _kind = "incr"
+
+    def __init__(self, N, Q, QN, R, xmin_t, xmax_t, dumin, dumax, maskA=DYN_MASK_A, maskB=DYN_MASK_B, device=0):
+        super().__init__(N, Q, QN, R, (xmin_t, xmax_t, dumin, dumax), maskA, maskB, device)
+        self.nxa = self.nx + self.nu
 
     def assemble(self, Ad, Bd, gd, xt0, Xr, out=None):
         """Ad (B,N,nx,nx), Bd (B,N,nx,nu), gd (B,N,nx), xt0 (B,nx+nu), Xr (B,nx,N+1), all
@@ -182,9 +210,7 @@ class IncrementalLayout:
         import torch
         B = Ad.shape[0]
         if out is None:
-            kw = dict(dtype=torch.float64, device=Ad.device)
-            out = (torch.empty((B, self.nnzA), **kw), torch.empty((B, self.n), **kw),
-                   torch.empty((B, self.m), **kw), torch.empty((B, self.m), **kw))
+            out = self._empty_out(B, Ad.device)
         for t in (Ad, Bd, gd, xt0, Xr):
             if not t.is_contiguous() or t.dtype != torch.float64:
                 raise ValueError("assemble inputs must be contiguous float64 tensors")
@@ -361,7 +387,103 @@ def warm_shift(N, nxa, nu, x, y=None):
     return xs, ys
 
 
-class DynamicMPC:
+class _ClosedLoop:
+    """What the three closed loops share.  A subclass's __init__ builds its layout, calls
+    ``_setup`` (solver, path, solve outputs), allocates its own state tensors and calls
+    ``_start``; it states ``_linearise`` (the model's linearisation), ``_initial_horizon``,
+    ``_reference``, ``_horizon`` (initial state, predicted states, predicted inputs) and ``_shift``.
+
+    Every kernel of a step runs on ``self.stream``, in order; a null (legacy default) torch
+    stream would be passed as NULL, which the solver's C ABI reads as "the handle's own
+    stream" -- unordered with torch's kernels."""
+
+    def _setup(self, x0, u0, N, veh, device, layout, paths, settings, shift_warm):
+        """x0 (B, layout.nx), u0 (B, 2); paths: name -> points, each kept as a device tensor
+        under its name; settings: DeviceBatch's; shift_warm: start each solve from the last
+        solution shifted one stage.  Returns x0, u0 as 2-D float64 arrays."""
+        import torch
+        self.torch = torch
+        self.dev = torch.device("cuda", device)
+        self.veh, self.N, self.layout = veh, int(N), layout
+        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
+        if x0.shape[1] != layout.nx or u0.shape != (x0.shape[0], 2):
+            raise ValueError(f"x0 must be (B, {layout.nx}) and u0 (B, 2)")
+        self.B = x0.shape[0]
+        P, A, _, _ = layout.pattern()
+        settings.pop("verbose", None)
+        self.shift_warm = bool(shift_warm)
+        self.have_sol = False
+        self.last = None
+        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
+        for name, p in paths.items():
+            setattr(self, name, torch.as_tensor(np.ascontiguousarray(np.asarray(p, np.float64)), **kw).contiguous())
+        if not all(getattr(self, name).numel() == self.path_x.numel() >= 2 for name in paths):
+            raise ValueError(f"{', '.join(paths)} must have one length, at least 2")
+        self.sol = torch.empty((self.B, layout.n), **kw)
+        self.y = torch.empty((self.B, layout.m), **kw)
+        self.status = torch.empty(self.B, **ikw)
+        self.iters = torch.empty(self.B, **ikw)
+        return x0, u0
+
+    def _start(self):
+        torch = self.torch
+        self.stream = torch.cuda.Stream(self.dev)
+        self._on_stream(self._initial_horizon)
+
+    def _on_stream(self, fn):
+        """fn() on self.stream, ordered after the caller's current stream; the caller's stream
+        is ordered after it."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            out = fn()
+        caller.wait_stream(self.stream)
+        return out
+
+    def _linearised_rollout(self):
+        """Initial guess of the two incremental loops (mpc_dynamics.py:513-522,
+        mpc_incre_kine_func.py:289-308): roll the linearised model forward with zero increments."""
+        torch = self.torch
+        nx = self.layout.nx
+        pred = torch.empty((self.B, self.N + 1, nx + 2), dtype=torch.float64, device=self.dev)
+        pred[:, 0] = self.xt
+        xk = self.xt.clone()
+        for i in range(self.N):
+            Ad, Bd, gd = self._linearise(self.veh, xk[:, :nx].contiguous(), xk[:, nx:].contiguous(),
+                                         self.dev.index or 0)
+            x1 = torch.einsum("bij,bj->bi", Ad, xk[:, :nx]) + torch.einsum("bij,bj->bi", Bd, xk[:, nx:]) + gd
+            xk = torch.cat([x1, xk[:, nx:] + self.pdu[:, i]], dim=1)
+            pred[:, i + 1] = xk
+        return pred
+
+    def step(self):
+        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
+        Asynchronous: ordered after the caller's current stream, and the caller's stream
+        is ordered after the step."""
+        return self._on_stream(self._step)
+
+    def _step(self):
+        N = self.N
+        Xr = self._reference()
+        x0, xs, us = self._horizon()
+        Ad, Bd, gd = self._linearise(self.veh, xs[:, :N], us[:, :N], self.dev.index or 0)
+        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, x0, Xr)
+        st = _stream(self.torch, self.dev)  # self.stream
+        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
+        if self.shift_warm and self.have_sol:
+            self.solver.warm_start(*warm_shift(N, self.layout.nxa, 2, self.sol, self.y), stream=st)
+        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
+        self.have_sol = True
+        self._shift(_bind(), Ad, Bd, gd, Xr, st)
+        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
+        return self.status, self.iters
+
+
+class DynamicMPC(_ClosedLoop):
     """B copies of mpc_dynamics.main's closed loop (:437-617), every step on the device.
 
     State per vehicle: x~ = (X, Y, yaw, vx, vy, r, steer, accel), the predicted
@@ -378,87 +500,31 @@ class DynamicMPC:
     DUMIN = np.array([-np.deg2rad(2.0), -0.5])                      # :461-464
     XMIN_T = np.array([-np.inf, -np.inf, -2 * np.pi, -100., -30., -0.5 * np.pi, -np.deg2rad(15), -3.])
     XMAX_T = np.array([np.inf, np.inf, 2 * np.pi, 100., 30., 0.5 * np.pi, np.deg2rad(15), 1.])
+    _linearise = staticmethod(linearise)
 
     def __init__(self, x0, u0, path_x, path_y, N=30, veh: Vehicle | None = None, device=0, **solver_settings):
-        import torch
-        self.torch = torch
-        self.dev = torch.device("cuda", device)
-        self.veh = veh or Vehicle()
-        self.N = int(N)
-        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
-        self.B = x0.shape[0]
-        self.layout = IncrementalLayout(self.N, self.Q, self.QN, self.R, self.XMIN_T, self.XMAX_T, self.DUMIN,
-                                        -self.DUMIN, device=device)
-        P, A, _, _ = self.layout.pattern()
-        settings = dict(verbose=False, polish=False, warm_start=False)   # mpc_dynamics.py:393
-        settings.update(solver_settings)
-        settings.pop("verbose", None)
-        self.warm = bool(settings.pop("warm_start"))
-        self.have_sol = False
-        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
-        kw = dict(dtype=torch.float64, device=self.dev)
-        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
-        self.path_x = torch.as_tensor(np.asarray(path_x, np.float64), **kw).contiguous()
-        self.path_y = torch.as_tensor(np.asarray(path_y, np.float64), **kw).contiguous()
-        self.xt = torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
-        n, m = self.layout.n, self.layout.m
-        self.sol = torch.empty((self.B, n), **kw)
-        self.y = torch.empty((self.B, m), **kw)
-        self.status = torch.empty(self.B, dtype=torch.int32, device=self.dev)
-        self.iters = torch.empty(self.B, dtype=torch.int32, device=self.dev)
-        self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)
-        # every kernel of a step runs on this stream, in order; a null (legacy default)
-        # torch stream would be passed as NULL, which the solver's C ABI reads as "the
-        # handle's own stream" -- unordered with torch's kernels
-        self.stream = torch.cuda.Stream(self.dev)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            self.pred = self._initial_rollout()
-        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        layout = IncrementalLayout(int(N), self.Q, self.QN, self.R, self.XMIN_T, self.XMAX_T, self.DUMIN,
+                                   -self.DUMIN, device=device)
+        settings = {"polish": False, "warm_start": False, **solver_settings}   # mpc_dynamics.py:393
+        x0, u0 = self._setup(x0, u0, N, veh or Vehicle(), device, layout, dict(path_x=path_x, path_y=path_y),
+                             settings, settings.pop("warm_start"))
+        kw = dict(dtype=self.torch.float64, device=self.dev)
+        self.xt = self.torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
+        self.pdu = self.torch.zeros((self.B, self.N + 1, 2), **kw)
+        self._start()
 
-    def _initial_rollout(self):
-        """Initial guess (:513-522): roll the linearised model forward with zero increments."""
-        torch = self.torch
-        pred = torch.empty((self.B, self.N + 1, 8), dtype=torch.float64, device=self.dev)
-        pred[:, 0] = self.xt
-        xk = self.xt.clone()
-        for i in range(self.N):
-            Ad, Bd, gd = linearise(self.veh, xk[:, :6].contiguous(), xk[:, 6:].contiguous(), self.dev.index or 0)
-            x1 = torch.einsum("bij,bj->bi", Ad, xk[:, :6]) + torch.einsum("bij,bj->bi", Bd, xk[:, 6:]) + gd
-            xk = torch.cat([x1, xk[:, 6:] + self.pdu[:, i]], dim=1)
-            pred[:, i + 1] = xk
-        return pred
+    def _initial_horizon(self):
+        self.pred = self._linearised_rollout()
 
-    def step(self):
-        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
-        Asynchronous: ordered after the caller's current stream, and the caller's stream
-        is ordered after the step."""
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            out = self._step()
-        caller.wait_stream(self.stream)
-        return out
+    def _reference(self):
+        return reference_search(self.path_x, self.path_y, self.pred, self.veh.dt)
 
-    def _step(self):
-        L = _bind()
-        torch = self.torch
-        Xr = reference_search(self.path_x, self.path_y, self.pred, self.veh.dt)
-        Ad, Bd, gd = linearise(self.veh, self.pred[:, :self.N, :6], self.pred[:, :self.N, 6:], self.dev.index or 0)
-        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, self.xt, Xr)
-        st = _stream(torch, self.dev)  # self.stream
-        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
-        if self.warm and self.have_sol:
-            xs, ys = warm_shift(self.N, 8, 2, self.sol, self.y)
-            self.solver.warm_start(xs, ys, stream=st)
-        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
-        self.have_sol = True
+    def _horizon(self):
+        return self.xt, self.pred[:, :, :6], self.pred[:, :, 6:]
+
+    def _shift(self, L, Ad, Bd, gd, Xr, st):
         _check(L.mpcqp_incr_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
-                                         _p(gd), _p(self.xt), _p(self.pred), _p(self.pdu),
-                                         _stream(torch, self.dev)), "incr_shift")
-        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
-        return self.status, self.iters
+                                         _p(gd), _p(self.xt), _p(self.pred), _p(self.pdu), st), "incr_shift")
 
 
 # ------------------------------------------------------------ kinematic bicycle --
@@ -468,24 +534,7 @@ def linearise_kinematics(veh: KinVehicle, x, u, device=0):
     x: (B, N, 4) or (B, 4) float64 device tensor (X, Y, v, yaw), u: (B, N, 2) or (B, 2)
     (steer, accel), any strides with a contiguous last dimension -> Ad (B, N, 4, 4),
     Bd (B, N, 4, 2), gd (B, N, 4) (N axis dropped for 2-D inputs).  Inputs are not modified."""
-    import torch
-    L = _bind()
-    squeeze = x.dim() == 2
-    if squeeze:
-        x, u = x[:, None, :], u[:, None, :]
-    B, N = x.shape[0], x.shape[1]
-    if x.shape[2] != 4 or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
-        raise ValueError("x must be (B, N, 4) and u (B, N, 2)")
-    if x.stride(2) != 1 or u.stride(2) != 1:
-        raise ValueError("the state / input axis must be contiguous")
-    kw = dict(dtype=torch.float64, device=x.device)
-    Ad = torch.empty((B, N, 4, 4), **kw); Bd = torch.empty((B, N, 4, 2), **kw); gd = torch.empty((B, N, 4), **kw)
-    _check(L.mpcqp_kin_linearise_device(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0),
-                                        u.stride(1), _p(Ad), _p(Bd), _p(gd), x.device.index or 0,
-                                        _stream(torch, x.device)), "kin_linearise")
-    if squeeze:
-        return Ad[:, 0], Bd[:, 0], gd[:, 0]
-    return Ad, Bd, gd
+    return _linearise("kin_linearise", veh, x, u, 4)
 
 
 def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):
@@ -507,7 +556,7 @@ def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):
     return Xr
 
 
-class KinematicMPC:
+class KinematicMPC(_ClosedLoop):
     """B copies of mpc_incre_kine_func.simulate(init_state, path_x, path_y, path_yaw)
     (:223-436), every step on the device.
 
@@ -531,44 +580,24 @@ class KinematicMPC:
     ``warm_start=True`` (an extension; the reference solves every step cold) starts
     each solve from the previous step's solution shifted one stage (warm_shift)."""
 
+    _linearise = staticmethod(linearise_kinematics)
+
     def __init__(self, x0, u0, path_x, path_y, path_yaw, N=40, veh: KinVehicle | None = None, device=0, traj_cap=0,
                  **solver_settings):
-        import torch
         from . import mpc
-        self.torch = torch
-        self.dev = torch.device("cuda", device)
-        self.veh = veh or KinVehicle()
-        self.N = int(N)
-        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
-        if x0.shape[1] != 4 or u0.shape != (x0.shape[0], 2):
-            raise ValueError("x0 must be (B, 4) and u0 (B, 2)")
-        self.B = x0.shape[0]
-        self.traj_cap = int(traj_cap)
-        self.layout = IncrementalLayout(self.N, mpc.KIN_Q, mpc.KIN_QN, mpc.KIN_R, mpc.KIN_XMIN_T, mpc.KIN_XMAX_T,
-                                        mpc.KIN_DUMIN, -mpc.KIN_DUMIN, maskA=mpc.KIN_MASK_A, maskB=mpc.KIN_MASK_B,
-                                        device=device)
-        P, A, _, _ = self.layout.pattern()
-        settings = dict(verbose=False, polish=False, warm_start=False)   # mpc_incre_kine_func.py:180
-        settings.update(solver_settings)
-        settings.pop("verbose", None)
-        self.warm = bool(settings.pop("warm_start"))
-        self.have_sol = False
-        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
+        layout = IncrementalLayout(int(N), mpc.KIN_Q, mpc.KIN_QN, mpc.KIN_R, mpc.KIN_XMIN_T, mpc.KIN_XMAX_T,
+                                   mpc.KIN_DUMIN, -mpc.KIN_DUMIN, maskA=mpc.KIN_MASK_A, maskB=mpc.KIN_MASK_B,
+                                   device=device)
+        settings = {"polish": False, "warm_start": False, **solver_settings}   # mpc_incre_kine_func.py:180
+        x0, u0 = self._setup(x0, u0, N, veh or KinVehicle(), device, layout,
+                             dict(path_x=path_x, path_y=path_y, path_yaw=path_yaw), settings,
+                             settings.pop("warm_start"))
+        torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
-        self.path_x, self.path_y, self.path_yaw = (
-            torch.as_tensor(np.ascontiguousarray(np.asarray(p, np.float64)), **kw).contiguous()
-            for p in (path_x, path_y, path_yaw))
-        if not (self.path_x.numel() == self.path_y.numel() == self.path_yaw.numel() >= 2):
-            raise ValueError("path_x, path_y, path_yaw must have one length, at least 2")
+        self.traj_cap = int(traj_cap)
         self.xt = torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
         self.set_speed = torch.from_numpy(np.ascontiguousarray(x0[:, 2])).to(**kw).contiguous()
-        n, m = self.layout.n, self.layout.m
-        self.sol = torch.empty((self.B, n), **kw)
-        self.y = torch.empty((self.B, m), **kw)
-        self.status = torch.empty(self.B, **ikw)
-        self.iters = torch.empty(self.B, **ikw)
         self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)             # del_u0 = 0 (:276, :293-296)
         self.finish_cnt = torch.zeros(self.B, **ikw)
         self.done = torch.zeros(self.B, **ikw)
@@ -577,59 +606,22 @@ class KinematicMPC:
         traj0[:, 0] = np.stack([x0[:, 0], x0[:, 1], x0[:, 3], u0[:, 1]], axis=1)
         self.traj = torch.from_numpy(traj0).to(**kw).contiguous()
         self.traj_len = torch.full((self.B,), 1 if self.traj_cap > 0 else 0, **ikw)
-        # every kernel of a step runs on this stream, in order (see DynamicMPC)
-        self.stream = torch.cuda.Stream(self.dev)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            self.pred = self._initial_rollout()
-        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        self._start()
 
-    def _initial_rollout(self):
-        """Initial guess (:289-308): roll the linearised model forward with zero increments."""
-        torch = self.torch
-        pred = torch.empty((self.B, self.N + 1, 6), dtype=torch.float64, device=self.dev)
-        pred[:, 0] = self.xt
-        xk = self.xt.clone()
-        for i in range(self.N):
-            Ad, Bd, gd = linearise_kinematics(self.veh, xk[:, :4].contiguous(), xk[:, 4:].contiguous(),
-                                              self.dev.index or 0)
-            x1 = torch.einsum("bij,bj->bi", Ad, xk[:, :4]) + torch.einsum("bij,bj->bi", Bd, xk[:, 4:]) + gd
-            xk = torch.cat([x1, xk[:, 4:] + self.pdu[:, i]], dim=1)
-            pred[:, i + 1] = xk
-        return pred
+    def _initial_horizon(self):
+        self.pred = self._linearised_rollout()
 
-    def step(self):
-        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
-        Asynchronous: ordered after the caller's current stream, and the caller's stream
-        is ordered after the step."""
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            out = self._step()
-        caller.wait_stream(self.stream)
-        return out
+    def _reference(self):
+        return reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred, self.veh.dt)
 
-    def _step(self):
-        L = _bind()
-        torch = self.torch
-        N = self.N
-        Xr = reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred, self.veh.dt)
-        Ad, Bd, gd = linearise_kinematics(self.veh, self.pred[:, :N, :4], self.pred[:, :N, 4:], self.dev.index or 0)
-        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, self.xt, Xr)
-        st = _stream(torch, self.dev)  # self.stream
-        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
-        if self.warm and self.have_sol:
-            xs, ys = warm_shift(N, 6, 2, self.sol, self.y)
-            self.solver.warm_start(xs, ys, stream=st)
-        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
-        self.have_sol = True
+    def _horizon(self):
+        return self.xt, self.pred[:, :, :4], self.pred[:, :, 4:]
+
+    def _shift(self, L, Ad, Bd, gd, Xr, st):
         _check(L.mpcqp_kin_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
                                         _p(gd), _p(Xr), _p(self.xt), _p(self.pred), _p(self.pdu),
                                         _p(self.finish_cnt), _p(self.done), _p(self.traj), self.traj_cap,
                                         _p(self.traj_len), st), "kin_shift")
-        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
-        return self.status, self.iters
 
     def trajectories(self):
         """(traj, traj_len) as host arrays: traj (B, traj_cap, 4) = x, y, yaw, steer increment;
@@ -655,54 +647,23 @@ class KinematicMPC:
 
 
 # ------------------------------------------------- LTV in the inputs themselves --
-class LTVLayout:
+class LTVLayout(_Layout):
     """The QP of mpc__ (Control/MPC/mpc_kinematics_pred_matrix.py:268-352), mpc
     (mpc_dynamics.py:160-279) and mpc_ (mpc_kinematics.py:202-265) -- osqp_amd.mpc.ltv_qp --
     for a batch sharing N, weights, bounds and the structural nonzeros of Ad / Bd: variables
     (x_0..x_N, u_0..u_{N-1}), no u_prev augmentation.  ``pattern()`` gives the CSC templates,
     ``assemble()`` the per-instance values on the device (mpcqp_ltv_*)."""
 
+    _kind = "ltv"
+
     def __init__(self, N, Q, QN, R, xmin, xmax, umin, umax, maskA, maskB, device=0):
-        L = _bind()
-        Q = np.ascontiguousarray(np.asarray(sparse.csr_matrix(Q).todense(), np.float64))
-        QN = np.ascontiguousarray(np.asarray(sparse.csr_matrix(QN).todense(), np.float64))
-        R = np.ascontiguousarray(np.asarray(sparse.csr_matrix(R).todense(), np.float64))
-        self.N, self.nx, self.nu = int(N), Q.shape[0], R.shape[0]
-        arrs = [np.ascontiguousarray(np.asarray(a, np.float64).ravel()) for a in (xmin, xmax, umin, umax)]
-        mA = np.ascontiguousarray(np.asarray(maskA, np.uint8))
-        mB = np.ascontiguousarray(np.asarray(maskB, np.uint8))
+        super().__init__(N, Q, QN, R, (xmin, xmax, umin, umax), maskA, maskB, device)
+        self.nxa = self.nx  # no augmentation
+
+    def _validate(self, Q, QN, R, arrs, mA, mB):
         if QN.shape != Q.shape or mA.shape != Q.shape or mB.shape != (self.nx, self.nu) or \
                 [a.size for a in arrs] != [self.nx, self.nx, self.nu, self.nu]:
             raise ValueError("LTVLayout: Q, QN, maskA must be nx x nx, R nu x nu, maskB nx x nu, bounds nx / nu long")
-        h = C.c_void_p()
-        _check(L.mpcqp_ltv_layout_create(self.N, self.nx, self.nu, _np_ptr(Q), _np_ptr(QN), _np_ptr(R),
-                                         *(_np_ptr(a) for a in arrs), _np_ptr(mA), _np_ptr(mB), int(device),
-                                         C.byref(h)), "ltv_layout_create")
-        self._h = h.value
-        self._free = L.mpcqp_ltv_layout_free  # held: module globals may be gone at interpreter exit
-        n, m, nP, nA = (C.c_int32() for _ in range(4))
-        _check(L.mpcqp_ltv_layout_dims(self._h, C.byref(n), C.byref(m), C.byref(nP), C.byref(nA)), "dims")
-        self.n, self.m, self.nnzP, self.nnzA = n.value, m.value, nP.value, nA.value
-        self.device = int(device)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._free(h)
-
-    def pattern(self):
-        """(P, A, l_template, u_template): scipy CSC templates (P upper triangle with its
-        constant values; A with the constant entries and zeros at the stage entries) and
-        the box rows' bounds (clipped to +-1e30; equality rows 0)."""
-        n, m = self.n, self.m
-        Pp = np.zeros(n + 1, np.int32); Pi = np.zeros(self.nnzP, np.int32); Px = np.zeros(self.nnzP)
-        Ap = np.zeros(n + 1, np.int32); Ai = np.zeros(self.nnzA, np.int32); At = np.zeros(self.nnzA)
-        lt = np.zeros(m); ut = np.zeros(m)
-        _check(lib().mpcqp_ltv_layout_pattern(self._h, *(_np_ptr(a) for a in (Pp, Pi, Px, Ap, Ai, At, lt, ut))),
-               "pattern")
-        P = sparse.csc_matrix((Px, Pi, Pp), shape=(n, n))
-        A = sparse.csc_matrix((At, Ai, Ap), shape=(m, n))
-        return P, A, lt, ut
 
     def assemble(self, Ad, Bd, gd, x0, Xr, xlo=None, xhi=None, out=None):
         """Ad (B,N,nx,nx), Bd (B,N,nx,nu), gd (B,N,nx), x0 (B,nx), Xr (B,nx,N+1) and the optional
@@ -717,9 +678,7 @@ class LTVLayout:
                 raise ValueError(f"assemble inputs must be contiguous float64 tensors; expected shape {shape}, "
                                  f"got {tuple(t.shape)}")
         if out is None:
-            kw = dict(dtype=torch.float64, device=Ad.device)
-            out = (torch.empty((B, self.nnzA), **kw), torch.empty((B, self.n), **kw),
-                   torch.empty((B, self.m), **kw), torch.empty((B, self.m), **kw))
+            out = self._empty_out(B, Ad.device)
         Ax, q, l, u = out
         for t, w in ((Ax, self.nnzA), (q, self.n), (l, self.m), (u, self.m)):
             if tuple(t.shape) != (B, w) or not t.is_contiguous() or t.dtype != torch.float64:
@@ -748,7 +707,7 @@ def rollout_kin(veh: KinVehicle, x0, u0, N):
     return pred_x, pred_u
 
 
-class KinematicLTVMPC:
+class KinematicLTVMPC(_ClosedLoop):
     """B copies of mpc_kinematics_pred_matrix.main's closed loop (:355-563), every step on
     the device.
 
@@ -773,89 +732,45 @@ class KinematicLTVMPC:
     step's solution shifted one stage (warm_shift)."""
 
     SET_SPEED = 10.0  # reference_search's x_ref[2] (:62)
+    _linearise = staticmethod(linearise_kinematics)
 
     def __init__(self, x0, u0, path_x, path_y, N=100, veh: KinVehicle | None = None, device=0, traj_cap=0,
                  shift_warm=False, **solver_settings):
-        import torch
         from . import mpc
-        self.torch = torch
-        self.dev = torch.device("cuda", device)
-        self.veh = veh or KinVehicle()
-        self.N = int(N)
-        x0 = np.atleast_2d(np.asarray(x0, np.float64)); u0 = np.atleast_2d(np.asarray(u0, np.float64))
-        if x0.shape[1] != 4 or u0.shape != (x0.shape[0], 2):
-            raise ValueError("x0 must be (B, 4) and u0 (B, 2)")
-        self.B = x0.shape[0]
-        self.traj_cap = int(traj_cap)
-        self.layout = LTVLayout(self.N, mpc.KINLTV_Q, mpc.KINLTV_QN, mpc.KINLTV_R, mpc.KINLTV_XMIN, mpc.KINLTV_XMAX,
-                                mpc.KINLTV_UMIN, mpc.KINLTV_UMAX, mpc.KIN_MASK_A, mpc.KIN_MASK_B, device=device)
-        P, A, _, _ = self.layout.pattern()
-        settings = dict(verbose=False, polish=False, warm_start=True)   # mpc_kinematics_pred_matrix.py:347
-        settings.update(solver_settings)
-        settings.pop("verbose", None)
-        self.shift_warm = bool(shift_warm)
-        self.have_sol = False
-        self.solver = DeviceBatch(P, A, self.B, device=device, **settings)
+        layout = LTVLayout(int(N), mpc.KINLTV_Q, mpc.KINLTV_QN, mpc.KINLTV_R, mpc.KINLTV_XMIN, mpc.KINLTV_XMAX,
+                           mpc.KINLTV_UMIN, mpc.KINLTV_UMAX, mpc.KIN_MASK_A, mpc.KIN_MASK_B, device=device)
+        settings = {"polish": False, "warm_start": True, **solver_settings}   # mpc_kinematics_pred_matrix.py:347
+        x0, u0 = self._setup(x0, u0, N, veh or KinVehicle(), device, layout, dict(path_x=path_x, path_y=path_y),
+                             settings, shift_warm)
+        torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.Px = torch.from_numpy(np.tile(P.data, (self.B, 1))).to(**kw).contiguous()
-        self.path_x, self.path_y = (torch.as_tensor(np.ascontiguousarray(np.asarray(p, np.float64)), **kw).contiguous()
-                                    for p in (path_x, path_y))
-        if not (self.path_x.numel() == self.path_y.numel() >= 2):
-            raise ValueError("path_x, path_y must have one length, at least 2")
+        self.traj_cap = int(traj_cap)
         self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:63)
         self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
         self.x = torch.from_numpy(x0).to(**kw).contiguous()
         self.u = torch.from_numpy(u0).to(**kw).contiguous()
-        n, m = self.layout.n, self.layout.m
-        self.sol = torch.empty((self.B, n), **kw)
-        self.y = torch.empty((self.B, m), **kw)
-        self.status = torch.empty(self.B, **ikw)
-        self.iters = torch.empty(self.B, **ikw)
         self.skipped = torch.zeros(self.B, **ikw)
         self.steps_taken = torch.zeros(self.B, **ikw)
         self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
         self.traj_len = torch.zeros(self.B, **ikw)
-        self.last = None
-        # every kernel of a step runs on this stream, in order (see DynamicMPC)
-        self.stream = torch.cuda.Stream(self.dev)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            self.pred_x, self.pred_u = rollout_kin(self.veh, self.x, self.u, self.N)
-        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        self._start()
 
-    def step(self):
-        """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
-        Asynchronous: ordered after the caller's current stream, and the caller's stream
-        is ordered after the step."""
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            out = self._step()
-        caller.wait_stream(self.stream)
-        return out
+    def _initial_horizon(self):
+        self.pred_x, self.pred_u = rollout_kin(self.veh, self.x, self.u, self.N)
 
-    def _step(self):
-        L = _bind()
-        torch = self.torch
-        N = self.N
-        Xr = reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred_x, self.veh.dt)
-        Ad, Bd, gd = linearise_kinematics(self.veh, self.pred_x[:, :N], self.pred_u[:, :N], self.dev.index or 0)
-        Ax, q, l, u = self.layout.assemble(Ad, Bd, gd, self.x, Xr)
-        st = _stream(torch, self.dev)  # self.stream
-        self.solver.setup(self.Px, Ax, q, l, u, stream=st)
-        if self.shift_warm and self.have_sol:
-            xs, ys = warm_shift(N, 4, 2, self.sol, self.y)
-            self.solver.warm_start(xs, ys, stream=st)
-        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
-        self.have_sol = True
+    def _reference(self):
+        return reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred_x,
+                                    self.veh.dt)
+
+    def _horizon(self):
+        return self.x, self.pred_x, self.pred_u
+
+    def _shift(self, L, Ad, Bd, gd, Xr, st):
         _check(L.mpcqp_kin_ltv_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(self.status),
                                             _p(Ad), _p(Bd), _p(gd), _p(self.x), _p(self.u), _p(self.pred_x),
                                             _p(self.pred_u), _p(self.skipped), _p(self.steps_taken), _p(self.traj),
                                             self.traj_cap, _p(self.traj_len), st), "kin_ltv_shift")
-        self.last = dict(Ad=Ad, Bd=Bd, gd=gd, Xr=Xr, Ax=Ax, q=q, l=l, u=u)
-        return self.status, self.iters
 
     def run(self, steps):
         """`steps` calls of step(); returns the last (status, iters)."""
