@@ -491,6 +491,42 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout *L, const mpcqp_kin_vehicl
                                int32_t *dskipped, int32_t *dsteps_taken, double *dtraj, int32_t traj_cap,
                                int32_t *dtraj_len, void *stream);
 
+/* ======================================================================
+ * The closed loop that keeps one problem alive: vehicle_lateral_mpc_slack_increment.py
+ * (setup once :121, then per step update(q=, l=, u=) :237 and a warm-started solve :248).
+ * q, l, u come from mpcqp_affine_apply_device, the update and the solve from
+ * mpcqp_update_device / mpcqp_solve_device; this is the tail of the loop (:252-269).
+ * ====================================================================== */
+
+/* For any LTI model x~+ = At x~ + Bt du with nxa <= 8 states and 1 <= nu <= min(2, nxa) inputs
+ * (else MPCQP_EUNSUPPORTED; so is nsw > 8).  At (nxa x nxa) and Bt (nxa x nu) are HOST arrays,
+ * row-major; switch_steps[nsw] and regimes[nsw + 1] are HOST arrays too.  Everything else is
+ * on the device: sol[b*n] with du_0[j] = sol[b*n + du_off + j] and the recorded slack
+ * sol[b*n + slack_off] (slack_off < 0: none, 0 is recorded), status[b] the solver's code,
+ * x~ of vehicle b at xt[b*xt_stride .. + nxa) (in/out), and int32[B] step, regime, failed,
+ * fail_step, traj_len.
+ *
+ * A vehicle with failed[b] != 0 is left untouched.  If status[b] != MPCQP_SOLVED (`solved
+ * inaccurate` included) -- the script's raise, :252-253 -- failed[b] = 1, fail_step[b] = step[b]
+ * and nothing else of the vehicle changes, on this call or any later one.  Otherwise:
+ *   1. while traj_len[b] < traj_cap, append a row of nxa + nu + 1 doubles to
+ *      traj[(b*traj_cap + traj_len[b])*(nxa + nu + 1)] and count it: the first nxa - nu states
+ *      BEFORE the step, the last nu states AFTER it, du_0, the slack (the script's plt_x_1..4,
+ *      plt_u, plt_del_u, plt_s);
+ *   2. plant step, every product and every sum rounded on its own (no fused multiply-add), per
+ *      row i:  acc = At[i][0] x[0];  acc = acc + At[i][j] x[j] for j = 1..nxa-1 in order;
+ *      bu = Bt[i][0] du[0] (+ Bt[i][1] du[1]);  x+[i] = acc + bu  -- the order
+ *      osqp_amd.mpc.lti_step restates on the host, bit for bit;
+ *   3. step[b] += 1, then regime[b] = regimes[#{j < nsw : step[b] > switch_steps[j]}]: the
+ *      regime the NEXT step assembles with (the script: switch_steps (400, 900), regimes
+ *      (0, 1, 0), :158-172).
+ * traj / traj_len may be NULL when traj_cap is 0. */
+int mpcqp_lti_step_device(int64_t B, int32_t nxa, int32_t nu, const double *At, const double *Bt, int32_t n,
+                          int32_t du_off, int32_t slack_off, const double *dsol, const int32_t *dstatus, double *dxt,
+                          int64_t xt_stride, int32_t nsw, const int32_t *switch_steps, const int32_t *regimes,
+                          int32_t *dstep, int32_t *dregime, int32_t *dfailed, int32_t *dfail_step, double *dtraj,
+                          int32_t traj_cap, int32_t *dtraj_len, int32_t device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

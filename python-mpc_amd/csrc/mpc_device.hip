@@ -15,6 +15,9 @@
 // same two assembly kernels), with the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:main:
 //       k_kin_rollout                 initial horizon (nonlinear Euler)       :405-419
 //       k_kin_ltv_shift               skip rule, record, plant step, shift    :479-563
+// and the one closed loop that keeps its problem alive, vehicle_lateral_mpc_slack_increment.py
+// (setup once, update(q, l, u) + warm-started solve per step; k_affine assembles its vectors):
+//       k_lti_step                    raise rule, record, plant step, schedule :158-172, :252-269
 // The two bicycles are model structs (DynamicBicycle, KinematicBicycle) over which the
 // linearisation and the reference walk are written once; the three shift kernels share the plant
 // step, the trajectory append and kin_update, and keep their own shift and terminal-state rules.
@@ -635,6 +638,69 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     if (steps_taken) steps_taken[b] += 1;
 }
 
+// ---- the LTI closed loop that keeps one problem alive (vehicle_lateral_mpc_slack_increment.py) ----
+// The model x~+ = At x~ + Bt du and the step schedule of the bound regimes, by value.
+struct LtiK {
+    int nxa, nu, n, du_off, slack_off, nsw;
+    int sw[8], reg[9];          // regime = reg[#{j < nsw : step > sw[j]}]
+    double At[64], Bt[16];      // row-major nxa x nxa, nxa x nu
+};
+
+// x+ = At x + Bt du with every product and every sum rounded on its own, in this order, so that
+// osqp_amd.mpc.lti_step reproduces it bit for bit in numpy: per row acc = At[i][0] x[0], then
+// + At[i][j] x[j] for j = 1.., bu = Bt[i][0] du[0] (+ Bt[i][1] du[1]), x+[i] = acc + bu.
+__device__ __forceinline__ void lti_plant_step(const LtiK& K, const double* x, const double* du, double* xnext) {
+#pragma clang fp contract(off)
+    const int nxa = K.nxa, nu = K.nu;
+    for (int i = 0; i < nxa; ++i) {
+        double acc = K.At[i * nxa] * x[0];
+        for (int j = 1; j < nxa; ++j) acc = acc + K.At[i * nxa + j] * x[j];
+        double bu = K.Bt[i * nu] * du[0];
+        for (int j = 1; j < nu; ++j) bu = bu + K.Bt[i * nu + j] * du[j];
+        xnext[i] = acc + bu;
+    }
+}
+
+// Tail of the slack script's loop (:252-269), per vehicle: the `raise` on a solve that did not
+// end `solved` (the vehicle is frozen: failed, fail_step), the record (plt_x_1..4, plt_u,
+// plt_del_u, plt_s: the states the step started from, the control after it, du_0, the slack),
+// the plant step, and the step counter with the bound regime the NEXT step assembles with
+// (:158-172).  xt: x~ of vehicle b at xt[b * xt_stride], in/out.
+__global__ __launch_bounds__(128) void k_lti_step(LtiK K, long B, const double* __restrict__ sol,
+                                                  const int* __restrict__ status, double* __restrict__ xt,
+                                                  long xt_stride, int* __restrict__ step, int* __restrict__ regime,
+                                                  int* __restrict__ failed, int* __restrict__ fail_step,
+                                                  double* __restrict__ traj, int traj_cap,
+                                                  int* __restrict__ traj_len) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (failed[b]) return;
+    if (status[b] != MPCQP_SOLVED) {
+        failed[b] = 1;
+        fail_step[b] = step[b];
+        return;
+    }
+    const int nxa = K.nxa, nu = K.nu;
+    const double* s = sol + b * K.n;
+    double* xb = xt + b * xt_stride;
+    double x[8], xnext[8], du[2];
+    for (int i = 0; i < nxa; ++i) x[i] = xb[i];
+    for (int j = 0; j < nu; ++j) du[j] = s[K.du_off + j];
+    lti_plant_step(K, x, du, xnext);
+    if (double* tr = traj_append(traj, traj_cap, traj_len, b, nxa + nu + 1)) {
+        for (int i = 0; i < nxa - nu; ++i) tr[i] = x[i];
+        for (int i = nxa - nu; i < nxa; ++i) tr[i] = xnext[i];
+        for (int j = 0; j < nu; ++j) tr[nxa + j] = du[j];
+        tr[nxa + nu] = K.slack_off >= 0 ? s[K.slack_off] : 0.0;
+    }
+    for (int i = 0; i < nxa; ++i) xb[i] = xnext[i];
+    const int k = step[b] + 1;
+    step[b] = k;
+    int r = 0;
+    for (int j = 0; j < K.nsw; ++j) r += k > K.sw[j] ? 1 : 0;
+    regime[b] = K.reg[r];
+}
+
 // ---- F1 for the LTI (lateral) layouts: affine vector assembly ----
 // vehicle_lateral_mpc_slack_increment.py:32-121 / its loop :201-229 and
 // Control/MPC/mpc_kinematics.py:148-191 rebuild P, q, A, l, u every step although with the
@@ -1062,6 +1128,28 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicl
     if (B == 0) return 0;
     return launch(L->dev, stream, B, 128, k_kin_ltv_shift, *veh, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
                   dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
+}
+
+int mpcqp_lti_step_device(int64_t B, int32_t nxa, int32_t nu, const double* At, const double* Bt, int32_t n,
+                          int32_t du_off, int32_t slack_off, const double* dsol, const int32_t* dstatus, double* dxt,
+                          int64_t xt_stride, int32_t nsw, const int32_t* switch_steps, const int32_t* regimes,
+                          int32_t* dstep, int32_t* dregime, int32_t* dfailed, int32_t* dfail_step, double* dtraj,
+                          int32_t traj_cap, int32_t* dtraj_len, int32_t device, void* stream) {
+    if (nxa < 1 || nxa > 8 || nu < 1 || nu > 2 || nu > nxa || nsw > 8)
+        return set_error(MPCQP_EUNSUPPORTED, "lti_step: need 1 <= nxa <= 8, 1 <= nu <= min(2, nxa), nsw <= 8");
+    if (!At || !Bt || !dsol || !dstatus || !dxt || !regimes || !dstep || !dregime || !dfailed || !dfail_step ||
+        B < 0 || nsw < 0 || (nsw > 0 && !switch_steps) || n < 1 || du_off < 0 || du_off + nu > n || slack_off >= n ||
+        xt_stride < nxa || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "lti_step: bad arguments");
+    if (B == 0) return 0;
+    LtiK K = {};
+    K.nxa = nxa; K.nu = nu; K.n = n; K.du_off = du_off; K.slack_off = slack_off; K.nsw = nsw;
+    std::copy(At, At + nxa * nxa, K.At);
+    std::copy(Bt, Bt + nxa * nu, K.Bt);
+    std::copy(switch_steps, switch_steps + nsw, K.sw);
+    std::copy(regimes, regimes + nsw + 1, K.reg);
+    return launch(device, stream, B, 128, k_lti_step, K, B, dsol, dstatus, dxt, xt_stride, dstep, dregime, dfailed,
+                  dfail_step, dtraj, traj_cap, dtraj_len);
 }
 
 int mpcqp_incr_warm_shift_device(int64_t B, int32_t N, int32_t nxa, int32_t nu, const double* dx, const double* dy,

@@ -147,6 +147,66 @@ def slack_qp(N, x0, xr=None, regime=0):
     return _csc(P), q, _csc(A), np.concatenate([leq, lineq]), np.concatenate([leq, uineq])
 
 
+SLACK_SWITCH_STEPS = (400, 900)                              # :158-172: i <= 400 / i <= 900 / else
+SLACK_REGIMES = (0, 1, 0)
+
+
+def slack_regime(k, switch_steps=SLACK_SWITCH_STEPS, regimes=SLACK_REGIMES):
+    """The bound regime step k assembles with (the script's if / elif / else, :158-172):
+    regimes[#{j : k > switch_steps[j]}], elementwise over k."""
+    k = np.asarray(k)
+    r = sum((k > s).astype(np.int64) for s in switch_steps) if len(switch_steps) else np.zeros(k.shape, np.int64)
+    return np.asarray(regimes, np.int32)[r]
+
+
+def lti_step(At, Bt, sol, status, xt, step, regime, failed, fail_step, du_off, slack_off=-1,
+             switch_steps=SLACK_SWITCH_STEPS, regimes=SLACK_REGIMES, traj=None, traj_len=None):
+    """The tail of the slack script's loop (:252-269) for B vehicles: the arithmetic of
+    mpc_device.hip::k_lti_step (mpcqp_lti_step_device) in numpy, in the kernel's operation order
+    (elementwise numpy rounds every product and every sum on its own, as the kernel does).
+
+    At (nxa, nxa), Bt (nxa, nu); sol (B, n) with du_0 = sol[:, du_off:du_off + nu] and the
+    recorded slack sol[:, slack_off] (slack_off < 0: 0); status (B,) solver codes; xt (B, nxa);
+    step, regime, failed, fail_step (B,) int32; traj (B, traj_cap, nxa + nu + 1) and traj_len (B,)
+    or None.  Nothing is modified; returns (xt, step, regime, failed, fail_step, traj, traj_len).
+
+    A failed vehicle is returned unchanged.  One whose status is not 1 (`solved`) gets failed = 1
+    and fail_step = step -- the script's raise -- and is otherwise unchanged.  Every other one:
+    record row (first nxa - nu states before the step, last nu after it, du_0, slack) while
+    traj_len < traj_cap; x+ = At x + Bt du_0; step += 1; regime = slack_regime(step)."""
+    At = np.asarray(At, float); Bt = np.asarray(Bt, float)
+    nxa, nu = Bt.shape
+    xt = np.array(xt, float); sol = np.asarray(sol, float)
+    step, regime, failed, fail_step = (np.array(a, np.int32) for a in (step, regime, failed, fail_step))
+    live = failed == 0
+    bad = live & (np.asarray(status) != 1)
+    go = live & ~bad
+    fail_step[bad] = step[bad]
+    failed[bad] = 1
+    x = xt[:, :nxa]
+    du = sol[:, du_off:du_off + nu]
+    xn = np.empty_like(x)
+    for i in range(nxa):
+        acc = At[i, 0] * x[:, 0]
+        for j in range(1, nxa):
+            acc = acc + At[i, j] * x[:, j]
+        bu = Bt[i, 0] * du[:, 0]
+        for j in range(1, nu):
+            bu = bu + Bt[i, j] * du[:, j]
+        xn[:, i] = acc + bu
+    if traj is not None:
+        traj = np.array(traj, float); traj_len = np.array(traj_len, np.int32)
+        slack = sol[:, slack_off] if slack_off >= 0 else np.zeros(len(xt))
+        row = np.concatenate([x[:, :nxa - nu], xn[:, nxa - nu:], du, slack[:, None]], axis=1)
+        rec = np.flatnonzero(go & (traj_len >= 0) & (traj_len < traj.shape[1]))
+        traj[rec, traj_len[rec]] = row[rec]
+        traj_len[rec] += 1
+    xt[go, :nxa] = xn[go]
+    step[go] += 1
+    regime[go] = slack_regime(step[go], switch_steps, regimes)
+    return xt, step, regime, failed, fail_step, traj, traj_len
+
+
 # ------------------------------------------------------- incremental LTV (cfg 5) --
 def incremental_qp(Ad_list, Bd_list, gd_list, xt0, Xr, Q, QN, R, N, xmin_t, xmax_t, dumin, dumax):
     """Control/MPC/mpc_dynamics.py:281-389 (`mpc_increment`): augmented LTV MPC in increments."""

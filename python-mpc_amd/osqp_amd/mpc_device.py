@@ -20,6 +20,10 @@ mpcqp_kin_reference_search_device, mpcqp_kin_shift_device).
 LTVLayout is the LTV MPC in the inputs themselves (mpc__, mpc_dynamics.mpc, mpc_'s corridor;
 mpcqp_ltv_*), and KinematicLTVMPC the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:
 main (:355-563) on it (mpcqp_kin_rollout_device, mpcqp_kin_ltv_shift_device).
+
+LateralMPC is the closed loop of vehicle_lateral_mpc_slack_increment.py (:123-269), the one loop
+that keeps a problem alive: one setup, then per step LateralAssembler -> DeviceBatch.update ->
+warm-started DeviceBatch.solve -> mpcqp_lti_step_device.
 """
 from __future__ import annotations
 
@@ -54,6 +58,7 @@ class KinVehicle(C.Structure):
 
 # structural nonzeros of get_dynamics_model's Ad and Bd (kept under these names here too)
 from .mpc import DYN_MASK_A, DYN_MASK_B  # noqa: E402
+from .mpc import SLACK_REGIMES, SLACK_SWITCH_STEPS  # noqa: E402  (the slack script's bound schedule)
 
 
 def _bind():
@@ -87,6 +92,8 @@ def _bind():
     L.mpcqp_ltv_layout_free.restype = None
     L.mpcqp_kin_rollout_device.argtypes = [_P(KinVehicle), i64, i32, vp, vp, vp, vp, i32, vp]
     L.mpcqp_kin_ltv_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 12 + [i32, vp, vp]
+    L.mpcqp_lti_step_device.argtypes = [i64, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp,
+                                        vp, vp, i32, vp, i32, vp]
     L._mpc_bound = True
     return L
 
@@ -392,6 +399,8 @@ class _ClosedLoop:
     ``_setup`` (solver, path, solve outputs), allocates its own state tensors and calls
     ``_start``; it states ``_linearise`` (the model's linearisation), ``_initial_horizon``,
     ``_reference``, ``_horizon`` (initial state, predicted states, predicted inputs) and ``_shift``.
+    (LateralMPC, whose problem outlives the step, takes only ``step`` / ``_on_stream`` from here and
+    states its own ``_step``.)
 
     Every kernel of a step runs on ``self.stream``, in order; a null (legacy default) torch
     stream would be passed as NULL, which the solver's C ABI reads as "the handle's own
@@ -782,4 +791,126 @@ class KinematicLTVMPC(_ClosedLoop):
     def trajectories(self):
         """(traj, traj_len) as host arrays: traj (B, traj_cap, 6) = x, y, v, yaw, steer, accel;
         traj_len[b] rows of traj[b] are filled, one per executed step."""
+        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
+
+
+# ------------------------------------------- the loop that keeps one problem alive --
+class LateralMPC(_ClosedLoop):
+    """B copies of vehicle_lateral_mpc_slack_increment.py's closed loop (:123-269), every step
+    on the device: the one loop of the reference that keeps ONE osqp object alive -- setup()
+    once with warm_start=True (:121), then per step update(q=, l=, u=) (:237) and a solve that
+    starts from the previous step's iterates (:248).
+
+    x0 is (B, 5): x~ = (beta, r, e_psi, e_y, u_prev), the script's own (0, 0, 5 deg, 3, 0); xr is
+    (B, 4), default 0; step0 (B,) int, default 0, is the schedule step each vehicle starts at,
+    so one batch can hold vehicles in different bound regimes (:158-172: switch_steps, regimes).
+    ``theta`` (B, 9) = (x~, xr) is live: ``xt`` = theta[:, :5] is advanced by every step, and
+    ``xr`` = theta[:, 5:] may be written between steps (the script's "dynamic reference", :125-129).
+
+    Construction sets the problem up from assemble(theta, regime 0), as :87-121 set it up before
+    the loop.  ``step()`` = LateralAssembler.assemble(theta, regime) -> DeviceBatch.update(q, l, u)
+    -> DeviceBatch.solve -> mpcqp_lti_step_device (raise rule, record, plant step, schedule).
+    The script's second update(l=, u=) with the new initial state (:267-269) is dropped: the
+    next step's update overwrites it before any solve, and a bounds update only stores scaled
+    data (no iterate, no rho changes with it).
+
+    Failure rule (:252-253): a vehicle whose solve did not end `solved` (`solved inaccurate`
+    included) is frozen where the script raises -- ``failed`` = 1, ``fail_step`` = its step
+    counter, and xt, ``steps``, ``regime`` and its record never change again.  It is still
+    solved with the rest of the batch; its solution is discarded.
+
+    ``trajectories()`` gives (traj (B, traj_cap, 7), traj_len): plt_x_1..4 (the state a step
+    started from), plt_u (the control after it), plt_del_u, plt_s, one row per executed step,
+    rows beyond traj_cap dropped.
+
+    Settings are the script's (warm_start=True, everything else OSQP's default) unless given."""
+
+    def __init__(self, x0, xr=None, N=20, step0=None, device=0, traj_cap=0, switch_steps=SLACK_SWITCH_STEPS,
+                 regimes=SLACK_REGIMES, **solver_settings):
+        import torch
+        from . import mpc
+        self.torch = torch
+        self.dev = torch.device("cuda", device)
+        self.N = int(N)
+        x0 = np.atleast_2d(np.asarray(x0, np.float64))
+        self.B = B = x0.shape[0]
+        xr = np.zeros((B, 4)) if xr is None else np.atleast_2d(np.asarray(xr, np.float64))
+        step0 = np.zeros(B, np.int32) if step0 is None else np.asarray(step0, np.int32).reshape(-1)
+        if x0.shape != (B, 5) or xr.shape != (B, 4) or step0.shape != (B,):
+            raise ValueError("x0 must be (B, 5), xr (B, 4) and step0 (B,)")
+        self.switch_steps = np.ascontiguousarray(switch_steps, np.int32).reshape(-1)
+        self.regimes = np.ascontiguousarray(regimes, np.int32).reshape(-1)
+        if self.regimes.size != self.switch_steps.size + 1 or self.switch_steps.size > 8:
+            raise ValueError("regimes must have one entry more than switch_steps (at most 8)")
+        self.asm = LateralAssembler("slack", N=self.N, device=device)
+        if self.regimes.min() < 0 or self.regimes.max() >= self.asm.nregimes:
+            raise ValueError(f"regimes must lie in [0, {self.asm.nregimes})")
+        At, Bt = mpc.augment(mpc.LATERAL_AD, mpc.LATERAL_BD)
+        self.At, self.Bt = np.ascontiguousarray(At), np.ascontiguousarray(Bt)
+        self.nxa, self.nu = self.Bt.shape
+        # x = (x~_0..x~_N, du_0..du_{N-1}, s_0..s_N): du_0 (:256) and the slack of e_y in s_0 (:259)
+        self.du_off = (self.N + 1) * self.nxa
+        self.slack_off = self.du_off + self.N * self.nu + 3
+        settings = {"warm_start": True, **solver_settings}                 # :121
+        settings.pop("verbose", None)
+        self.solver = DeviceBatch(self.asm.P, self.asm.A, B, device=device, **settings)
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.Px, self.Ax = (torch.from_numpy(v).to(**kw).contiguous() for v in self.asm.matrices())
+        self.theta = torch.from_numpy(np.concatenate([x0, xr], axis=1)).to(**kw).contiguous()
+        self.xt, self.xr = self.theta[:, :5], self.theta[:, 5:]
+        self.steps = torch.from_numpy(step0.copy()).to(**ikw)
+        self.regime = torch.from_numpy(mpc.slack_regime(step0, self.switch_steps, self.regimes)).to(**ikw)
+        self.failed = torch.zeros(B, **ikw)
+        self.fail_step = torch.zeros(B, **ikw)
+        self.traj_cap = int(traj_cap)
+        self.traj = torch.zeros((B, max(self.traj_cap, 1), self.nxa + self.nu + 1), **kw)
+        self.traj_len = torch.zeros(B, **ikw)
+        n, m = self.asm.n, self.asm.m
+        self.q, self.l, self.u = torch.empty((B, n), **kw), torch.empty((B, m), **kw), torch.empty((B, m), **kw)
+        self.sol, self.y = torch.empty((B, n), **kw), torch.empty((B, m), **kw)
+        self.status, self.iters = torch.empty(B, **ikw), torch.empty(B, **ikw)
+        self.last = None
+        self.stream = torch.cuda.Stream(self.dev)
+        self._on_stream(self._setup_problem)
+
+    def _setup_problem(self):
+        st = _stream(self.torch, self.dev)  # self.stream
+        self.asm.assemble(self.theta, None, out=(self.q, self.l, self.u), stream=st)
+        self.solver.setup(self.Px, self.Ax, self.q, self.l, self.u, stream=st)
+
+    def _step(self):
+        st = _stream(self.torch, self.dev)  # self.stream
+        self.asm.assemble(self.theta, self.regime, out=(self.q, self.l, self.u), stream=st)
+        self.solver.update(self.q, self.l, self.u, stream=st)
+        self.solver.solve(self.sol, self.y, self.status, self.iters, stream=st)
+        self._tail(st)
+        self.last = dict(q=self.q, l=self.l, u=self.u)
+        return self.status, self.iters
+
+    def _tail(self, st):
+        """The loop's tail (:252-269) from sol / status: mpcqp_lti_step_device on stream `st`."""
+        _check(_bind().mpcqp_lti_step_device(
+            self.B, self.nxa, self.nu, _np_ptr(self.At), _np_ptr(self.Bt), self.asm.n, self.du_off, self.slack_off,
+            _p(self.sol), _p(self.status), _p(self.theta), self.theta.stride(0), self.switch_steps.size,
+            _np_ptr(self.switch_steps), _np_ptr(self.regimes), _p(self.steps), _p(self.regime), _p(self.failed),
+            _p(self.fail_step), _p(self.traj), self.traj_cap, _p(self.traj_len), self.dev.index or 0, st), "lti_step")
+
+    def run(self, nsim, strict=False, check_every=64):
+        """`nsim` calls of step(); returns the last (status, iters).  With `strict`, ``failed`` is
+        read back (one host synchronisation) every `check_every` steps and after the last one,
+        and the script's ValueError('OSQP did not solve the problem!') is raised once any
+        vehicle has failed -- up to check_every - 1 steps after it did."""
+        check_every, nsim = max(int(check_every), 1), int(nsim)
+        out = None
+        for k in range(1, nsim + 1):
+            out = self.step()
+            if strict and (k % check_every == 0 or k == nsim) and bool(self.failed.any().item()):
+                raise ValueError("OSQP did not solve the problem!")
+        return out
+
+    def trajectories(self):
+        """(traj, traj_len) as host arrays: traj (B, traj_cap, 7) = beta, r, e_psi, e_y before the
+        step, u after it, du_0, the slack of e_y; traj_len[b] rows of traj[b] are filled, one per
+        executed step."""
         return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
