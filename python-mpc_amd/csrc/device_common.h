@@ -250,9 +250,14 @@ __device__ __forceinline__ double xmax_swap(double v) {
 // instructions of K separate DPP trees.  The sums keep block_sum's order (wave_sum, then
 // wave 0 + wave 1 + ...), so they are bit-identical to it.  red: 4 * NW * K2 + NW * KS
 // doubles, 16-byte aligned.
-template <int TT, int K, int KS>
+// LANE (four waves): after the LDS round lane k < K folds value k over the waves and lane K + k
+// forms sum k -- the same folds in the same order -- and every lane takes the K + KS results
+// by v_readlane, instead of every lane reading all 4 (K + KS) partials back (76 broadcast LDS
+// reads a lane for K = 17, against two).  Called by all lanes of the workgroup together.
+template <int TT, int K, int KS, bool LANE = false>
 __device__ __forceinline__ void block_max_sum_tr(double (&v)[K], double (&sm)[KS], double* red) {
     constexpr int NW = TT / 64, K1 = (K + 1) / 2, K2 = (K1 + 1) / 2;
+    static_assert(!LANE || (NW == 4 && K + KS <= 64), "the lane form: four waves, a lane per result");
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     double t1[K1], t2[K2];
     tmax_step<0xB1, K>(v, t1, lane & 1);          // quad_perm [1,0,3,2]: lane ^ 1
@@ -286,6 +291,34 @@ __device__ __forceinline__ void block_max_sum_tr(double (&v)[K], double (&sm)[KS
         for (int k = 0; k < KS; ++k) rs[wq * KS + k] = s[k];
     }
     __syncthreads();
+    if constexpr (LANE) {
+        int lq = lane;
+        asm volatile("" : "+v"(lq));  // (as at the writes above: the read addresses are formed here)
+        const int k = lq < K ? lq : 0, b0 = k >= K1, r1 = k - K1 * b0, b1 = r1 >= K2, j = r1 - K2 * b1;
+        const double* src = red + ((b0 + 2 * b1) * K2 + j) * NW;
+        double r = src[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) r = vmax(r, src[w]);
+        const int ks = (lq >= K && lq < K + KS) ? lq - K : 0;
+        const double s4 = (rs[ks] + rs[KS + ks]) + (rs[2 * KS + ks] + rs[3 * KS + ks]);  // block_sum's order
+        const double res = lq < K ? r : s4;
+        const int lo = __double2loint(res), hi = __double2hiint(res);
+        // (the results into vector registers through an empty asm: what the caller derives from
+        // them -- rho -- stays a per-lane value, as from the LDS reads of the general form, and
+        // takes no scalar register across the solve loop)
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            v[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, q), __builtin_amdgcn_readlane(lo, q));
+            asm volatile("" : "+v"(v[q]));
+        }
+#pragma unroll
+        for (int q = 0; q < KS; ++q) {
+            sm[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, K + q), __builtin_amdgcn_readlane(lo, K + q));
+            asm volatile("" : "+v"(sm[q]));
+        }
+        __syncthreads();
+        return;
+    }
     if constexpr (NW > 4) {
         // eight waves: thread k < K folds value k over the waves first (every thread
         // loading all K x NW partials would hold them all in registers at once)

@@ -1201,6 +1201,13 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     // eliminated columns and amax <= 5, the headline's instantiation.  Its tiles never leave LDS
     // (no RU / factor_only copy, no dense rows); the other instantiations' stay row-major
     constexpr bool SWZ = ONE && GL == 1 && !EL && !DK && QR <= 5;
+    // LEAN (the same instantiation): the work between its ADMM runs cut to what the result needs
+    // -- the run start reads the G blocks where the factorisation left them (no gl copy) and
+    // divides once, the check takes its column list from the run's registers and combines the
+    // waves' maxima a lane each (block_max_sum_tr's LANE), and the rho step keeps the check's
+    // residuals in registers.  Every floating-point operation, operand and order is the
+    // general code's
+    constexpr bool LEAN = SWZ;
 
     if (p.err[b]) {
         for (int j = tid; j < n; j += T4) if (xo) xo[b * n + j] = __builtin_nan("");
@@ -1364,7 +1371,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 const auto yp = opaque_gptr(p.y + b * m);
                 for (int i = tid; i < mp; i += T4) L.ys[i] = (have_y && i < m) ? yp[i] : 0.0;
             }
-            if constexpr (GL != 2) {
+            if constexpr (GL != 2 && !LEAN) {  // (LEAN: the run start reads the blocks at Hg)
                 for (int o = tid; o < (NP + 1) * 8 * S; o += T4) {
                     const int q = o >> 8, t = (o >> 5) & 7;
                     L.gl[o] = (q < NP && t < p.amax) ? Hg[(long)q * p.amax * S + (o & 255)] : 0.0;
@@ -1426,6 +1433,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         const double Q = L.qv[xc];
         // phase-C slots: pairs (j, w), j > w, split over the halves; pair NP is zero
         int gslot[2], tslot[2];
+        bool gz[2];  // (LEAN) the slot's pair is the zero pair
         {
             int pr[2] = {NP, NP}, jj[2] = {3, 3};
             if (w == 0) {
@@ -1439,7 +1447,11 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                gslot[s] = lds_addr(L.gl + pr[s] * 8 * S + r);
+                // (LEAN: column r of the pair's block at Hg, amax rows; the zero pair's lanes
+                // read pair 0 and take zeros below)
+                gslot[s] = LEAN ? lds_addr(Hg + (pr[s] < NP ? pr[s] : 0) * p.amax * S + r)
+                                : lds_addr(L.gl + pr[s] * 8 * S + r);
+                gz[s] = pr[s] == NP;
                 tslot[s] = lds_addr(L.tv + jj[s] * 8);
             }
         }
@@ -1463,11 +1475,25 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         const double rlo = L.lo[ri], rup = L.up[ri];
         const signed char cl = L.ct[ri];
         const double rv = cl < 0 ? RHO_MIN : (cl > 0 ? r_hi : rho);
-        const double rvi = cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho);
+        // (LEAN: one division, of the class's own rv -- the operands of the one selected below)
+        const double rvi = LEAN ? 1.0 / rv : (cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho));
         __syncthreads();  // (the G copy of a refactorisation is complete)
         // phase A's G values (rows rr < 8 of G_wj, columns [4 ch, 4 ch + 4), j < w) in registers for the run
         double ga[NB - 1][4];
-        if constexpr (!DK) {
+        if constexpr (LEAN) {
+            // rows rr < amax at Hg (pair stride amax S: the factorisation's own layout, after
+            // its closing barrier); the copy's zero rows are constants
+            const int gs = p.amax * S * 8;
+            const unsigned gq = lds_addr(Hg) + (w * (w - 1) / 2) * gs + (rr * S + 4 * ch) * 8;
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j) {
+                ga[j][0] = ga[j][1] = ga[j][2] = ga[j][3] = 0.0;
+                if (j < w && rr < p.amax) {
+                    lds_at2(gq + j * gs, ga[j][0], ga[j][1]);
+                    lds_at2(gq + j * gs + 16, ga[j][2], ga[j][3]);
+                }
+            }
+        } else if constexpr (!DK) {
             const double* gq = L.gl + (w * (w - 1) / 2) * 8 * S + rr * S + 4 * ch;
 #pragma unroll
             for (int j = 0; j < NB - 1; ++j) {
@@ -1481,7 +1507,13 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         }
         // phase C's G values (column r of the slots' pairs, rows < QR) in registers for the run
         double gc[2][QR];
-        if constexpr (!DK) {
+        if constexpr (LEAN) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int q = 0; q < QR; ++q)
+                    gc[s][q] = (s < nsw && !gz[s] && q < p.amax) ? lds_at(gslot[s] + q * S * 8) : 0.0;
+        } else if constexpr (!DK) {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -1492,7 +1524,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
         if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
         __syncthreads();
-        PH(5)
+        PH(15)  // (the run starts; slot 5 keeps the kernel's start and finalize)
         double* const cw = L.cor + w * 8;                 // c_w rows < 8
         const double* const cwh = L.cor + (h ? 32 : w * 8);  // the half's correction (upper half: zeros)
         while (iter < stop_at) {
@@ -1696,16 +1728,28 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         if (!can_check && !do_rho) break;
         info_iter = iter;
         bool stop = false;
+        Res Rk;  // (LEAN) the check's residuals, for the rho step
         {
             // the check's per-lane operands come from the plan (shared by every instance: L2
             // hits) and the workspace here, not from registers held through the run: the lane's
             // column (EL: the upper half checks its eliminated column pe) with its A and P lists
             // and D, the row's E
             const int col = EL ? (low ? pc : pe) : pc;
-            const bool cv = col >= 0 && (EL || low) && opaque_gptr(p.pad_var)[col] >= 0;
+            // (LEAN: col is pc, so cv is the run's colv and the column list is the run's own chs:
+            // half h holds entries [h KH, h KH + KH) in the same encoding, and one permlane32
+            // swap gives every lane both halves' -- no global load at the head of the check)
+            const bool cv = LEAN ? colv : col >= 0 && (EL || low) && opaque_gptr(p.pad_var)[col] >= 0;
             GatherW<KC> cg;
             GatherW<KPK> pg;
-            if (col >= 0) {
+            if constexpr (LEAN) {
+#pragma unroll
+                for (int k = 0; k < KH; ++k) {
+                    const auto e2 = __builtin_amdgcn_permlane32_swap(chs.e[k], chs.e[k], false, false);
+                    cg.e[k] = e2[0];       // the lower half's: entry k
+                    cg.e[KH + k] = e2[1];  // the upper half's: entry KH + k
+                }
+                pg.load(p.gpsym + col, npad, lds_addr(L.Pv), Xbase);
+            } else if (col >= 0) {
                 cg.load(p.gcol + col, npad, abase, wbase);
                 pg.load(p.gpsym + col, npad, lds_addr(L.Pv), Xbase);
             } else {
@@ -1784,20 +1828,22 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 }
             }
             if (tid < npad && opaque_gptr(p.pad_var)[tid] >= 0) sm[1] = L.qv[tid + oz] * L.dx[tid + oz];
+            PH(6)  // (a check up to its reduction: write-back, operands, gathers)
             if (do_rho || !unscale) {
-                block_max_sum_tr<T4, 17, 2>(mx, sm, L.red);
+                block_max_sum_tr<T4, 17, 2, LEAN>(mx, sm, L.red);
             } else {
                 // a check that adapts no rho decides with the unscaled norms and the
                 // certificates' only: 10 maxima instead of 17 (R's scaled norms are then stale
                 // and unread: only a rho step restores them)
                 double m10[10] = {mx[0], mx[1], mx[2], mx[3], mx[4], mx[5], mx[6], mx[14], mx[15], mx[16]};
-                block_max_sum_tr<T4, 10, 2>(m10, sm, L.red);
+                block_max_sum_tr<T4, 10, 2, LEAN>(m10, sm, L.red);
 #pragma unroll
                 for (int k = 0; k < 7; ++k) mx[k] = m10[k];
                 mx[14] = m10[7];
                 mx[15] = m10[8];
                 mx[16] = m10[9];
             }
+            PH(7)  // (the reduction)
             Res R;
             if (unscale) {
                 R.pri = mx[0]; R.dua = cscal(1) * mx[1];
@@ -1809,6 +1855,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             R.rpri = mx[7]; R.rdua = mx[8]; R.rz = mx[9]; R.rax = mx[10]; R.rq = mx[11]; R.raty = mx[12]; R.rpx = mx[13];
             if (m == 0) R.pri = 0.0;
             if (tid == 0) R.save(L.res);
+            if constexpr (LEAN) Rk = R;
             if (can_check) {
                 int st = MPCQP_UNSOLVED_;
                 bool done = false;
@@ -1862,17 +1909,20 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                         done = true;
                     }
                 }
-                __syncthreads();
+                // (LEAN: nothing reads the flag before the pass-end barrier, and the rho step takes
+                // the residuals from Rk, not from thread 0's res)
+                if constexpr (!LEAN) __syncthreads();
                 // (the objective of an infeasible / non-convex status is set by finalize_ph)
                 if (done && tid == 0) L.flag[1] = st;
-                __syncthreads();
+                if constexpr (!LEAN) __syncthreads();
                 status = done ? st : MPCQP_UNSOLVED_;
                 stop = done;
             }
         }
         if (!stop && do_rho) {
             Res R;
-            R.restore(L.res);
+            if constexpr (LEAN) R = Rk;  // (every thread formed the same Res from the reduced maxima)
+            else R.restore(L.res);
             const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
             const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
             double rn = rho * sqrt(pr / (du + DIVISION_TOL));
@@ -1912,6 +1962,13 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
 #pragma unroll
             for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
             p.prof[b * kProfSlots + 2] = L.pacc[12] + L.pacc[13] + L.pacc[14];
+            // the check's and the tail's splits: slots 16-18 (a check up to its reduction, the
+            // reduction, the run starts); 4 and 5 keep their totals
+            p.prof[b * kProfSlots + 4] = L.pacc[4] + L.pacc[6] + L.pacc[7];
+            p.prof[b * kProfSlots + 5] = L.pacc[5] + L.pacc[15];
+            p.prof[b * kProfSlots + 16] = L.pacc[6];
+            p.prof[b * kProfSlots + 17] = L.pacc[7];
+            p.prof[b * kProfSlots + 18] = L.pacc[15];
             p.prof[b * kProfSlots + 6] = clock64() - t0c;
             p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
             p.prof[b * kProfSlots + 15] = t0w;
