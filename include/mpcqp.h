@@ -492,6 +492,69 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout *L, const mpcqp_kin_vehicl
                                int32_t *dtraj_len, void *stream);
 
 /* ======================================================================
+ * A bank of paths with a per-vehicle selection, and the two closed loops built on the layouts
+ * above that remain in Control/MPC: mpc_increment_kinematics_pred_matrix.main (:281-476, the
+ * double lane change) and mpc_kinematics.main (:268-461, one linearisation per step).
+ * ====================================================================== */
+
+/* mpcqp_kin_reference_search_device over `npaths` paths of npath points each: path p is
+ * paths_x / paths_y / paths_yaw[p*npath .. (p+1)*npath), and vehicle b walks path path_id[b]
+ * (int32[B]; NULL: path 0 for every vehicle).  A path_id outside [0, npaths) never indexes the
+ * bank: it is clamped to the nearest valid path (negative -> 0, too large -> npaths - 1).
+ * paths_yaw may be NULL: row 3 of Xr is then 0 on every point (the reference_search of
+ * mpc_increment_kinematics_pred_matrix.py:41-83 and mpc_kinematics.py:39-81).  The nearest-point
+ * search, the walk and the hold of the last segment are those of the one-path entry point; with
+ * npaths = 1 and path_id = NULL the output equals its output bit for bit. */
+int mpcqp_kin_reference_search_paths_device(int64_t B, int32_t N, int32_t nxa, int32_t npaths, int32_t npath,
+                                            const double *dpaths_x, const double *dpaths_y, const double *dpaths_yaw,
+                                            const int32_t *dpath_id, const double *dset_speed, const double *dpred,
+                                            double dt, double *dXr, int32_t device, void *stream);
+
+/* The tail of mpc_increment_kinematics_pred_matrix.main's loop (:423-472) for an incremental
+ * layout with nx 4, nu 2 (any other: MPCQP_EUNSUPPORTED; so is nsw > 8).  switch_steps[nsw] and
+ * paths_of[nsw + 1] are HOST arrays (the convention of mpcqp_lti_step_device); everything else
+ * is on the device.  There is no skip rule: mpc_increment uses the solution whatever the
+ * solver's status (:248-252).  Per vehicle b, in the reference's order:
+ *   1. while traj_len[b] < traj_cap, append (x, y, v, yaw, steer, accel) of xt[b*6] as the step
+ *      started -- plt_states / plt_actions, :423-424: the input is the one held BEFORE the
+ *      step -- to traj[(b*traj_cap + traj_len[b])*6] and count it;
+ *   2. plant step u = u_prev + du_0, x+ = Ad_0 x + Bd_0 u + gd_0 into xt[b*6] (:442-449);
+ *   3. horizon shift (:451-472) into pred[b*(N+1)*6], pred_du[b*(N+1)*2], as step 5 of
+ *      mpcqp_kin_shift_device (the same text in the reference: the terminal Euler step takes the
+ *      solution's stage-N state and stage-N control, v advanced before yaw reads it);
+ *   4. step[b] += 1, then path_id[b] = paths_of[#{j < nsw : step[b] > switch_steps[j]}]: the
+ *      path the NEXT step's reference search runs on (the script, sim_time 1000: switch_steps
+ *      (50, 150), paths_of (0, 1, 0), :380-391).  paths_of is not range-checked here; the
+ *      search clamps.
+ * step, path_id, traj_len: int32[B].  traj / traj_len may be NULL when traj_cap is 0. */
+int mpcqp_lane_tail_device(const mpcqp_incr_layout *L, const mpcqp_kin_vehicle *veh, int64_t B, const double *dsol,
+                           const double *dAd, const double *dBd, const double *dgd, double *dxt, double *dpred,
+                           double *dpdu, int32_t nsw, const int32_t *switch_steps, const int32_t *paths_of,
+                           int32_t *dstep, int32_t *dpath_id, double *dtraj, int32_t traj_cap, int32_t *dtraj_len,
+                           void *stream);
+
+/* The tail of mpc_kinematics.main's loop (:397-456) for an LTV layout with nx 4, nu 2 (any
+ * other: MPCQP_EUNSUPPORTED).  sol[b*n] = (S_0..S_N, U_0..U_{N-1}); Ad[b*N*16], Bd[b*N*8],
+ * gd[b*N*4] are the lists the assembly took, of which stage 0 is read (the loop uses one model,
+ * linearised at the current (x, u), on every stage).  status[b] is the solver's code (NULL: all
+ * solved).  A vehicle whose status is not 1 (solved) is skipped as the reference's `continue`
+ * skips it (:398-402): x, u, pred_x, traj, traj_len and steps_taken stay bit for bit and
+ * skipped[b] goes up.  Otherwise:
+ *   1. pred_x[b*(N+1)*4]: stage k = S_k for every k = 0..N (stage 0 is the solution's, not the
+ *      plant state; there is no shift, :410-420);
+ *   2. while traj_len[b] < traj_cap, append (x, y, v, yaw, U_0[steer], U_0[accel]) -- the state
+ *      the step started from and the control applied (:452-453) -- to
+ *      traj[(b*traj_cap + traj_len[b])*6] and count it;
+ *   3. plant step x <- Ad_0 x + Bd_0 U_0 + gd_0 (x[b*4]), u <- U_0 (u[b*2]);
+ *   4. steps_taken[b] goes up.
+ * skipped, steps_taken, traj_len: int32[B]; steps_taken may be NULL, traj / traj_len when
+ * traj_cap is 0. */
+int mpcqp_kin_frozen_tail_device(const mpcqp_ltv_layout *L, int64_t B, const double *dsol, const int32_t *dstatus,
+                                 const double *dAd, const double *dBd, const double *dgd, double *dx, double *du,
+                                 double *dpred_x, int32_t *dskipped, int32_t *dsteps_taken, double *dtraj,
+                                 int32_t traj_cap, int32_t *dtraj_len, void *stream);
+
+/* ======================================================================
  * The closed loop that keeps one problem alive: vehicle_lateral_mpc_slack_increment.py
  * (setup once :121, then per step update(q=, l=, u=) :237 and a warm-started solve :248).
  * q, l, u come from mpcqp_affine_apply_device, the update and the solve from

@@ -15,6 +15,12 @@
 // same two assembly kernels), with the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:main:
 //       k_kin_rollout                 initial horizon (nonlinear Euler)       :405-419
 //       k_kin_ltv_shift               skip rule, record, plant step, shift    :479-563
+// and the two remaining loops of Control/MPC: mpc_increment_kinematics_pred_matrix.py:main (the
+// double lane change: a bank of paths, one selected per vehicle by a step schedule) and
+// mpc_kinematics.py:main (one linearisation per step for every stage, no shift):
+//       k_kin_reference_paths         reference_search on path_id[b] of a path bank   :41-83
+//       k_lane_tail                   record, plant step, shift, path schedule        :380-391, :423-472
+//       k_kin_frozen_tail             skip rule, unpack, record, plant step           mpc_kinematics.py:397-456
 // and the one closed loop that keeps its problem alive, vehicle_lateral_mpc_slack_increment.py
 // (setup once, update(q, l, u) + warm-started solve per step; k_affine assembles its vectors):
 //       k_lti_step                    raise rule, record, plant step, schedule :158-172, :252-269
@@ -424,6 +430,35 @@ __global__ __launch_bounds__(128) void k_reference(long B, int N, int nxa, int n
     }
 }
 
+// k_reference<KinematicBicycle> over a bank of `npaths` paths of np points each (path p at
+// px / py / pyaw + p * np), vehicle b on path path_id[b] (null: path 0; clamped into the bank).
+// pyaw null: yaw 0 on every point (reference_search of the two pred_matrix scripts and of
+// mpc_kinematics.py, x_ref[3] = deg2rad(0)).
+__global__ __launch_bounds__(128) void k_kin_reference_paths(long B, int N, int nxa, int npaths, int np,
+                                                             const double* __restrict__ px,
+                                                             const double* __restrict__ py,
+                                                             const double* __restrict__ pyaw,
+                                                             const int* __restrict__ path_id,
+                                                             const double* __restrict__ set_speed,
+                                                             const double* __restrict__ pred, double dt,
+                                                             double* __restrict__ Xr) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int p = path_id ? min(max(path_id[b], 0), npaths - 1) : 0;
+    const double* bx = px + (long)p * np;
+    const double* by = py + (long)p * np;
+    const double* pb = pred + b * (long)(N + 1) * nxa;
+    PathWalk walk(bx, by, np, pb[0], pb[1]);
+    double* Xb = Xr + b * (long)4 * (N + 1);
+    for (int i = 0; i <= N; ++i) {
+        const int ind = walk.advance(pb[i * nxa + KinematicBicycle::SPEED], dt);
+        Xb[0 * (N + 1) + i] = bx[ind];
+        Xb[1 * (N + 1) + i] = by[ind];
+        Xb[2 * (N + 1) + i] = set_speed[b];
+        Xb[3 * (N + 1) + i] = pyaw ? pyaw[(long)p * np + ind] : 0.0;
+    }
+}
+
 // x_next = (A0 x + B0 u) + g0 of the linearised stage-0 model, in the reference's association.
 // Inlined, so nx / nu are compile-time where the caller's are (the kinematic kernels) and run-time
 // where they come from the layout (k_incr_shift; unrolled for nx = 6 the compiler orders the fma
@@ -510,6 +545,34 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
     for (int j = 0; j < nu; ++j) db[N * nu + j] = db[(N - 1) * nu + j];
 }
 
+// Plant step and in-place horizon shift that mpc_incre_kine_func.simulate (:385-387, :403-428) and
+// mpc_increment_kinematics_pred_matrix.main (:442-472) share word for word, for one vehicle:
+// s = (x~_0..x~_N, du_0..du_{N-1}) the solution, A0 / B0 / g0 stage 0 of the linearisation,
+// xb = x~ (in/out), pb = pred_x~ (N+1 stages of 6), db = pred_du (N+1 stages of 2).
+__device__ __forceinline__ void kin_incr_step_shift(const mpcqp_kin_vehicle& vk, int N, const double* s,
+                                                    const double* A0, const double* B0, const double* g0,
+                                                    double* xb, double* pb, double* db) {
+    constexpr int nx = 4, nu = 2, nxa = 6;
+    const double* D = s + (N + 1) * nxa;  // du_0 .. du_{N-1}
+    // plant step, stage 0 of the linearisation
+    double xnext[nx], uu[nu];
+    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + D[j];
+    plant_step(nx, nu, A0, B0, g0, xb, uu, xnext);
+    for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
+    for (int j = 0; j < nu; ++j) xb[nx + j] = uu[j];
+    // shift, from the solution
+    for (int i = 0; i < nxa; ++i) pb[i] = xb[i];
+    for (int k = 1; k <= N - 1; ++k)
+        for (int i = 0; i < nxa; ++i) pb[k * nxa + i] = s[(k + 1) * nxa + i];
+    for (int k = 0; k <= N - 2; ++k)
+        for (int j = 0; j < nu; ++j) db[k * nu + j] = D[(k + 1) * nu + j];
+    for (int j = 0; j < nu; ++j) db[(N - 1) * nu + j] = db[N * nu + j] = D[(N - 1) * nu + j];
+    // terminal state: update_kinematics_model on (x_N, u_N) of the solution, v first
+    const double* sN = s + N * nxa;
+    kin_update(vk, sN, sN + nx, pb + N * nxa);
+    for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = sN[nx + j];
+}
+
 // Tail of mpc_incre_kine_func.simulate's loop (:382-428), per vehicle, in the reference's
 // order: unpack the solution (mpc_increment :194-217), record the trajectory point
 // (:389-393), stop rule (:395-401), plant step (:385-387, :403-405), horizon shift
@@ -553,23 +616,46 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
             return;
         }
     }
-    // plant step, stage 0 of the linearisation
-    double xnext[nx], uu[nu];
-    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + D[j];
-    plant_step(nx, nu, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, uu, xnext);
-    for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
-    for (int j = 0; j < nu; ++j) xb[nx + j] = uu[j];
-    // shift, from the solution
-    for (int i = 0; i < nxa; ++i) pb[i] = xb[i];
-    for (int k = 1; k <= N - 1; ++k)
-        for (int i = 0; i < nxa; ++i) pb[k * nxa + i] = s[(k + 1) * nxa + i];
-    for (int k = 0; k <= N - 2; ++k)
-        for (int j = 0; j < nu; ++j) db[k * nu + j] = D[(k + 1) * nu + j];
-    for (int j = 0; j < nu; ++j) db[(N - 1) * nu + j] = db[N * nu + j] = D[(N - 1) * nu + j];
-    // terminal state: update_kinematics_model on (x_N, u_N) of the solution, v first
-    const double* sN = s + N * nxa;
-    kin_update(vk, sN, sN + nx, pb + N * nxa);
-    for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = sN[nx + j];
+    kin_incr_step_shift(vk, N, s, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, pb,
+                        db);
+}
+
+// A step schedule by value: value = val[#{j < nsw : step > sw[j]}] (k_lti_step's convention).
+struct StepSchedule {
+    int nsw;
+    int sw[8], val[9];
+    __device__ int at(int step) const {
+        int r = 0;
+        for (int j = 0; j < nsw; ++j) r += step > sw[j] ? 1 : 0;
+        return val[r];
+    }
+};
+
+// Tail of mpc_increment_kinematics_pred_matrix.main's loop (:423-472), per vehicle, in the
+// reference's order: record plt_states / plt_actions (x~ as the step started: the input is the
+// one held BEFORE the step), plant step and in-place shift (the text of simulate's, so
+// kin_incr_step_shift), then the step counter and the path the NEXT step's reference search
+// runs on (the double lane change of :380-391).  No skip rule: mpc_increment uses the solution
+// whatever its status (:248-252).
+__global__ __launch_bounds__(128) void k_lane_tail(mpcqp_kin_vehicle vk, IncrK L, StepSchedule sched, long B,
+                                                   const double* __restrict__ sol, const double* __restrict__ Ad,
+                                                   const double* __restrict__ Bd, const double* __restrict__ gd,
+                                                   double* __restrict__ xt, double* __restrict__ pred,
+                                                   double* __restrict__ pdu, int* __restrict__ step,
+                                                   int* __restrict__ path_id, double* __restrict__ traj,
+                                                   int traj_cap, int* __restrict__ traj_len) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    constexpr int nx = 4, nu = 2, nxa = 6;
+    const int N = L.N;
+    double* xb = xt + b * nxa;
+    if (double* tr = traj_append(traj, traj_cap, traj_len, b, nxa))
+        for (int i = 0; i < nxa; ++i) tr[i] = xb[i];
+    kin_incr_step_shift(vk, N, sol + b * L.n, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu,
+                        gd + b * (long)N * nx, xb, pred + b * (long)(N + 1) * nxa, pdu + b * (long)(N + 1) * nu);
+    const int k = step[b] + 1;
+    step[b] = k;
+    path_id[b] = sched.at(k);
 }
 
 // Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): u0 in every stage, the
@@ -635,6 +721,43 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     for (int k = 0; k <= N - 2; ++k)
         for (int j = 0; j < nu; ++j) pu[k * nu + j] = U[(k + 1) * nu + j];
     for (int j = 0; j < nu; ++j) pu[(N - 1) * nu + j] = pu[N * nu + j] = U[(N - 1) * nu + j];
+    if (steps_taken) steps_taken[b] += 1;
+}
+
+// Tail of mpc_kinematics.main's loop (:397-456), per vehicle.  One model (the linearisation at
+// the current (x, u)) serves every stage, so Ad / Bd / gd are read at stage 0 of the (B, N, ..)
+// lists the assembly took.  A vehicle whose status is not `solved` is skipped whole (:398-402).
+// Otherwise pred_x takes the solution's states S_0..S_N with no shift -- stage 0 is S_0, not the
+// plant state (:410-420) -- the record is (x before the step, U_0) (:452-453), and the plant
+// steps with that same linear model (:449-455).
+__global__ __launch_bounds__(128) void k_kin_frozen_tail(int N, int n, long B, const double* __restrict__ sol,
+                                                         const int* __restrict__ status,
+                                                         const double* __restrict__ Ad, const double* __restrict__ Bd,
+                                                         const double* __restrict__ gd, double* __restrict__ x,
+                                                         double* __restrict__ u, double* __restrict__ pred_x,
+                                                         int* __restrict__ skipped, int* __restrict__ steps_taken,
+                                                         double* __restrict__ traj, int traj_cap,
+                                                         int* __restrict__ traj_len) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (status && status[b] != MPCQP_SOLVED) {
+        skipped[b] += 1;
+        return;
+    }
+    constexpr int nx = 4, nu = 2;
+    const double* S = sol + b * n;
+    const double* U = S + (N + 1) * nx;
+    double* xb = x + b * nx;
+    double* px = pred_x + b * (long)(N + 1) * nx;
+    for (int i = 0; i < (N + 1) * nx; ++i) px[i] = S[i];
+    if (double* tr = traj_append(traj, traj_cap, traj_len, b, 6)) {
+        for (int i = 0; i < nx; ++i) tr[i] = xb[i];
+        tr[4] = U[0]; tr[5] = U[1];
+    }
+    double xnext[nx];
+    plant_step(nx, nu, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, U, xnext);
+    for (int i = 0; i < nx; ++i) xb[i] = xnext[i];
+    for (int j = 0; j < nu; ++j) u[b * nu + j] = U[j];
     if (steps_taken) steps_taken[b] += 1;
 }
 
@@ -1128,6 +1251,55 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicl
     if (B == 0) return 0;
     return launch(L->dev, stream, B, 128, k_kin_ltv_shift, *veh, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
                   dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
+}
+
+int mpcqp_kin_reference_search_paths_device(int64_t B, int32_t N, int32_t nxa, int32_t npaths, int32_t npath,
+                                            const double* dpaths_x, const double* dpaths_y, const double* dpaths_yaw,
+                                            const int32_t* dpath_id, const double* dset_speed, const double* dpred,
+                                            double dt, double* dXr, int32_t device, void* stream) {
+    if (!dpaths_x || !dpaths_y || !dset_speed || !dpred || !dXr || B < 0 || N < 1 || nxa < 4 || npaths < 1 ||
+        npath < 2)
+        return set_error(MPCQP_EINVAL, "kin_reference_search_paths: bad arguments");
+    if (B == 0) return 0;
+    return launch(device, stream, B, 128, k_kin_reference_paths, B, N, nxa, npaths, npath, dpaths_x, dpaths_y,
+                  dpaths_yaw, dpath_id, dset_speed, dpred, dt, dXr);
+}
+
+int mpcqp_lane_tail_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
+                           const double* dAd, const double* dBd, const double* dgd, double* dxt, double* dpred,
+                           double* dpdu, int32_t nsw, const int32_t* switch_steps, const int32_t* paths_of,
+                           int32_t* dstep, int32_t* dpath_id, double* dtraj, int32_t traj_cap, int32_t* dtraj_len,
+                           void* stream) {
+    if (nsw > 8) return set_error(MPCQP_EUNSUPPORTED, "lane_tail: need nsw <= 8");
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dxt || !dpred || !dpdu || !paths_of || !dstep || !dpath_id ||
+        B < 0 || nsw < 0 || (nsw > 0 && !switch_steps) || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "lane_tail: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "lane_tail: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    StepSchedule sched = {};
+    sched.nsw = nsw;
+    std::copy(switch_steps, switch_steps + nsw, sched.sw);
+    std::copy(paths_of, paths_of + nsw + 1, sched.val);
+    return launch(L->dev, stream, B, 128, k_lane_tail, *veh, incr_k(*L), sched, B, dsol, dAd, dBd, dgd, dxt, dpred,
+                  dpdu, dstep, dpath_id, dtraj, traj_cap, dtraj_len);
+}
+
+int mpcqp_kin_frozen_tail_device(const mpcqp_ltv_layout* L, int64_t B, const double* dsol, const int32_t* dstatus,
+                                 const double* dAd, const double* dBd, const double* dgd, double* dx, double* du,
+                                 double* dpred_x, int32_t* dskipped, int32_t* dsteps_taken, double* dtraj,
+                                 int32_t traj_cap, int32_t* dtraj_len, void* stream) {
+    if (!L || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dskipped || B < 0 || traj_cap < 0 ||
+        (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_frozen_tail: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_frozen_tail: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0) return 0;
+    return launch(L->dev, stream, B, 128, k_kin_frozen_tail, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
+                  dpred_x, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
 }
 
 int mpcqp_lti_step_device(int64_t B, int32_t nxa, int32_t nu, const double* At, const double* Bt, int32_t n,

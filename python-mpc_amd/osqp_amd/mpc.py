@@ -346,6 +346,16 @@ def linearise_kinematics(l_f, l_r, dt, x, u):
     return Ad, Bd, gd
 
 
+def kin_update(l_f, l_r, dt, x, u):
+    """Vehicle_Kinematics.update_kinematics_model (vehicle_models.py:866-883) for x (.., 4), u (.., 2):
+    the reference updates in place, so v advances before yaw reads it.  Returns the new state."""
+    x, u = np.asarray(x, float), np.asarray(u, float)
+    X, Y, v, yaw = x[..., 0], x[..., 1], x[..., 2], x[..., 3]
+    v1 = v + u[..., 1] * dt
+    return np.stack([X + v * np.cos(yaw) * dt, Y + v * np.sin(yaw) * dt, v1,
+                     yaw + v1 / (l_f + l_r) * np.tan(u[..., 0]) * dt], axis=-1)
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),
@@ -388,6 +398,27 @@ KINLTV_UMAX = np.array([np.deg2rad(15), 1.])
 KINLTV_XMIN = np.array([-np.inf, -np.inf, -100., -2 * np.pi])
 KINLTV_XMAX = np.array([np.inf, np.inf, 100., 2 * np.pi])
 
+# mpc_increment_kinematics_pred_matrix.py:302-312 (the lane-change loop): KIN_*'s bounds, R and
+# QN; only Q differs (50, 50, 10, 50 against 100, 100, 10, 100)
+LANE_Q = np.diag([50.0, 50.0, 10.0, 50.0])
+LANE_QN = np.diag([1000.0, 1000.0, 100.0, 1000.0])
+LANE_R = np.diag([100., 100.])
+LANE_DUMIN = np.array([-np.deg2rad(0.5), -0.5])
+LANE_XMIN_T = np.array([-np.inf, -np.inf, -100., -2 * np.pi, -np.deg2rad(15), -3.])
+LANE_XMAX_T = np.array([np.inf, np.inf, 100., 2 * np.pi, np.deg2rad(15), 1.])
+LANE_SWITCH_STEPS = (50, 150)                                    # :380-391 with sim_time = 1000
+LANE_PATHS_OF = (0, 1, 0)
+
+# mpc_kinematics.py:381-391, the weights and bounds INSIDE main's loop (QN's last entry is 50
+# there, 100 before the loop, :353)
+KINFROZEN_Q = np.diag([1.0, 1.0, 5.0, 10.0])
+KINFROZEN_QN = np.diag([10.0, 10.0, 50.0, 50.0])
+KINFROZEN_R = np.diag([0.1, 0.1])
+KINFROZEN_UMIN = np.array([-np.deg2rad(15), -3.])
+KINFROZEN_UMAX = np.array([np.deg2rad(15), 1.])
+KINFROZEN_XMIN = np.array([-np.inf, -np.inf, -100., -np.pi])
+KINFROZEN_XMAX = np.array([np.inf, np.inf, 100., np.pi])
+
 # structural nonzeros of get_dynamics_model's Ad = I + dt Ac and Bd = dt Bc (vehicle_models.py:273-292)
 DYN_MASK_A = np.eye(6, dtype=np.uint8)
 for _i, _j in [(0, 2), (0, 3), (0, 4), (1, 2), (1, 3), (1, 4), (2, 5), (3, 3), (3, 4), (3, 5), (4, 3), (4, 4),
@@ -395,6 +426,109 @@ for _i, _j in [(0, 2), (0, 3), (0, 4), (1, 2), (1, 3), (1, 4), (2, 5), (3, 3), (
     DYN_MASK_A[_i, _j] = 1
 DYN_MASK_B = np.zeros((6, 2), np.uint8)
 DYN_MASK_B[3:, :] = 1
+
+
+# --------------------------------------- path bank, lane-change loop, frozen-model loop --
+def reference_search_paths(paths_x, paths_y, paths_yaw, path_id, set_speed, pred, dt):
+    """mpc_device.hip::k_kin_reference_paths (mpcqp_kin_reference_search_paths_device) in numpy:
+    reference_search / nearest_point of the kinematic scripts (reversed scan, strict <,
+    look_ind 1) for B vehicles, vehicle b on path path_id[b] of the bank.
+
+    paths_x, paths_y (npaths, npath); paths_yaw the same or None (yaw 0); path_id (B,) or None
+    (path 0), clamped into [0, npaths); set_speed (B,); pred (B, N+1, nxa) stage-major with the
+    speed in state 2 -> Xr (B, 4, N+1).  Where the reference would read past the path's end
+    (IndexError) the index holds the start of the last segment."""
+    paths_x, paths_y = np.atleast_2d(np.asarray(paths_x, float)), np.atleast_2d(np.asarray(paths_y, float))
+    npaths, npt = paths_x.shape
+    pred = np.asarray(pred, float)
+    B, N1 = pred.shape[:2]
+    pid = np.zeros(B, int) if path_id is None else np.clip(np.asarray(path_id), 0, npaths - 1)
+    paths_yaw = np.zeros_like(paths_x) if paths_yaw is None else np.atleast_2d(np.asarray(paths_yaw, float))
+    Xr = np.empty((B, 4, N1))
+    for b in range(B):
+        px, py = paths_x[pid[b]], paths_y[pid[b]]
+        seg = lambda i: np.sqrt((px[i + 1] - px[i]) ** 2 + (py[i + 1] - py[i]) ** 2)
+        min_d, ind = np.inf, -1
+        for i in reversed(range(npt)):
+            d = np.sqrt((px[i] - pred[b, 0, 0]) ** 2 + (py[i] - pred[b, 0, 1]) ** 2)
+            if d < min_d:
+                min_d, ind = d, i
+        ind = min(ind + 1, npt - 2)
+        path_d, cumul = seg(ind), 0.0
+        for i in range(N1):
+            cumul = cumul + abs(pred[b, i, 2]) * dt
+            while cumul >= path_d and ind + 1 < npt - 1:
+                ind += 1
+                path_d = path_d + seg(ind)
+            Xr[b, :, i] = px[ind], py[ind], set_speed[b], paths_yaw[pid[b], ind]
+    return Xr
+
+
+def lane_path_id(step, switch_steps=LANE_SWITCH_STEPS, paths_of=LANE_PATHS_OF):
+    """The path loop pass `step` of mpc_increment_kinematics_pred_matrix.main searches (its two
+    `if i > ...`, :380-391): paths_of[#{j : step > switch_steps[j]}], elementwise over step."""
+    return slack_regime(step, switch_steps, paths_of)
+
+
+def lane_tail(sol, Ad0, Bd0, gd0, xt, step, N, l_f, l_r, dt, switch_steps=LANE_SWITCH_STEPS,
+              paths_of=LANE_PATHS_OF):
+    """The tail of mpc_increment_kinematics_pred_matrix.main's loop (:423-472) for one vehicle,
+    without its aliasing -- mpc_device.hip::k_lane_tail (mpcqp_lane_tail_device) in numpy.
+
+    sol = (x~_0..x~_N, du_0..du_{N-1}); Ad0, Bd0, gd0 stage 0 of the linearisation; xt = x~ (6,)
+    as the step started; step the number of steps taken so far.  Returns (row, xt, pred, pdu,
+    step, path_id): row = x~ as the step started (plt_states, plt_actions: the input held BEFORE
+    the step); xt = (Ad0 x + Bd0 u + gd0, u) with u = u_prev + du_0; pred (N+1, 6) = (xt,
+    x~_2..x~_N, (update_kinematics_model(x_N, u_N), u_N)) -- the in-place shift makes the
+    terminal control the solution's stage-N one; pdu (N+1, 2) = (du_1..du_{N-1}, du_{N-1},
+    du_{N-1}); step + 1 and the path the next step searches."""
+    sol, xt = np.asarray(sol, float), np.asarray(xt, float)
+    S = sol[:(N + 1) * 6].reshape(N + 1, 6)
+    D = sol[(N + 1) * 6:].reshape(N, 2)
+    row = xt.copy()
+    u = xt[4:] + D[0]
+    xt = np.concatenate([(Ad0 @ xt[:4] + Bd0 @ u) + gd0, u])
+    pred = np.empty((N + 1, 6)); pdu = np.empty((N + 1, 2))
+    pred[0] = xt
+    pred[1:N] = S[2:N + 1]
+    pred[N] = np.concatenate([kin_update(l_f, l_r, dt, S[N, :4], S[N, 4:]), S[N, 4:]])
+    pdu[0:N - 1] = D[1:N]
+    pdu[N - 1] = pdu[N] = D[N - 1]
+    step = int(step) + 1
+    return row, xt, pred, pdu, step, int(lane_path_id(step, switch_steps, paths_of))
+
+
+def kinfrozen_rollout(x0, pred_u0, N, l_f, l_r, dt):
+    """Initial horizon of mpc_kinematics.main (:318-329) for one vehicle or a batch: x0 (.., 4);
+    pred_u0 (.., N+1, 2) is the initial pred_u (the script's u0 + noise, last column repeated);
+    pred_x (.., N+1, 4) has stage 0 = x0, stage i = update_kinematics_model(stage i-1,
+    pred_u0[i]) for 1 <= i <= N-1 (the index is i, not i-1) and stage N = 0.  Returns (pred_x,
+    x_start): the script rolls its own state forward in place (x0 IS x, :304), so its plant
+    starts from x_start = pred_x[N-1], not x0."""
+    x0, pred_u0 = np.asarray(x0, float), np.asarray(pred_u0, float)
+    pred_x = np.zeros(x0.shape[:-1] + (N + 1, 4))
+    pred_x[..., 0, :] = x0
+    for i in range(1, N):
+        pred_x[..., i, :] = kin_update(l_f, l_r, dt, pred_x[..., i - 1, :], pred_u0[..., i, :])
+    return pred_x, pred_x[..., N - 1, :].copy()
+
+
+def kinfrozen_tail(sol, status, Ad, Bd, gd, x, u, pred_x, N):
+    """The tail of mpc_kinematics.main's loop (:397-456) for one vehicle --
+    mpc_device.hip::k_kin_frozen_tail (mpcqp_kin_frozen_tail_device) in numpy.
+
+    sol = (S_0..S_N, U_0..U_{N-1}); status the solver's code; Ad, Bd, gd the step's one model.
+    Returns (row, x, u, pred_x, skipped).  A status other than 1 (`solved`) is the script's
+    `continue`: (None, x, u, pred_x, True), everything as given.  Otherwise pred_x (N+1, 4) = the
+    solution's states, stage 0 included, no shift; row = (x before the step, U_0); x = Ad x +
+    Bd U_0 + gd; u = U_0."""
+    if status != 1:
+        return None, x, u, pred_x, True
+    sol, x = np.asarray(sol, float), np.asarray(x, float)
+    S = sol[:(N + 1) * 4].reshape(N + 1, 4)
+    U0 = sol[(N + 1) * 4:(N + 1) * 4 + 2]
+    row = np.concatenate([x, U0])
+    return row, (Ad @ x + Bd @ U0) + gd, U0.copy(), S.copy(), False
 
 
 def _lateral_x0(rng, B):

@@ -21,6 +21,12 @@ LTVLayout is the LTV MPC in the inputs themselves (mpc__, mpc_dynamics.mpc, mpc_
 mpcqp_ltv_*), and KinematicLTVMPC the closed loop of Control/MPC/mpc_kinematics_pred_matrix.py:
 main (:355-563) on it (mpcqp_kin_rollout_device, mpcqp_kin_ltv_shift_device).
 
+LaneChangeMPC is the closed loop of Control/MPC/mpc_increment_kinematics_pred_matrix.py:main
+(:281-476, the double lane change) on IncrementalLayout, over a bank of paths with one selected per
+vehicle (mpcqp_kin_reference_search_paths_device, mpcqp_lane_tail_device); KinematicFrozenMPC the
+closed loop of Control/MPC/mpc_kinematics.py:main (:268-461) on LTVLayout with one linearisation per
+step on every stage (mpcqp_kin_frozen_tail_device).
+
 LateralMPC is the closed loop of vehicle_lateral_mpc_slack_increment.py (:123-269), the one loop
 that keeps a problem alive: one setup, then per step LateralAssembler -> DeviceBatch.update ->
 warm-started DeviceBatch.solve -> mpcqp_lti_step_device.
@@ -59,6 +65,7 @@ class KinVehicle(C.Structure):
 # structural nonzeros of get_dynamics_model's Ad and Bd (kept under these names here too)
 from .mpc import DYN_MASK_A, DYN_MASK_B  # noqa: E402
 from .mpc import SLACK_REGIMES, SLACK_SWITCH_STEPS  # noqa: E402  (the slack script's bound schedule)
+from .mpc import LANE_PATHS_OF, LANE_SWITCH_STEPS  # noqa: E402  (the lane-change script's path schedule)
 
 
 def _bind():
@@ -94,6 +101,10 @@ def _bind():
     L.mpcqp_kin_ltv_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 12 + [i32, vp, vp]
     L.mpcqp_lti_step_device.argtypes = [i64, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp,
                                         vp, vp, i32, vp, i32, vp]
+    L.mpcqp_kin_reference_search_paths_device.argtypes = [i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, d, vp, i32,
+                                                          vp]
+    L.mpcqp_lane_tail_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 7 + [i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.mpcqp_kin_frozen_tail_device.argtypes = [vp, i64] + [vp] * 11 + [i32, vp, vp]
     L._mpc_bound = True
     return L
 
@@ -792,6 +803,210 @@ class KinematicLTVMPC(_ClosedLoop):
         """(traj, traj_len) as host arrays: traj (B, traj_cap, 6) = x, y, v, yaw, steer, accel;
         traj_len[b] rows of traj[b] are filled, one per executed step."""
         return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
+
+
+# ------------------------------------- a bank of paths, one selected per vehicle --
+def reference_search_paths(paths_x, paths_y, paths_yaw, path_id, set_speed, pred, dt):
+    """reference_search_kin over a bank of paths: paths_x, paths_y (npaths, npath) device tensors,
+    paths_yaw the same or None (yaw 0 on every point), path_id (B,) int32 or None (path 0; an id
+    outside the bank is clamped into it), set_speed (B,), pred (B, N+1, nxa)
+    -> Xr (B, 4, N+1) (mpcqp_kin_reference_search_paths_device)."""
+    import torch
+    L = _bind()
+    B, N1, nxa = pred.shape
+    if paths_x.dim() != 2 or paths_y.shape != paths_x.shape or set_speed.numel() != B or \
+            (paths_yaw is not None and paths_yaw.shape != paths_x.shape):
+        raise ValueError("paths_x, paths_y, paths_yaw must be (npaths, npath) and set_speed have B entries")
+    for t in (paths_x, paths_y, paths_yaw, set_speed, pred):
+        if t is not None and (not t.is_contiguous() or t.dtype != torch.float64):
+            raise ValueError("reference_search_paths inputs must be contiguous float64 tensors")
+    if path_id is not None and (path_id.dtype != torch.int32 or tuple(path_id.shape) != (B,)
+                                or not path_id.is_contiguous()):
+        raise ValueError("path_id must be a contiguous int32 (B,) tensor")
+    Xr = torch.empty((B, 4, N1), dtype=torch.float64, device=pred.device)
+    _check(L.mpcqp_kin_reference_search_paths_device(
+        B, N1 - 1, nxa, paths_x.shape[0], paths_x.shape[1], _p(paths_x), _p(paths_y),
+        None if paths_yaw is None else _p(paths_yaw), None if path_id is None else _p(path_id), _p(set_speed),
+        _p(pred), float(dt), _p(Xr), pred.device.index or 0, _stream(torch, pred.device)), "kin_reference_search_paths")
+    return Xr
+
+
+class LaneChangeMPC(_ClosedLoop):
+    """B copies of mpc_increment_kinematics_pred_matrix.main's closed loop (:281-476, the double
+    lane change), every step on the device.
+
+    State per vehicle: x~ = (X, Y, v, yaw, steer, accel), the predicted horizon pred_x~ (N+1
+    stages) and pred_du, as on KinematicMPC.  x0 is (B, 4), u0 (B, 2) (main's own are (0, 0, 20, 0)
+    and (0, 0.01)).  path_x (npath,) is shared by the paths, paths_y is (npaths, npath): the
+    script's scenario is paths_y = [0 x, 0 x + 4].  ``path_id`` (B,) says which path each vehicle's
+    reference search runs on; it follows the step schedule of :380-391,
+    path_id = paths_of[#{j : steps > switch_steps[j]}] (the script with sim_time = 1000: its
+    switches are i > 50 and i > 150).  step0 (B,) int, default 0, is the schedule step each vehicle
+    starts at, so one batch can hold vehicles at different points of the scenario.
+
+    ``step()`` = reference search on the vehicle's path (set speed 10, yaw 0, :41-83) ->
+    linearisation of every predicted stage -> mpc_increment's QP (IncrementalLayout with the
+    mpc.LANE_* weights) -> batched OSQP solve (settings of :242: polish off, warm_start off) ->
+    record, plant step, shift and schedule (mpcqp_lane_tail_device).  There is no skip rule: the
+    script uses the solution whatever the solver's status (:248-252).
+
+    ``trajectories()`` gives (traj (B, traj_cap, 6), traj_len): x, y, v, yaw, steer, accel of x~
+    as each step started (plt_states / plt_actions: the input is the one held BEFORE the step),
+    rows beyond traj_cap dropped.
+
+    ``shift_warm=True`` (an extension; the script solves every step cold) starts each solve from
+    the previous step's solution shifted one stage (warm_shift)."""
+
+    SET_SPEED = 10.0  # reference_search's x_ref[2] (:63)
+    _linearise = staticmethod(linearise_kinematics)
+
+    def __init__(self, x0, u0, path_x, paths_y, N=40, switch_steps=LANE_SWITCH_STEPS, paths_of=LANE_PATHS_OF,
+                 step0=None, veh: KinVehicle | None = None, device=0, traj_cap=0, shift_warm=False,
+                 **solver_settings):
+        from . import mpc
+        self.switch_steps = np.ascontiguousarray(switch_steps, np.int32).reshape(-1)
+        self.paths_of = np.ascontiguousarray(paths_of, np.int32).reshape(-1)
+        path_x = np.asarray(path_x, np.float64).reshape(-1)
+        paths_y = np.atleast_2d(np.asarray(paths_y, np.float64))
+        if paths_y.shape[1] != path_x.size:
+            raise ValueError("paths_y must be (npaths, npath) with npath = len(path_x)")
+        if self.paths_of.size != self.switch_steps.size + 1 or self.switch_steps.size > 8:
+            raise ValueError("paths_of must have one entry more than switch_steps (at most 8)")
+        if self.paths_of.min() < 0 or self.paths_of.max() >= paths_y.shape[0]:
+            raise ValueError(f"paths_of must lie in [0, {paths_y.shape[0]})")
+        layout = IncrementalLayout(int(N), mpc.LANE_Q, mpc.LANE_QN, mpc.LANE_R, mpc.LANE_XMIN_T, mpc.LANE_XMAX_T,
+                                   mpc.LANE_DUMIN, -mpc.LANE_DUMIN, maskA=mpc.KIN_MASK_A, maskB=mpc.KIN_MASK_B,
+                                   device=device)
+        settings = {"polish": False, "warm_start": False, **solver_settings}   # :242
+        settings.pop("warm_start")  # every solve follows a fresh setup: cold unless shift_warm starts it
+        x0, u0 = self._setup(x0, u0, N, veh or KinVehicle(), device, layout, dict(path_x=path_x), settings,
+                             shift_warm)
+        step0 = np.zeros(self.B, np.int32) if step0 is None else np.asarray(step0, np.int32).reshape(-1)
+        if step0.shape != (self.B,):
+            raise ValueError("step0 must be (B,)")
+        torch = self.torch
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.traj_cap = int(traj_cap)
+        self.paths_x = self.path_x.repeat(paths_y.shape[0], 1).contiguous()
+        self.paths_y = torch.from_numpy(np.ascontiguousarray(paths_y)).to(**kw).contiguous()
+        self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
+        self.xt = torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
+        self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)              # del_u0 = 0 (:331, :353-356)
+        self.steps = torch.from_numpy(step0.copy()).to(**ikw)
+        self.path_id = torch.from_numpy(mpc.lane_path_id(step0, self.switch_steps, self.paths_of)).to(**ikw)
+        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
+        self.traj_len = torch.zeros(self.B, **ikw)
+        self._start()
+
+    def _initial_horizon(self):
+        self.pred = self._linearised_rollout()                              # :350-368
+
+    def _reference(self):
+        return reference_search_paths(self.paths_x, self.paths_y, None, self.path_id, self.set_speed, self.pred,
+                                      self.veh.dt)
+
+    def _horizon(self):
+        return self.xt, self.pred[:, :, :4], self.pred[:, :, 4:]
+
+    def _shift(self, L, Ad, Bd, gd, Xr, st):
+        _check(L.mpcqp_lane_tail_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
+                                        _p(gd), _p(self.xt), _p(self.pred), _p(self.pdu), self.switch_steps.size,
+                                        _np_ptr(self.switch_steps), _np_ptr(self.paths_of), _p(self.steps),
+                                        _p(self.path_id), _p(self.traj), self.traj_cap, _p(self.traj_len), st),
+               "lane_tail")
+
+    run = KinematicLTVMPC.run
+    trajectories = KinematicLTVMPC.trajectories
+
+
+class KinematicFrozenMPC(_ClosedLoop):
+    """B copies of mpc_kinematics.main's closed loop (:268-461), every step on the device: the
+    loop around the QP of `mpc` (:148-200) with ONE model per step, the linearisation at the
+    current (x, u) -- u the control applied last -- on all N stages.
+
+    State per vehicle: x = (X, Y, v, yaw), u = (steer, accel) and the predicted states pred_x
+    (B, N+1, 4), which only the reference search reads.  x0 is (B, 4), u0 (B, 2) (main's own are
+    (0, 0, 5, 30 deg) and (0, 0.01)).  pred_u0 (B, N+1, 2), default u0 in every stage, is the
+    initial pred_u: the script draws it as u0 + noise (:318-323); the noise is the caller's.
+
+    Initial horizon (:325-329, mpc.kinfrozen_rollout, on the host): pred_x stage 0 = x0, stage i
+    = update_kinematics_model(stage i-1, pred_u0[i]) for 1 <= i <= N-1, stage N = 0.  The script
+    rolls its own state forward while it does so (x0 IS x, :304), so the plant starts from
+    pred_x stage N-1, not from x0; so does ``x`` here.
+
+    ``step()`` = reference search on pred_x (set speed 10, yaw 0, :39-81) -> one linearisation
+    (mpcqp_kin_linearise_device with stage stride 0) -> mpc's QP (LTVLayout with the
+    mpc.KINFROZEN_* weights of the loop, :381-391) -> batched OSQP solve -> skip rule, unpack,
+    record and plant step (mpcqp_kin_frozen_tail_device).  pred_x becomes the solution's states,
+    stage 0 included, with no shift; the plant steps with the step's own linear model.
+
+    Skip rule (:398-402): a vehicle whose solve did not end `solved` keeps x, u, pred_x and its
+    trajectory, and ``skipped`` goes up.  It meets the same QP again, so it stays skipped for
+    good, as in the reference.  ``steps_taken`` counts executed steps.
+
+    ``trajectories()`` gives (traj (B, traj_cap, 6), traj_len): x, y, v, yaw a step started from
+    and the steer, accel it applied, one row per executed step.
+
+    Settings are the script's (:195, warm_start=True, polish off); a fresh problem is set up
+    every step, so every solve is cold.  The loop has no shift, so no shift_warm is offered."""
+
+    SET_SPEED = 10.0  # reference_search's x_ref[2] (:61)
+    _linearise = staticmethod(linearise_kinematics)
+
+    def __init__(self, x0, u0, path_x, path_y, N=100, pred_u0=None, veh: KinVehicle | None = None, device=0,
+                 traj_cap=0, **solver_settings):
+        from . import mpc
+        if "shift_warm" in solver_settings:
+            raise TypeError("KinematicFrozenMPC takes no shift_warm: the loop has no shift to warm-start from")
+        if pred_u0 is not None:
+            pred_u0 = np.asarray(pred_u0, np.float64)
+            if pred_u0.shape != (np.atleast_2d(np.asarray(x0)).shape[0], int(N) + 1, 2):
+                raise ValueError("pred_u0 must be (B, N+1, 2)")
+        layout = LTVLayout(int(N), mpc.KINFROZEN_Q, mpc.KINFROZEN_QN, mpc.KINFROZEN_R, mpc.KINFROZEN_XMIN,
+                           mpc.KINFROZEN_XMAX, mpc.KINFROZEN_UMIN, mpc.KINFROZEN_UMAX, mpc.KIN_MASK_A, mpc.KIN_MASK_B,
+                           device=device)
+        settings = {"polish": False, "warm_start": True, **solver_settings}   # mpc_kinematics.py:195
+        x0, u0 = self._setup(x0, u0, N, veh or KinVehicle(), device, layout, dict(path_x=path_x, path_y=path_y),
+                             settings, False)
+        if pred_u0 is None:
+            pred_u0 = np.repeat(u0[:, None], self.N + 1, 1)
+        torch = self.torch
+        kw = dict(dtype=torch.float64, device=self.dev)
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        self.traj_cap = int(traj_cap)
+        self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:62)
+        self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
+        v = self.veh
+        pred_x, x_start = mpc.kinfrozen_rollout(x0, pred_u0, self.N, v.l_f, v.l_r, v.dt)
+        self.pred_x = torch.from_numpy(pred_x).to(**kw).contiguous()
+        self.x = torch.from_numpy(x_start).to(**kw).contiguous()
+        self.u = torch.from_numpy(u0).to(**kw).contiguous()
+        self.skipped = torch.zeros(self.B, **ikw)
+        self.steps_taken = torch.zeros(self.B, **ikw)
+        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
+        self.traj_len = torch.zeros(self.B, **ikw)
+        self._start()
+
+    def _initial_horizon(self):
+        pass  # rolled out on the host in __init__
+
+    def _reference(self):
+        return reference_search_kin(self.path_x, self.path_y, self.path_yaw, self.set_speed, self.pred_x,
+                                    self.veh.dt)
+
+    def _horizon(self):
+        # the one model on every stage: (x, u) with stage stride 0
+        return self.x, self.x[:, None, :].expand(self.B, self.N, 4), self.u[:, None, :].expand(self.B, self.N, 2)
+
+    def _shift(self, L, Ad, Bd, gd, Xr, st):
+        _check(L.mpcqp_kin_frozen_tail_device(self.layout._h, self.B, _p(self.sol), _p(self.status), _p(Ad), _p(Bd),
+                                              _p(gd), _p(self.x), _p(self.u), _p(self.pred_x), _p(self.skipped),
+                                              _p(self.steps_taken), _p(self.traj), self.traj_cap, _p(self.traj_len),
+                                              st), "kin_frozen_tail")
+
+    run = KinematicLTVMPC.run
+    trajectories = KinematicLTVMPC.trajectories
 
 
 # ------------------------------------------- the loop that keeps one problem alive --
