@@ -410,8 +410,9 @@ class _ClosedLoop:
     ``_setup`` (solver, path, solve outputs), allocates its own state tensors and calls
     ``_start``; it states ``_linearise`` (the model's linearisation), ``_initial_horizon``,
     ``_reference``, ``_horizon`` (initial state, predicted states, predicted inputs) and ``_shift``.
-    (LateralMPC, whose problem outlives the step, takes only ``step`` / ``_on_stream`` from here and
-    states its own ``_step``.)
+    (LateralMPC, whose problem outlives the step, takes only ``step`` / ``_on_stream`` and the record
+    from here and states its own ``_step``.)  A loop that records its trajectory allocates the
+    record with ``_alloc_record`` and hands it out with ``trajectories``; DynamicMPC keeps none.
 
     Every kernel of a step runs on ``self.stream``, in order; a null (legacy default) torch
     stream would be passed as NULL, which the solver's C ABI reads as "the handle's own
@@ -480,11 +481,30 @@ class _ClosedLoop:
             pred[:, i + 1] = xk
         return pred
 
+    def _alloc_record(self, traj_cap, width):
+        """The trajectory record: traj (B, max(traj_cap, 1), width) zeros and traj_len (B,) zeros."""
+        torch = self.torch
+        self.traj_cap = int(traj_cap)
+        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), width), dtype=torch.float64, device=self.dev)
+        self.traj_len = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+
     def step(self):
         """One receding-horizon step for every vehicle; returns (status, iters) device tensors.
         Asynchronous: ordered after the caller's current stream, and the caller's stream
         is ordered after the step."""
         return self._on_stream(self._step)
+
+    def run(self, steps):
+        """`steps` calls of step(); returns the last (status, iters)."""
+        out = None
+        for _ in range(int(steps)):
+            out = self.step()
+        return out
+
+    def trajectories(self):
+        """(traj, traj_len) as host arrays: traj (B, traj_cap, width) with the columns the class
+        docstring names; traj_len[b] rows of traj[b] are filled."""
+        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
 
     def _step(self):
         N = self.N
@@ -615,17 +635,15 @@ class KinematicMPC(_ClosedLoop):
         torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.traj_cap = int(traj_cap)
         self.xt = torch.from_numpy(np.concatenate([x0, u0], axis=1)).to(**kw).contiguous()
         self.set_speed = torch.from_numpy(np.ascontiguousarray(x0[:, 2])).to(**kw).contiguous()
         self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)             # del_u0 = 0 (:276, :293-296)
         self.finish_cnt = torch.zeros(self.B, **ikw)
         self.done = torch.zeros(self.B, **ikw)
         # the lists' first entries (:320-323): x0, y0, yaw0 and u0[1] (see the class docstring)
-        traj0 = np.zeros((self.B, max(self.traj_cap, 1), 4))
-        traj0[:, 0] = np.stack([x0[:, 0], x0[:, 1], x0[:, 3], u0[:, 1]], axis=1)
-        self.traj = torch.from_numpy(traj0).to(**kw).contiguous()
-        self.traj_len = torch.full((self.B,), 1 if self.traj_cap > 0 else 0, **ikw)
+        self._alloc_record(traj_cap, 4)
+        self.traj[:, 0] = torch.from_numpy(np.stack([x0[:, 0], x0[:, 1], x0[:, 3], u0[:, 1]], axis=1)).to(**kw)
+        self.traj_len.fill_(1 if self.traj_cap > 0 else 0)
         self._start()
 
     def _initial_horizon(self):
@@ -642,12 +660,6 @@ class KinematicMPC(_ClosedLoop):
                                         _p(gd), _p(Xr), _p(self.xt), _p(self.pred), _p(self.pdu),
                                         _p(self.finish_cnt), _p(self.done), _p(self.traj), self.traj_cap,
                                         _p(self.traj_len), st), "kin_shift")
-
-    def trajectories(self):
-        """(traj, traj_len) as host arrays: traj (B, traj_cap, 4) = x, y, yaw, steer increment;
-        traj_len[b] rows of traj[b] are filled (row 0: the initial state and u0[1], as the
-        reference's lists start)."""
-        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
 
     def run(self, max_steps, check_every=16):
         """step() until every vehicle is done or max_steps steps were taken; returns the number
@@ -765,15 +777,13 @@ class KinematicLTVMPC(_ClosedLoop):
         torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.traj_cap = int(traj_cap)
         self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:63)
         self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
         self.x = torch.from_numpy(x0).to(**kw).contiguous()
         self.u = torch.from_numpy(u0).to(**kw).contiguous()
         self.skipped = torch.zeros(self.B, **ikw)
         self.steps_taken = torch.zeros(self.B, **ikw)
-        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
-        self.traj_len = torch.zeros(self.B, **ikw)
+        self._alloc_record(traj_cap, 6)
         self._start()
 
     def _initial_horizon(self):
@@ -791,18 +801,6 @@ class KinematicLTVMPC(_ClosedLoop):
                                             _p(Ad), _p(Bd), _p(gd), _p(self.x), _p(self.u), _p(self.pred_x),
                                             _p(self.pred_u), _p(self.skipped), _p(self.steps_taken), _p(self.traj),
                                             self.traj_cap, _p(self.traj_len), st), "kin_ltv_shift")
-
-    def run(self, steps):
-        """`steps` calls of step(); returns the last (status, iters)."""
-        out = None
-        for _ in range(int(steps)):
-            out = self.step()
-        return out
-
-    def trajectories(self):
-        """(traj, traj_len) as host arrays: traj (B, traj_cap, 6) = x, y, v, yaw, steer, accel;
-        traj_len[b] rows of traj[b] are filled, one per executed step."""
-        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()
 
 
 # ------------------------------------- a bank of paths, one selected per vehicle --
@@ -887,7 +885,6 @@ class LaneChangeMPC(_ClosedLoop):
         torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.traj_cap = int(traj_cap)
         self.paths_x = self.path_x.repeat(paths_y.shape[0], 1).contiguous()
         self.paths_y = torch.from_numpy(np.ascontiguousarray(paths_y)).to(**kw).contiguous()
         self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
@@ -895,8 +892,7 @@ class LaneChangeMPC(_ClosedLoop):
         self.pdu = torch.zeros((self.B, self.N + 1, 2), **kw)              # del_u0 = 0 (:331, :353-356)
         self.steps = torch.from_numpy(step0.copy()).to(**ikw)
         self.path_id = torch.from_numpy(mpc.lane_path_id(step0, self.switch_steps, self.paths_of)).to(**ikw)
-        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
-        self.traj_len = torch.zeros(self.B, **ikw)
+        self._alloc_record(traj_cap, 6)
         self._start()
 
     def _initial_horizon(self):
@@ -915,9 +911,6 @@ class LaneChangeMPC(_ClosedLoop):
                                         _np_ptr(self.switch_steps), _np_ptr(self.paths_of), _p(self.steps),
                                         _p(self.path_id), _p(self.traj), self.traj_cap, _p(self.traj_len), st),
                "lane_tail")
-
-    run = KinematicLTVMPC.run
-    trajectories = KinematicLTVMPC.trajectories
 
 
 class KinematicFrozenMPC(_ClosedLoop):
@@ -974,7 +967,6 @@ class KinematicFrozenMPC(_ClosedLoop):
         torch = self.torch
         kw = dict(dtype=torch.float64, device=self.dev)
         ikw = dict(dtype=torch.int32, device=self.dev)
-        self.traj_cap = int(traj_cap)
         self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:62)
         self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
         v = self.veh
@@ -984,8 +976,7 @@ class KinematicFrozenMPC(_ClosedLoop):
         self.u = torch.from_numpy(u0).to(**kw).contiguous()
         self.skipped = torch.zeros(self.B, **ikw)
         self.steps_taken = torch.zeros(self.B, **ikw)
-        self.traj = torch.zeros((self.B, max(self.traj_cap, 1), 6), **kw)
-        self.traj_len = torch.zeros(self.B, **ikw)
+        self._alloc_record(traj_cap, 6)
         self._start()
 
     def _initial_horizon(self):
@@ -1004,9 +995,6 @@ class KinematicFrozenMPC(_ClosedLoop):
                                               _p(gd), _p(self.x), _p(self.u), _p(self.pred_x), _p(self.skipped),
                                               _p(self.steps_taken), _p(self.traj), self.traj_cap, _p(self.traj_len),
                                               st), "kin_frozen_tail")
-
-    run = KinematicLTVMPC.run
-    trajectories = KinematicLTVMPC.trajectories
 
 
 # ------------------------------------------- the loop that keeps one problem alive --
@@ -1078,9 +1066,7 @@ class LateralMPC(_ClosedLoop):
         self.regime = torch.from_numpy(mpc.slack_regime(step0, self.switch_steps, self.regimes)).to(**ikw)
         self.failed = torch.zeros(B, **ikw)
         self.fail_step = torch.zeros(B, **ikw)
-        self.traj_cap = int(traj_cap)
-        self.traj = torch.zeros((B, max(self.traj_cap, 1), self.nxa + self.nu + 1), **kw)
-        self.traj_len = torch.zeros(B, **ikw)
+        self._alloc_record(traj_cap, self.nxa + self.nu + 1)
         n, m = self.asm.n, self.asm.m
         self.q, self.l, self.u = torch.empty((B, n), **kw), torch.empty((B, m), **kw), torch.empty((B, m), **kw)
         self.sol, self.y = torch.empty((B, n), **kw), torch.empty((B, m), **kw)
@@ -1123,9 +1109,3 @@ class LateralMPC(_ClosedLoop):
             if strict and (k % check_every == 0 or k == nsim) and bool(self.failed.any().item()):
                 raise ValueError("OSQP did not solve the problem!")
         return out
-
-    def trajectories(self):
-        """(traj, traj_len) as host arrays: traj (B, traj_cap, 7) = beta, r, e_psi, e_y before the
-        step, u after it, du_0, the slack of e_y; traj_len[b] rows of traj[b] are filled, one per
-        executed step."""
-        return self.traj[:, :self.traj_cap].cpu().numpy(), self.traj_len.cpu().numpy()

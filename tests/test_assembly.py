@@ -5,11 +5,8 @@ import json
 import numpy as np
 import pytest
 
+from loop_checks import dense
 from osqp_amd import mpc
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def test_slack_setup_matches_reference(golden):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from loop_checks import stage_shift as _stage_shift
 from osqp_amd import OSQPBatch, mpc
 from parity import check_agreement, subset, termination_detail as _termination_holds
 
@@ -54,19 +55,6 @@ def test_cfg3_full_batch_meets_the_termination_test():
                               nthreads=16, **s)
     check_agreement("cfg3 B=65536, oracle sample 256", subset(b, idx), r1.x[idx], r1.y[idx], r1.status_val[idx],
                     r1.iter[idx], bo)
-
-
-def _stage_shift(v, N, nxa, nu, groups):
-    """One-stage shift of incremental-layout iterates (mpcqp_incr_warm_shift_device; the
-    reference's horizon shift, mpc_dynamics.py:589-610)."""
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nxa:(g + 1) * (N + 1) * nxa].reshape(B, N + 1, nxa)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    du = v[:, groups * (N + 1) * nxa:].reshape(B, N, nu)
-    out.append(np.concatenate([du[:, 1:], du[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
 
 
 def test_cfg5_full_batch_warm_meets_the_termination_test():

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from loop_checks import stage_shift as _stage_shift
 from osqp_amd import OSQP, OSQPBatch, mpc
 from parity import check_agreement
 
@@ -290,18 +291,6 @@ def test_slack_script_configs0_free_running():
     assert mism.size <= 30, mism
     env_o, env_g = np.abs(xo).max(axis=0), np.abs(xg).max(axis=0)
     assert np.all(np.abs(env_g - env_o) <= 0.03 * env_o + 1e-9), (env_g, env_o)
-
-
-def _stage_shift(v, N, nxa, nu, groups):
-    """One-stage shift of incremental-layout iterates (mpcqp_incr_warm_shift_device)."""
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nxa:(g + 1) * (N + 1) * nxa].reshape(B, N + 1, nxa)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    du = v[:, groups * (N + 1) * nxa:].reshape(B, N, nu)
-    out.append(np.concatenate([du[:, 1:], du[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
 
 
 def test_cfg5_warm_started_batch():

@@ -23,17 +23,14 @@ import json
 import numpy as np
 import pytest
 
+from loop_checks import (EUNSUPPORTED, INF, check_assembled, check_solutions, dense, dev as _t, host, oracle_solve,
+                         sim_qp as _sim_qp, stage_shift as _stage_shift)
 from osqp_amd import canonical_data, mpc
 from osqp_amd.mpc_device import IncrementalLayout
 
-INF = 1e30  # OSQP_INFTY: bounds are clipped to it
 L_F, L_R, DT = 1.25, 1.40, 0.02  # simulate's vehicle (:238-251)
 KIN = (mpc.KIN_Q, mpc.KIN_QN, mpc.KIN_R)
 KIN_BOUNDS = (mpc.KIN_XMIN_T, mpc.KIN_XMAX_T, mpc.KIN_DUMIN, -mpc.KIN_DUMIN)
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def _layout(N, **kw):
@@ -45,29 +42,10 @@ def _qp(Ad, Bd, gd, xt, Xr, N):
 
 
 # ------------------------------------------------------------------ host restatements --
-def nearest_point(path_x, path_y, x, y, look_ind=0):
-    """mpc_incre_kine_func.py:28-40 (reversed scan, strict <)."""
-    min_d, min_ind = np.inf, -1
-    for i in reversed(range(len(path_x))):
-        d = np.sqrt((path_x[i] - x) ** 2 + (path_y[i] - y) ** 2)
-        if d < min_d:
-            min_d, min_ind = d, i
-    return min_ind + look_ind
-
-
 def reference_search(path_x, path_y, path_yaw, set_speed, pred_state, dt, N):
-    """mpc_incre_kine_func.py:42-81: pred_state (4, N+1), speed in row 2 -> Xr (4, N+1)."""
-    x_ref = np.zeros((4, N + 1))
-    cumul_d = 0.0
-    ind = nearest_point(path_x, path_y, pred_state[0, 0], pred_state[1, 0], look_ind=1)
-    path_d = np.sqrt((path_x[ind + 1] - path_x[ind]) ** 2 + (path_y[ind + 1] - path_y[ind]) ** 2)
-    for i in range(N + 1):
-        cumul_d = cumul_d + abs(pred_state[2, i]) * dt
-        while cumul_d >= path_d:
-            ind = ind + 1
-            path_d = path_d + np.sqrt((path_x[ind + 1] - path_x[ind]) ** 2 + (path_y[ind + 1] - path_y[ind]) ** 2)
-        x_ref[:, i] = path_x[ind], path_y[ind], set_speed, path_yaw[ind]
-    return x_ref
+    """mpc_incre_kine_func.py:28-81: pred_state (4, N+1), speed in row 2 -> Xr (4, N+1)."""
+    return mpc.reference_search_paths(path_x[None], path_y[None], path_yaw[None], None, [set_speed], pred_state.T[None],
+                                      dt)[0]
 
 
 def tail(sol, Ad0, Bd0, gd0, Xr, xt, cnt, N):
@@ -93,11 +71,8 @@ def tail(sol, Ad0, Bd0, gd0, Xr, xt, cnt, N):
     pdu[0:N - 1] = D[1:N]
     pdu[N - 1] = pdu[N] = D[N - 1]
     # terminal state: update_kinematics_model(column N's state, column N-1's control) -- and
-    # column N-1 already holds column N.  v first, then yaw with the new v.
-    X, Y, v, yaw = S[N, :nx]
-    steer, accel = S[N, nx:]
-    v1 = v + accel * DT
-    pred[N, :nx] = X + v * np.cos(yaw) * DT, Y + v * np.sin(yaw) * DT, v1, yaw + v1 / (L_F + L_R) * np.tan(steer) * DT
+    # column N-1 already holds column N.
+    pred[N, :nx] = mpc.kin_update(L_F, L_R, DT, S[N, :nx], S[N, nx:])
     pred[N, nx:] = S[N, nx:]
     return row, dist, cnt, False, xt_new, pred, pdu
 
@@ -133,19 +108,7 @@ def simulate(x0, path_x, path_y, path_yaw, N, max_steps, solve):
     return np.stack(traj), len(dists), np.array(dists)
 
 
-def _oracle_solve(P, q, A, l, u):
-    import pyoracle
-    o = pyoracle.OSQP()
-    o.setup(P, q, A, l, u, polish=False, warm_start=False)
-    r = o.solve()
-    assert r.info.status == "solved"
-    return r.x
-
-
-def _sim_qp(g, t):
-    A = __import__("scipy.sparse", fromlist=["csc_matrix"]).csc_matrix(
-        (g[f"A{t}_data"], g[f"A{t}_indices"], g[f"A{t}_indptr"]), shape=tuple(g[f"A{t}_shape"]))
-    return g["P"], g["q"][t], A, g["l"][t], g["u"][t]
+_oracle_solve = oracle_solve(dict(polish=False, warm_start=False))
 
 
 def _fixture_traj(g):
@@ -236,11 +199,6 @@ def test_layout_pattern_matches_host_builder(N):
 
 
 # ------------------------------------------------------------------------- GPU tests --
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64, device="cuda")
-
-
 @pytest.mark.gpu
 def test_kin_linearise_matches_reference_fixture(golden):
     import torch
@@ -375,28 +333,19 @@ def test_closed_loop_matches_host_restatement():
         xt, pred = ctl.xt.cpu().numpy(), ctl.pred.cpu().numpy()
         status, iters = ctl.step()
         status, iters = status.cpu().numpy(), iters.cpu().numpy()
-        last = {k: v.cpu().numpy() for k, v in ctl.last.items()}
-        sol = ctl.sol.cpu().numpy()
+        last, sol = host(ctl)
         for b in range(B):
             Xr = reference_search(px, py, pyaw, x0[b, 2], pred[b].T[:4], DT, N)
             assert np.array_equal(last["Xr"][b], Xr)
             Ad, Bd, gd = mpc.linearise_kinematics(L_F, L_R, DT, pred[b, :N, :4], pred[b, :N, 4:])
-            assert np.allclose(last["Ad"][b], Ad, rtol=1e-13, atol=1e-15)
-            assert np.allclose(last["gd"][b], gd, rtol=1e-12, atol=1e-13)
             P, q, A, l, u = _qp(Ad, Bd, gd, xt[b], Xr, N)
-            A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-            assert np.allclose(dense(A_dev), dense(A), rtol=1e-12, atol=1e-15)
-            assert np.allclose(last["q"][b], q, rtol=1e-12, atol=1e-12)
-            assert np.allclose(last["l"][b], np.clip(l, -INF, INF), rtol=1e-12, atol=1e-14)
+            check_assembled(last, b, Ad, Bd, gd, (P, q, A, l, u), Apat)
             o = pyoracle.OSQP()
             o.setup(P, q, A, l, u, polish=False, warm_start=False)
             ro = o.solve()
             assert status[b] == 1 and ro.info.status == "solved"
             n_iter_match += int(iters[b] == ro.info.iter)
-            scale = max(1.0, np.abs(ro.x).max())
-            assert np.abs(sol[b] - ro.x).max() < 1e-5 * scale, (step, b)
-            du = slice((N + 1) * 6, None)
-            assert np.abs(sol[b, du] - ro.x[du]).max() < 1e-4
+            check_solutions(sol[b:b + 1], ro.x[None], slice((N + 1) * 6, None))
             # record, stop rule, plant step + shift from the device's own solution
             row, dist, cnt[b], done, xt_new, pred_new, pdu_new = tail(sol[b], last["Ad"][b, 0], last["Bd"][b, 0],
                                                                       last["gd"][b, 0], Xr, xt[b], cnt[b], N)
@@ -457,17 +406,6 @@ def test_stop_and_freeze(golden):
     assert tlen2[1] == 63 and not np.array_equal(xt2[1], xt[1])
 
 
-def _stage_shift(v, N, nxa, nu, groups):
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nxa:(g + 1) * (N + 1) * nxa].reshape(B, N + 1, nxa)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    d = v[:, groups * (N + 1) * nxa:].reshape(B, N, nu)
-    out.append(np.concatenate([d[:, 1:], d[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
-
-
 @pytest.mark.gpu
 def test_closed_loop_warm_start_matches_oracle():
     """warm_start=True (an extension): every step's solve starts from the previous solution
@@ -513,7 +451,6 @@ def test_shift_entry_points_reject_the_other_model():
     import torch
     from osqp_amd import lib
     from osqp_amd.mpc_device import KinVehicle, Vehicle, _bind, _p
-    EUNSUPPORTED = 2
     N, B = 4, 2
     L6 = IncrementalLayout(N, mpc.DYN_Q, mpc.DYN_QN, mpc.DYN_R, mpc.DYN_XMIN_T, mpc.DYN_XMAX_T, mpc.DYN_DUMIN,
                            -mpc.DYN_DUMIN)

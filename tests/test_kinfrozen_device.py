@@ -24,24 +24,19 @@ import json
 
 import numpy as np
 import pytest
-import scipy.sparse as sparse
 
+from loop_checks import (EINVAL, EUNSUPPORTED, check_assembled, check_fixture_step, check_solutions, check_whole_run,
+                         dense, dev as _t, host, oracle_batch, oracle_solve, same_csc as _same_csc, sim_qp as _sim_qp)
 from osqp_amd import mpc
 from osqp_amd.mpc_device import LTVLayout, _bind
 
-INF = 1e30  # OSQP_INFTY: bounds are clipped to it
 L_F, L_R, DT = 1.25, 1.40, 0.02  # main's vehicle (:270-283)
 VEH = (L_F, L_R, DT)
 W = (mpc.KINFROZEN_Q, mpc.KINFROZEN_QN, mpc.KINFROZEN_R)
 BOUNDS = (mpc.KINFROZEN_XMIN, mpc.KINFROZEN_XMAX, mpc.KINFROZEN_UMIN, mpc.KINFROZEN_UMAX)
 SETTINGS = dict(polish=False, warm_start=True)  # :195
-EINVAL, EUNSUPPORTED = 1, 2
 SIMS = [("kinfrozen_sim_n2.npz", 2), ("kinfrozen_sim_n3.npz", 3), ("kinfrozen_sim_n20.npz", 20),
         ("kinfrozen_sim_n100.npz", 100)]
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def _layout(N, **kw):
@@ -51,19 +46,6 @@ def _layout(N, **kw):
 def _qp(Ad, Bd, gd, x, Xr, N):
     """mpc (:148-191): the one model on every stage."""
     return mpc.ltv_qp([Ad] * N, [Bd] * N, [gd] * N, x, Xr, *W, N, *BOUNDS)
-
-
-def _sim_qp(g, t):
-    A = sparse.csc_matrix((g[f"A{t}_data"], g[f"A{t}_indices"], g[f"A{t}_indptr"]), shape=tuple(g[f"A{t}_shape"]))
-    return g["P"], g["q"][t], A, g["l"][t], g["u"][t]
-
-
-def _same_csc(M, Mr):
-    """The same pattern once explicit zeros are gone (the reference's scipy products store some)."""
-    M, Mr = sparse.csc_matrix(M, copy=True), sparse.csc_matrix(Mr, copy=True)
-    M.eliminate_zeros(); Mr.eliminate_zeros()
-    M.sort_indices(); Mr.sort_indices()
-    return np.array_equal(M.indptr, Mr.indptr) and np.array_equal(M.indices, Mr.indices)
 
 
 def _search(path_x, path_y, pred_x):
@@ -89,13 +71,7 @@ def loop(x0, u0, pred_u0, path_x, path_y, N, steps, solve):
     return np.stack(rows)
 
 
-def _oracle_solve(P, q, A, l, u):
-    import pyoracle
-    o = pyoracle.OSQP()
-    o.setup(P, q, A, l, u, **SETTINGS)
-    r = o.solve()
-    assert r.info.status == "solved"
-    return r.x
+_oracle_solve = oracle_solve(SETTINGS)
 
 
 # ----------------------------------------------------------------------- CPU tests --
@@ -209,11 +185,6 @@ def test_argument_errors():
 
 
 # ------------------------------------------------------------------------- GPU tests --
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64, device="cuda")
-
-
 def _tail(L, sol, status, Ad, Bd, gd, x, u, px, skipped, steps, traj, cap, tlen):
     """mpcqp_kin_frozen_tail_device on device tensors, on the null stream; returns the call's code."""
     import torch
@@ -340,34 +311,20 @@ def _state(ctl):
 def _check_step(ctl, before, N, status, Ppat, Apat, Px):
     """One step of the class against the host restatement fed the device's own state, the oracle
     on that QP, and the host tail of the device's own solution."""
-    import pyoracle
     x, u, pred_x = before
     px, py = ctl.path_x.cpu().numpy(), ctl.path_y.cpu().numpy()
     B = x.shape[0]
-    last = {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    sol = ctl.sol.cpu().numpy()
+    last, sol = host(ctl)
     for b in range(B):
         Xr = _search(px, py, pred_x[b])
         assert np.array_equal(last["Xr"][b], Xr)
         Ad, Bd, gd = _model(x[b], u[b])
         assert last["Ad"][b].shape == (N, 4, 4)                               # the one model on every stage
-        assert np.allclose(last["Ad"][b], Ad[None], rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["Bd"][b], Bd[None], rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["gd"][b], gd[None], rtol=1e-12, atol=1e-13)
         assert all(np.array_equal(last[k][b], np.repeat(last[k][b][:1], N, 0)) for k in ("Ad", "Bd", "gd"))
-        P, q, A, l, uu = _qp(Ad, Bd, gd, x[b], Xr, N)
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(A), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], q, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(l, -INF, INF), rtol=1e-12, atol=1e-14)
-        assert np.allclose(last["u"][b], np.clip(uu, -INF, INF), rtol=1e-12, atol=1e-14)
-    ro = pyoracle.solve_batch(Ppat, Apat, Px, last["q"], last["Ax"], last["l"], last["u"], nthreads=8, **SETTINGS)
-    assert np.array_equal(status, ro.status_val) and (status == 1).all()
-    du = slice((N + 1) * 4, None)
+        check_assembled(last, b, Ad[None], Bd[None], gd[None], _qp(Ad, Bd, gd, x[b], Xr, N), Apat)
+    ro = oracle_batch(last, status, Ppat, Apat, Px, SETTINGS)
+    check_solutions(sol, ro.x, slice((N + 1) * 4, None))
     for b in range(B):
-        scale = max(1.0, np.abs(ro.x[b]).max())
-        assert np.abs(sol[b] - ro.x[b]).max() < 1e-5 * scale, b
-        assert np.abs(sol[b, du] - ro.x[b, du]).max() < 1e-4, b
         row, xn, un, pxn, _ = mpc.kinfrozen_tail(sol[b], 1, last["Ad"][b, 0], last["Bd"][b, 0], last["gd"][b, 0], x[b],
                                                  u[b], pred_x[b], N)
         assert np.allclose(ctl.x[b].cpu().numpy(), xn, rtol=1e-13, atol=1e-13)
@@ -433,17 +390,7 @@ def test_one_step_at_the_shipped_horizon(golden):
     before = _state(ctl)
     status, iters = ctl.step()
     _check_step(ctl, before, N, status.cpu().numpy(), P, Apat, np.tile(P.data, (2, 1)))
-    sol, last = ctl.sol.cpu().numpy(), {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    du = slice((N + 1) * 4, None)
-    for b in range(2):
-        _, qr, Ar, lr, ur = _sim_qp(g, b)
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(Ar), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], qr, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(lr, -INF, INF), rtol=1e-12, atol=1e-14)
-        scale = max(1.0, np.abs(g["sol"][b]).max())
-        assert np.abs(sol[b] - g["sol"][b]).max() < 1e-5 * scale
-        assert np.abs(sol[b, du] - g["sol"][b, du]).max() < 1e-4
+    check_fixture_step(ctl, g, Apat, slice((N + 1) * 4, None))
     print("iters", iters.cpu().numpy(), "fixture", g["sol_iter"])
 
 
@@ -479,7 +426,4 @@ def test_whole_run_within_solver_tolerance(golden):
     status, _ = ctl.run(steps)
     traj, tlen = ctl.trajectories()
     assert np.array_equal(tlen, [steps, steps]) and not ctl.skipped.any() and (status.cpu().numpy() == 1).all()
-    assert np.array_equal(traj[0], traj[1]) and not traj[:, steps:].any()
-    err = np.abs(traj[0, :steps] - g["traj"]).max(0)
-    print("max |device - fixture| per column", err, "traj_sens", g["traj_sens"])
-    assert (err < g["traj_sens"]).all(), (err, g["traj_sens"])
+    check_whole_run(traj, steps, g)

@@ -22,23 +22,19 @@ import json
 
 import numpy as np
 import pytest
-import scipy.sparse as sparse
 
+from loop_checks import (EINVAL, EUNSUPPORTED, check_assembled, check_fixture_step, check_solutions, check_whole_run,
+                         dense, dev as _t, host, oracle_batch, oracle_solve, same_csc as _same_csc, sim_qp as _sim_qp,
+                         stage_shift as _stage_shift)
 from osqp_amd import mpc
 from osqp_amd.mpc_device import IncrementalLayout, KinVehicle, _bind
 
-INF = 1e30  # OSQP_INFTY: bounds are clipped to it
 L_F, L_R, DT = 1.25, 1.40, 0.02  # main's vehicle (:283-296)
 VEH = (L_F, L_R, DT)
 W = (mpc.LANE_Q, mpc.LANE_QN, mpc.LANE_R)
 BOUNDS = (mpc.LANE_XMIN_T, mpc.LANE_XMAX_T, mpc.LANE_DUMIN, -mpc.LANE_DUMIN)
 SETTINGS = dict(polish=False, warm_start=False)  # :242
-EINVAL, EUNSUPPORTED = 1, 2
 SIMS = [("lane_sim_n2.npz", 2), ("lane_sim_n3.npz", 3), ("lane_sim_n10.npz", 10), ("lane_sim_n40.npz", 40)]
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def _layout(N, **kw):
@@ -47,19 +43,6 @@ def _layout(N, **kw):
 
 def _qp(Ad, Bd, gd, xt, Xr, N):
     return mpc.incremental_qp(list(Ad), list(Bd), list(gd), xt, Xr, *W, N, *BOUNDS)
-
-
-def _sim_qp(g, t):
-    A = sparse.csc_matrix((g[f"A{t}_data"], g[f"A{t}_indices"], g[f"A{t}_indptr"]), shape=tuple(g[f"A{t}_shape"]))
-    return g["P"], g["q"][t], A, g["l"][t], g["u"][t]
-
-
-def _same_csc(M, Mr):
-    """The same pattern once explicit zeros are gone (the reference's scipy products store some)."""
-    M, Mr = sparse.csc_matrix(M, copy=True), sparse.csc_matrix(Mr, copy=True)
-    M.eliminate_zeros(); Mr.eliminate_zeros()
-    M.sort_indices(); Mr.sort_indices()
-    return np.array_equal(M.indptr, Mr.indptr) and np.array_equal(M.indices, Mr.indices)
 
 
 def _search(paths_x, paths_y, path_id, pred):
@@ -93,13 +76,7 @@ def loop(x0, u0, path_x, paths_y, switch_steps, paths_of, N, steps, solve):
     return np.stack(rows)
 
 
-def _oracle_solve(P, q, A, l, u):
-    import pyoracle
-    o = pyoracle.OSQP()
-    o.setup(P, q, A, l, u, **SETTINGS)
-    r = o.solve()
-    assert r.info.status == "solved"
-    return r.x
+_oracle_solve = oracle_solve(SETTINGS)
 
 
 # ----------------------------------------------------------------------- CPU tests --
@@ -234,11 +211,6 @@ def test_argument_errors():
 
 
 # ------------------------------------------------------------------------- GPU tests --
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64, device="cuda")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("B", [1, 130])
 def test_paths_search_matches_host(B):
@@ -365,34 +337,19 @@ def _state(ctl):
 def _check_step(ctl, before, N, status, Ppat, Apat, Px, settings=SETTINGS, warm=None):
     """One step of the class against the host restatement fed the device's own state, the oracle
     on that QP, and the host tail of the device's own solution."""
-    import pyoracle
     xt, pred, pdu, steps, pid = before
     paths_x, paths_y = ctl.paths_x.cpu().numpy(), ctl.paths_y.cpu().numpy()
     B = xt.shape[0]
-    last = {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    sol = ctl.sol.cpu().numpy()
+    last, sol = host(ctl)
     for b in range(B):
         Xr = _search(paths_x, paths_y, pid[b], pred[b])
         assert np.array_equal(last["Xr"][b], Xr)
         Ad, Bd, gd = mpc.linearise_kinematics(*VEH, pred[b, :N, :4], pred[b, :N, 4:])
-        assert np.allclose(last["Ad"][b], Ad, rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["Bd"][b], Bd, rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["gd"][b], gd, rtol=1e-12, atol=1e-13)
-        P, q, A, l, u = _qp(Ad, Bd, gd, xt[b], Xr, N)
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(A), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], q, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(l, -INF, INF), rtol=1e-12, atol=1e-14)
-        assert np.allclose(last["u"][b], np.clip(u, -INF, INF), rtol=1e-12, atol=1e-14)
-    ro = pyoracle.solve_batch(Ppat, Apat, Px, last["q"], last["Ax"], last["l"], last["u"], nthreads=8, **settings,
-                              **(warm or {}))
-    assert np.array_equal(status, ro.status_val) and (status == 1).all()
-    du = slice((N + 1) * 6, None)
+        check_assembled(last, b, Ad, Bd, gd, _qp(Ad, Bd, gd, xt[b], Xr, N), Apat)
+    ro = oracle_batch(last, status, Ppat, Apat, Px, settings, warm)
+    if warm is None:
+        check_solutions(sol, ro.x, slice((N + 1) * 6, None))
     for b in range(B):
-        if warm is None:
-            scale = max(1.0, np.abs(ro.x[b]).max())
-            assert np.abs(sol[b] - ro.x[b]).max() < 1e-5 * scale, b
-            assert np.abs(sol[b, du] - ro.x[b, du]).max() < 1e-4, b
         row, xn, pxn, pun, s1, p1 = mpc.lane_tail(sol[b], last["Ad"][b, 0], last["Bd"][b, 0], last["gd"][b, 0], xt[b],
                                                   steps[b], N, *VEH, ctl.switch_steps, ctl.paths_of)
         assert np.allclose(ctl.xt[b].cpu().numpy(), xn, rtol=1e-13, atol=1e-13)
@@ -456,18 +413,8 @@ def test_one_step_at_the_shipped_horizon(golden):
     before = _state(ctl)
     status, iters = ctl.step()
     _check_step(ctl, before, N, status.cpu().numpy(), P, Apat, np.tile(P.data, (2, 1)))
-    sol, last = ctl.sol.cpu().numpy(), {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    du = slice((N + 1) * 6, None)
-    for b in range(2):
-        _, qr, Ar, lr, ur = _sim_qp(g, b)
-        assert np.array_equal(last["Xr"][b], g["in_Xr"][b])
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(Ar), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], qr, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(lr, -INF, INF), rtol=1e-12, atol=1e-14)
-        scale = max(1.0, np.abs(g["sol"][b]).max())
-        assert np.abs(sol[b] - g["sol"][b]).max() < 1e-5 * scale
-        assert np.abs(sol[b, du] - g["sol"][b, du]).max() < 1e-4
+    assert np.array_equal(ctl.last["Xr"].cpu().numpy(), g["in_Xr"][:2])
+    check_fixture_step(ctl, g, Apat, slice((N + 1) * 6, None))
     print("iters", iters.cpu().numpy(), "fixture", g["sol_iter"])
 
 
@@ -485,22 +432,8 @@ def test_whole_run_within_solver_tolerance(golden):
     status, _ = ctl.run(steps)
     traj, tlen = ctl.trajectories()
     assert np.array_equal(tlen, [steps, steps]) and (status.cpu().numpy() == 1).all()
-    assert np.array_equal(traj[0], traj[1]) and not traj[:, steps:].any()
     assert np.array_equal(ctl.steps.cpu().numpy(), [steps, steps]) and not ctl.path_id.any()
-    err = np.abs(traj[0, :steps] - g["traj"]).max(0)
-    print("max |device - fixture| per column", err, "traj_sens", g["traj_sens"])
-    assert (err < g["traj_sens"]).all(), (err, g["traj_sens"])
-
-
-def _stage_shift(v, N, nx, nu, groups):
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nx:(g + 1) * (N + 1) * nx].reshape(B, N + 1, nx)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    d = v[:, groups * (N + 1) * nx:].reshape(B, N, nu)
-    out.append(np.concatenate([d[:, 1:], d[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
+    check_whole_run(traj, steps, g)
 
 
 @pytest.mark.gpu

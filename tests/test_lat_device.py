@@ -18,13 +18,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from loop_checks import EINVAL, EUNSUPPORTED
 from osqp_amd import canonical_data, mpc
 
 DEG = mpc.DEG
 S = (0.0, 0.0, 5 * DEG, 3.0, 0.0)
 AT, BT = mpc.augment(mpc.LATERAL_AD, mpc.LATERAL_BD)
 U_TOL = 1e-4  # the project's bar on the first control (tests/test_gpu_parity.py)
-EINVAL, EUNSUPPORTED = 1, 2
 
 
 def _script_regime(i):

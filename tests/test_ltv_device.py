@@ -30,21 +30,17 @@ import json
 
 import numpy as np
 import pytest
-import scipy.sparse as sparse
 
+from loop_checks import (EUNSUPPORTED, INF, check_assembled, check_fixture_step, check_solutions, check_whole_run, dense,
+                         dev as _t, host, oracle_batch, oracle_solve, same_csc as _same_csc, sim_qp as _sim_qp,
+                         stage_shift as _stage_shift)
 from osqp_amd import canonical_data, mpc
 from osqp_amd.mpc_device import KinVehicle, LTVLayout, _bind
 
-INF = 1e30  # OSQP_INFTY: bounds are clipped to it
 L_F, L_R, DT = 1.25, 1.40, 0.02  # main's vehicle (:357-370)
 W = (mpc.KINLTV_Q, mpc.KINLTV_QN, mpc.KINLTV_R)
 BOUNDS = (mpc.KINLTV_XMIN, mpc.KINLTV_XMAX, mpc.KINLTV_UMIN, mpc.KINLTV_UMAX)
 SETTINGS = dict(polish=False, warm_start=True)  # :347
-EUNSUPPORTED = 2
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def _layout(N, **kw):
@@ -57,31 +53,12 @@ def _qp(Ad, Bd, gd, x, Xr, N):
 
 # ------------------------------------------------------------------ host restatements --
 def reference_search(path_x, path_y, pred_x, dt, N):
-    """mpc_kinematics_pred_matrix.py:26-82 (nearest_point: reversed scan, strict <, look_ind 1):
-    pred_x (N+1, 4) stage-major -> Xr (4, N+1)."""
-    min_d, ind = np.inf, -1
-    for i in reversed(range(len(path_x))):
-        d = np.sqrt((path_x[i] - pred_x[0, 0]) ** 2 + (path_y[i] - pred_x[0, 1]) ** 2)
-        if d < min_d:
-            min_d, ind = d, i
-    ind += 1
-    x_ref = np.zeros((4, N + 1))
-    cumul_d = 0.0
-    path_d = np.sqrt((path_x[ind + 1] - path_x[ind]) ** 2 + (path_y[ind + 1] - path_y[ind]) ** 2)
-    for i in range(N + 1):
-        cumul_d = cumul_d + abs(pred_x[i, 2]) * dt
-        while cumul_d >= path_d:
-            ind = ind + 1
-            path_d = path_d + np.sqrt((path_x[ind + 1] - path_x[ind]) ** 2 + (path_y[ind + 1] - path_y[ind]) ** 2)
-        x_ref[:, i] = path_x[ind], path_y[ind], 10.0, 0.0
-    return x_ref
+    """mpc_kinematics_pred_matrix.py:26-82 (speed 10, yaw 0): pred_x (N+1, 4) stage-major -> Xr (4, N+1)."""
+    return mpc.reference_search_paths(path_x[None], path_y[None], None, None, [10.0], pred_x[None], dt)[0]
 
 
 def kin_update(x, u):
-    """update_kinematics_model (vehicle_models.py:866-883): in place there, so v first."""
-    X, Y, v, yaw = x
-    v1 = v + u[1] * DT
-    return np.array([X + v * np.cos(yaw) * DT, Y + v * np.sin(yaw) * DT, v1, yaw + v1 / (L_F + L_R) * np.tan(u[0]) * DT])
+    return mpc.kin_update(L_F, L_R, DT, x, u)
 
 
 def rollout(x0, u0, N):
@@ -122,27 +99,7 @@ def loop(x0, u0, path_x, path_y, N, steps, solve):
     return np.stack(rows)
 
 
-def _oracle_solve(P, q, A, l, u):
-    import pyoracle
-    o = pyoracle.OSQP()
-    o.setup(P, q, A, l, u, **SETTINGS)
-    r = o.solve()
-    assert r.info.status == "solved"
-    return r.x
-
-
-def _sim_qp(g, t):
-    A = sparse.csc_matrix((g[f"A{t}_data"], g[f"A{t}_indices"], g[f"A{t}_indptr"]), shape=tuple(g[f"A{t}_shape"]))
-    return g["P"], g["q"][t], A, g["l"][t], g["u"][t]
-
-
-def _same_csc(M, Mr):
-    """The same pattern once explicit zeros are gone (scipy's kron / block_diag of the
-    reference's DIA weights store some; mpc.ltv_qp, like the other builders, drops them)."""
-    M, Mr = sparse.csc_matrix(M, copy=True), sparse.csc_matrix(Mr, copy=True)
-    M.eliminate_zeros(); Mr.eliminate_zeros()
-    M.sort_indices(); Mr.sort_indices()
-    return np.array_equal(M.indptr, Mr.indptr) and np.array_equal(M.indices, Mr.indices)
+_oracle_solve = oracle_solve(SETTINGS)
 
 
 # ----------------------------------------------------------------------- CPU tests --
@@ -316,11 +273,6 @@ def test_argument_errors_are_unsupported():
 
 
 # ------------------------------------------------------------------------- GPU tests --
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64, device="cuda")
-
-
 def _rep(a, B):
     """B instances cycling through the leading axis of a."""
     return np.ascontiguousarray(a[np.arange(B) % a.shape[0]])
@@ -489,33 +441,18 @@ def _main_path():
 def _check_step(ctl, before, N, status, Ppat, Apat, Px):
     """One step of the class against the host restatement fed the device's own state, the oracle
     on that QP, and the host tail of the device's own solution."""
-    import pyoracle
     x, pred_x, pred_u = before
     px, py = _main_path()
     B = x.shape[0]
-    last = {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    sol = ctl.sol.cpu().numpy()
-    qs, ls, us, Axs = [], [], [], []
+    last, sol = host(ctl)
     for b in range(B):
         Xr = reference_search(px, py, pred_x[b], DT, N)
         assert np.array_equal(last["Xr"][b], Xr)
         Ad, Bd, gd = mpc.linearise_kinematics(L_F, L_R, DT, pred_x[b, :N], pred_u[b, :N])
-        assert np.allclose(last["Ad"][b], Ad, rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["Bd"][b], Bd, rtol=1e-13, atol=1e-15)
-        assert np.allclose(last["gd"][b], gd, rtol=1e-12, atol=1e-13)
-        P, q, A, l, u = _qp(Ad, Bd, gd, x[b], Xr, N)
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(A), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], q, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(l, -INF, INF), rtol=1e-12, atol=1e-14)
-        assert np.allclose(last["u"][b], np.clip(u, -INF, INF), rtol=1e-12, atol=1e-14)
-    ro = pyoracle.solve_batch(Ppat, Apat, Px, last["q"], last["Ax"], last["l"], last["u"], nthreads=8, **SETTINGS)
-    assert np.array_equal(status, ro.status_val) and (status == 1).all()
-    du = slice((N + 1) * 4, None)
+        check_assembled(last, b, Ad, Bd, gd, _qp(Ad, Bd, gd, x[b], Xr, N), Apat)
+    ro = oracle_batch(last, status, Ppat, Apat, Px, SETTINGS)
+    check_solutions(sol, ro.x, slice((N + 1) * 4, None))
     for b in range(B):
-        scale = max(1.0, np.abs(ro.x[b]).max())
-        assert np.abs(sol[b] - ro.x[b]).max() < 1e-5 * scale, b
-        assert np.abs(sol[b, du] - ro.x[b, du]).max() < 1e-4, b
         row, xn, un, pxn, pun = tail(sol[b], last["Ad"][b, 0], last["Bd"][b, 0], last["gd"][b, 0], x[b], N)
         assert np.allclose(ctl.x[b].cpu().numpy(), xn, rtol=1e-13, atol=1e-13)
         assert np.array_equal(ctl.u[b].cpu().numpy(), un)
@@ -577,17 +514,7 @@ def test_one_step_at_the_shipped_horizon(golden):
     before = _state(ctl)
     status, iters = ctl.step()
     _check_step(ctl, before, N, status.cpu().numpy(), P, Apat, np.tile(P.data, (2, 1)))
-    sol, last = ctl.sol.cpu().numpy(), {k: v.cpu().numpy() for k, v in ctl.last.items()}
-    du = slice((N + 1) * 4, None)
-    for b in range(2):
-        _, qr, Ar, lr, ur = _sim_qp(g, b)
-        A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-        assert np.allclose(dense(A_dev), dense(Ar), rtol=1e-12, atol=1e-15)
-        assert np.allclose(last["q"][b], qr, rtol=1e-12, atol=1e-12)
-        assert np.allclose(last["l"][b], np.clip(lr, -INF, INF), rtol=1e-12, atol=1e-14)
-        scale = max(1.0, np.abs(g["sol"][b]).max())
-        assert np.abs(sol[b] - g["sol"][b]).max() < 1e-5 * scale
-        assert np.abs(sol[b, du] - g["sol"][b, du]).max() < 1e-4
+    check_fixture_step(ctl, g, Apat, slice((N + 1) * 4, None))
     print("iters", iters.cpu().numpy(), "fixture", g["sol_iter"])
 
 
@@ -623,21 +550,7 @@ def test_whole_run_within_solver_tolerance(golden):
     status, _ = ctl.run(steps)
     traj, tlen = ctl.trajectories()
     assert np.array_equal(tlen, [steps, steps]) and not ctl.skipped.any() and (status.cpu().numpy() == 1).all()
-    assert np.array_equal(traj[0], traj[1]) and not traj[:, steps:].any()
-    err = np.abs(traj[0, :steps] - g["traj"]).max(0)
-    print("max |device - fixture| per column", err, "traj_sens", g["traj_sens"])
-    assert (err < g["traj_sens"]).all(), (err, g["traj_sens"])
-
-
-def _stage_shift(v, N, nx, nu, groups):
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nx:(g + 1) * (N + 1) * nx].reshape(B, N + 1, nx)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    d = v[:, groups * (N + 1) * nx:].reshape(B, N, nu)
-    out.append(np.concatenate([d[:, 1:], d[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
+    check_whole_run(traj, steps, g)
 
 
 @pytest.mark.gpu

@@ -21,14 +21,10 @@ import json
 import numpy as np
 import pytest
 
+from loop_checks import (INF, check_assembled, check_solutions, dense, host, sim_qp as _main_qp,
+                         stage_shift as _stage_shift)
 from osqp_amd import canonical_data, mpc
 from osqp_amd.mpc_device import DYN_MASK_A, DYN_MASK_B, IncrementalLayout
-
-INF = 1e30  # OSQP_INFTY: bounds are clipped to it (osqp 0.6 osqp_setup / update_bounds)
-
-
-def dense(M):
-    return np.asarray(M.todense())
 
 
 def _layout(N, **kw):
@@ -130,12 +126,6 @@ def test_reference_search_restatement_matches_reference(golden):
     N = g["pred"].shape[2] - 1
     for b in range(g["pred"].shape[0]):
         assert np.array_equal(reference_search(g["path_x"], g["path_y"], g["pred"][b], float(g["dt"]), N), g["Xr"][b])
-
-
-def _main_qp(g, t):
-    A = __import__("scipy.sparse", fromlist=["csc_matrix"]).csc_matrix(
-        (g[f"A{t}_data"], g[f"A{t}_indices"], g[f"A{t}_indptr"]), shape=tuple(g[f"A{t}_shape"]))
-    return g["P"], g["q"][t], A, g["l"][t], g["u"][t]
 
 
 def test_main_steps_restatements_match_reference(golden):
@@ -333,30 +323,21 @@ def test_closed_loop_matches_host_restatement():
         xt, pred = ctl.xt.cpu().numpy(), ctl.pred.cpu().numpy()
         status, iters = ctl.step()
         status, iters = status.cpu().numpy(), iters.cpu().numpy()
-        last = {k: v.cpu().numpy() for k, v in ctl.last.items()}
-        sol = ctl.sol.cpu().numpy()
+        last, sol = host(ctl)
         for b in range(B):
             Xr = reference_search(px, py, pred[b].T[:6], 0.05, N)
             assert np.array_equal(last["Xr"][b], Xr)
             Ad, Bd, gd = mpc.linearise_dynamics(veh, pred[b, :N, :6], pred[b, :N, 6:])
-            assert np.allclose(last["Ad"][b], Ad, rtol=1e-13, atol=1e-15)
-            assert np.allclose(last["gd"][b], gd, rtol=1e-12, atol=1e-13)
             P, q, A, l, u = mpc.incremental_qp(list(Ad), list(Bd), list(gd), xt[b], Xr, mpc.DYN_Q, mpc.DYN_QN,
                                                mpc.DYN_R, N, mpc.DYN_XMIN_T, mpc.DYN_XMAX_T, mpc.DYN_DUMIN,
                                                -mpc.DYN_DUMIN)
-            A_dev = Apat.copy(); A_dev.data = last["Ax"][b]
-            assert np.allclose(dense(A_dev), dense(A), rtol=1e-12, atol=1e-15)
-            assert np.allclose(last["q"][b], q, rtol=1e-12, atol=1e-12)
-            assert np.allclose(last["l"][b], np.clip(l, -INF, INF), rtol=1e-12, atol=1e-14)
+            check_assembled(last, b, Ad, Bd, gd, (P, q, A, l, u), Apat)
             o = pyoracle.OSQP()
             o.setup(P, q, A, l, u, polish=False, warm_start=False)
             ro = o.solve()
             assert status[b] == 1 and ro.info.status == "solved"
             n_iter_match += int(iters[b] == ro.info.iter)
-            scale = max(1.0, np.abs(ro.x).max())
-            assert np.abs(sol[b] - ro.x).max() < 1e-5 * scale, (step, b)
-            du = slice((N + 1) * 8, None)
-            assert np.abs(sol[b, du] - ro.x[du]).max() < 1e-4
+            check_solutions(sol[b:b + 1], ro.x[None], slice((N + 1) * 8, None))
             # plant step + shift from the device's own solution
             xt_new, pred_new, pdu_new = shift(sol[b], last["Ad"][b, 0], last["Bd"][b, 0], last["gd"][b, 0], xt[b],
                                               veh, N)
@@ -378,18 +359,8 @@ def test_warm_shift_moves_every_block_one_stage():
     rng = np.random.default_rng(0)
     x = rng.standard_normal((B, n)); y = rng.standard_normal((B, m))
     xs, ys = warm_shift(N, nxa, nu, torch.tensor(x, device="cuda"), torch.tensor(y, device="cuda"))
-
-    def shift(v, groups):
-        out = []
-        for g in range(groups):
-            blk = v[:, g * (N + 1) * nxa:(g + 1) * (N + 1) * nxa].reshape(B, N + 1, nxa)
-            out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-        du = v[:, groups * (N + 1) * nxa:].reshape(B, N, nu)
-        out.append(np.concatenate([du[:, 1:], du[:, -1:]], 1).reshape(B, -1))
-        return np.concatenate(out, 1)
-
-    assert np.array_equal(xs.cpu().numpy(), shift(x, 1))
-    assert np.array_equal(ys.cpu().numpy(), shift(y, 2))
+    assert np.array_equal(xs.cpu().numpy(), _stage_shift(x, N, nxa, nu, 1))
+    assert np.array_equal(ys.cpu().numpy(), _stage_shift(y, N, nxa, nu, 2))
 
 
 @pytest.mark.gpu
@@ -427,17 +398,6 @@ def test_closed_loop_warm_start_matches_oracle():
         prev = (x, warm.y.cpu().numpy())
     assert match >= 0.9 * B * steps
     assert iw < ic
-
-
-def _stage_shift(v, N, nxa, nu, groups):
-    B = v.shape[0]
-    out = []
-    for g in range(groups):
-        blk = v[:, g * (N + 1) * nxa:(g + 1) * (N + 1) * nxa].reshape(B, N + 1, nxa)
-        out.append(np.concatenate([blk[:, 1:], blk[:, -1:]], 1).reshape(B, -1))
-    d = v[:, groups * (N + 1) * nxa:].reshape(B, N, nu)
-    out.append(np.concatenate([d[:, 1:], d[:, -1:]], 1).reshape(B, -1))
-    return np.concatenate(out, 1)
 
 
 @pytest.mark.gpu
