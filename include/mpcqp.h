@@ -209,6 +209,42 @@ int mpcqp_setup_warm_fused(const mpcqp_handle *h);
 int mpcqp_setup_solve_device(mpcqp_handle *h, const double *dPx, const double *dAx, const double *dq,
                              const double *dl, const double *du, double *dx, double *dy, int32_t *dstatus,
                              int32_t *diters, void *stream);
+/* Gradients of the last solve's solution with respect to the problem data ("Gradients
+ * of the solution"; not an osqp call).  For every instance whose status is "solved" and every
+ * one of its nrhs seeds (g_x, g_y), with L = g_x . x + g_y . y, in the caller's units:
+ *   row classes act[i]: 3 equality (l_i == u_i, always active), 1 lower (z_i - l_i < -y_i),
+ *     2 upper (u_i - z_i < y_i) -- polish's rule on the workspace's scaled z and y --, 0 inactive;
+ *   K [r_x; r_y] = [g_x; g_y] with K = [[P, A_act'], [A_act, 0]] over the active rows (g_y is read
+ *     on active rows only; r_y = 0 on the others);
+ *   gq = -r_x;  gl_i = r_y,i on a lower row, gu_i = r_y,i on an upper row, on an equality row
+ *     r_y,i goes to gl_i when y_i <= 0 and to gu_i when y_i > 0; zero elsewhere and where the
+ *     bound is infinite;
+ *   gAx = -(y_i r_x,j + r_y,i x_j) per stored entry (i, j) of A;  gPx = -(r_x,i x_j + r_x,j x_i)
+ *     per stored entry i < j of triu(P), -r_x,i x_i on the diagonal; both in the CSC order of the
+ *     value arrays the setup took (per instance also in shared-matrix mode: the caller sums).
+ * The linear solve is polish's: the settings' delta regularises, polish_refine_iter refinement
+ * steps follow (both changeable through mpcqp_update_settings; settings.polish need not be on).
+ * ares[b*nrhs + r] = ||K s - g||_inf / max(||g||_inf, tiny) on the scaled system after the last
+ * step.  astat[b]: 0 the instance is not "solved" (every output of it is zero), 1 every seed's
+ * ares is below 1e-8, -1 otherwise (K singular on the active set -- the slack layouts, whose
+ * slack columns carry no quadratic cost -- or too ill-conditioned for the refinement steps
+ * taken; a factorisation that fails or a solve that does not stay finite returns zeros with
+ * ares = 1).  Seeds: gx (B, nrhs, n), gy (B, nrhs, m), either may be NULL (zeros), not both.
+ * Outputs, any may be NULL: rx, gq (B, nrhs, n); ry, gl, gu (B, nrhs, m); gPx (B, nrhs, nnzP);
+ * gAx (B, nrhs, nnzA); act (B, m); ares (B, nrhs); astat (B).
+ * MPCQP_EINVAL: nrhs < 1, both seeds NULL, no solve since the last setup, or the workspace state
+ * is gone (one-shot mode).  A handle whose plan eliminated variables moves to the plain plan
+ * first, as under mpcqp_update_settings(polish = 1).  Like polish the call takes the workspace's
+ * factor tiles (the next solve refactors) and leaves the iterates, the info and the statuses
+ * alone.  mpcqp_adjoint_device: device pointers, enqueued on `stream` as mpcqp_solve_device.
+ * mpcqp_adjoint_batch: host pointers, any handle of mpcqp_setup_batch (shards included), blocks
+ * until the outputs are on the host. */
+int mpcqp_adjoint_device(mpcqp_handle *h, int32_t nrhs, const double *dgx, const double *dgy, double *drx,
+                         double *dry, double *dgq, double *dgl, double *dgu, double *dgPx, double *dgAx,
+                         int8_t *dact, double *dares, int32_t *dastat, void *stream);
+int mpcqp_adjoint_batch(mpcqp_handle *h, int32_t nrhs, const double *gx, const double *gy, double *rx, double *ry,
+                        double *gq, double *gl, double *gu, double *gPx, double *gAx, int8_t *act, double *ares,
+                        int32_t *astat);
 /* LTI batches ("LTI shared-matrix mode"): with shared != 0 the following
  * mpcqp_setup_device / mpcqp_setup_solve_device calls read ONE Px[nnzP] and ONE Ax[nnzA]
  * for every instance of the batch instead of B copies (the lateral MPC's P and A do not

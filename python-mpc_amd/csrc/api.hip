@@ -130,6 +130,7 @@ struct mpcqp_handle {
     bool staged = false;  // every shard's hstage holds the last mpcqp_solve_batch's results
     bool one_shot = false;    // mpcqp_set_one_shot: setup_solve_device persists no workspace state
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
+    bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
 };
 
 namespace {
@@ -1313,6 +1314,7 @@ int mpcqp_solve_batch(mpcqp_handle* h, double* x, double* y, int32_t* status, in
         if (iters) std::copy(g.iter, g.iter + s.B, iters + s.b0);
     }
     h->staged = all_staged;
+    h->solved = true;
     float ms = 0.f;
     h->last_ms = -1.0;
     if (evs && h->shards.size() == 1 && hipEventElapsedTime(&ms, h->shards[0].ev0, h->shards[0].ev1) == hipSuccess) {
@@ -1426,6 +1428,7 @@ int mpcqp_setup_device(mpcqp_handle* h, const double* dPx, const double* dAx, co
     if (h->collect_setup)
         if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
     h->state_gone = false;
+    h->solved = false;
     return stream_leave(s, st);
 }
 
@@ -1469,6 +1472,7 @@ int mpcqp_setup_warm_device(mpcqp_handle* h, const double* dPx, const double* dA
     if (h->collect_setup)
         if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
     h->state_gone = false;
+    h->solved = false;
     s.kp.warm_start = 1;
     h->set.warm_start = 1;
     return stream_leave(s, st);
@@ -1500,6 +1504,7 @@ int mpcqp_solve_device(mpcqp_handle* h, double* dx, double* dy, int32_t* dstatus
     }
     HIPCHK(launch_order(k, s.B, st));
     h->timed = true;
+    h->solved = true;
     return stream_leave(s, st);
 }
 
@@ -1529,7 +1534,117 @@ int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* d
     }
     HIPCHK(launch_order(k, s.B, st));
     h->timed = true;
+    h->solved = true;
     return stream_leave(s, st);
+}
+
+// what both adjoint entry points check before any device work; a handle on an eliminated plan
+// moves to the plain plan (the adjoint system is factored over all of K, as polish's)
+static int adjoint_enter(mpcqp_handle* h, int32_t nrhs, const void* gx, const void* gy, const char* what) {
+    if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
+    if (nrhs < 1) return fail(MPCQP_EINVAL, "%s: nrhs must be at least 1 (got %d)", what, (int)nrhs);
+    if (!gx && !gy) return fail(MPCQP_EINVAL, "%s: both seeds are NULL", what);
+    if (int e = need_state(h, what)) return e;
+    if (!h->solved) return fail(MPCQP_EINVAL, "%s: no solve has run on this handle's setup yet", what);
+    if (h->plan->ne > 0)
+        if (int e = replan_plain(h)) return e;
+    return 0;
+}
+
+int mpcqp_adjoint_device(mpcqp_handle* h, int32_t nrhs, const double* dgx, const double* dgy, double* drx,
+                         double* dry, double* dgq, double* dgl, double* dgu, double* dgPx, double* dgAx,
+                         int8_t* dact, double* dares, int32_t* dastat, void* stream) {
+    if (int e = adjoint_enter(h, nrhs, dgx, dgy, "mpcqp_adjoint_device")) return e;
+    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    Shard& s = h->shards[0];
+    hipStream_t st = pick(s, stream);
+    HIPCHK(hipSetDevice(s.dev));
+    if (int e = stream_enter(s, st)) return e;
+    const AdjointIO io{nrhs, dgx, dgy, drx, dry, dgq, dgl, dgu, dgPx, dgAx, (signed char*)dact, dares, dastat};
+    HIPCHK(launch_adjoint(s.kp, s.B, io, st));
+    return stream_leave(s, st);
+}
+
+int mpcqp_adjoint_batch(mpcqp_handle* h, int32_t nrhs, const double* gx, const double* gy, double* rx, double* ry,
+                        double* gq, double* gl, double* gu, double* gPx, double* gAx, int8_t* act, double* ares,
+                        int32_t* astat) {
+    if (int e = adjoint_enter(h, nrhs, gx, gy, "mpcqp_adjoint_batch")) return e;
+    const long n = h->n, m = h->m, nP = h->plan->nnzP, nA = h->plan->nnzA, R = nrhs;
+    // per shard one device block and (small shards) one pinned block of the same layout: the
+    // seeds, then every output the caller asked for; freed (to the pool) after the call
+    struct Seg { const void* in; void* out; long per; int sz; size_t off; };  // per: elements per instance
+    struct Tmp { void* d = nullptr; char* hb = nullptr; size_t bytes = 0; };
+    std::vector<Tmp> tmp(h->shards.size());
+    auto release = [&]() {
+        for (size_t i = 0; i < tmp.size(); ++i) {
+            pool_free(h->shards[i].dev, tmp[i].bytes, tmp[i].d, false);
+            pool_free(h->shards[i].dev, tmp[i].bytes, tmp[i].hb, true);
+        }
+    };
+    std::vector<std::vector<Seg>> segs(h->shards.size());
+    auto enqueue = [&](size_t si) -> int {
+        Shard& s = h->shards[si];
+        const long Bs = s.B;
+        std::vector<Seg>& sg = segs[si];
+        sg = {{gx, nullptr, R * n, 8, 0},  {gy, nullptr, R * m, 8, 0},  {nullptr, rx, R * n, 8, 0},
+              {nullptr, ry, R * m, 8, 0},  {nullptr, gq, R * n, 8, 0},  {nullptr, gl, R * m, 8, 0},
+              {nullptr, gu, R * m, 8, 0},  {nullptr, gPx, R * nP, 8, 0}, {nullptr, gAx, R * nA, 8, 0},
+              {nullptr, ares, R, 8, 0},    {nullptr, astat, 1, 4, 0},   {nullptr, act, m, 1, 0}};
+        size_t off = 0;
+        for (auto& g : sg) {
+            if (!g.in && !g.out) continue;
+            g.off = carve<char>(off, (size_t)Bs * g.per * g.sz);
+        }
+        Tmp& t = tmp[si];
+        t.bytes = off + 256;
+        HIPCHK(hipSetDevice(s.dev));
+        HIPCHK(pool_malloc(s.dev, t.bytes, &t.d, false));
+        if (t.bytes <= kStageMax) HIPCHK(pool_malloc(s.dev, t.bytes, (void**)&t.hb, true));
+        char* const db = (char*)t.d;
+        if (int e = stream_enter(s, s.stream)) return e;
+        if (t.hb) {  // the seeds lie first: one copy up
+            size_t up = 0;
+            for (auto& g : sg)
+                if (g.in) {
+                    const size_t by = (size_t)Bs * g.per * g.sz;
+                    memcpy(t.hb + g.off, (const char*)g.in + (size_t)s.b0 * g.per * g.sz, by);
+                    up = g.off + by;
+                }
+            HIPCHK(hipMemcpyAsync(db, t.hb, up, hipMemcpyHostToDevice, s.stream));
+        } else {
+            for (auto& g : sg)
+                if (g.in)
+                    HIPCHK(hipMemcpyAsync(db + g.off, (const char*)g.in + (size_t)s.b0 * g.per * g.sz,
+                                          (size_t)Bs * g.per * g.sz, hipMemcpyHostToDevice, s.stream));
+        }
+        auto dp = [&](int k) { return (sg[k].in || sg[k].out) ? db + sg[k].off : nullptr; };
+        const AdjointIO io{nrhs, (const double*)dp(0), (const double*)dp(1), (double*)dp(2), (double*)dp(3),
+                           (double*)dp(4), (double*)dp(5), (double*)dp(6), (double*)dp(7), (double*)dp(8),
+                           (signed char*)dp(11), (double*)dp(9), (int*)dp(10)};
+        HIPCHK(launch_adjoint(s.kp, Bs, io, s.stream));
+        if (t.hb) {
+            HIPCHK(hipMemcpyAsync(t.hb, db, off, hipMemcpyDeviceToHost, s.stream));
+        } else {
+            for (auto& g : sg)
+                if (g.out)
+                    HIPCHK(hipMemcpyAsync((char*)g.out + (size_t)s.b0 * g.per * g.sz, db + g.off,
+                                          (size_t)Bs * g.per * g.sz, hipMemcpyDeviceToHost, s.stream));
+        }
+        return stream_leave(s, s.stream);
+    };
+    int err = 0;
+    for (size_t si = 0; si < h->shards.size() && !err; ++si) err = enqueue(si);
+    if (int e = sync_all(h); e && !err) err = e;  // (also on an error: no block goes back to the pool in use)
+    if (!err)
+        for (size_t si = 0; si < h->shards.size(); ++si) {
+            if (!tmp[si].hb) continue;
+            const Shard& s = h->shards[si];
+            for (auto& g : segs[si])
+                if (g.out)
+                    memcpy((char*)g.out + (size_t)s.b0 * g.per * g.sz, tmp[si].hb + g.off, (size_t)s.B * g.per * g.sz);
+        }
+    release();
+    return err;
 }
 
 void* mpcqp_get_stream(const mpcqp_handle* h) {

@@ -190,6 +190,20 @@ size_t lds_dense_bytes(const KParams& p);
 size_t lds_w2_bytes(const KParams& p);  // solve_wave.hip, variant 10
 // solution polishing (OSQP 0.6 polish.c) after the solve; launch_solve runs it when p.polish
 hipError_t launch_polish(const KParams& p, long B, double* xo, double* yo, hipStream_t st);
+// Gradients of the solution map (adjoint.hip::k_adjoint; mpcqp_adjoint_device): the seeds and
+// outputs of one call, device pointers, instance-major with nrhs seeds per instance.  Either
+// seed and any output may be null.
+struct AdjointIO {
+    int nrhs;
+    const double *gx, *gy;           // (B, nrhs, n), (B, nrhs, m)
+    double *rx, *ry;                 // (B, nrhs, n), (B, nrhs, m)
+    double *gq, *gl, *gu;            // (B, nrhs, n | m | m)
+    double *gPx, *gAx;               // (B, nrhs, nnzP | nnzA), the user's CSC order
+    signed char* act;                // (B, m): 0 inactive, 1 lower, 2 upper, 3 equality
+    double* ares;                    // (B, nrhs)
+    int* astat;                      // (B): 0 not run (status not solved), 1 every seed below 1e-8, -1
+};
+hipError_t launch_adjoint(const KParams& p, long B, const AdjointIO& io, hipStream_t st);
 // one-wave-per-QP kernel (solve_wave.hip), variants 8 and 9
 hipError_t launch_solve_wave(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
                         KernelRef* ref = nullptr);

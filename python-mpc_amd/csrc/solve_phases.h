@@ -1726,6 +1726,39 @@ __device__ __noinline__ bool factorize_pol_nl(const KParams* gp, long b) {
     return factorize<TT, KPc, true>(p, c.L, 1.0 / p.delta, p.F + b * (long)p.nb * SS, p.H + b * (long)p.nb * SS,
                                     p.Si + b * (long)p.nb * SS);
 }
+// x~ = K_pol^{-1} rb (rb overwritten) with the mode-1 factor in the workspace:
+// F_k rows < amax, S_k^{-1}.  Block Thomas, 2 nb - 1 barriers.  (solve.hip::k_polish, adjoint.hip::k_adjoint)
+__device__ inline void pol_solve(const KParams& p, const double* __restrict__ Fg, const double* __restrict__ Sg,
+                          double* rb, double* xt) {
+    const int tid = threadIdx.x, i = tid >> 3, jg = tid & 7, nb = p.nb, amax = p.amax;
+    for (int k = 0; k < nb; ++k) {
+        const double* v = rb + k * S;
+        const double* Sk = Sg + (long)k * SS + i * S;
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a += Sk[jg + 8 * c] * v[jg + 8 * c];
+        const double t = reduce8(a);
+        if (k + 1 < nb && i < amax) {
+            const double* Fk = Fg + (long)(k + 1) * SS + i * S;
+            double f = 0.0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) f += Fk[jg + 8 * c] * v[jg + 8 * c];
+            f = reduce8(f);
+            if (jg == 0) rb[(k + 1) * S + i] -= f;
+        }
+        if (jg == 0) xt[k * S + i] = t;
+        __syncthreads();
+    }
+    for (int k = nb - 2; k >= 0; --k) {  // x_k = t_k - F_{k+1}' x_{k+1}[0, amax)
+        const double* F1 = Fg + (long)(k + 1) * SS;
+        double a = 0.0;
+        for (int r = jg; r < amax; r += 8) a += F1[r * S + i] * xt[(k + 1) * S + r];
+        a = reduce8(a);
+        if (jg == 0) xt[k * S + i] -= a;
+        __syncthreads();
+    }
+}
+
 // sdst: where the S_k^{-1} tiles go (default: the workspace; the two-wave kernel keeps
 // them in LDS)
 template <int TT, bool ROT = false>

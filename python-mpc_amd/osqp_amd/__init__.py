@@ -137,6 +137,8 @@ def lib():
     L.mpcqp_setup_warm_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpcqp_setup_warm_fused.argtypes = [vp]
     L.mpcqp_solve_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mpcqp_adjoint_device.argtypes = [vp, C.c_int32] + [vp] * 13
+    L.mpcqp_adjoint_batch.argtypes = [vp, C.c_int32] + [dp] * 9 + [_P(C.c_int8), dp, i32p]
     L.mpcqp_synchronize.argtypes = [vp]
     L.mpcqp_set_shared_matrices.argtypes = [vp, C.c_int32]
     L.mpcqp_set_one_shot.argtypes = [vp, C.c_int32]
@@ -349,6 +351,8 @@ class OSQPBatch:
         self._keep = (kp, ka)
         self._pmap = self._amap = None
         self._nnz_user = (P.nnz, A.nnz)
+        self._user_pattern = (P.indptr, P.indices, A.indptr, A.indices)  # (adjoint: dropped entries)
+        self._last_xy = None
         P, Px = _drop_common_zeros(P, Px, kp)
         A, Ax = _drop_common_zeros(A, Ax, ka)
         Px = np.ascontiguousarray(Px, np.float64)
@@ -460,6 +464,7 @@ class OSQPBatch:
         t0 = time.perf_counter()
         _check(lib().mpcqp_solve_batch(h, _dp(x), _dp(y), _ip(st), _ip(it)), "solve")
         solve_time = time.perf_counter() - t0
+        self._last_xy = (x, y)
         obj = np.empty(B); pri = np.empty(B); dua = np.empty(B); rho = np.empty(B)
         ru = np.empty(B, np.int32)
         _check(lib().mpcqp_get_info_batch(h, _dp(obj), _dp(pri), _dp(dua), _dp(rho), _ip(ru)), "info")
@@ -471,6 +476,64 @@ class OSQPBatch:
                                rho_estimate=rho, rho_updates=ru, prim_inf_cert=pc, dual_inf_cert=dc,
                                status_polish=sp, solve_time=solve_time,
                                status=[STATUS.get(int(v), "unknown") for v in st])
+
+    def adjoint(self, gx=None, gy=None):
+        """Gradients of L = gx . x + gy . y at the last solve's solution (mpcqp_adjoint_batch;
+        mpcqp.h has the definition).  gx: (B, n) or (B, nrhs, n), gy: (B, m) or (B, nrhs, m), one
+        may be None.  Returns rx, gq (B, nrhs, n), ry, gl, gu (B, nrhs, m), gPx (B, nrhs, nnz(triu(P))),
+        gAx (B, nrhs, nnz(A)) in the setup's CSC value order, act (B, m) int8 (0 inactive, 1 lower,
+        2 upper, 3 equality), ares (B, nrhs), astat (B,); 2-D seeds drop the nrhs axis.  An entry of
+        P or A that was zero in every instance at setup (not in the device's pattern) gets its
+        gradient from the same formula, evaluated here from rx, ry and the last solve's x, y."""
+        h = self._need()
+        if gx is None and gy is None:
+            raise ValueError("adjoint: gx or gy must be given")
+        B, n, m = self.B, self.n, self.m
+        seeds = []
+        for g, k in ((gx, n), (gy, m)):
+            if g is not None:
+                g = np.asarray(g, np.float64)
+                if g.ndim not in (2, 3) or g.shape[0] != B or g.shape[-1] != k:
+                    raise ValueError(f"adjoint: a seed must have shape ({B}, {k}) or ({B}, nrhs, {k})")
+            seeds.append(g)
+        flat = all(g is None or g.ndim == 2 for g in seeds)
+        seeds = [None if g is None else np.ascontiguousarray(g.reshape(B, -1, g.shape[-1])) for g in seeds]
+        R = next(g.shape[1] for g in seeds if g is not None)
+        if any(g is not None and g.shape[1] != R for g in seeds):
+            raise ValueError("adjoint: gx and gy must have the same number of seeds")
+        kp, ka = self._keep
+        nP, nA = int(kp.sum()), int(ka.sum())
+        o = SimpleNamespace(rx=np.empty((B, R, n)), ry=np.empty((B, R, m)), gq=np.empty((B, R, n)),
+                            gl=np.empty((B, R, m)), gu=np.empty((B, R, m)), gPx=np.empty((B, R, nP)),
+                            gAx=np.empty((B, R, nA)), act=np.empty((B, m), np.int8), ares=np.empty((B, R)),
+                            astat=np.empty(B, np.int32))
+        _check(lib().mpcqp_adjoint_batch(h, R, _dp(seeds[0]), _dp(seeds[1]), _dp(o.rx), _dp(o.ry), _dp(o.gq),
+                                         _dp(o.gl), _dp(o.gu), _dp(o.gPx), _dp(o.gAx),
+                                         o.act.ctypes.data_as(_P(C.c_int8)), _dp(o.ares), _ip(o.astat)), "adjoint")
+        if not (kp.all() and ka.all()):  # back onto the user's patterns
+            x, y = self._last_xy
+            Pp, Pi, Ap, Ai = self._user_pattern
+            ok = (o.astat == 1)[:, None, None]
+            if not kp.all():
+                full = np.empty((B, R, kp.size))
+                full[:, :, kp] = o.gPx
+                i = Pi[~kp]
+                j = np.repeat(np.arange(n), np.diff(Pp))[~kp]
+                g = -(o.rx[:, :, i] * x[:, None, j] + o.rx[:, :, j] * x[:, None, i])
+                full[:, :, ~kp] = np.where(ok, np.where(i == j, 0.5 * g, g), 0.0)
+                o.gPx = full
+            if not ka.all():
+                full = np.empty((B, R, ka.size))
+                full[:, :, ka] = o.gAx
+                i = Ai[~ka]
+                j = np.repeat(np.arange(n), np.diff(Ap))[~ka]
+                g = -(y[:, None, i] * o.rx[:, :, j] + o.ry[:, :, i] * x[:, None, j])
+                full[:, :, ~ka] = np.where(ok, g, 0.0)
+                o.gAx = full
+        if flat:
+            for k in ("rx", "ry", "gq", "gl", "gu", "gPx", "gAx", "ares"):
+                setattr(o, k, getattr(o, k)[:, 0])
+        return o
 
     def plan_info(self):
         info = _PlanInfo()
@@ -558,6 +621,23 @@ class OSQP:
         return SimpleNamespace(x=r.x[0], y=r.y[0], info=info, prim_inf_cert=r.prim_inf_cert[0],
                                dual_inf_cert=r.dual_inf_cert[0], dua_inf_cert=r.dual_inf_cert[0])
 
+    def adjoint(self, gx=None, gy=None):
+        """(gP, gq, gA, gl, gu): the gradients of gx . x + gy . y at the last solve's solution
+        with respect to the setup's data; gP (upper triangle) and gA are scipy CSC matrices on the
+        setup's patterns.  ``adjoint_info`` then holds act, ares, astat, rx, ry of the call
+        (astat -1: the gradients did not reach the 1e-8 residual, see OSQPBatch.adjoint)."""
+        if self._b is None:
+            raise ValueError("Workspace not initialized!")
+        b = self._b
+        o = b.adjoint(None if gx is None else np.asarray(gx, np.float64).reshape(1, b.n),
+                      None if gy is None else np.asarray(gy, np.float64).reshape(1, b.m))
+        Pp, Pi, Ap, Ai = b._user_pattern
+        gP = sparse.csc_matrix((o.gPx[0], Pi, Pp), shape=(b.n, b.n))
+        gA = sparse.csc_matrix((o.gAx[0], Ai, Ap), shape=(b.m, b.n))
+        self.adjoint_info = SimpleNamespace(act=o.act[0], ares=float(o.ares[0]), astat=int(o.astat[0]),
+                                            rx=o.rx[0], ry=o.ry[0])
+        return gP, o.gq[0], gA, o.gl[0], o.gu[0]
+
 
 class DeviceBatch:
     """Device-resident batch on one GPU: inputs and outputs stay in HBM.
@@ -582,6 +662,7 @@ class DeviceBatch:
                          np.ascontiguousarray(A.indptr, np.int32), np.ascontiguousarray(A.indices, np.int32))
         Pp, Pi, Ap, Ai = self._pattern
         s = _make_settings(**settings)
+        self._settings_kw = dict(settings)
         h = C.c_void_p()
         _check(lib().mpcqp_create(self.n, self.m, _ip(Pp), _ip(Pi), _ip(Ap), _ip(Ai), self.B, C.byref(s),
                                   int(device), C.byref(h)), "create")
@@ -635,6 +716,63 @@ class DeviceBatch:
         _check(lib().mpcqp_setup_solve_device(self._h.ptr, self._ptr(Px), self._ptr(Ax), self._ptr(q), self._ptr(l),
                                               self._ptr(u), self._ptr(x), self._ptr(y), self._ptr(status),
                                               self._ptr(iters), stream), "setup_solve_device")
+
+    def update_settings(self, **kw):
+        """OSQPBatch.update_settings on the device handle (mpcqp_update_settings; it waits for the
+        handle's queued work).  delta and polish_refine_iter also steer adjoint()'s linear solve."""
+        bad = sorted(set(kw) - _UPDATABLE)
+        if bad:
+            raise ValueError(f"setting(s) {', '.join(bad)} cannot be changed after setup")
+        new = dict(self._settings_kw, **kw)
+        s = _make_settings(**new)
+        _check(lib().mpcqp_update_settings(self._h.ptr, C.byref(s), int("rho" in kw)), "update_settings")
+        self._settings_kw = new
+
+    def adjoint(self, gx=None, gy=None, *, rx=None, ry=None, gq=None, gl=None, gu=None, gPx=None, gAx=None,
+                act=None, ares=None, astat=None, stream=None):
+        """Gradients of L = gx . x + gy . y at the last solve's solution (mpcqp_adjoint_device;
+        mpcqp.h has the definition).  gx (B, n) or (B, nrhs, n) and gy (B, m) or (B, nrhs, m) are
+        contiguous float64 torch tensors on the handle's device, one may be None.  Outputs not
+        passed are allocated (torch, on the seeds' device): rx, gq (B, nrhs, n), ry, gl, gu
+        (B, nrhs, m), gPx (B, nrhs, nnzP), gAx (B, nrhs, nnzA), act (B, m) int8, ares (B, nrhs),
+        astat (B,) int32; 2-D seeds drop the nrhs axis.  Returns a namespace of them."""
+        import torch
+        seed = gx if gx is not None else gy
+        if seed is None:
+            raise ValueError("adjoint: gx or gy must be given")
+        B, n, m = self.B, self.n, self.m
+        for g, k in ((gx, n), (gy, m)):
+            if g is None:
+                continue
+            if g.dim() not in (2, 3) or g.shape[0] != B or g.shape[-1] != k or g.dim() != seed.dim() or \
+                    g.shape[:-1] != seed.shape[:-1]:
+                raise ValueError(f"adjoint: seeds must have shapes ({B}, [nrhs,] {n}) and ({B}, [nrhs,] {m})")
+            if g.dtype != torch.float64 or not g.is_contiguous():
+                raise ValueError("adjoint: seeds must be contiguous float64 tensors")
+        flat = seed.dim() == 2
+        R = 1 if flat else int(seed.shape[1])
+        mid = () if flat else (R,)
+        shapes = dict(rx=(B, *mid, n), ry=(B, *mid, m), gq=(B, *mid, n), gl=(B, *mid, m), gu=(B, *mid, m),
+                      gPx=(B, *mid, self.nnzP), gAx=(B, *mid, self.nnzA), ares=(B, *mid))
+        given = dict(rx=rx, ry=ry, gq=gq, gl=gl, gu=gu, gPx=gPx, gAx=gAx, ares=ares)
+        o = SimpleNamespace()
+        for k, shp in shapes.items():
+            t = given[k]
+            if t is None:
+                t = torch.empty(shp, dtype=torch.float64, device=seed.device)
+            elif tuple(t.shape) != shp or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError(f"adjoint: {k} must be a contiguous float64 tensor of shape {shp}")
+            setattr(o, k, t)
+        o.act = torch.empty((B, m), dtype=torch.int8, device=seed.device) if act is None else act
+        o.astat = torch.empty(B, dtype=torch.int32, device=seed.device) if astat is None else astat
+        if tuple(o.act.shape) != (B, m) or o.act.dtype != torch.int8 or tuple(o.astat.shape) != (B,) or \
+                o.astat.dtype != torch.int32:
+            raise ValueError("adjoint: act must be (B, m) int8 and astat (B,) int32")
+        _check(lib().mpcqp_adjoint_device(self._h.ptr, R, self._ptr(gx), self._ptr(gy), self._ptr(o.rx),
+                                          self._ptr(o.ry), self._ptr(o.gq), self._ptr(o.gl), self._ptr(o.gu),
+                                          self._ptr(o.gPx), self._ptr(o.gAx), self._ptr(o.act), self._ptr(o.ares),
+                                          self._ptr(o.astat), stream), "adjoint_device")
+        return o
 
     def one_shot(self, on=True):
         """mpcqp_set_one_shot: setup_solve keeps no workspace state (the scaled problem, the G
