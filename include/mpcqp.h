@@ -626,6 +626,93 @@ int mpcqp_lti_step_device(int64_t B, int32_t nxa, int32_t nu, const double *At, 
                           int32_t *dstep, int32_t *dregime, int32_t *dfailed, int32_t *dfail_step, double *dtraj,
                           int32_t traj_cap, int32_t *dtraj_len, int32_t device, void *stream);
 
+/* ======================================================================
+ * The MPC step differentiated: vector-Jacobian products of the assembly of both
+ * layouts, of the affine lateral assembler and of the kinematic linearisation, and the assembly
+ * with weights given per call.  Chained after mpcqp_adjoint_device they give d(solution) /
+ * d(x0, Xr, Q, QN, R, Ad, Bd, gd, x, u).  Device pointers, enqueued on `stream`.  Every output
+ * pointer may be NULL (not wanted: not written); a NULL cotangent reads as zero; B == 0 returns 0.
+ * No atomics: every output element is written by one thread that sums its contributions in a
+ * fixed order, so two calls return the same bits.
+ * ====================================================================== */
+
+/* mpcqp_ltv_assemble_device / mpcqp_incr_assemble_device with the weights of this call: dQ, dQN
+ * (nx*nx) and dR (nu*nu) are device arrays, dense row-major, shared by the batch, each NULL = the
+ * layout's own.  dPx[nnzP] (may be NULL) receives ONE copy of P's stored values from those
+ * weights in the pattern fixed at creation: a stored entry whose weight is now 0 stays as an
+ * explicit zero, and a weight the pattern does not store (zero at creation) enters q only.
+ * With dQ = dQN = dR = NULL the outputs are those of the plain entry point, bit for bit, and dPx
+ * is mpcqp_*_layout_pattern's Px.  The weights pass through a scratch the layout owns: calls
+ * with weights on one layout are to be ordered on one stream. */
+int mpcqp_ltv_assemble_w_device(const mpcqp_ltv_layout *L, int64_t B, const double *dAd, const double *dBd,
+                                const double *dgd, const double *dx0, const double *dXr, const double *dxlo,
+                                const double *dxhi, const double *dQ, const double *dQN, const double *dR, double *dAx,
+                                double *dq, double *dl, double *du, double *dPx, void *stream);
+int mpcqp_incr_assemble_w_device(const mpcqp_incr_layout *L, int64_t B, const double *dAd, const double *dBd,
+                                 const double *dgd, const double *dxt0, const double *dXr, const double *dQ,
+                                 const double *dQN, const double *dR, double *dAx, double *dq, double *dl, double *du,
+                                 double *dPx, void *stream);
+
+/* The transpose of mpcqp_ltv_assemble_device / mpcqp_incr_assemble_device (nxa = nx for the LTV
+ * layout, nx + nu for the incremental one).  Cotangents: gPx[b*nnzP], gAx[b*nnzA], gq[b*n],
+ * gl[b*m], gu[b*m].  Of the forward call's inputs: Xr (read for gQ / gQN only), xlo / xhi (read
+ * for gxlo / gxhi only), and dQ / dQN when the forward was *_assemble_w_device with them (NULL:
+ * the layout's own).  Outputs, shaped as the forward's inputs:
+ *   gAd[b,k,i,j] = gAx at the slot of that entry;  0 where maskA is 0;
+ *   gBd[b,k,i,j] = the sum of gAx over its slots in CSC order -- one in the LTV layout, two in the
+ *     incremental one (A~_k's upper-right block, then B~_k);  0 where maskB is 0;
+ *   ggd[b,k,i]   = -(gl + gu)[(k+1) nxa + i];
+ *   gx0[b,i]     = -(gl + gu)[i], i < nxa  (gxt0 of the incremental layout);
+ *   gXr[b,j,k]   = -sum_{i < nx} W_k[i][j] gq[k nxa + i], i ascending, W_k what the forward
+ *     multiplied with: Q (k < N) / QN (k = N) in the LTV layout, (Q C)' = Q' / QN' in the
+ *     incremental one;
+ *   gxlo / gxhi[b,k,i] = gl / gu[(N+1) nxa + k nxa + i] where -1e30 < xlo / xhi < 1e30, 0 where
+ *     the forward clipped the bound (LTV layout only; MPCQP_EINVAL without the forward's xlo / xhi);
+ *   gQ[b,i,j] = sum_{k < N} gPx[slot of stage k's Q[i][j]] - sum_{k < N} gq[k nxa + i] Xr[j,k]  (LTV),
+ *     with gq[k nxa + j] Xr[i,k] in the second sum for the incremental layout (its q reads Q');
+ *     gQN[b,i,j] the same over k = N alone;  gR[b,i,j] = sum_{k < N} gPx[slot of stage k's R[i][j]].
+ *     Each sum runs over k ascending, the P part first.  These are the gradients WITH RESPECT TO
+ *     THE STORED WEIGHTS, in the orientation of the Q, QN, R given to *_layout_create: P stores
+ *     W[i][j] for i <= j where it was nonzero at creation, so only those entries have a P part
+ *     (which, as mpcqp_adjoint_device's gPx, counts both symmetric positions); every other entry
+ *     gets its q part alone.  Per instance: the caller sums over the batch for shared weights. */
+int mpcqp_ltv_assemble_vjp_device(const mpcqp_ltv_layout *L, int64_t B, const double *dgPx, const double *dgAx,
+                                  const double *dgq, const double *dgl, const double *dgu, const double *dXr,
+                                  const double *dxlo, const double *dxhi, const double *dQ, const double *dQN,
+                                  double *dgAd, double *dgBd, double *dggd, double *dgx0, double *dgXr, double *dgxlo,
+                                  double *dgxhi, double *dgQ, double *dgQN, double *dgR, void *stream);
+int mpcqp_incr_assemble_vjp_device(const mpcqp_incr_layout *L, int64_t B, const double *dgPx, const double *dgAx,
+                                   const double *dgq, const double *dgl, const double *dgu, const double *dXr,
+                                   const double *dQ, const double *dQN, double *dgAd, double *dgBd, double *dggd,
+                                   double *dgxt0, double *dgXr, double *dgQ, double *dgQN, double *dgR, void *stream);
+
+/* The transpose of mpcqp_affine_apply_device: with g the concatenation of the cotangents of the
+ * three segments, g0[b*seglen0], g1[b*seglen1], g2[b*seglen2],
+ *     gtheta[b*gtheta_stride + p] = sum over entries i and terms t with idx[i*T + t] == p of
+ *                                   coef[i*T + t] * g[i]      (i ascending, then t;  p < nparam,
+ * nparam = 1 + the largest idx given to mpcqp_affine_create; columns beyond are not written).
+ * The regime selects only the base, which has no derivative: dregime is taken for symmetry with
+ * the forward call and ignored. */
+int mpcqp_affine_vjp_device(const mpcqp_affine *a, int64_t B, const double *dg0, const double *dg1, const double *dg2,
+                            const int32_t *dregime, double *dgtheta, int32_t gtheta_stride, void *stream);
+
+/* The VJP of mpcqp_kin_linearise_device per (vehicle, stage), from the closed form of
+ * get_kinematics_model: x, u with the forward call's strides; cotangents gAd[(b*N + k)*16],
+ * gBd[(b*N + k)*8], ggd[(b*N + k)*4]; outputs DENSE gx[(b*N + k)*4], gu[(b*N + k)*2] whatever the
+ * strides (a forward with stage stride 0 -- one model for every stage -- leaves the sum over the
+ * stages to the caller).  Only v, yaw and steer carry derivative; with c = cos, s = sin of yaw,
+ * d = steer, wb = l_f + l_r, sec2 = 1 / cos^2 d, dsec2 = 2 sin d / cos^3 d:
+ *   gx[2] = dt ((gAd13 c - gAd03 s) + (ggd0 s - ggd1 c) yaw + (gBd30 - ggd3 d) sec2 / wb)
+ *   gx[3] = dt ((gAd12 c - gAd02 s) - v (gAd03 c + gAd13 s) + v (ggd0 (c yaw + s) + ggd1 (s yaw - c)))
+ *   gu[0] = dt / wb (gAd32 sec2 + v (gBd30 dsec2 - ggd3 (sec2 + d dsec2)))
+ * and gx[0] = gx[1] = gu[1] = 0 are written.  The dynamic bicycle's linearisation (Pacejka tyres,
+ * the low-speed guard) has no VJP here: a caller differentiates what is downstream of its
+ * (Ad, Bd, gd) and stops there. */
+int mpcqp_kin_linearise_vjp_device(const mpcqp_kin_vehicle *veh, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                                   int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, const double *dgAd,
+                                   const double *dgBd, const double *dggd, double *dgx, double *dgu, int32_t device,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,17 @@ struct IncrLayout {
     std::vector<double> Px, Atpl, ltpl, utpl, Qt;
     int* d_asrc = nullptr;
     double *d_Atpl = nullptr, *d_ltpl = nullptr, *d_utpl = nullptr, *d_Qt = nullptr;
+    // The reverse maps of the assembly, for its VJP and for weights given per call (indexed at
+    // creation, uploaded by the first call that needs them):
+    //   adst[N nx nx]: the Ax slot of Ad_k[i][j], -1 where maskA is 0;
+    //   bdst[N nx nu][2]: the Ax slots of Bd_k[i][j] in CSC order (one in the LTV layout, two in the
+    //     augmented one: A~_k's upper-right block, then B~_k), -1 for none;
+    //   W: (Q | QN | R) dense row-major as the caller gave them; psrc[nnzP]: the entry of W a stored
+    //     entry of P holds; wptr / wlist: per entry of W the P slots that hold it, ascending.
+    std::vector<int> adst, bdst, psrc, wptr, wlist;
+    std::vector<double> W;
+    int *d_adst = nullptr, *d_bdst = nullptr, *d_psrc = nullptr, *d_wptr = nullptr, *d_wlist = nullptr;
+    double *d_W = nullptr, *d_Qtw = nullptr;  // d_Qtw: [2][nx*nx], Qt of the weights of the last *_assemble_w call
 };
 
 struct IncrK {  // what the device kernels need (by value)
@@ -373,6 +384,170 @@ __global__ __launch_bounds__(128) void k_incr_assemble_vec(IncrK L, long B, cons
         for (int i = 0; i < ns; ++i) lb[ns + i] = fmin(fmax(xlo[b * (long)ns + i], -INF), INF);
     if (xhi)
         for (int i = 0; i < ns; ++i) ub[ns + i] = fmin(fmax(xhi[b * (long)ns + i], -INF), INF);
+}
+
+// ------------------------------------------- the assembly's VJP, weights per call --
+// Transposes of the two kernels above (mpcqp_*_assemble_vjp_device): every output element is
+// written by one thread, which gathers its contributions in a fixed order -- no atomics, so two
+// calls give the same bits.  A null cotangent reads as zero, a null output is not written.
+struct VjpK {
+    int N, nx, nu, nxa, n, m, nnzA, nnzP, tr;  // tr: W_k[i][j] = Wp[j][i] (the caller's Q under the augmented layout)
+    const int *adst, *bdst, *wptr, *wlist;
+    const double *Wst, *Wtm;  // stage / terminal weights the forward multiplied with (through tr)
+};
+
+// one thread per (instance, entry of Ad_0..Ad_{N-1} then of Bd_0..Bd_{N-1})
+__global__ __launch_bounds__(256) void k_assemble_vjp_AB(VjpK L, long B, const double* __restrict__ gAx,
+                                                         double* __restrict__ gAd, double* __restrict__ gBd) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int na = L.N * L.nx * L.nx, nb = L.N * L.nx * L.nu, per = na + nb;
+    if (t >= B * per) return;
+    const long b = t / per;
+    const int e = (int)(t - b * per);
+    const double* g = gAx ? gAx + b * L.nnzA : nullptr;
+    if (e < na) {
+        if (!gAd) return;
+        const int s = L.adst[e];
+        gAd[b * na + e] = (g && s >= 0) ? g[s] : 0.0;
+    } else {
+        if (!gBd) return;
+        const int c = e - na, s0 = L.bdst[2 * c], s1 = L.bdst[2 * c + 1];
+        double v = 0.0;
+        if (g && s0 >= 0) v = s1 >= 0 ? g[s0] + g[s1] : g[s0];
+        gBd[b * nb + c] = v;
+    }
+}
+
+// one thread per (instance, element of ggd | gx0 | gXr | gxlo | gxhi)
+__global__ __launch_bounds__(256) void k_assemble_vjp_vec(VjpK L, long B, const double* __restrict__ gq,
+                                                          const double* __restrict__ gl,
+                                                          const double* __restrict__ gu,
+                                                          const double* __restrict__ xlo,
+                                                          const double* __restrict__ xhi, double* __restrict__ ggd,
+                                                          double* __restrict__ gx0, double* __restrict__ gXr,
+                                                          double* __restrict__ gxlo, double* __restrict__ gxhi) {
+    const int N = L.N, nx = L.nx, nxa = L.nxa, ns = (N + 1) * nxa;
+    const int n0 = N * nx, n1 = n0 + nxa, n2 = n1 + nx * (N + 1), n3 = n2 + ns, per = n3 + ns;
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * per) return;
+    const long b = t / per;
+    const int e = (int)(t - b * per);
+    const double INF = 1e30;
+    const double* lb = gl ? gl + b * L.m : nullptr;
+    const double* ub = gu ? gu + b * L.m : nullptr;
+    if (e < n1) {  // the equality rows: l = u = (-x~_0; -g~_k)
+        const int k = e / nx, i = e - k * nx;
+        const int row = e < n0 ? (k + 1) * nxa + i : e - n0;
+        const double v = -((lb ? lb[row] : 0.0) + (ub ? ub[row] : 0.0));
+        if (e < n0) { if (ggd) ggd[b * n0 + e] = v; }
+        else if (gx0) gx0[b * nxa + (e - n0)] = v;
+    } else if (e < n2) {  // q_k = -W_k Xr_k
+        if (!gXr) return;
+        const int c = e - n1, j = c / (N + 1), k = c - j * (N + 1);
+        const double* W = k == N ? L.Wtm : L.Wst;
+        double acc = 0.0;
+        if (gq)
+            for (int i = 0; i < nx; ++i) acc += W[L.tr ? j * nx + i : i * nx + j] * gq[b * L.n + k * nxa + i];
+        gXr[b * (long)nx * (N + 1) + c] = -acc;
+    } else if (e < n3) {  // the state rows of the box where the forward did not clip
+        if (!gxlo) return;
+        const int i = e - n2;
+        const double x = xlo[b * (long)ns + i];
+        gxlo[b * (long)ns + i] = (lb && x > -INF && x < INF) ? lb[ns + i] : 0.0;
+    } else {
+        if (!gxhi) return;
+        const int i = e - n3;
+        const double x = xhi[b * (long)ns + i];
+        gxhi[b * (long)ns + i] = (ub && x > -INF && x < INF) ? ub[ns + i] : 0.0;
+    }
+}
+
+// one thread per (instance, entry of gQ | gQN | gR): the stored entries of P that hold it, summed
+// in stage order, minus sum_k gq_k (x) Xr_k through the forward's own W
+__global__ __launch_bounds__(256) void k_assemble_vjp_w(VjpK L, long B, const double* __restrict__ gPx,
+                                                        const double* __restrict__ gq,
+                                                        const double* __restrict__ Xr, double* __restrict__ gQ,
+                                                        double* __restrict__ gQN, double* __restrict__ gR) {
+    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, nq = nx * nx, per = 2 * nq + nu * nu;
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * per) return;
+    const long b = t / per;
+    const int w = (int)(t - b * per);
+    double* out = w < nq ? gQ : (w < 2 * nq ? gQN : gR);
+    if (!out) return;
+    double pp = 0.0;
+    if (gPx)
+        for (int s = L.wptr[w]; s < L.wptr[w + 1]; ++s) pp += gPx[b * L.nnzP + L.wlist[s]];
+    if (w >= 2 * nq) {
+        out[b * (nu * nu) + (w - 2 * nq)] = pp;
+        return;
+    }
+    const int el = w < nq ? w : w - nq, r = el / nx, c = el - r * nx;
+    const int gi = L.tr ? c : r, xj = L.tr ? r : c;  // d q_k[gi] / d Q[r][c] = -Xr[xj][k]
+    double qq = 0.0;
+    if (gq && Xr) {
+        const double* Xb = Xr + b * (long)nx * (N + 1);
+        const double* qb = gq + b * L.n;
+        if (w < nq)
+            for (int k = 0; k < N; ++k) qq += qb[k * nxa + gi] * Xb[xj * (N + 1) + k];
+        else
+            qq = qb[N * nxa + gi] * Xb[xj * (N + 1) + N];
+    }
+    out[b * nq + el] = pp - qq;
+}
+
+// Weights given per call (mpcqp_*_assemble_w_device): the Qt-form scratch k_incr_assemble_vec
+// reads, and P's stored values in the pattern fixed at creation.  One thread per entry.
+__global__ __launch_bounds__(256) void k_weights(int nx, int nnzP, int tr, const int* __restrict__ psrc,
+                                                 const double* __restrict__ Q, const double* __restrict__ QN,
+                                                 const double* __restrict__ R, double* __restrict__ Qt,
+                                                 double* __restrict__ Px) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, nq = nx * nx;
+    if (t < 2 * nq) {
+        const int el = t < nq ? t : t - nq, i = el / nx, j = el - i * nx;
+        Qt[t] = (t < nq ? Q : QN)[tr ? j * nx + i : i * nx + j];
+    } else if (t < 2 * nq + nnzP) {
+        if (!Px) return;
+        const int e = t - 2 * nq, s = psrc[e];
+        Px[e] = s < nq ? Q[s] : (s < 2 * nq ? QN[s - nq] : R[s - 2 * nq]);
+    }
+}
+
+// VJP of linearise_one(const mpcqp_kin_vehicle&, ...) per (vehicle, stage): only v, yaw and steer
+// carry derivative; the outputs are dense (B, N, 4) / (B, N, 2) whatever the input strides.
+__global__ __launch_bounds__(256) void k_kin_linearise_vjp(mpcqp_kin_vehicle k, long B, int N,
+                                                           const double* __restrict__ x, long x_sb, long x_sk,
+                                                           const double* __restrict__ u, long u_sb, long u_sk,
+                                                           const double* __restrict__ gAd,
+                                                           const double* __restrict__ gBd,
+                                                           const double* __restrict__ ggd, double* __restrict__ gx,
+                                                           double* __restrict__ gu) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * N) return;
+    const long b = t / N, s = t - b * N;
+    const double* xs = x + b * x_sb + s * x_sk;
+    const double v = xs[2], yaw = xs[3], st = u[b * u_sb + s * u_sk];
+    const double dt = k.dt, wb = k.l_f + k.l_r;
+    const double cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
+    const double sec2 = 1.0 / (cs * cs), dsec2 = 2.0 * ss / (cs * cs * cs);
+    const double* A = gAd ? gAd + t * 16 : nullptr;
+    const double a02 = A ? A[0 * 4 + 2] : 0.0, a03 = A ? A[0 * 4 + 3] : 0.0, a12 = A ? A[1 * 4 + 2] : 0.0,
+                 a13 = A ? A[1 * 4 + 3] : 0.0, a32 = A ? A[3 * 4 + 2] : 0.0;
+    const double b30 = gBd ? gBd[t * 8 + 3 * 2 + 0] : 0.0;
+    const double g0 = ggd ? ggd[t * 4 + 0] : 0.0, g1 = ggd ? ggd[t * 4 + 1] : 0.0, g3 = ggd ? ggd[t * 4 + 3] : 0.0;
+    if (gx) {
+        const double gv = dt * ((a13 * cy - a03 * sy) + (g0 * sy - g1 * cy) * yaw + (b30 - g3 * st) * sec2 / wb);
+        const double gyaw = dt * ((a12 * cy - a02 * sy) - v * (a03 * cy + a13 * sy) +
+                                  v * (g0 * (cy * yaw + sy) + g1 * (sy * yaw - cy)));
+        gx[t * 4 + 0] = 0.0;
+        gx[t * 4 + 1] = 0.0;
+        gx[t * 4 + 2] = gv;
+        gx[t * 4 + 3] = gyaw;
+    }
+    if (gu) {
+        gu[t * 2 + 0] = dt / wb * (a32 * sec2 + v * (b30 * dsec2 - g3 * (sec2 + st * dsec2)));
+        gu[t * 2 + 1] = 0.0;
+    }
 }
 
 // ---------------------------------------------------------- receding horizon --
@@ -866,6 +1041,37 @@ __global__ __launch_bounds__(256) void k_affine(AffineK a, long B, const double*
     else o2[b * (a.L - a.seg1) + (i - a.seg1)] = v;
 }
 
+// Transpose of k_affine's linear part: gtheta[b][p] = sum of coef[i][t] g[i] over the terms with
+// idx[i][t] == p, in the order of the by-parameter lists (entry, then term).  One thread per
+// (instance, parameter); a null cotangent segment reads as zero.
+struct AffineVjpK {
+    int L, seg0, seg1, nparam;
+    const int *pptr, *pent;
+    const double* pcoef;
+};
+
+__global__ __launch_bounds__(256) void k_affine_vjp(AffineVjpK a, long B, const double* __restrict__ g0,
+                                                    const double* __restrict__ g1, const double* __restrict__ g2,
+                                                    double* __restrict__ gtheta, long gstride) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= B * a.nparam) return;
+    const long b = t / a.nparam;
+    const int p = (int)(t - b * a.nparam);
+    double v = 0.0;
+    bool any = false;
+    for (int s = a.pptr[p]; s < a.pptr[p + 1]; ++s) {
+        const int i = a.pent[s];
+        double g;
+        if (i < a.seg0) g = g0 ? g0[b * a.seg0 + i] : 0.0;
+        else if (i < a.seg1) g = g1 ? g1[b * (a.seg1 - a.seg0) + (i - a.seg0)] : 0.0;
+        else g = g2 ? g2[b * (a.L - a.seg1) + (i - a.seg1)] : 0.0;
+        const double term = a.pcoef[s] * g;
+        v = any ? v + term : term;
+        any = true;
+    }
+    gtheta[b * gstride + p] = v;
+}
+
 }  // namespace mpcqp
 
 using namespace mpcqp;
@@ -877,6 +1083,9 @@ struct mpcqp_affine {
     int dev = 0, L = 0, R = 0, T = 0, seg0 = 0, seg1 = 0, nparam = 0;
     double *d_base = nullptr, *d_coef = nullptr;
     int* d_idx = nullptr;
+    // the terms by parameter (for the VJP): parameter p's are pent / pcoef[pptr[p] .. pptr[p+1])
+    int *d_pptr = nullptr, *d_pent = nullptr;
+    double* d_pcoef = nullptr;
 };
 
 namespace {
@@ -906,6 +1115,20 @@ int ensure_device(IncrLayout& L) {
     return 0;
 }
 
+// the reverse maps, the caller's weights and the per-call Qt scratch (VJP, *_assemble_w)
+int ensure_reverse(IncrLayout& L) {
+    if (L.d_Qtw) return 0;
+    MHIPCHK(hipSetDevice(L.dev));
+    if (int e = upload(L.adst, &L.d_adst)) return e;
+    if (int e = upload(L.bdst, &L.d_bdst)) return e;
+    if (int e = upload(L.psrc, &L.d_psrc)) return e;
+    if (int e = upload(L.wptr, &L.d_wptr)) return e;
+    if (int e = upload(L.wlist, &L.d_wlist)) return e;
+    if (int e = upload(L.W, &L.d_W)) return e;
+    if (int e = upload(L.Qt, &L.d_Qtw)) return e;
+    return 0;
+}
+
 IncrK incr_k(const IncrLayout& L) {
     IncrK k;
     k.N = L.N; k.nx = L.nx; k.nu = L.nu; k.nxa = L.nxa; k.n = L.n; k.m = L.m; k.nnzA = (int)L.Ai.size();
@@ -916,7 +1139,7 @@ IncrK incr_k(const IncrLayout& L) {
 // P = blockdiag(kron(I_N, C'QC), C'QN C, kron(I_N, R)), upper triangle, zeros dropped
 // (mpc_dynamics.py:304-307); with nxa = nx, C = I: blockdiag(Q x N, QN, R x N)
 void build_P(IncrLayout& L, const double* Q, const double* QN, const double* R) {
-    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, n = L.n;
+    const int N = L.N, nx = L.nx, nu = L.nu, nxa = L.nxa, n = L.n, nq = nx * nx;
     L.Pp.assign(n + 1, 0);
     for (int c = 0; c < n; ++c) {
         if (c < (N + 1) * nxa) {
@@ -925,17 +1148,34 @@ void build_P(IncrLayout& L, const double* Q, const double* QN, const double* R) 
             if (j < nx)
                 for (int i = 0; i <= j; ++i) {
                     const double v = W[i * nx + j];
-                    if (v != 0.0) { L.Pi.push_back(k * nxa + i); L.Px.push_back(v); }
+                    if (v != 0.0) {
+                        L.Pi.push_back(k * nxa + i); L.Px.push_back(v);
+                        L.psrc.push_back((k == N ? nq : 0) + i * nx + j);
+                    }
                 }
         } else {
             const int c0 = c - (N + 1) * nxa, k = c0 / nu, j = c0 % nu;
             for (int i = 0; i <= j; ++i) {
                 const double v = R[i * nu + j];
-                if (v != 0.0) { L.Pi.push_back((N + 1) * nxa + k * nu + i); L.Px.push_back(v); }
+                if (v != 0.0) {
+                    L.Pi.push_back((N + 1) * nxa + k * nu + i); L.Px.push_back(v);
+                    L.psrc.push_back(2 * nq + i * nu + j);
+                }
             }
         }
         L.Pp[c + 1] = (int)L.Pi.size();
     }
+    // W and, per entry of it, the slots of P that hold it (ascending: stage order)
+    L.W.assign(Q, Q + nq);
+    L.W.insert(L.W.end(), QN, QN + nq);
+    L.W.insert(L.W.end(), R, R + nu * nu);
+    const int nw = (int)L.W.size();
+    L.wptr.assign(nw + 1, 0);
+    for (int s : L.psrc) L.wptr[s + 1] += 1;
+    for (int w = 0; w < nw; ++w) L.wptr[w + 1] += L.wptr[w];
+    L.wlist.assign(L.psrc.size(), 0);
+    std::vector<int> fill(L.wptr.begin(), L.wptr.end() - 1);
+    for (int e = 0; e < (int)L.psrc.size(); ++e) L.wlist[fill[L.psrc[e]]++] = e;
 }
 
 // dims / pattern / free of either layout (mpcqp_incr_layout, mpcqp_ltv_layout)
@@ -961,7 +1201,10 @@ int layout_pattern(const IncrLayout* L, const char* what, int32_t* Pp, int32_t* 
 
 void layout_free_device(IncrLayout* L) {
     if (L->d_asrc) (void)hipSetDevice(L->dev);
-    for (void* p : {(void*)L->d_asrc, (void*)L->d_Atpl, (void*)L->d_ltpl, (void*)L->d_utpl, (void*)L->d_Qt})
+    if (!L->d_asrc && L->d_Qtw) (void)hipSetDevice(L->dev);
+    for (void* p : {(void*)L->d_asrc, (void*)L->d_Atpl, (void*)L->d_ltpl, (void*)L->d_utpl, (void*)L->d_Qt,
+                    (void*)L->d_adst, (void*)L->d_bdst, (void*)L->d_psrc, (void*)L->d_wptr, (void*)L->d_wlist,
+                    (void*)L->d_W, (void*)L->d_Qtw})
         if (p) (void)hipFree(p);
 }
 
@@ -1005,6 +1248,18 @@ void build_layout(IncrLayout& L, int N, int nx, int nu, int nxa, int device, con
         }
         push(ns + c, kConstSrc, 1.0);  // A_ineq = I
         L.Ap[c + 1] = (int)L.Ai.size();
+    }
+    // where each stage entry went: asrc read backwards (slots ascend, so bdst's pair is in CSC order)
+    L.adst.assign(N * nx * nx, -1);
+    L.bdst.assign(2 * N * nx * nu, -1);
+    for (int e = 0; e < (int)L.asrc.size(); ++e) {
+        const int s = L.asrc[e];
+        if (s == kConstSrc) continue;
+        if (s >= 0) L.adst[s] = e;
+        else {
+            int* d = &L.bdst[2 * (-1 - s)];
+            d[d[0] < 0 ? 0 : 1] = e;
+        }
     }
     L.Qt.assign(2 * nx * nx, 0.0);
     for (int i = 0; i < nx; ++i)
@@ -1080,6 +1335,76 @@ int assemble_device(const char* what, const IncrLayout* L, int64_t B, const doub
     const IncrK k = incr_k(*L);
     if (int e = launch(L->dev, stream, B * k.nnzA, 256, k_incr_assemble_A, k, B, dAd, dBd, dAx)) return e;
     return launch(L->dev, stream, B, 128, k_incr_assemble_vec, k, B, dgd, dx0, dXr, dxlo, dxhi, dq, dl, du);
+}
+
+// assemble_device with the weights of this call (each null: the layout's own): k_weights writes
+// the Qt scratch and dPx, then the forward kernels run unchanged with IncrK::Qt on the scratch
+int assemble_w_device(const char* what, const IncrLayout* L, int64_t B, const double* dAd, const double* dBd,
+                      const double* dgd, const double* dx0, const double* dXr, const double* dxlo, const double* dxhi,
+                      const double* dQ, const double* dQN, const double* dR, double* dAx, double* dq, double* dl,
+                      double* du, double* dPx, void* stream) {
+    if (!L || !dAd || !dBd || !dgd || !dx0 || !dXr || !dAx || !dq || !dl || !du || B < 0)
+        return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (B == 0) return 0;
+    IncrLayout& M = *const_cast<IncrLayout*>(L);
+    if (int e = ensure_device(M)) return e;
+    if (int e = ensure_reverse(M)) return e;
+    const int nq = L->nx * L->nx, nnzP = (int)L->Pi.size();
+    if (int e = launch(L->dev, stream, 2 * nq + nnzP, 256, k_weights, L->nx, nnzP, (int)(L->nxa != L->nx), L->d_psrc,
+                       dQ ? dQ : L->d_W, dQN ? dQN : L->d_W + nq, dR ? dR : L->d_W + 2 * nq, L->d_Qtw, dPx))
+        return e;
+    IncrK k = incr_k(*L);
+    k.Qt = L->d_Qtw;
+    if (int e = launch(L->dev, stream, B * k.nnzA, 256, k_incr_assemble_A, k, B, dAd, dBd, dAx)) return e;
+    return launch(L->dev, stream, B, 128, k_incr_assemble_vec, k, B, dgd, dx0, dXr, dxlo, dxhi, dq, dl, du);
+}
+
+// The transpose of assemble_device (and of assemble_w_device: dQ / dQN the weights that call took,
+// null the layout's own).  Every cotangent and every output may be null.
+int assemble_vjp_device(const char* what, const IncrLayout* L, int64_t B, const double* dgPx, const double* dgAx,
+                        const double* dgq, const double* dgl, const double* dgu, const double* dXr,
+                        const double* dxlo, const double* dxhi, const double* dQ, const double* dQN, double* dgAd,
+                        double* dgBd, double* dggd, double* dgx0, double* dgXr, double* dgxlo, double* dgxhi,
+                        double* dgQ, double* dgQN, double* dgR, void* stream) {
+    if (!L) return set_error(MPCQP_EINVAL, "%s: NULL layout", what);
+    if (B < 0) return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if ((dgxlo && !dxlo) || (dgxhi && !dxhi))
+        return set_error(MPCQP_EINVAL, "%s: gxlo / gxhi need the forward call's xlo / xhi", what);
+    if ((dgQ || dgQN) && dgq && !dXr)
+        return set_error(MPCQP_EINVAL, "%s: gQ / gQN from gq need the forward call's Xr", what);
+    if (B == 0) return 0;
+    IncrLayout& M = *const_cast<IncrLayout*>(L);
+    if (int e = ensure_device(M)) return e;
+    if (int e = ensure_reverse(M)) return e;
+    const int N = L->N, nx = L->nx, nu = L->nu, nxa = L->nxa, nq = nx * nx;
+    VjpK k;
+    k.N = N; k.nx = nx; k.nu = nu; k.nxa = nxa; k.n = L->n; k.m = L->m;
+    k.nnzA = (int)L->Ai.size(); k.nnzP = (int)L->Pi.size();
+    k.adst = L->d_adst; k.bdst = L->d_bdst; k.wptr = L->d_wptr; k.wlist = L->d_wlist;
+    // the forward's W_k[i][j]: the layout's Qt as it stands, or the caller's Q read transposed
+    // under the augmented layout
+    k.tr = 0; k.Wst = L->d_Qt; k.Wtm = L->d_Qt + nq;
+    if (dQ || dQN) {
+        k.tr = nxa != nx;
+        k.Wst = dQ ? dQ : L->d_W;
+        k.Wtm = dQN ? dQN : L->d_W + nq;
+    }
+    if (dgAd || dgBd)
+        if (int e = launch(L->dev, stream, B * N * (nq + nx * nu), 256, k_assemble_vjp_AB, k, B, dgAx, dgAd, dgBd))
+            return e;
+    if (dggd || dgx0 || dgXr || dgxlo || dgxhi) {
+        const long per = (long)N * nx + nxa + (long)nx * (N + 1) + 2L * (N + 1) * nxa;
+        if (int e = launch(L->dev, stream, B * per, 256, k_assemble_vjp_vec, k, B, dgq, dgl, dgu, dxlo, dxhi, dggd,
+                           dgx0, dgXr, dgxlo, dgxhi))
+            return e;
+    }
+    if (dgQ || dgQN || dgR) {
+        k.tr = nxa != nx;  // here the orientation is the caller's Q's, whatever W the forward read
+        if (int e = launch(L->dev, stream, B * (2 * nq + nu * nu), 256, k_assemble_vjp_w, k, B, dgPx, dgq, dXr, dgQ,
+                           dgQN, dgR))
+            return e;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1187,6 +1512,49 @@ int mpcqp_ltv_assemble_device(const mpcqp_ltv_layout* L, int64_t B, const double
                               const double* dgd, const double* dx0, const double* dXr, const double* dxlo,
                               const double* dxhi, double* dAx, double* dq, double* dl, double* du, void* stream) {
     return assemble_device("ltv_assemble", L, B, dAd, dBd, dgd, dx0, dXr, dxlo, dxhi, dAx, dq, dl, du, stream);
+}
+
+int mpcqp_incr_assemble_w_device(const mpcqp_incr_layout* L, int64_t B, const double* dAd, const double* dBd,
+                                 const double* dgd, const double* dxt0, const double* dXr, const double* dQ,
+                                 const double* dQN, const double* dR, double* dAx, double* dq, double* dl, double* du,
+                                 double* dPx, void* stream) {
+    return assemble_w_device("incr_assemble_w", L, B, dAd, dBd, dgd, dxt0, dXr, nullptr, nullptr, dQ, dQN, dR, dAx, dq,
+                             dl, du, dPx, stream);
+}
+
+int mpcqp_ltv_assemble_w_device(const mpcqp_ltv_layout* L, int64_t B, const double* dAd, const double* dBd,
+                                const double* dgd, const double* dx0, const double* dXr, const double* dxlo,
+                                const double* dxhi, const double* dQ, const double* dQN, const double* dR, double* dAx,
+                                double* dq, double* dl, double* du, double* dPx, void* stream) {
+    return assemble_w_device("ltv_assemble_w", L, B, dAd, dBd, dgd, dx0, dXr, dxlo, dxhi, dQ, dQN, dR, dAx, dq, dl, du,
+                             dPx, stream);
+}
+
+int mpcqp_incr_assemble_vjp_device(const mpcqp_incr_layout* L, int64_t B, const double* dgPx, const double* dgAx,
+                                   const double* dgq, const double* dgl, const double* dgu, const double* dXr,
+                                   const double* dQ, const double* dQN, double* dgAd, double* dgBd, double* dggd,
+                                   double* dgxt0, double* dgXr, double* dgQ, double* dgQN, double* dgR, void* stream) {
+    return assemble_vjp_device("incr_assemble_vjp", L, B, dgPx, dgAx, dgq, dgl, dgu, dXr, nullptr, nullptr, dQ, dQN,
+                               dgAd, dgBd, dggd, dgxt0, dgXr, nullptr, nullptr, dgQ, dgQN, dgR, stream);
+}
+
+int mpcqp_ltv_assemble_vjp_device(const mpcqp_ltv_layout* L, int64_t B, const double* dgPx, const double* dgAx,
+                                  const double* dgq, const double* dgl, const double* dgu, const double* dXr,
+                                  const double* dxlo, const double* dxhi, const double* dQ, const double* dQN,
+                                  double* dgAd, double* dgBd, double* dggd, double* dgx0, double* dgXr, double* dgxlo,
+                                  double* dgxhi, double* dgQ, double* dgQN, double* dgR, void* stream) {
+    return assemble_vjp_device("ltv_assemble_vjp", L, B, dgPx, dgAx, dgq, dgl, dgu, dXr, dxlo, dxhi, dQ, dQN, dgAd,
+                               dgBd, dggd, dgx0, dgXr, dgxlo, dgxhi, dgQ, dgQN, dgR, stream);
+}
+
+int mpcqp_kin_linearise_vjp_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                                   int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                                   const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
+                                   void* stream) {
+    if (!veh || !dx || !du || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "kin_linearise_vjp: bad arguments");
+    if (B == 0 || (!dgx && !dgu)) return 0;
+    return launch(device, stream, B * N, 256, k_kin_linearise_vjp, *veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd,
+                  dgBd, dggd, dgx, dgu);
 }
 
 void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {
@@ -1365,8 +1733,40 @@ int mpcqp_affine_create(int32_t nseg, const int32_t* seglen, int32_t nregimes, i
     if (int e = upload(vb, &a->d_base)) return e;
     if (int e = upload(vc, &a->d_coef)) return e;
     if (int e = upload(vi, &a->d_idx)) return e;
+    // the same terms listed by parameter, entries ascending and an entry's terms in their order
+    std::vector<int> pptr(a->nparam + 1, 0), pent;
+    std::vector<double> pcoef;
+    for (int k : vi)
+        if (k >= 0) pptr[k + 1] += 1;
+    for (int p = 0; p < a->nparam; ++p) pptr[p + 1] += pptr[p];
+    pent.assign(pptr[a->nparam], 0);
+    pcoef.assign(pptr[a->nparam], 0.0);
+    std::vector<int> fill(pptr.begin(), pptr.end() - 1);
+    for (size_t s = 0; s < vi.size(); ++s)
+        if (vi[s] >= 0) {
+            const int at = fill[vi[s]]++;
+            pent[at] = (int)(s / (size_t)std::max(T, 1));
+            pcoef[at] = vc[s];
+        }
+    if (int e = upload(pptr, &a->d_pptr)) return e;
+    if (int e = upload(pent, &a->d_pent)) return e;
+    if (int e = upload(pcoef, &a->d_pcoef)) return e;
     *out = a.release();
     return 0;
+}
+
+int mpcqp_affine_vjp_device(const mpcqp_affine* a, int64_t B, const double* dg0, const double* dg1, const double* dg2,
+                            const int32_t* dregime, double* dgtheta, int32_t gtheta_stride, void* stream) {
+    if (!a) return set_error(MPCQP_EINVAL, "affine_vjp: NULL affine map");
+    if (B < 0 || (dgtheta && gtheta_stride < a->nparam))
+        return set_error(MPCQP_EINVAL, "affine_vjp: bad arguments (gtheta_stride must cover the %d parameters)",
+                         a->nparam);
+    (void)dregime;  // the regime selects the base, which has no derivative
+    if (B == 0 || !dgtheta || a->nparam == 0) return 0;
+    AffineVjpK k;
+    k.L = a->L; k.seg0 = a->seg0; k.seg1 = a->seg1; k.nparam = a->nparam;
+    k.pptr = a->d_pptr; k.pent = a->d_pent; k.pcoef = a->d_pcoef;
+    return launch(a->dev, stream, B * a->nparam, 256, k_affine_vjp, k, B, dg0, dg1, dg2, dgtheta, gtheta_stride);
 }
 
 int mpcqp_affine_apply_device(const mpcqp_affine* a, int64_t B, const double* dtheta, int32_t theta_stride,
@@ -1390,7 +1790,8 @@ int mpcqp_affine_apply_device(const mpcqp_affine* a, int64_t B, const double* dt
 void mpcqp_affine_free(mpcqp_affine* a) {
     if (!a) return;
     (void)hipSetDevice(a->dev);
-    for (void* p : {(void*)a->d_base, (void*)a->d_coef, (void*)a->d_idx})
+    for (void* p : {(void*)a->d_base, (void*)a->d_coef, (void*)a->d_idx, (void*)a->d_pptr, (void*)a->d_pent,
+                    (void*)a->d_pcoef})
         if (p) (void)hipFree(p);
     delete a;
 }

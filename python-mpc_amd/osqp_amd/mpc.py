@@ -356,6 +356,142 @@ def kin_update(l_f, l_r, dt, x, u):
                      yaw + v1 / (l_f + l_r) * np.tan(u[..., 0]) * dt], axis=-1)
 
 
+# ------------------------------------------- the MPC step differentiated (host) --
+def _slots(M, rows, cols):
+    """Positions in M.data (sorted CSC) of the entries (rows[i], cols[i]); -1 where not stored."""
+    out = np.full(len(rows), -1, np.int64)
+    for t, (r, c) in enumerate(zip(rows, cols)):
+        lo, hi = M.indptr[c], M.indptr[c + 1]
+        k = lo + np.searchsorted(M.indices[lo:hi], r)
+        if k < hi and M.indices[k] == r:
+            out[t] = k
+    return out
+
+
+def _take(g, slots):
+    """g[:, slots] with zeros where the slot is -1."""
+    return np.where(slots >= 0, g[:, np.maximum(slots, 0)], 0.0)
+
+
+def _assemble_vjp(nxa, P, A, N, nx, nu, Q, QN, Xr, gPx, gAx, gq, gl, gu, xlo, xhi):
+    """The transpose of ltv_qp (nxa = nx) / incremental_qp (nxa = nx + nu) in the order of
+    mpc_device.hip's k_assemble_vjp_* (include/mpcqp.h, mpcqp_*_assemble_vjp_device)."""
+    from types import SimpleNamespace
+    A = sparse.csc_matrix(A); A.sort_indices()
+    P = sparse.triu(sparse.csc_matrix(P), format="csc"); P.sort_indices()
+    n, m, ns = P.shape[0], A.shape[0], (N + 1) * nxa
+    given = [g for g in (gPx, gAx, gq, gl, gu) if g is not None]
+    if not given:
+        raise ValueError("at least one cotangent must be given")
+    flat = all(np.ndim(g) == 1 for g in given)
+    B = np.atleast_2d(given[0]).shape[0]
+
+    def arr(g, w):
+        return np.zeros((B, w)) if g is None else np.atleast_2d(np.asarray(g, float))
+
+    gPx, gAx, gq, gl, gu = arr(gPx, P.nnz), arr(gAx, A.nnz), arr(gq, n), arr(gl, m), arr(gu, m)
+    Q = np.asarray(sparse.csr_matrix(Q).todense(), float); QN = np.asarray(sparse.csr_matrix(QN).todense(), float)
+    tr = nxa != nx
+    W = (Q.T, QN.T) if tr else (Q, QN)                       # what the forward multiplies Xr_k with
+    o = SimpleNamespace()
+    # Ad_k[i][j] at (row (k+1) nxa + i, column k nxa + j); Bd_k[i][j] at column k nxa + nx + j (A~_k,
+    # augmented layout only) and at column ns + k nu + j (B~_k)
+    k, i, j = np.meshgrid(np.arange(N), np.arange(nx), np.arange(nx), indexing="ij")
+    o.gAd = _take(gAx, _slots(A, ((k + 1) * nxa + i).ravel(), (k * nxa + j).ravel())).reshape(B, N, nx, nx)
+    k, i, j = np.meshgrid(np.arange(N), np.arange(nx), np.arange(nu), indexing="ij")
+    rows = ((k + 1) * nxa + i).ravel()
+    gB = _take(gAx, _slots(A, rows, (ns + k * nu + j).ravel()))
+    if tr:
+        gB = _take(gAx, _slots(A, rows, (k * nxa + nx + j).ravel())) + gB
+    o.gBd = gB.reshape(B, N, nx, nu)
+    ge = -(gl + gu)
+    o.ggd = np.ascontiguousarray(ge[:, nxa:ns].reshape(B, N, nxa)[:, :, :nx])
+    o.gx0 = ge[:, :nxa].copy()
+    gqs = gq[:, :ns].reshape(B, N + 1, nxa)
+    o.gXr = np.empty((B, nx, N + 1))
+    for kk in range(N + 1):
+        Wk = W[1] if kk == N else W[0]
+        for jj in range(nx):
+            acc = np.zeros(B)
+            for ii in range(nx):
+                acc = acc + Wk[ii, jj] * gqs[:, kk, ii]
+            o.gXr[:, jj, kk] = -acc
+    INF = 1e30
+    o.gxlo = o.gxhi = None
+    if xlo is not None:
+        x = np.asarray(xlo, float).reshape(-1, ns)
+        o.gxlo = np.where((x > -INF) & (x < INF), gl[:, ns:2 * ns], 0.0).reshape(B, N + 1, nxa)
+    if xhi is not None:
+        x = np.asarray(xhi, float).reshape(-1, ns)
+        o.gxhi = np.where((x > -INF) & (x < INF), gu[:, ns:2 * ns], 0.0).reshape(B, N + 1, nxa)
+    # the weights: P's stored entry of stage k's W[i][j] (i <= j), stages ascending, minus the q part
+    o.gQ, o.gQN, o.gR = np.zeros((B, nx, nx)), np.zeros((B, nx, nx)), np.zeros((B, nu, nu))
+    Xr = None if Xr is None else np.asarray(Xr, float).reshape(-1, nx, N + 1)
+    for ii in range(nx):
+        for jj in range(nx):
+            gi, xj = (jj, ii) if tr else (ii, jj)
+            for out, stages in ((o.gQ, range(N)), (o.gQN, [N])):
+                pp, qq = np.zeros(B), np.zeros(B)
+                if ii <= jj:
+                    for s in _slots(P, [kk * nxa + ii for kk in stages], [kk * nxa + jj for kk in stages]):
+                        if s >= 0:
+                            pp = pp + gPx[:, s]
+                if Xr is not None:
+                    for kk in stages:
+                        qq = qq + gqs[:, kk, gi] * Xr[:, xj, kk]
+                out[:, ii, jj] = pp - qq
+    for ii in range(nu):
+        for jj in range(ii, nu):
+            pp = np.zeros(B)
+            for s in _slots(P, [ns + kk * nu + ii for kk in range(N)], [ns + kk * nu + jj for kk in range(N)]):
+                if s >= 0:
+                    pp = pp + gPx[:, s]
+            o.gR[:, ii, jj] = pp
+    if flat:
+        for key, v in vars(o).items():
+            if v is not None:
+                setattr(o, key, v[0])
+    return o
+
+
+def ltv_qp_vjp(P, A, N, nx, nu, Q, QN, Xr=None, gPx=None, gAx=None, gq=None, gl=None, gu=None, xlo=None, xhi=None):
+    """The transpose of ltv_qp: cotangents on the stored values of triu(P) and A (sorted CSC, the
+    patterns given -- the builder's or a layout's; an entry the pattern lacks has no gradient), on
+    q, l and u, one instance (1-D) or a batch (leading axis) -> a namespace of gAd (N,nx,nx), gBd
+    (N,nx,nu), ggd (N,nx), gx0 (nx), gXr (nx,N+1), gxlo / gxhi (N+1,nx; None without xlo / xhi:
+    the forward's per-stage bounds, zero gradient where it clipped them to +-1e30), and gQ, gQN, gR
+    with respect to the stored weights (include/mpcqp.h, mpcqp_ltv_assemble_vjp_device; Xr, the
+    forward's, is read for gQ / gQN alone)."""
+    return _assemble_vjp(nx, P, A, N, nx, nu, Q, QN, Xr, gPx, gAx, gq, gl, gu, xlo, xhi)
+
+
+def incremental_qp_vjp(P, A, N, nx, nu, Q, QN, Xr=None, gPx=None, gAx=None, gq=None, gl=None, gu=None):
+    """The transpose of incremental_qp, as ltv_qp_vjp: gx0 is gxt0 (nx+nu), gBd sums the two
+    slots Bd_k has in A (A~_k's upper-right block, then B~_k), and q reads (Q C)', so gQ[i][j]
+    takes gq[k nxa + j] Xr[i,k]."""
+    return _assemble_vjp(nx + nu, P, A, N, nx, nu, Q, QN, Xr, gPx, gAx, gq, gl, gu, None, None)
+
+
+def linearise_kinematics_vjp(l_f, l_r, dt, x, u, gAd, gBd, ggd):
+    """The VJP of linearise_kinematics in the order of mpc_device.hip's k_kin_linearise_vjp:
+    x (..., 4), u (..., 2), gAd (..., 4, 4), gBd (..., 4, 2), ggd (..., 4) -> gx (..., 4),
+    gu (..., 2); only v, yaw and steer carry derivative."""
+    x, u = np.asarray(x, float), np.asarray(u, float)
+    gAd, gBd, ggd = np.asarray(gAd, float), np.asarray(gBd, float), np.asarray(ggd, float)
+    wb = l_f + l_r
+    v, yaw, st = x[..., 2], x[..., 3], u[..., 0]
+    cy, sy, cs, ss = np.cos(yaw), np.sin(yaw), np.cos(st), np.sin(st)
+    sec2, dsec2 = 1.0 / (cs * cs), 2.0 * ss / (cs * cs * cs)
+    a02, a03, a12, a13, a32 = gAd[..., 0, 2], gAd[..., 0, 3], gAd[..., 1, 2], gAd[..., 1, 3], gAd[..., 3, 2]
+    b30, g0, g1, g3 = gBd[..., 3, 0], ggd[..., 0], ggd[..., 1], ggd[..., 3]
+    gx, gu = np.zeros(x.shape), np.zeros(u.shape)
+    gx[..., 2] = dt * ((a13 * cy - a03 * sy) + (g0 * sy - g1 * cy) * yaw + (b30 - g3 * st) * sec2 / wb)
+    gx[..., 3] = dt * ((a12 * cy - a02 * sy) - v * (a03 * cy + a13 * sy)
+                       + v * (g0 * (cy * yaw + sy) + g1 * (sy * yaw - cy)))
+    gu[..., 0] = dt / wb * (a32 * sec2 + v * (b30 * dsec2 - g3 * (sec2 + st * dsec2)))
+    return gx, gu
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),

@@ -105,12 +105,24 @@ def _bind():
                                                           vp]
     L.mpcqp_lane_tail_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 7 + [i32, vp, vp, vp, vp, vp, i32, vp, vp]
     L.mpcqp_kin_frozen_tail_device.argtypes = [vp, i64] + [vp] * 11 + [i32, vp, vp]
+    L.mpcqp_ltv_assemble_w_device.argtypes = [vp, i64] + [vp] * 16
+    L.mpcqp_incr_assemble_w_device.argtypes = [vp, i64] + [vp] * 14
+    L.mpcqp_ltv_assemble_vjp_device.argtypes = [vp, i64] + [vp] * 21
+    L.mpcqp_incr_assemble_vjp_device.argtypes = [vp, i64] + [vp] * 17
+    L.mpcqp_affine_vjp_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp]
+    L.mpcqp_kin_linearise_vjp_device.argtypes = [_P(KinVehicle), i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp,
+                                                 vp, i32, vp]
     L._mpc_bound = True
     return L
 
 
 def _p(t):
     return C.c_void_p(t.data_ptr())
+
+
+def _po(t):
+    """_p, or NULL for None (an optional argument of the C ABI)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _np_ptr(a):
@@ -210,6 +222,87 @@ class _Layout:
         return (torch.empty((B, self.nnzA), **kw), torch.empty((B, self.n), **kw),
                 torch.empty((B, self.m), **kw), torch.empty((B, self.m), **kw))
 
+    def _weights(self, weights):
+        """weights = (Q, QN, R) of one call: float64 device tensors (nx,nx), (nx,nx), (nu,nu) shared
+        by the batch, each None = the layout's own -> the three, checked and contiguous."""
+        import torch
+        if weights is None:
+            return None, None, None
+        out = []
+        for t, w in zip(weights, (self.nx, self.nx, self.nu)):
+            if t is not None and (tuple(t.shape) != (w, w) or t.dtype != torch.float64 or not t.is_cuda):
+                raise ValueError(f"weights must be float64 device tensors of shapes ({self.nx}, {self.nx}), "
+                                 f"({self.nx}, {self.nx}), ({self.nu}, {self.nu}) or None")
+            out.append(None if t is None else t.contiguous())
+        return out
+
+    def _assemble_w(self, B, ins, bounds, weights, out, dev):
+        """mpcqp_<kind>_assemble_w_device: `ins` the forward's five inputs, `bounds` (xlo, xhi) for
+        the LTV layout and () for the incremental one -> (Ax, q, l, u, Px) with Px (nnzP,)."""
+        import torch
+        Ax, q, l, u = self._empty_out(B, dev) if out is None else out
+        Px = torch.empty(self.nnzP, dtype=torch.float64, device=dev)
+        keep = self._weights(weights)
+        _check(getattr(lib(), f"mpcqp_{self._kind}_assemble_w_device")(
+            self._h, B, *(_p(t) for t in ins), *(_po(t) for t in bounds), *(_po(t) for t in keep), _p(Ax), _p(q),
+            _p(l), _p(u), _p(Px), _stream(torch, dev)), f"{self._kind}_assemble_w")
+        return Ax, q, l, u, Px
+
+    VJP_OUTPUTS = ("gAd", "gBd", "ggd", "gx0", "gXr", "gxlo", "gxhi", "gQ", "gQN", "gR")
+
+    def assemble_vjp(self, gAx=None, gq=None, gl=None, gu=None, gPx=None, Xr=None, xlo=None, xhi=None,
+                     weights=None, want=None, out=None):
+        """The transpose of assemble() (mpcqp_<kind>_assemble_vjp_device; mpcqp.h has the formulas).
+        Cotangents gAx (B,nnzA), gq (B,n), gl, gu (B,m), gPx (B,nnzP): contiguous float64 device
+        tensors, None = zero (at least one given).  Xr, xlo, xhi, weights: the forward call's (Xr is
+        read for gQ / gQN, xlo / xhi for gxlo / gxhi).  want: the outputs to form, of VJP_OUTPUTS
+        (default: all the arguments allow); out: {name: tensor} to write into.  Returns a namespace
+        with gAd (B,N,nx,nx), gBd (B,N,nx,nu), ggd (B,N,nx), gx0 (B,nxa), gXr (B,nx,N+1), gxlo, gxhi
+        (B,N+1,nxa), gQ, gQN (B,nx,nx), gR (B,nu,nu) -- per instance, with respect to the stored
+        weights -- and None for what was not wanted."""
+        import torch
+        from types import SimpleNamespace
+        N, nx, nu, nxa = self.N, self.nx, self.nu, self.nxa
+        cots = dict(gPx=(gPx, self.nnzP), gAx=(gAx, self.nnzA), gq=(gq, self.n), gl=(gl, self.m), gu=(gu, self.m))
+        given = [t for t, _ in cots.values() if t is not None]
+        if not given:
+            raise ValueError("assemble_vjp: at least one cotangent must be given")
+        B, dev = given[0].shape[0], given[0].device
+        for k, (t, w) in cots.items():
+            if t is not None and (tuple(t.shape) != (B, w) or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"assemble_vjp: {k} must be a contiguous float64 tensor of shape ({B}, {w})")
+        fwd = dict(Xr=(Xr, (B, nx, N + 1)), xlo=(xlo, (B, N + 1, nxa)), xhi=(xhi, (B, N + 1, nxa)))
+        for k, (t, shape) in fwd.items():
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"assemble_vjp: {k} must be a contiguous float64 tensor of shape {shape}")
+        if self._kind != "ltv" and (xlo is not None or xhi is not None):
+            raise ValueError("assemble_vjp: only the LTV layout takes per-stage bounds")
+        shapes = dict(gAd=(B, N, nx, nx), gBd=(B, N, nx, nu), ggd=(B, N, nx), gx0=(B, nxa), gXr=(B, nx, N + 1),
+                      gxlo=(B, N + 1, nxa), gxhi=(B, N + 1, nxa), gQ=(B, nx, nx), gQN=(B, nx, nx), gR=(B, nu, nu))
+        if want is None:
+            want = ["gAd", "gBd", "ggd", "gx0", "gXr"] + ["gxlo"] * (xlo is not None) + ["gxhi"] * (xhi is not None)
+            if gPx is not None or (gq is not None and Xr is not None):
+                want += ["gQ", "gQN", "gR"]
+        bad = sorted(set(want) - set(shapes) | (set() if self._kind == "ltv" else set(want) & {"gxlo", "gxhi"}))
+        if bad:
+            raise ValueError(f"assemble_vjp: unknown output(s) {', '.join(bad)}")
+        o = SimpleNamespace(**{k: None for k in shapes})
+        for k in want:
+            t = None if out is None else out.get(k)
+            if t is None:
+                t = torch.empty(shapes[k], dtype=torch.float64, device=dev)
+            elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError(f"assemble_vjp: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
+            setattr(o, k, t)
+        Q, QN, _ = self._weights(weights)
+        ltv = self._kind == "ltv"
+        args = [_po(gPx), _po(gAx), _po(gq), _po(gl), _po(gu), _po(Xr)] + ([_po(xlo), _po(xhi)] if ltv else [])
+        args += [_po(Q), _po(QN)]
+        args += [_po(getattr(o, k)) for k in self.VJP_OUTPUTS if ltv or k not in ("gxlo", "gxhi")]
+        _check(getattr(lib(), f"mpcqp_{self._kind}_assemble_vjp_device")(self._h, B, *args, _stream(torch, dev)),
+               f"{self._kind}_assemble_vjp")
+        return o
+
 
 class IncrementalLayout(_Layout):
     """The QP of mpc_increment (mpc_dynamics.py:281-389) for a batch sharing N, weights,
@@ -222,16 +315,21 @@ class IncrementalLayout(_Layout):
         super().__init__(N, Q, QN, R, (xmin_t, xmax_t, dumin, dumax), maskA, maskB, device)
         self.nxa = self.nx + self.nu
 
-    def assemble(self, Ad, Bd, gd, xt0, Xr, out=None):
+    def assemble(self, Ad, Bd, gd, xt0, Xr, out=None, weights=None):
         """Ad (B,N,nx,nx), Bd (B,N,nx,nu), gd (B,N,nx), xt0 (B,nx+nu), Xr (B,nx,N+1), all
-        contiguous float64 device tensors -> (Ax, q, l, u) in the layout's pattern order."""
+        contiguous float64 device tensors -> (Ax, q, l, u) in the layout's pattern order.
+        weights = (Q, QN, R) device tensors (each None: the layout's own) assembles with the
+        weights of this call (mpcqp_incr_assemble_w_device) and returns (Ax, q, l, u, Px), Px
+        (nnzP,) being P's stored values from them, one copy for the batch."""
         import torch
         B = Ad.shape[0]
-        if out is None:
-            out = self._empty_out(B, Ad.device)
         for t in (Ad, Bd, gd, xt0, Xr):
             if not t.is_contiguous() or t.dtype != torch.float64:
                 raise ValueError("assemble inputs must be contiguous float64 tensors")
+        if weights is not None:
+            return self._assemble_w(B, (Ad, Bd, gd, xt0, Xr), (), weights, out, Ad.device)
+        if out is None:
+            out = self._empty_out(B, Ad.device)
         Ax, q, l, u = out
         _check(lib().mpcqp_incr_assemble_device(self._h, B, _p(Ad), _p(Bd), _p(gd), _p(xt0), _p(Xr), _p(Ax), _p(q),
                                                 _p(l), _p(u), _stream(torch, Ad.device)), "incr_assemble")
@@ -289,6 +387,24 @@ class AffineMap:
                 out[b, i] = bv[i] if not anyt else (bv[i] + v if bv[i] != 0.0 else v)
         s0, s1 = self.seglen[0], self.seglen[0] + self.seglen[1]
         return out[:, :s0], out[:, s0:s1], out[:, s1:]
+
+    def vjp(self, gq, gl, gu):
+        """The transpose of evaluate's linear part in the device kernel's order
+        (mpc_device.hip::k_affine_vjp): gtheta[b, p] = sum of coef[i, t] * g[b, i] over the terms with
+        idx[i, t] == p, entries ascending, then terms; g = (gq | gl | gu), each (B, seglen) or None."""
+        segs = [None if g is None else np.atleast_2d(np.asarray(g, float)) for g in (gq, gl, gu)]
+        B = next(g for g in segs if g is not None).shape[0]
+        g = np.concatenate([np.zeros((B, w)) if s is None else s for s, w in zip(segs, self.seglen)], axis=1)
+        out = np.zeros((B, self.nparam))
+        first = np.ones(self.nparam, bool)
+        for i in range(self.idx.shape[0]):
+            for t in range(self.T):
+                p = self.idx[i, t]
+                if p >= 0:
+                    term = self.coef[i, t] * g[:, i]
+                    out[:, p] = term if first[p] else out[:, p] + term
+                    first[p] = False
+        return out
 
 
 def lateral_builder(layout, N):
@@ -376,6 +492,31 @@ class LateralAssembler:
         _check(L.mpcqp_affine_apply_device(self._h, B, _p(theta), theta.stride(0),
                                            None if regime is None else _p(regime), *(_p(t) for t in out), st),
                "affine_apply")
+        return out
+
+    def assemble_vjp(self, gq=None, gl=None, gu=None, regime=None, out=None, stream=None):
+        """The transpose of assemble() (mpcqp_affine_vjp_device): cotangents gq (B, n), gl, gu
+        (B, m), contiguous float64 device tensors, None = zero (at least one given) -> gtheta
+        (B, nparam) (into `out` when given: (B, >= nparam) with a contiguous last axis).  The regime
+        selects only the base, which has no derivative; it is accepted and ignored."""
+        import torch
+        L = _bind()
+        given = [t for t in (gq, gl, gu) if t is not None]
+        if not given:
+            raise ValueError("assemble_vjp: at least one cotangent must be given")
+        B, dev = given[0].shape[0], given[0].device
+        for t, w in ((gq, self.n), (gl, self.m), (gu, self.m)):
+            if t is not None and (tuple(t.shape) != (B, w) or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"assemble_vjp: cotangents must be contiguous float64 ({B}, {self.n} / {self.m} / "
+                                 f"{self.m}) tensors")
+        if out is None:
+            out = torch.empty((B, self.nparam), dtype=torch.float64, device=dev)
+        elif out.dim() != 2 or out.shape[0] != B or out.shape[1] < self.nparam or out.stride(1) != 1 or \
+                out.dtype != torch.float64:
+            raise ValueError(f"assemble_vjp: out must be float64 (B, >= {self.nparam}) with a contiguous last axis")
+        st = stream if stream is not None else _stream(torch, dev)
+        _check(L.mpcqp_affine_vjp_device(self._h, B, _po(gq), _po(gl), _po(gu), _po(regime), _p(out), out.stride(0),
+                                         st), "affine_vjp")
         return out
 
 
@@ -577,6 +718,36 @@ def linearise_kinematics(veh: KinVehicle, x, u, device=0):
     return _linearise("kin_linearise", veh, x, u, 4)
 
 
+def linearise_kinematics_vjp(veh: KinVehicle, x, u, gAd, gBd, ggd):
+    """The VJP of linearise_kinematics (mpcqp_kin_linearise_vjp_device): x, u as the forward took
+    them (any strides with a contiguous last dimension -- a stage stride of 0 included), cotangents
+    gAd (B, N, 4, 4), gBd (B, N, 4, 2), ggd (B, N, 4) contiguous float64 device tensors, None =
+    zero -> dense gx (B, N, 4), gu (B, N, 2) (N axis dropped for 2-D inputs).  Only v, yaw and
+    steer carry derivative; a caller whose stages share one (x, u) sums over the stage axis."""
+    import torch
+    L = _bind()
+    squeeze = x.dim() == 2
+    if squeeze:
+        x, u = x[:, None, :], u[:, None, :]
+    B, N = x.shape[0], x.shape[1]
+    if x.shape[2] != 4 or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
+        raise ValueError("x must be (B, N, 4) and u (B, N, 2)")
+    if x.stride(2) != 1 or u.stride(2) != 1:
+        raise ValueError("the state / input axis must be contiguous")
+    for t, tail in ((gAd, (4, 4)), (gBd, (4, 2)), (ggd, (4,))):
+        if t is not None and (t.numel() != B * N * int(np.prod(tail)) or tuple(t.shape[-len(tail):]) != tail or
+                              t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("cotangents must be contiguous float64 (B, N, 4, 4), (B, N, 4, 2), (B, N, 4) tensors")
+    kw = dict(dtype=torch.float64, device=x.device)
+    gx = torch.empty((B, N, 4), **kw); gu = torch.empty((B, N, 2), **kw)
+    _check(L.mpcqp_kin_linearise_vjp_device(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0),
+                                            u.stride(1), _po(gAd), _po(gBd), _po(ggd), _p(gx), _p(gu),
+                                            x.device.index or 0, _stream(torch, x.device)), "kin_linearise_vjp")
+    if squeeze:
+        return gx[:, 0], gu[:, 0]
+    return gx, gu
+
+
 def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):
     """reference_search of mpc_incre_kine_func.py (:42-81) per vehicle: pred (B, N+1, nxa)
     device tensor of predicted augmented states (speed in state 2), set_speed (B,)
@@ -697,10 +868,13 @@ class LTVLayout(_Layout):
                 [a.size for a in arrs] != [self.nx, self.nx, self.nu, self.nu]:
             raise ValueError("LTVLayout: Q, QN, maskA must be nx x nx, R nu x nu, maskB nx x nu, bounds nx / nu long")
 
-    def assemble(self, Ad, Bd, gd, x0, Xr, xlo=None, xhi=None, out=None):
+    def assemble(self, Ad, Bd, gd, x0, Xr, xlo=None, xhi=None, out=None, weights=None):
         """Ad (B,N,nx,nx), Bd (B,N,nx,nu), gd (B,N,nx), x0 (B,nx), Xr (B,nx,N+1) and the optional
         per-stage state bounds xlo / xhi (B,N+1,nx), all contiguous float64 device tensors
-        -> (Ax, q, l, u) in the layout's pattern order."""
+        -> (Ax, q, l, u) in the layout's pattern order.  weights = (Q, QN, R) device tensors (each
+        None: the layout's own) assembles with the weights of this call
+        (mpcqp_ltv_assemble_w_device) and returns (Ax, q, l, u, Px), Px (nnzP,) being P's stored
+        values from them, one copy for the batch."""
         import torch
         B, N, nx, nu = Ad.shape[0], self.N, self.nx, self.nu
         shapes = [(Ad, (B, N, nx, nx)), (Bd, (B, N, nx, nu)), (gd, (B, N, nx)), (x0, (B, nx)), (Xr, (B, nx, N + 1))]
@@ -715,6 +889,8 @@ class LTVLayout(_Layout):
         for t, w in ((Ax, self.nnzA), (q, self.n), (l, self.m), (u, self.m)):
             if tuple(t.shape) != (B, w) or not t.is_contiguous() or t.dtype != torch.float64:
                 raise ValueError("assemble outputs must be contiguous float64 (B, nnzA / n / m / m) tensors")
+        if weights is not None:
+            return self._assemble_w(B, (Ad, Bd, gd, x0, Xr), (xlo, xhi), weights, out, Ad.device)
         _check(lib().mpcqp_ltv_assemble_device(self._h, B, _p(Ad), _p(Bd), _p(gd), _p(x0), _p(Xr),
                                                None if xlo is None else _p(xlo), None if xhi is None else _p(xhi),
                                                _p(Ax), _p(q), _p(l), _p(u), _stream(torch, Ad.device)),
