@@ -129,6 +129,7 @@ struct mpcqp_handle {
     std::pair<hipEvent_t, hipEvent_t> last_pair{nullptr, nullptr};  // events of the last device solve
     bool staged = false;  // every shard's hstage holds the last mpcqp_solve_batch's results
     bool one_shot = false;    // mpcqp_set_one_shot: setup_solve_device persists no workspace state
+    bool one_shot_lds = false;  // MPCQP_ONE_SHOT_LOOP=lds at creation: the one-shot cfg-2 kernel's GL 1 form (A/B)
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
     bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
 };
@@ -632,6 +633,7 @@ int make_handle(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, cons
     if (settings) h->set = *settings;
     else mpcqp_default_settings(&h->set);
     if (int e = validate_settings(h->set)) return e;
+    if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP"); ev && !strcmp(ev, "lds")) h->one_shot_lds = true;
     strace().mark("(enter)");
     std::string err = cached_plan(n, m, Pp, Pi, Ap, Ai, h->set, h->plan);
     strace().mark("plan");
@@ -1526,7 +1528,7 @@ int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* d
     k.ostat = dstatus;
     k.oiter = diters;
     const bool one = h->one_shot && one_shot_form(k) > 0;
-    HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one));
+    HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? (h->one_shot_lds ? 2 : 1) : 0));
     h->state_gone = one;
     if (h->collect) {
         if (int e = ev_end(h->collect, h->ev_solve, st)) return e;

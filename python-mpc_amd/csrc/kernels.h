@@ -165,10 +165,12 @@ int solve_threads(int variant);  // workgroup size of the variant's kernel
 bool variant_fits(const KParams& p, int variant);
 hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st);
 // setup + solve of the same inputs (solve_wave.hip): one fused kernel where the variant
-// allows it, else launch_setup then launch_solve
+// allows it, else launch_setup then launch_solve.  one_shot: 0 the persisting form, 1 the one-shot
+// form (one_shot_form), 2 the same with the headline plan's earlier instantiation (GL 1 instead of
+// GL 3: MPCQP_ONE_SHOT_LOOP=lds, the A/B baseline)
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                              bool one_shot = false);
+                              int one_shot = 0);
 // the one-shot fused kernel's form for the plan (solve_wave.hip): 0 none (not the fused four-wave
 // kernel, or polish), 1 the G blocks in the workspace, 2 the G blocks in an LDS region of their
 // own (two workgroups per CU still fit), 3 the G blocks straight into the solve's LDS copy

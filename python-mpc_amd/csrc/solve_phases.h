@@ -263,6 +263,12 @@ __device__ __forceinline__ bool gj_wave(double* __restrict__ T, double* __restri
     return minpiv > 0.0;
 }
 
+// KParams for factorize_w4 with the Gauss-Jordan pivot taken in registers (gj_seg's SEG 3 / 4):
+// the one-shot cfg-2 kernel's GL 3 instantiation (solve_wave.hip, factorize_gp_nl).  The same
+// data; the type alone selects the form, so that the other kernels' factorisation keeps its code
+struct KParamsPR : KParams {};
+typedef __attribute__((address_space(4))) const KParamsPR KPcPR;
+
 // Gauss-Jordan of one tile in two segments, by one wave, in place (the split
 // factorisations factorize_w2 / factorize_g).  S_k = D_k - F_k E_k' differs from the
 // assembled D_k only in the corner [0, a)^2 of its coupling rows (E_k has a nonzero
@@ -279,10 +285,16 @@ __device__ __forceinline__ bool gj_wave(double* __restrict__ T, double* __restri
 // Rot (unrolled form only): the tile rows are read and written in ld_row16's rotated order.
 // Swz (unrolled form only): T has tile_at<true>'s layout -- the lane's column pair s is at
 // position s ^ (i & 7) of its half, read into and stored from v[2 s], v[2 s + 1] directly.
+// SEG 3 / 4 (unrolled form only): SEG 1 / 2 with the pivot read by v_readlane from the lane that
+// publishes it, and its reciprocal formed before the wave sync instead of after the LDS read --
+// the same value and operations.
 template <int SEG, bool Compact = false, bool Rot = false, bool Swz = false>
 __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restrict__ buf, const int a, const int npiv,
                                        const double* __restrict__ dl) {
     static_assert(!Swz || (!Rot && !Compact), "the swizzled tiles: the unrolled form, reads in place order");
+    constexpr bool PR = SEG > 2;             // SEG 3 / 4: segments 1 / 2 with the pivot taken in registers
+    constexpr int SG = PR ? SEG - 2 : SEG;
+    static_assert(SEG >= 1 && SEG <= 4 && (!PR || !Compact), "the register pivot: the unrolled form (p a constant)");
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     double v[16];
     if constexpr (Swz) {
@@ -302,7 +314,7 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
     } else {
         ld_row16(T + i * S + 16 * h, i, v);
     }
-    if (SEG == 2 && h == 0 && i < a) {
+    if (SG == 2 && h == 0 && i < a) {
 #pragma unroll
         for (int jj = 0; jj < 16; ++jj)
             if (jj < a) v[jj] += dl[i * 16 + jj];
@@ -311,14 +323,27 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
     auto step = [&](const int p, const int pj, const bool pv) __attribute__((always_inline)) {
         const int ph = p >> 4;
         double* rb = buf + (pj & 1) * S;
-        if (h == ph) {
+        double piv, d;
+        if constexpr (PR) {
+            // lane p of half ph publishes rb[p] = vp unflipped (pv is false for i == p): the
+            // same value by v_readlane, and its reciprocal while the column's LDS round trip
+            // is in flight
+            const double vp = sc * v[pj];
+            if (h == ph) rb[i] = pv ? -vp : vp;
+            const int sl = p + 32 * ph;
+            piv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(vp), sl),
+                                   __builtin_amdgcn_readlane(__double2loint(vp), sl));
+            d = __builtin_amdgcn_rcp(piv);
+            d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+            d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+        } else if (h == ph) {
             const double vp = sc * (Compact ? pick16(v, pj) : v[pj]);
             rb[i] = pv ? -vp : vp;  // row p = +-column p
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double piv = rb[p];
+        if constexpr (!PR) piv = rb[p];
         const double mi = rb[i];
         double rowv[16];
 #pragma unroll
@@ -329,9 +354,11 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
         }
         const double colv = pv ? -mi : mi;
         minpiv = piv > 0.0 ? minpiv : -1.0;
-        double d = __builtin_amdgcn_rcp(piv);
-        d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
-        d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+        if constexpr (!PR) {
+            d = __builtin_amdgcn_rcp(piv);
+            d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+            d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+        }
         const bool self = i == p;
         if constexpr (Compact) {
             const double cd = self ? 0.0 : (colv * d) * iv;
@@ -353,7 +380,7 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
         }
     };
     if constexpr (Compact) {
-        if constexpr (SEG == 1) {
+        if constexpr (SG == 1) {
 #pragma unroll 1
             for (int p = a; p < npiv; ++p) step(p, __builtin_amdgcn_readfirstlane(p & 15), i >= a && i < p);
         } else {
@@ -361,7 +388,7 @@ __device__ __forceinline__ bool gj_seg(double* __restrict__ T, double* __restric
 #pragma unroll 1
             for (int p = 0; p < a; ++p) step(p, __builtin_amdgcn_readfirstlane(p & 15), done || i < p);
         }
-    } else if constexpr (SEG == 1) {
+    } else if constexpr (SG == 1) {
 #pragma unroll
         for (int p = 0; p < S; ++p)
             if (p >= a && p < npiv) step(p, p & 15, i >= a && i < p);
@@ -633,6 +660,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
 #define FPH(k)
 #endif
     const bool sw = TT == 256 || w < 4;  // a stage-1 wave (wave w: block w)
+    constexpr bool PR = __is_base_of(KParamsPR, KP);  // the pivot in registers (gj_seg SEG 3 / 4)
     // an eliminated column's pivot K_jj is a pivot of the full KKT factorisation too: a
     // non-positive (or NaN) one makes the instance non-convex, as OSQP's LDL' of the
     // quasi-definite matrix would find, even though the reduced blocks may still factor
@@ -667,7 +695,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
     FPH(8)
     bool okw = true;
     if (sw) {
-        okw = gj_seg<1, false, ROT, SWZ>(Sg + (long)w * SS, bufw, w ? amax : 0, p.bsize[w], nullptr);
+        okw = gj_seg<PR ? 3 : 1, false, ROT, SWZ>(Sg + (long)w * SS, bufw, w ? amax : 0, p.bsize[w], nullptr);
         okw = okw && __builtin_amdgcn_ballot_w64(!oke) == 0;
     }
     FPH(10)
@@ -701,7 +729,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
                 dl[r * 16 + c] = -sacc;
             }
             wave_sync();
-            okw = gj_seg<2, false, ROT, SWZ>(Sg + (long)k * SS, bufw, amax, p.bsize[k], dl) && okw;
+            okw = gj_seg<PR ? 4 : 2, false, ROT, SWZ>(Sg + (long)k * SS, bufw, amax, p.bsize[k], dl) && okw;
         } else {
             // waves 1-3 meanwhile: G_kj = -F_k G_{k-1,j} (j < k-1), off the chain's path
 #pragma unroll 1
@@ -1806,6 +1834,16 @@ __device__ __noinline__ bool factorize_g_nl(const KParams* gp, long b, double rh
     SL2 c = carve(p);
     double* const sg = w4_tiles(p, c);
     return factorize<TT, KPc, false, ROT, SWZ>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
+}
+// factorize_g_nl with the Gauss-Jordan pivot taken in registers (KPcPR): the one-shot cfg-2
+// kernel's GL 3 instantiation only, so that factorize_g_nl keeps its code for the others
+template <int TT, bool ROT = false, bool SWZ = false>
+__device__ __noinline__ bool factorize_gp_nl(const KParams* gp, long b, double rho) {
+    static_assert(SWZ && TT == 256, "factorize_w4's swizzled form");
+    KPcPR& p = static_cast<KPcPR&>(kconst(gp));
+    SL2 c = carve(p);
+    double* const sg = w4_tiles(p, c);
+    return factorize<TT, KPcPR, false, ROT, SWZ>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
 }
 
 

@@ -1176,7 +1176,10 @@ __device__ __forceinline__ void form_dense_rows(__attribute__((address_space(1))
 // allows it, one_shot_form 2): the G blocks go to an LDS region after the S_k^{-1} tiles instead
 // of the instance's H tiles, a refactorisation keeps y there instead of in the workspace, and
 // the setup leaves E and D in the carve (edl_E / edl_D); GL 2 (one_shot_form 3): the G blocks go
-// straight into gl (factorize_w4_gl)
+// straight into gl (factorize_w4_gl); GL 3 (form 2 without eliminated columns and amax <= 5, the
+// headline's plan): GL 1 with the loop's phase A and B reads issued earlier (WV below) and the
+// Gauss-Jordan pivot's reciprocal taken off its LDS round trip (factorize_gp_nl) -- the same sums
+// and operands; GL 1 stays as the A/B baseline (MPCQP_ONE_SHOT_LOOP=lds) and keeps its code
 template <int K, int KPK, int QR, bool EL = false, int KC = K, bool DK = false, bool RU = false, bool ONE = false,
           int GL = 0>
 __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restrict__ xo, double* __restrict__ yo,
@@ -1192,15 +1195,18 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
+    static_assert(GL >= 0 && GL <= 3 && (GL != 3 || (ONE && !EL && !DK && QR <= 5)), "GL 3: the headline's plan only");
+    constexpr bool G1 = GL == 1 || GL == 3;  // the one-shot form 2 (G blocks, y, E and D on chip)
+    constexpr bool WV = GL == 3;             // ... with the loop's phase A / B reads issued earlier
     // GL 1: the G blocks (amax x S per pair) go to LDS after the S_k^{-1} tiles; GL 2: straight
     // into gl (factorize_w4_gl), no copy
-    const double* Hg = GL == 1 ? C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16) + (long)NB * SS
+    const double* Hg = G1 ? C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16) + (long)NB * SS
                            : p.H + b * (long)p.nb * SS;
     double* const Sg = C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16);  // S_k^{-1} tiles in LDS (lds_w2_bytes)
     // SWZ: the tiles in tile_at<true>'s layout (solve_phases.h) -- the one-shot form 2 without
     // eliminated columns and amax <= 5, the headline's instantiation.  Its tiles never leave LDS
     // (no RU / factor_only copy, no dense rows); the other instantiations' stay row-major
-    constexpr bool SWZ = ONE && GL == 1 && !EL && !DK && QR <= 5;
+    constexpr bool SWZ = ONE && G1 && !EL && !DK && QR <= 5;
     // LEAN (the same instantiation): the work between its ADMM runs cut to what the result needs
     // -- the run start reads the G blocks where the factorisation left them (no gl copy) and
     // divides once, the check takes its column list from the run's registers and combines the
@@ -1302,7 +1308,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         if (need_factor) {
             need_factor = false;
             if (iter > 0) {
-                if constexpr (GL == 1) {  // (y kept on chip, after the G blocks)
+                if constexpr (G1) {  // (y kept on chip, after the G blocks)
                     double* const ysv = Sg + (long)NB * SS + (long)(NB * (NB - 1) / 2) * p.amax * S;
                     for (int i = tid; i < m; i += T4) ysv[i] = L.ys[i];
                 } else {
@@ -1330,7 +1336,9 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 }
                 __syncthreads();
                 if (tid == 0) p.ffresh[b] = 0;
-            } else if constexpr (GL == 1) {
+            } else if constexpr (WV) {  // (the Gauss-Jordan pivot in registers: gj_seg SEG 3 / 4)
+                ok = factorize_gp_nl<T4, EL, SWZ>(p.self, b, rho);
+            } else if constexpr (G1) {
                 ok = factorize_g_nl<T4, EL, SWZ>(p.self, b, rho);
             } else if constexpr (GL == 2) {
                 ok = factorize_gl_nl<T4, EL>(p.self, b, rho);
@@ -1364,7 +1372,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             }
             __syncthreads();
             const bool have_y = iter > 0 || warm;
-            if constexpr (GL == 1) {
+            if constexpr (G1) {
                 const double* const ysv = Sg + (long)NB * SS + (long)(NB * (NB - 1) / 2) * p.amax * S;
                 for (int i = tid; i < mp; i += T4) L.ys[i] = (have_y && i < m) ? ysv[i] : 0.0;
             } else {
@@ -1597,6 +1605,37 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 DX = xnew - X;
                 X = xnew;
             } else {
+            // WV: every pair's b_j is read at once (blocks j >= w too: read and not used), so
+            // that wave 3 waits for LDS once and not once per branch of the pair nest, and
+            // phase B's b_w reads are issued ahead of the reduction (they depend on nothing of
+            // phase A): they return while its DPP steps and the c_w round trip run.  c_w still
+            // goes through L.cor: taking it from the reduction's lanes by v_readlane was
+            // measured slower in three forms
+            double vb[WV ? 16 : 1];
+            if constexpr (WV) {
+                double sa = 0.0;
+                if (w > 0) {
+                    double bj[NB - 1][4];
+#pragma unroll
+                    for (int j = 0; j < NB - 1; ++j) {
+                        ld2(L.rb + j * S + 4 * ch, bj[j][0], bj[j][1]);
+                        ld2(L.rb + j * S + 4 * ch + 2, bj[j][2], bj[j][3]);
+                    }
+                    double acc[NB - 1] = {0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int j = 0; j < NB - 1; ++j) {
+                        if (j < w) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) acc[j] += ga[j][e] * bj[j][e];
+                        }
+                    }
+                    sa = (acc[0] + acc[1]) + acc[2];
+                }
+#pragma unroll
+                for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, vb[c], vb[c + 1]);
+                const double cs = reduce8(sa);
+                if (w > 0) cw[rr] = cs;
+            } else {
             // A: c_w = sum_{j<w} G_wj b_j (rows < 8), wave w only
             if (w > 0) {
                 // one accumulator per pair (wave 3: three 4-deep FMA chains instead of one 12-deep)
@@ -1613,6 +1652,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 }
                 cw[rr] = reduce8((acc[0] + acc[1]) + acc[2]);
             }
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1622,8 +1662,13 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             {
                 constexpr int QE = (QR + 1) & ~1;  // c_w's nonzero rows (< amax), read in pairs
                 double v[16], cc[QE];
+                if constexpr (WV) {
 #pragma unroll
-                for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, v[c], v[c + 1]);
+                    for (int c = 0; c < 16; ++c) v[c] = vb[c];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, v[c], v[c + 1]);
+                }
 #pragma unroll
                 for (int c = 0; c < QE; c += 2) ld2(cwh + c, cc[c], cc[c + 1]);
 #pragma unroll
@@ -1758,7 +1803,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             }
             const int oz = opaque_zero();
             double Dv, Ev;
-            if constexpr (GL == 1) {  // (E and D on chip: the one-shot form 2, edl_E / edl_D)
+            if constexpr (G1) {  // (E and D on chip: the one-shot form 2, edl_E / edl_D)
                 Dv = col >= 0 ? edl_D(p, C)[col] : 1.0;
                 Ev = ri < m ? edl_E(p, C)[ri] : 1.0;
             } else {
@@ -1939,19 +1984,19 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     }
     const double cval = cscal(0), cinv = cscal(1);
     if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<T4, GL == 1>(p.self, b, cinv);
+        update_info_nl<T4, G1>(p.self, b, cinv);
         info_iter = iter;
-        status = check_termination_nl<T4, GL == 1>(p.self, b, cval, cinv, 0);
+        status = check_termination_nl<T4, G1>(p.self, b, cval, cinv, 0);
     }
     const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
                            status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
                            status == MPCQP_NON_CVX_);
     if (has_sol) objective_nl<T4>(p.self, cinv);
     if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<T4, GL == 1>(p.self, b, cval, cinv, 1);
+        status = check_termination_nl<T4, G1>(p.self, b, cval, cinv, 1);
         if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
     }
-    finalize_nl<T4, ONE, GL == 1>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    finalize_nl<T4, ONE, G1>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
@@ -1999,7 +2044,7 @@ __global__ __launch_bounds__(T4, 2) void k_setup_solve_w4(KParams p, const doubl
                                                           const double* __restrict__ u_in, double* __restrict__ xo,
                                                           double* __restrict__ yo) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    setup_r_body<T4, SK, 4, 1, SAS, 1, false, ONE, GL == 1>(p, instance_of(p), Px_in, Ax_in, q_in, l_in, u_in, sm);
+    setup_r_body<T4, SK, 4, 1, SAS, 1, false, ONE, GL == 1 || GL == 3>(p, instance_of(p), Px_in, Ax_in, q_in, l_in, u_in, sm);
     __syncthreads();
     solve_w4_body<K, KPK, QR, EL, KC, DK, false, ONE, GL>(p, xo, yo);
     order_epilogue<T4>(p, (int*)sm);
@@ -2562,14 +2607,15 @@ int one_shot_form(const KParams& p, size_t* lds) {
 
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                              bool one_shot) {
+                              int one_shot) {
     size_t lds1 = 0;
     const int form = one_shot ? one_shot_form(p, &lds1) : 0;
     if (form) {
         decltype(&k_setup_solve_w4<6, 4, 5, 6, 2>) k4;
         if (form == 2)
             k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8, false, true, 1>
-                      : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 1>
+                      : (p.amax <= 5 ? (one_shot == 2 ? k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 1>
+                                                      : k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 3>)
                                      : k_setup_solve_w4<6, 4, 8, 6, 2, false, 6, false, true, 1>);
         else if (form == 3)
             k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8, false, true, 2>
