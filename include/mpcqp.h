@@ -705,13 +705,40 @@ int mpcqp_affine_vjp_device(const mpcqp_affine *a, int64_t B, const double *dg0,
  *   gx[2] = dt ((gAd13 c - gAd03 s) + (ggd0 s - ggd1 c) yaw + (gBd30 - ggd3 d) sec2 / wb)
  *   gx[3] = dt ((gAd12 c - gAd02 s) - v (gAd03 c + gAd13 s) + v (ggd0 (c yaw + s) + ggd1 (s yaw - c)))
  *   gu[0] = dt / wb (gAd32 sec2 + v (gBd30 dsec2 - ggd3 (sec2 + d dsec2)))
- * and gx[0] = gx[1] = gu[1] = 0 are written.  The dynamic bicycle's linearisation (Pacejka tyres,
- * the low-speed guard) has no VJP here: a caller differentiates what is downstream of its
- * (Ad, Bd, gd) and stops there. */
+ * and gx[0] = gx[1] = gu[1] = 0 are written.  A NULL cotangent is zero; a NULL gx or gu is not
+ * written.  The dynamic bicycle's linearisation has its own: mpcqp_linearise_vjp_device. */
 int mpcqp_kin_linearise_vjp_device(const mpcqp_kin_vehicle *veh, int64_t B, int32_t N, const double *dx, int64_t x_sb,
                                    int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, const double *dgAd,
                                    const double *dgBd, const double *dggd, double *dgx, double *dgu, int32_t device,
                                    void *stream);
+
+/* The VJP of mpcqp_linearise_device (the dynamic bicycle: Pacejka tyres, the low-speed guard) per
+ * (vehicle, stage): x, u with the forward call's strides (a stage stride of 0 included; the sum
+ * over the stages is then the caller's); cotangents gAd[(b*N + k)*36], gBd[(b*N + k)*12],
+ * ggd[(b*N + k)*6], each NULL = zero; outputs DENSE gx[(b*N + k)*6], gu[(b*N + k)*2], either NULL
+ * = not written.  With (Ad, Bd, gd) = F(x, u) the forward AS IT COMPUTES,
+ *   gx[j] = sum_il gAd_il dAd_il/dx_j + sum_il gBd_il dBd_il/dx_j + sum_i ggd_i dgd_i/dx_j,
+ * and gu[j] alike in u_j, where
+ *   Ad = I + dt Ac,  Bd = dt Bc,  gd = dt (f - Ac x~ - Bc u~)
+ * at the guarded point (x~, u~), with get_dynamics_model's f, Ac and Bc.  That Ac is not
+ * everywhere the derivative of that f (its dFx/dvx = -cda vx is the derivative of
+ * -0.5 cda vx^2 sgn(vx) for vx > 0 only), so df/dx_j and Ac[:, j] in dgd/dx_j do not cancel and
+ * both are formed; sgn(vx) has derivative 0.  The derivatives are exact ones of those formulas
+ * (forward-mode dual numbers in yaw, vx, vy, r, steer, accel, contracted with the cotangents),
+ * not difference quotients.
+ *   X and Y never enter:                        gx[0] = gx[1] = 0 are written;
+ *   |vx| < 0.5 (vx = 0 on the positive side):   the guard replaced vy, r and steer by 0:
+ *                                               gx[4] = gx[5] = gu[0] = 0;
+ *   |vx| < 0.3:                                 it replaced vx by +-0.3 as well: gx[3] = 0;
+ * so below 0.3 only yaw and accel carry derivative, between 0.3 and 0.5 yaw, vx and accel, and
+ * above 0.5 yaw, vx, vy, r, steer and accel (accel through Fx = m accel - ..., which enters Bc's
+ * steer column and gd).  No atomics: each output element has one writer and identical calls give
+ * identical bits.  MPCQP_EINVAL ("linearise_vjp: bad arguments") for a NULL veh, dx or du, B < 0
+ * or N < 1, before any device call. */
+int mpcqp_linearise_vjp_device(const mpcqp_vehicle *veh, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                               int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, const double *dgAd,
+                               const double *dgBd, const double *dggd, double *dgx, double *dgu, int32_t device,
+                               void *stream);
 
 #ifdef __cplusplus
 }

@@ -94,33 +94,168 @@ __device__ __forceinline__ void low_speed_guard(double* x, double* u) {
     }
 }
 
+// Forward-mode dual number over the six inputs that carry derivative through linearise_one:
+// d[] = d/d(yaw, vx, vy, r, steer, accel).  The model below is written once over its scalar
+// type: double for the forward kernels, Dual for k_linearise_vjp.
+struct Dual {
+    static constexpr int ND = 6;
+    double v;
+    double d[ND];
+    __device__ explicit Dual(double v_ = 0.0) : v(v_) {
+        for (int j = 0; j < ND; ++j) d[j] = 0.0;
+    }
+    // the input `slot` at value v_; seed 0 where the low-speed guard replaced it by a constant
+    __device__ Dual(double v_, int slot, bool live) : Dual(v_) { d[slot] = live ? 1.0 : 0.0; }
+};
+__device__ __forceinline__ Dual operator-(const Dual& a) {
+    Dual o(-a.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = -a.d[j];
+    return o;
+}
+__device__ __forceinline__ Dual operator+(const Dual& a, const Dual& b) {
+    Dual o(a.v + b.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] + b.d[j];
+    return o;
+}
+__device__ __forceinline__ Dual operator-(const Dual& a, const Dual& b) {
+    Dual o(a.v - b.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] - b.d[j];
+    return o;
+}
+__device__ __forceinline__ Dual operator*(const Dual& a, const Dual& b) {
+    Dual o(a.v * b.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] * b.v + a.v * b.d[j];
+    return o;
+}
+__device__ __forceinline__ Dual operator/(const Dual& a, const Dual& b) {
+    Dual o(a.v / b.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = (a.d[j] - o.v * b.d[j]) / b.v;
+    return o;
+}
+__device__ __forceinline__ Dual operator+(const Dual& a, double b) {
+    Dual o = a;
+    o.v = a.v + b;
+    return o;
+}
+__device__ __forceinline__ Dual operator+(double a, const Dual& b) {
+    Dual o = b;
+    o.v = a + b.v;
+    return o;
+}
+__device__ __forceinline__ Dual operator-(const Dual& a, double b) {
+    Dual o = a;
+    o.v = a.v - b;
+    return o;
+}
+__device__ __forceinline__ Dual operator*(const Dual& a, double b) {
+    Dual o(a.v * b);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] * b;
+    return o;
+}
+__device__ __forceinline__ Dual operator*(double a, const Dual& b) {
+    Dual o(a * b.v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a * b.d[j];
+    return o;
+}
+// the double overloads stay visible beside Dual's in this namespace
+using ::atan;
+using ::atan2;
+using ::cos;
+using ::sin;
+// chain rule with the outer derivative dv
+__device__ __forceinline__ Dual chain(double v, double dv, const Dual& a) {
+    Dual o(v);
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = dv * a.d[j];
+    return o;
+}
+__device__ __forceinline__ Dual sin(const Dual& a) { return chain(::sin(a.v), ::cos(a.v), a); }
+__device__ __forceinline__ Dual cos(const Dual& a) { return chain(::cos(a.v), -::sin(a.v), a); }
+__device__ __forceinline__ Dual atan(const Dual& a) { return chain(::atan(a.v), 1.0 / (1.0 + a.v * a.v), a); }
+__device__ __forceinline__ Dual atan2(const Dual& y, const Dual& x) {
+    Dual o(::atan2(y.v, x.v));
+    const double n = x.v * x.v + y.v * y.v;
+    for (int j = 0; j < Dual::ND; ++j) o.d[j] = (x.v * y.d[j] - y.v * x.d[j]) / n;
+    return o;
+}
+__device__ __forceinline__ double sgn(const Dual& a) { return sgn(a.v); }  // derivative 0, as the reference's Jacobian has it
+
 // f(x, u) of the dynamic bicycle model (vehicle_models.py:238-245 / 470-475), plus the
 // tyre quantities the Jacobian needs
+template <class T>
 struct Tyre {
-    double af, ar, Fyf, Fyr, Fx;
+    T af, ar, Fyf, Fyr, Fx;
 };
-__device__ __forceinline__ Tyre tyre_forces(const VehicleK& k, const double* x, const double* u) {
-    Tyre t;
-    const double vx = x[3], vy = x[4], r = x[5], st = u[0], acc = u[1];
+template <class T>
+__device__ __forceinline__ Tyre<T> tyre_forces(const VehicleK& k, const T* x, const T* u) {
+    Tyre<T> t;
+    const T vx = x[3], vy = x[4], r = x[5], st = u[0], acc = u[1];
     t.af = -atan2(k.lf * r + vy, vx) + st;
     t.ar = -atan2(-k.lr * r + vy, vx);
     t.Fyf = k.Df * sin(k.Cf * atan(k.Bf * t.af));
     t.Fyr = k.Dr * sin(k.Cr * atan(k.Br * t.ar));
     const double R_roll = k.roll * sgn(vx);
-    const double F_aero = 0.5 * k.cda * vx * vx * sgn(vx);
+    const T F_aero = 0.5 * k.cda * vx * vx * sgn(vx);
     t.Fx = k.m * acc - F_aero - R_roll;
     return t;
 }
-__device__ __forceinline__ void dynamics(const VehicleK& k, const double* x, const double* u, const Tyre& t,
-                                         double* f) {
-    const double yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
-    const double cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
+template <class T>
+__device__ __forceinline__ void dynamics(const VehicleK& k, const T* x, const T* u, const Tyre<T>& t, T* f) {
+    const T yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
+    const T cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
     f[0] = vx * cy - vy * sy;
     f[1] = vy * cy + vx * sy;
     f[2] = r;
     f[3] = 1. / k.m * (t.Fx * cs - t.Fyf * ss + k.m * vy * r);
     f[4] = 1. / k.m * (t.Fx * ss + t.Fyr + t.Fyf * cs - k.m * vx * r);
     f[5] = 1. / k.Iz * (t.Fx * k.lf * ss + t.Fyf * k.lf * cs - t.Fyr * k.lr);
+}
+
+// get_dynamics_model's continuous-time pieces at a GUARDED (x, u): f, and the structural entries of
+// the reference's Jacobians Ac (6x6) and Bc (6x2; every other entry is the constant 0).  That Ac
+// is not everywhere the derivative of that f (dFx/dvx = -cda vx holds for vx > 0 only).  Each
+// value goes to `out` as soon as it exists: out.F(i, f_i), out.A(i, j, Ac_ij), out.B(i, j, Bc_ij).
+template <class T, class Out>
+__device__ __forceinline__ void continuous_model(const VehicleK& k, const T* x, const T* u, Out& out) {
+    const Tyre<T> t = tyre_forces(k, x, u);
+    T f[6];
+    dynamics(k, x, u, t, f);
+    for (int i = 0; i < 6; ++i) out.F(i, f[i]);
+    const T yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
+    const double m = k.m, Iz = k.Iz, lf = k.lf, lr = k.lr;
+    const T cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
+    // :251-270 tyre-force derivatives
+    const T dFxf_dvx = -k.cda * vx;
+    const double dFxf_daccel = m;
+    const T kf = (k.Bf * k.Cf * k.Df * cos(k.Cf * atan(k.Bf * t.af))) / (1 + k.Bf * k.Bf * t.af * t.af);
+    const T kr = (k.Br * k.Cr * k.Dr * cos(k.Cr * atan(k.Br * t.ar))) / (1 + k.Br * k.Br * t.ar * t.ar);
+    const T af_num = lf * r + vy, ar_num = -lr * r + vy;
+    const T nf = af_num * af_num + vx * vx, nr = ar_num * ar_num + vx * vx;
+    const T dFyf_dvx = kf * af_num / nf;
+    const T dFyf_dvy = kf * (-vx / nf);
+    const T dFyf_dr = kf * (-lf * vx) / nf;
+    const T dFyf_dst = kf;
+    const T dFyr_dvx = kr * ar_num / nr;
+    const T dFyr_dvy = kr * (-vx) / nr;
+    const T dFyr_dr = kr * (lr * vx) / nr;
+    // :273-292 Jacobians
+    out.A(0, 2, -vx * sy - vy * cy); out.A(0, 3, cy); out.A(0, 4, -sy);
+    out.A(1, 2, -vy * sy + vx * cy); out.A(1, 3, sy); out.A(1, 4, cy);
+    out.A(2, 5, T(1.));
+    out.A(3, 3, 1 / m * (dFxf_dvx * cs - dFyf_dvx * ss));
+    out.A(3, 4, 1 / m * (-dFyf_dvy * ss + m * r));
+    out.A(3, 5, 1 / m * (-dFyf_dr * ss + m * vy));
+    out.A(4, 3, 1 / m * (dFxf_dvx * ss + dFyr_dvx + dFyf_dvx * cs - m * r));
+    out.A(4, 4, 1 / m * (dFyr_dvy + dFyf_dvy * cs));
+    out.A(4, 5, 1 / m * (dFyr_dr + dFyf_dr * cs - m * vx));
+    out.A(5, 3, 1 / Iz * (dFxf_dvx * lf * ss + dFyf_dvx * lf * cs - dFyr_dvx * lr));
+    out.A(5, 4, 1 / Iz * (dFyf_dvy * lf * cs - dFyr_dvy * lr));
+    out.A(5, 5, 1 / Iz * (dFyf_dr * lf * cs - dFyr_dr * lr));
+    out.B(3, 0, 1 / m * (-t.Fx * ss - dFyf_dst * ss - t.Fyf * cs));
+    out.B(3, 1, 1 / m * (dFxf_daccel * cs));
+    out.B(4, 0, 1 / m * (t.Fx * cs + dFyf_dst * cs - t.Fyf * ss));
+    out.B(4, 1, 1 / m * (dFxf_daccel * ss));
+    out.B(5, 0, 1 / Iz * (t.Fx * lf * cs + dFyf_dst * lf * cs - t.Fyf * lf * ss));
+    out.B(5, 1, 1 / Iz * (dFxf_daccel * lf * ss));
 }
 
 // get_dynamics_model for one (x, u): Ad = I + dt Ac, Bd = dt Bc, gd = dt (f - Ac x - Bc u)
@@ -130,46 +265,14 @@ __device__ void linearise_one(const VehicleK& k, const double* xin, const double
     for (int i = 0; i < 6; ++i) x[i] = xin[i];
     u[0] = uin[0]; u[1] = uin[1];
     low_speed_guard(x, u);
-    const Tyre t = tyre_forces(k, x, u);
-    double f[6];
-    dynamics(k, x, u, t, f);
-    const double yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
-    const double m = k.m, Iz = k.Iz, lf = k.lf, lr = k.lr;
-    const double cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
-    // :251-270 tyre-force derivatives
-    const double dFxf_dvx = -k.cda * vx;
-    const double dFxf_daccel = m;
-    const double kf = (k.Bf * k.Cf * k.Df * cos(k.Cf * atan(k.Bf * t.af))) / (1 + k.Bf * k.Bf * t.af * t.af);
-    const double kr = (k.Br * k.Cr * k.Dr * cos(k.Cr * atan(k.Br * t.ar))) / (1 + k.Br * k.Br * t.ar * t.ar);
-    const double af_num = lf * r + vy, ar_num = -lr * r + vy;
-    const double nf = af_num * af_num + vx * vx, nr = ar_num * ar_num + vx * vx;
-    const double dFyf_dvx = kf * af_num / nf;
-    const double dFyf_dvy = kf * (-vx / nf);
-    const double dFyf_dr = kf * (-lf * vx) / nf;
-    const double dFyf_dst = kf;
-    const double dFyr_dvx = kr * ar_num / nr;
-    const double dFyr_dvy = kr * (-vx) / nr;
-    const double dFyr_dr = kr * (lr * vx) / nr;
-    // :273-292 Jacobians
-    double Ac[36] = {0.0}, Bc[12] = {0.0};
-    Ac[0 * 6 + 2] = -vx * sy - vy * cy; Ac[0 * 6 + 3] = cy; Ac[0 * 6 + 4] = -sy;
-    Ac[1 * 6 + 2] = -vy * sy + vx * cy; Ac[1 * 6 + 3] = sy; Ac[1 * 6 + 4] = cy;
-    Ac[2 * 6 + 5] = 1.;
-    Ac[3 * 6 + 3] = 1 / m * (dFxf_dvx * cs - dFyf_dvx * ss);
-    Ac[3 * 6 + 4] = 1 / m * (-dFyf_dvy * ss + m * r);
-    Ac[3 * 6 + 5] = 1 / m * (-dFyf_dr * ss + m * vy);
-    Ac[4 * 6 + 3] = 1 / m * (dFxf_dvx * ss + dFyr_dvx + dFyf_dvx * cs - m * r);
-    Ac[4 * 6 + 4] = 1 / m * (dFyr_dvy + dFyf_dvy * cs);
-    Ac[4 * 6 + 5] = 1 / m * (dFyr_dr + dFyf_dr * cs - m * vx);
-    Ac[5 * 6 + 3] = 1 / Iz * (dFxf_dvx * lf * ss + dFyf_dvx * lf * cs - dFyr_dvx * lr);
-    Ac[5 * 6 + 4] = 1 / Iz * (dFyf_dvy * lf * cs - dFyr_dvy * lr);
-    Ac[5 * 6 + 5] = 1 / Iz * (dFyf_dr * lf * cs - dFyr_dr * lr);
-    Bc[3 * 2 + 0] = 1 / m * (-t.Fx * ss - dFyf_dst * ss - t.Fyf * cs);
-    Bc[3 * 2 + 1] = 1 / m * (dFxf_daccel * cs);
-    Bc[4 * 2 + 0] = 1 / m * (t.Fx * cs + dFyf_dst * cs - t.Fyf * ss);
-    Bc[4 * 2 + 1] = 1 / m * (dFxf_daccel * ss);
-    Bc[5 * 2 + 0] = 1 / Iz * (t.Fx * lf * cs + dFyf_dst * lf * cs - t.Fyf * lf * ss);
-    Bc[5 * 2 + 1] = 1 / Iz * (dFxf_daccel * lf * ss);
+    double f[6], Ac[36] = {0.0}, Bc[12] = {0.0};
+    struct {
+        double *f, *Ac, *Bc;
+        __device__ void F(int i, double v) { f[i] = v; }
+        __device__ void A(int i, int j, double v) { Ac[i * 6 + j] = v; }
+        __device__ void B(int i, int j, double v) { Bc[i * 2 + j] = v; }
+    } store = {f, Ac, Bc};
+    continuous_model(k, x, u, store);
     // :294, :318-324
     for (int i = 0; i < 6; ++i) {
         double ax = 0.0;
@@ -189,7 +292,7 @@ __device__ void euler_step(const VehicleK& k, const double* xin, const double* u
     for (int i = 0; i < 6; ++i) x[i] = xin[i];
     u[0] = uin[0]; u[1] = uin[1];
     low_speed_guard(x, u);
-    const Tyre t = tyre_forces(k, x, u);
+    const Tyre<double> t = tyre_forces<double>(k, x, u);
     double f[6];
     dynamics(k, x, u, t, f);
     for (int i = 0; i < 6; ++i) xn[i] = x[i] + f[i] * k.dt;
@@ -547,6 +650,73 @@ __global__ __launch_bounds__(256) void k_kin_linearise_vjp(mpcqp_kin_vehicle k, 
     if (gu) {
         gu[t * 2 + 0] = dt / wb * (a32 * sec2 + v * (b30 * dsec2 - g3 * (sec2 + st * dsec2)));
         gu[t * 2 + 1] = 0.0;
+    }
+}
+
+// What k_linearise_vjp does with each value of continuous_model, a Dual: its tangent goes into the
+// sum g[] with the weight of everything the forward made of it,
+//   Ad_ij = delta_ij + dt Ac_ij,  Bd_ij = dt Bc_ij,  gd_i = dt (f_i - sum_j Ac_ij x_j - sum_j Bc_ij u_j),
+// so nothing but g[], the point and the cotangents of one row stays live.
+struct VjpFold {
+    const Dual *x, *u;
+    const double *gAd, *gBd;  // this thread's 36 / 12, or null
+    double ggd[6], dt;
+    double g[Dual::ND];
+    __device__ void fold(const Dual& o, double c) {
+        for (int q = 0; q < Dual::ND; ++q) g[q] += c * o.d[q];
+    }
+    __device__ void F(int i, const Dual& v) { fold(v, ggd[i] * dt); }
+    __device__ void A(int i, int j, const Dual& v) {
+        if (gAd) fold(v, gAd[i * 6 + j] * dt);
+        fold(v * x[j], -(ggd[i] * dt));
+    }
+    __device__ void B(int i, int j, const Dual& v) {
+        if (gBd) fold(v, gBd[i * 2 + j] * dt);
+        fold(v * u[j], -(ggd[i] * dt));
+    }
+};
+
+// VJP of linearise_one(const VehicleK&, ...) per (vehicle, stage), of the forward as it is
+// written: the low-speed guard first (what it replaces by a constant carries no derivative), then
+// continuous_model over forward-mode duals in (yaw, vx, vy, r, steer, accel), each output's
+// tangent contracted with its cotangent as soon as it exists.  Outputs dense (B, N, 6) / (B, N, 2).
+__global__ __launch_bounds__(256) void k_linearise_vjp(VehicleK k, long B, int N, const double* __restrict__ x,
+                                                       long x_sb, long x_sk, const double* __restrict__ u, long u_sb,
+                                                       long u_sk, const double* __restrict__ gAd,
+                                                       const double* __restrict__ gBd, const double* __restrict__ ggd,
+                                                       double* __restrict__ gx, double* __restrict__ gu) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * N) return;
+    const long b = t / N, s = t - b * N;
+    const double* xin = x + b * x_sb + s * x_sk;
+    const double* uin = u + b * u_sb + s * u_sk;
+    double xg[6], ug[2];
+    for (int i = 0; i < 6; ++i) xg[i] = xin[i];
+    ug[0] = uin[0]; ug[1] = uin[1];
+    const double vx_in = xg[3];
+    low_speed_guard(xg, ug);
+    // the guard's two regions: |vx| < 0.5 replaces vy, r, steer; |vx| < 0.3 replaces vx as well
+    const bool lat = !(vx_in > -0.5 && vx_in < 0.5), lon = !(vx_in > -0.3 && vx_in < 0.3);
+    const Dual xd[6] = {Dual(xg[0]),          Dual(xg[1]),         Dual(xg[2], 0, true),
+                        Dual(xg[3], 1, lon), Dual(xg[4], 2, lat), Dual(xg[5], 3, lat)};
+    const Dual ud[2] = {Dual(ug[0], 4, lat), Dual(ug[1], 5, true)};
+    VjpFold out = {xd, ud, gAd ? gAd + t * 36 : nullptr, gBd ? gBd + t * 12 : nullptr};
+    for (int i = 0; i < 6; ++i) out.ggd[i] = ggd ? ggd[t * 6 + i] : 0.0;
+    out.dt = k.dt;
+    for (int q = 0; q < Dual::ND; ++q) out.g[q] = 0.0;
+    continuous_model(k, xd, ud, out);
+    const double* g = out.g;
+    if (gx) {
+        gx[t * 6 + 0] = 0.0;
+        gx[t * 6 + 1] = 0.0;
+        gx[t * 6 + 2] = g[0];
+        gx[t * 6 + 3] = lon ? g[1] : 0.0;
+        gx[t * 6 + 4] = lat ? g[2] : 0.0;
+        gx[t * 6 + 5] = lat ? g[3] : 0.0;
+    }
+    if (gu) {
+        gu[t * 2 + 0] = lat ? g[4] : 0.0;
+        gu[t * 2 + 1] = g[5];
     }
 }
 
@@ -1555,6 +1725,16 @@ int mpcqp_kin_linearise_vjp_device(const mpcqp_kin_vehicle* veh, int64_t B, int3
     if (B == 0 || (!dgx && !dgu)) return 0;
     return launch(device, stream, B * N, 256, k_kin_linearise_vjp, *veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd,
                   dgBd, dggd, dgx, dgu);
+}
+
+int mpcqp_linearise_vjp_device(const mpcqp_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                               int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                               const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
+                               void* stream) {
+    if (!veh || !dx || !du || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "linearise_vjp: bad arguments");
+    if (B == 0 || (!dgx && !dgu)) return 0;
+    return launch(device, stream, B * N, 256, k_linearise_vjp, vehicle_constants(*veh), B, N, dx, x_sb, x_sk, du, u_sb,
+                  u_sk, dgAd, dgBd, dggd, dgx, dgu);
 }
 
 void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {

@@ -492,6 +492,159 @@ def linearise_kinematics_vjp(l_f, l_r, dt, x, u, gAd, gBd, ggd):
     return gx, gu
 
 
+class _Dual:
+    """mpc_device.hip's Dual in numpy: a value v (...) and its tangent d (..., 6) in
+    (yaw, vx, vy, r, steer, accel), with that struct's rules, operation by operation."""
+    __array_ufunc__ = None  # ndarray op _Dual -> _Dual's reflected operator
+
+    def __init__(self, v, d):
+        self.v, self.d = v, d
+
+    @staticmethod
+    def input(v, slot, live):
+        d = np.zeros(v.shape + (6,))
+        d[..., slot] = np.where(live, 1.0, 0.0)
+        return _Dual(v, d)
+
+    def __neg__(self):
+        return _Dual(-self.v, -self.d)
+
+    def __add__(self, o):
+        return _Dual(self.v + o.v, self.d + o.d) if isinstance(o, _Dual) else _Dual(self.v + o, self.d)
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        return _Dual(self.v - o.v, self.d - o.d) if isinstance(o, _Dual) else _Dual(self.v - o, self.d)
+
+    def __mul__(self, o):
+        if isinstance(o, _Dual):
+            return _Dual(self.v * o.v, self.d * o.v[..., None] + self.v[..., None] * o.d)
+        return _Dual(self.v * o, self.d * (o[..., None] if isinstance(o, np.ndarray) else o))
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        q = self.v / o.v
+        return _Dual(q, (self.d - q[..., None] * o.d) / o.v[..., None])
+
+    def chain(self, v, dv):
+        return _Dual(v, dv[..., None] * self.d)
+
+    def sin(self):
+        return self.chain(np.sin(self.v), np.cos(self.v))
+
+    def cos(self):
+        return self.chain(np.cos(self.v), -np.sin(self.v))
+
+    def atan(self):
+        return self.chain(np.arctan(self.v), 1.0 / (1.0 + self.v * self.v))
+
+    @staticmethod
+    def atan2(y, x):
+        n = x.v * x.v + y.v * y.v
+        return _Dual(np.arctan2(y.v, x.v), (x.v[..., None] * y.d - y.v[..., None] * x.d) / n[..., None])
+
+
+def linearise_dynamics_vjp(veh: VehicleParams, x, u, gAd=None, gBd=None, ggd=None):
+    """The VJP of linearise_dynamics in the order of mpc_device.hip's k_linearise_vjp: x (..., 6),
+    u (..., 2), cotangents gAd (..., 6, 6), gBd (..., 6, 2), ggd (..., 6) (None = zero) -> gx
+    (..., 6), gu (..., 2).
+
+    It differentiates the forward AS IT COMPUTES: the low-speed guard first (what it replaces by
+    a constant carries no derivative: vy, r, steer for |vx| < 0.5, vx too for |vx| < 0.3), then
+    f, Ac, Bc of get_dynamics_model over forward-mode duals in (yaw, vx, vy, r, steer, accel),
+    each value's tangent taken with the weight of what the forward makes of it:
+    Ad = I + dt Ac, Bd = dt Bc, gd = dt (f - Ac x - Bc u).  The reference's Ac is not everywhere
+    the derivative of its f (dFx/dvx = -cda vx against -0.5 cda vx^2 sgn(vx)), so nothing cancels
+    in gd; sgn(vx) has derivative 0.  X and Y never enter."""
+    x, u = np.array(x, float, copy=True), np.array(u, float, copy=True)
+    lead = x.shape[:-1]
+    x, u = x.reshape(-1, 6), u.reshape(-1, 2)
+    shape = x.shape[:-1]
+    zero = lambda g, tail: np.zeros(shape + tail) if g is None else np.asarray(g, float).reshape(shape + tail)
+    gAd, gBd, ggd = zero(gAd, (6, 6)), zero(gBd, (6, 2)), zero(ggd, (6,))
+    vx_in = x[..., 3].copy()
+    g1 = (vx_in >= 0) & (vx_in < 0.5)
+    g2 = (vx_in > -0.5) & (vx_in < 0)
+    gd_ = g1 | g2
+    x[gd_, 4] = 0.0; x[gd_, 5] = 0.0; u[gd_, 0] = 0.0
+    x[g1 & (vx_in < 0.3), 3] = 0.3
+    x[g2 & (vx_in > -0.3), 3] = -0.3
+    lat = ~((vx_in > -0.5) & (vx_in < 0.5))
+    lon = ~((vx_in > -0.3) & (vx_in < 0.3))
+    const = lambda v: _Dual(v, np.zeros(v.shape + (6,)))
+    xd = [const(x[..., 0]), const(x[..., 1]), _Dual.input(x[..., 2], 0, True), _Dual.input(x[..., 3], 1, lon),
+          _Dual.input(x[..., 4], 2, lat), _Dual.input(x[..., 5], 3, lat)]
+    ud = [_Dual.input(u[..., 0], 4, lat), _Dual.input(u[..., 1], 5, True)]
+    (Bf, Cf, Df), (Br, Cr, Dr) = veh.pacejka()
+    m, Iz, lf, lr, dt = veh.m, veh.Iz, veh.l_f, veh.l_r, veh.dt
+    cda, roll = veh.roh * veh.C_d * veh.A_f, veh.C_roll * m * 9.81
+    yaw, vx, vy, r = xd[2:]
+    st, acc = ud
+    # tyre_forces
+    af = -_Dual.atan2(lf * r + vy, vx) + st
+    ar = -_Dual.atan2(-lr * r + vy, vx)
+    Fyf = Df * (Cf * (Bf * af).atan()).sin()
+    Fyr = Dr * (Cr * (Br * ar).atan()).sin()
+    sg = np.sign(vx.v)
+    Fx = m * acc - 0.5 * cda * vx * vx * sg - roll * sg
+    # dynamics
+    cy, sy, cs, ss = yaw.cos(), yaw.sin(), st.cos(), st.sin()
+    f = [vx * cy - vy * sy, vy * cy + vx * sy, r,
+         1. / m * (Fx * cs - Fyf * ss + m * vy * r),
+         1. / m * (Fx * ss + Fyr + Fyf * cs - m * vx * r),
+         1. / Iz * (Fx * lf * ss + Fyf * lf * cs - Fyr * lr)]
+    # continuous_model
+    dFx_dvx = -cda * vx
+    dFx_da = m
+    kf = (Bf * Cf * Df * (Cf * (Bf * af).atan()).cos()) / (1 + Bf * Bf * af * af)
+    kr = (Br * Cr * Dr * (Cr * (Br * ar).atan()).cos()) / (1 + Br * Br * ar * ar)
+    af_num, ar_num = lf * r + vy, -lr * r + vy
+    nf, nr = af_num * af_num + vx * vx, ar_num * ar_num + vx * vx
+    dFyf_dvx = kf * af_num / nf
+    dFyf_dvy = kf * (-vx / nf)
+    dFyf_dr = kf * (-lf * vx) / nf
+    dFyf_dst = kf
+    dFyr_dvx = kr * ar_num / nr
+    dFyr_dvy = kr * (-vx) / nr
+    dFyr_dr = kr * (lr * vx) / nr
+    one = const(np.ones(shape))
+    Ac = {(0, 2): -vx * sy - vy * cy, (0, 3): cy, (0, 4): -sy,
+          (1, 2): -vy * sy + vx * cy, (1, 3): sy, (1, 4): cy,
+          (2, 5): one,
+          (3, 3): 1 / m * (dFx_dvx * cs - dFyf_dvx * ss),
+          (3, 4): 1 / m * (-dFyf_dvy * ss + m * r),
+          (3, 5): 1 / m * (-dFyf_dr * ss + m * vy),
+          (4, 3): 1 / m * (dFx_dvx * ss + dFyr_dvx + dFyf_dvx * cs - m * r),
+          (4, 4): 1 / m * (dFyr_dvy + dFyf_dvy * cs),
+          (4, 5): 1 / m * (dFyr_dr + dFyf_dr * cs - m * vx),
+          (5, 3): 1 / Iz * (dFx_dvx * lf * ss + dFyf_dvx * lf * cs - dFyr_dvx * lr),
+          (5, 4): 1 / Iz * (dFyf_dvy * lf * cs - dFyr_dvy * lr),
+          (5, 5): 1 / Iz * (dFyf_dr * lf * cs - dFyr_dr * lr)}
+    Bc = {(3, 0): 1 / m * (-Fx * ss - dFyf_dst * ss - Fyf * cs), (3, 1): 1 / m * (dFx_da * cs),
+          (4, 0): 1 / m * (Fx * cs + dFyf_dst * cs - Fyf * ss), (4, 1): 1 / m * (dFx_da * ss),
+          (5, 0): 1 / Iz * (Fx * lf * cs + dFyf_dst * lf * cs - Fyf * lf * ss), (5, 1): 1 / Iz * (dFx_da * lf * ss)}
+    # VjpFold: F, then A, then B, as continuous_model emits them
+    g = np.zeros(shape + (6,))
+    for i in range(6):
+        g += (ggd[..., i] * dt)[..., None] * f[i].d
+    for (i, j), v in Ac.items():
+        g += (gAd[..., i, j] * dt)[..., None] * v.d
+        g += (-(ggd[..., i] * dt))[..., None] * (v * xd[j]).d
+    for (i, j), v in Bc.items():
+        g += (gBd[..., i, j] * dt)[..., None] * v.d
+        g += (-(ggd[..., i] * dt))[..., None] * (v * ud[j]).d
+    gx, gu = np.zeros(shape + (6,)), np.zeros(shape + (2,))
+    gx[..., 2] = g[..., 0]
+    gx[..., 3] = np.where(lon, g[..., 1], 0.0)
+    gx[..., 4] = np.where(lat, g[..., 2], 0.0)
+    gx[..., 5] = np.where(lat, g[..., 3], 0.0)
+    gu[..., 0] = np.where(lat, g[..., 4], 0.0)
+    gu[..., 1] = g[..., 5]
+    return gx.reshape(lead + (6,)), gu.reshape(lead + (2,))
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),

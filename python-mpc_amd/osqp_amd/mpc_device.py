@@ -112,6 +112,8 @@ def _bind():
     L.mpcqp_affine_vjp_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp]
     L.mpcqp_kin_linearise_vjp_device.argtypes = [_P(KinVehicle), i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp,
                                                  vp, i32, vp]
+    L.mpcqp_linearise_vjp_device.argtypes = [_P(Vehicle), i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32,
+                                             vp]
     L._mpc_bound = True
     return L
 
@@ -163,6 +165,53 @@ def linearise(veh: Vehicle, x, u, device=0):
     (N axis dropped for 2-D inputs).  Inputs are not modified (the reference's
     low-speed guard writes into the caller's view; here it acts on copies)."""
     return _linearise("linearise", veh, x, u, 6)
+
+
+def _linearise_vjp(symbol, veh, x, u, gAd, gBd, ggd, nx, out=None):
+    """linearise_vjp / linearise_kinematics_vjp: the model's C entry point on (B, N, nx) states."""
+    import torch
+    L = _bind()
+    squeeze = x.dim() == 2
+    if squeeze:
+        x, u = x[:, None, :], u[:, None, :]
+    B, N = x.shape[0], x.shape[1]
+    if x.shape[2] != nx or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
+        raise ValueError(f"x must be (B, N, {nx}) and u (B, N, 2)")
+    if x.dtype != torch.float64 or u.dtype != torch.float64:
+        raise ValueError("x and u must be float64")
+    if x.stride(2) != 1 or u.stride(2) != 1:
+        raise ValueError("the state / input axis must be contiguous")
+    for t, tail in ((gAd, (nx, nx)), (gBd, (nx, 2)), (ggd, (nx,))):
+        if t is not None and (t.numel() != B * N * int(np.prod(tail)) or tuple(t.shape[-len(tail):]) != tail or
+                              t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"cotangents must be contiguous float64 (B, N, {nx}, {nx}), (B, N, {nx}, 2), "
+                             f"(B, N, {nx}) tensors")
+    kw = dict(dtype=torch.float64, device=x.device)
+    if out is None:
+        gx = torch.empty((B, N, nx), **kw); gu = torch.empty((B, N, 2), **kw)
+    else:
+        gx, gu = out
+        for t, w in ((gx, nx), (gu, 2)):
+            if tuple(t.shape) != (B, N, w) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != x.device:
+                raise ValueError(f"out must be contiguous float64 (B, N, {nx}) and (B, N, 2) tensors on x's device")
+    _check(getattr(L, f"mpcqp_{symbol}_device")(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u),
+                                                u.stride(0), u.stride(1), _po(gAd), _po(gBd), _po(ggd), _p(gx), _p(gu),
+                                                x.device.index or 0, _stream(torch, x.device)), symbol)
+    if squeeze:
+        return gx[:, 0], gu[:, 0]
+    return gx, gu
+
+
+def linearise_vjp(veh: Vehicle, x, u, gAd, gBd, ggd, out=None):
+    """The VJP of linearise (mpcqp_linearise_vjp_device): x (B, N, 6) or (B, 6), u (B, N, 2) or
+    (B, 2) as the forward took them (any strides with a contiguous last dimension -- a stage stride
+    of 0 included), cotangents gAd (B, N, 6, 6), gBd (B, N, 6, 2), ggd (B, N, 6) contiguous float64
+    device tensors, None = zero -> dense gx (B, N, 6), gu (B, N, 2) (N axis dropped for 2-D
+    inputs).  It differentiates the forward as it computes, the low-speed guard included: X and Y
+    carry no derivative, vy, r and steer none for |vx| < 0.5 and vx none for |vx| < 0.3
+    (include/mpcqp.h).  A caller whose stages share one (x, u) sums over the stage axis.
+    ``out`` = (gx, gu): contiguous (B, N, 6) / (B, N, 2) tensors to write into."""
+    return _linearise_vjp("linearise_vjp", veh, x, u, gAd, gBd, ggd, 6, out)
 
 
 class _Layout:
@@ -724,28 +773,7 @@ def linearise_kinematics_vjp(veh: KinVehicle, x, u, gAd, gBd, ggd):
     gAd (B, N, 4, 4), gBd (B, N, 4, 2), ggd (B, N, 4) contiguous float64 device tensors, None =
     zero -> dense gx (B, N, 4), gu (B, N, 2) (N axis dropped for 2-D inputs).  Only v, yaw and
     steer carry derivative; a caller whose stages share one (x, u) sums over the stage axis."""
-    import torch
-    L = _bind()
-    squeeze = x.dim() == 2
-    if squeeze:
-        x, u = x[:, None, :], u[:, None, :]
-    B, N = x.shape[0], x.shape[1]
-    if x.shape[2] != 4 or u.shape[2] != 2 or u.shape[:2] != x.shape[:2]:
-        raise ValueError("x must be (B, N, 4) and u (B, N, 2)")
-    if x.stride(2) != 1 or u.stride(2) != 1:
-        raise ValueError("the state / input axis must be contiguous")
-    for t, tail in ((gAd, (4, 4)), (gBd, (4, 2)), (ggd, (4,))):
-        if t is not None and (t.numel() != B * N * int(np.prod(tail)) or tuple(t.shape[-len(tail):]) != tail or
-                              t.dtype != torch.float64 or not t.is_contiguous()):
-            raise ValueError("cotangents must be contiguous float64 (B, N, 4, 4), (B, N, 4, 2), (B, N, 4) tensors")
-    kw = dict(dtype=torch.float64, device=x.device)
-    gx = torch.empty((B, N, 4), **kw); gu = torch.empty((B, N, 2), **kw)
-    _check(L.mpcqp_kin_linearise_vjp_device(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0),
-                                            u.stride(1), _po(gAd), _po(gBd), _po(ggd), _p(gx), _p(gu),
-                                            x.device.index or 0, _stream(torch, x.device)), "kin_linearise_vjp")
-    if squeeze:
-        return gx[:, 0], gu[:, 0]
-    return gx, gu
+    return _linearise_vjp("kin_linearise_vjp", veh, x, u, gAd, gBd, ggd, 4)
 
 
 def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):

@@ -7,6 +7,7 @@ here is a ``torch.autograd.Function`` over one forward entry point and its VJP (
 DESIGN.md §15):
 
   linearise_kinematics(veh, x, u)                       -> Ad, Bd, gd
+  linearise_dynamics(veh, x, u)                         -> Ad, Bd, gd
   ltv_assemble(layout, Ad, Bd, gd, x0, Xr, ...)         -> Ax, q, l, u [, Px]
   incr_assemble(layout, Ad, Bd, gd, xt0, Xr, ...)       -> Ax, q, l, u [, Px]
   affine_assemble(assembler, theta, regime)             -> q, l, u
@@ -14,15 +15,18 @@ DESIGN.md §15):
 and ``MPCLayer`` composes the assembly with one ``QPLayer``: (Ad, Bd, gd, x0, Xr[, weights]) ->
 (X, U, y), so that d u_0 / d x0 and d loss / d Q are one backward call on the device.  Every call
 runs on torch's current stream (the QP solve on the layer's own, ordered with it, as QPLayer does).
-Gradients are formed only for the inputs that require them.  The dynamic bicycle's linearisation
-has no VJP: a layer over it differentiates what is downstream of its (Ad, Bd, gd).
+Gradients are formed only for the inputs that require them.
+
+With ``linearise_dynamics`` the closed loop of mpc_dynamics.main is differentiable end to end: its
+plant step is Ad_0 x + Bd_0 u + gd_0 and its shift copies stages of the solution, both plain torch
+operations between one MPCLayer per control step.
 """
 from __future__ import annotations
 
 from . import mpc_device as md
 from .torch_qp import QPLayer
 
-__all__ = ["linearise_kinematics", "ltv_assemble", "incr_assemble", "affine_assemble", "MPCLayer"]
+__all__ = ["linearise_kinematics", "linearise_dynamics", "ltv_assemble", "incr_assemble", "affine_assemble", "MPCLayer"]
 
 _FN = None
 
@@ -39,21 +43,23 @@ def _functions():
     from types import SimpleNamespace
 
     class Linearise(torch.autograd.Function):
+        """inputs (model, veh, x, u); model = (forward, vjp) of mpc_device"""
+
         @staticmethod
-        def forward(ctx, veh, x, u):
-            ctx.veh = veh
+        def forward(ctx, model, veh, x, u):
+            ctx.vjp, ctx.veh = model[1], veh
             ctx.save_for_backward(x, u)
             ctx.set_materialize_grads(False)
-            return md.linearise_kinematics(veh, x.detach(), u.detach())
+            return model[0](veh, x.detach(), u.detach())
 
         @staticmethod
         def backward(ctx, gAd, gBd, ggd):
             x, u = ctx.saved_tensors
             if gAd is None and gBd is None and ggd is None:
-                return None, None, None
-            gx, gu = md.linearise_kinematics_vjp(ctx.veh, x.detach(), u.detach(), _c(gAd), _c(gBd), _c(ggd))
+                return None, None, None, None
+            gx, gu = ctx.vjp(ctx.veh, x.detach(), u.detach(), _c(gAd), _c(gBd), _c(ggd))
             need = ctx.needs_input_grad
-            return None, gx if need[1] else None, gu if need[2] else None
+            return None, None, gx if need[2] else None, gu if need[3] else None
 
     class Assemble(torch.autograd.Function):
         """inputs (layout, Ad, Bd, gd, x0, Xr, xlo, xhi, Q, QN, R, use_w)"""
@@ -118,7 +124,15 @@ def _functions():
 def linearise_kinematics(veh, x, u):
     """mpc_device.linearise_kinematics, differentiable in x and u (3-D (B, N, 4) / (B, N, 2), any
     strides with a contiguous last axis: an ``expand`` over the stages gets the stage sum)."""
-    return _functions().Linearise.apply(veh, x, u)
+    return _functions().Linearise.apply((md.linearise_kinematics, md.linearise_kinematics_vjp), veh, x, u)
+
+
+def linearise_dynamics(veh, x, u):
+    """mpc_device.linearise (the dynamic bicycle: Pacejka tyres, the low-speed guard), differentiable
+    in x and u (3-D (B, N, 6) / (B, N, 2) or 2-D, any strides with a contiguous last axis: an
+    ``expand`` over the stages gets the stage sum).  The gradient is that of the forward as it
+    computes (mpc_device.linearise_vjp): zero in X, Y and in what the guard replaced."""
+    return _functions().Linearise.apply((md.linearise, md.linearise_vjp), veh, x, u)
 
 
 def _split_weights(weights):
