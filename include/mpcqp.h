@@ -245,6 +245,31 @@ int mpcqp_adjoint_device(mpcqp_handle *h, int32_t nrhs, const double *dgx, const
 int mpcqp_adjoint_batch(mpcqp_handle *h, int32_t nrhs, const double *gx, const double *gy, double *rx, double *ry,
                         double *gq, double *gl, double *gu, double *gPx, double *gAx, int8_t *act, double *ares,
                         int32_t *astat);
+/* The solution record: everything mpcqp_adjoint_* reads of a finished solve that a
+ * setup does not rebuild.  n + 2m + 1 doubles per instance: the workspace's scaled iterates x~ (by
+ * variable), z~, y~ and the status, exactly as mpcqp_adjoint_* reads them.  Opaque; meaningful only
+ * to a handle of the same pattern whose current setup took the same data and settings the saving
+ * one had (setup rebuilds the scaled data, D, E and c bit for bit from them).  Then
+ *     mpcqp_setup_device(data); mpcqp_load_solution_device(record); mpcqp_adjoint_device(...)
+ * returns, bit for bit, what the adjoint call right after the original solve returned -- act, ares
+ * and astat included --, whatever the handle set up and solved in between: T differentiated solves
+ * need one workspace and T records, not T workspaces.
+ * save: one kernel on `stream`; needs a solve on the current setup (MPCQP_EINVAL as
+ *   mpcqp_adjoint_device: no solve since the last setup, or the workspace state is gone in one-shot
+ *   mode; also a NULL record).  A handle on an eliminated plan moves to the plain plan first, as
+ *   under mpcqp_adjoint_device, so the record does not depend on the plan the solve ran on.
+ * load: one kernel on `stream`; needs some setup on the handle (MPCQP_EINVAL before the first one,
+ *   after a one-shot setup, for a NULL record) and makes the same plan move.  It writes the
+ *   iterates and the statuses and marks the handle solved, so a following mpcqp_adjoint_* is
+ *   defined; it touches nothing else: not the scaled data, not an instance's rho, not the info
+ *   (obj, residuals, iteration counts, polish status, certificates stay those of the handle's last
+ *   solve or setup).
+ * A solve after a load is an ordinary solve of the current setup: with settings.warm_start on it
+ * starts from the loaded x~, z~, y~ -- as after mpcqp_warm_start_device, but z~ is the record's
+ * rather than A~ x~ -- at the rho the setup left (not the one the recorded solve had adapted to);
+ * with warm_start off it starts from zero, as always.  It overwrites the loaded status. */
+int mpcqp_save_solution_device(mpcqp_handle *h, double *drecord, void *stream);
+int mpcqp_load_solution_device(mpcqp_handle *h, const double *drecord, void *stream);
 /* LTI batches ("LTI shared-matrix mode"): with shared != 0 the following
  * mpcqp_setup_device / mpcqp_setup_solve_device calls read ONE Px[nnzP] and ONE Ax[nnzA]
  * for every instance of the batch instead of B copies (the lateral MPC's P and A do not
@@ -409,6 +434,25 @@ int mpcqp_reference_search_device(int64_t B, int32_t N, int32_t nxa, int32_t npa
 int mpcqp_incr_shift_device(const mpcqp_incr_layout *L, const mpcqp_vehicle *veh, int64_t B, const double *dsol,
                             const double *dAd, const double *dBd, const double *dgd, double *dxt, double *dpred,
                             double *dpdu, void *stream);
+/* The transpose of mpcqp_incr_shift_device as it computes: cotangents dgxt[b*8],
+ * dgpred[b*(N+1)*8], dgpdu[b*(N+1)*2] of the NEW xt, pred, pred_du (each may be NULL = zero) ->
+ * dgsol[b*n], the stage-0 model's dgAd0[b*36], dgBd0[b*12], dggd0[b*6] (the caller adds them into
+ * stage 0 of the linearisation's cotangents) and dgxt_before[b*8]; a NULL output is not written.
+ * dsol, dAd, dBd as the forward took them (stage 0 of dAd / dBd is read; dgd is not read -- the step
+ * is affine in it -- and may be NULL); dxt_before is x~ from BEFORE the step, which the forward
+ * overwrote.  The plant step is bilinear; the shift is copies, and where the forward wrote one
+ * source twice (pred_du[N-1] and [N]; the inputs of pred[N-1] and [N]) the cotangents add; the
+ * terminal state is differentiated as mpcqp_linearise_vjp_device differentiates the linearisation:
+ * the low-speed guard first (vy, r, steer carry nothing for |vx| < 0.5, vx nothing for |vx| < 0.3,
+ * exactly), then the Euler step of the same tyre and dynamics functions over forward-mode duals;
+ * sgn(vx) has derivative 0.  One writer per output element, no atomics: a repeated call returns
+ * the same bits.  MPCQP_EINVAL "incr_shift_vjp: bad arguments" (a NULL layout, vehicle, dsol, dAd,
+ * dBd or dxt_before, B < 0) and MPCQP_EUNSUPPORTED (a layout that is not nx 6, nu 2) before any
+ * device call. */
+int mpcqp_incr_shift_vjp_device(const mpcqp_incr_layout *L, const mpcqp_vehicle *veh, int64_t B, const double *dsol,
+                                const double *dAd, const double *dBd, const double *dgd, const double *dxt_before,
+                                const double *dgxt, const double *dgpred, const double *dgpdu, double *dgsol,
+                                double *dgAd0, double *dgBd0, double *dggd0, double *dgxt_before, void *stream);
 /* F3 -- warm start for the next step (cfg 5): shift a solution of
  * the incremental layout one stage forward, x[b*n], y[b*m] -> xs[b*n], ys[b*m].
  * Variable blocks x~_0..x~_N | du_0..du_{N-1} and row blocks eq_0..eq_N |

@@ -132,6 +132,7 @@ struct mpcqp_handle {
     bool one_shot_lds = false;  // MPCQP_ONE_SHOT_LOOP=lds at creation: the one-shot cfg-2 kernel's GL 1 form (A/B)
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
     bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
+    bool has_setup = false;   // some setup has written the workspace (mpcqp_load_solution_device needs one)
 };
 
 namespace {
@@ -1035,6 +1036,7 @@ int mpcqp_setup_batch(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi
     strace().mark("inputs + setup launch");
     if (int e = check_setup(h)) { mpcqp_free(h); return e; }
     strace().mark("setup + convexity wait");
+    h->has_setup = true;
     *out = h;
     return 0;
 }
@@ -1431,6 +1433,7 @@ int mpcqp_setup_device(mpcqp_handle* h, const double* dPx, const double* dAx, co
         if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
     h->state_gone = false;
     h->solved = false;
+    h->has_setup = true;
     return stream_leave(s, st);
 }
 
@@ -1475,6 +1478,7 @@ int mpcqp_setup_warm_device(mpcqp_handle* h, const double* dPx, const double* dA
         if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
     h->state_gone = false;
     h->solved = false;
+    h->has_setup = true;
     s.kp.warm_start = 1;
     h->set.warm_start = 1;
     return stream_leave(s, st);
@@ -1530,6 +1534,7 @@ int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* d
     const bool one = h->one_shot && one_shot_form(k) > 0;
     HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? (h->one_shot_lds ? 2 : 1) : 0));
     h->state_gone = one;
+    h->has_setup = true;
     if (h->collect) {
         if (int e = ev_end(h->collect, h->ev_solve, st)) return e;
         h->last_pair = h->ev_solve.back();
@@ -1647,6 +1652,45 @@ int mpcqp_adjoint_batch(mpcqp_handle* h, int32_t nrhs, const double* gx, const d
         }
     release();
     return err;
+}
+
+// The solution record (mpcqp.h): what k_adjoint reads of a finished solve -- x~ by variable, z~, y~,
+// the status -- out of the workspace and back into it.  Both move a handle on an eliminated plan to
+// the plain plan first, as the adjoint does, so a record is the same whichever plan the solve ran on.
+int mpcqp_save_solution_device(mpcqp_handle* h, double* drecord, void* stream) {
+    const char* what = "mpcqp_save_solution_device";
+    if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
+    if (!drecord) return fail(MPCQP_EINVAL, "%s: NULL record", what);
+    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    if (int e = need_state(h, what)) return e;
+    if (!h->solved) return fail(MPCQP_EINVAL, "%s: no solve has run on this handle's setup yet", what);
+    if (h->plan->ne > 0)
+        if (int e = replan_plain(h)) return e;
+    Shard& s = h->shards[0];
+    hipStream_t st = pick(s, stream);
+    HIPCHK(hipSetDevice(s.dev));
+    if (int e = stream_enter(s, st)) return e;
+    HIPCHK(launch_save_solution(s.kp, s.B, drecord, st));
+    return stream_leave(s, st);
+}
+
+int mpcqp_load_solution_device(mpcqp_handle* h, const double* drecord, void* stream) {
+    const char* what = "mpcqp_load_solution_device";
+    if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
+    if (!drecord) return fail(MPCQP_EINVAL, "%s: NULL record", what);
+    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    if (int e = need_state(h, what)) return e;
+    if (!h->has_setup) return fail(MPCQP_EINVAL, "%s: no setup has run on this handle yet", what);
+    if (h->plan->ne > 0)
+        if (int e = replan_plain(h)) return e;
+    h->staged = false;  // (device work: the staged results of the last solve are stale)
+    Shard& s = h->shards[0];
+    hipStream_t st = pick(s, stream);
+    HIPCHK(hipSetDevice(s.dev));
+    if (int e = stream_enter(s, st)) return e;
+    HIPCHK(launch_load_solution(s.kp, s.B, drecord, st));
+    h->solved = true;
+    return stream_leave(s, st);
 }
 
 void* mpcqp_get_stream(const mpcqp_handle* h) {

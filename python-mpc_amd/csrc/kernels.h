@@ -206,6 +206,10 @@ struct AdjointIO {
     int* astat;                      // (B): 0 not run (status not solved), 1 every seed below 1e-8, -1
 };
 hipError_t launch_adjoint(const KParams& p, long B, const AdjointIO& io, hipStream_t st);
+// The solution record: per instance n + 2m + 1 doubles -- x~ by variable, z~, y~, the status --,
+// all k_adjoint reads of a finished solve.  One kernel each way, one thread per workspace element.
+hipError_t launch_save_solution(const KParams& p, long B, double* rec, hipStream_t st);
+hipError_t launch_load_solution(const KParams& p, long B, const double* rec, hipStream_t st);
 // one-wave-per-QP kernel (solve_wave.hip), variants 8 and 9
 hipError_t launch_solve_wave(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
                         KernelRef* ref = nullptr);

@@ -484,6 +484,49 @@ hipError_t launch_iota(int* order, long B, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------- solution record --
+// One thread per workspace element of the instance-major arrays x (npad per instance), z, y (m)
+// and status (1): consecutive threads on consecutive workspace addresses.  The record holds x by
+// variable (pad_var: padded column -> variable, -1 padding, which the record leaves out and a
+// load leaves as setup wrote it), then z, y and the status as a double.
+template <bool LOAD>
+__global__ __launch_bounds__(256) void k_solution_record(KParams p, long B, double* __restrict__ rec) {
+    const long npad = p.npad, m = p.m, n = p.n, per = npad + 2 * m + 1, W = n + 2 * m + 1;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= B * per) return;
+    const long b = t / per, k = t - b * per;
+    double* r = rec + b * W;
+    if (k < npad) {
+        const int j = p.pad_var[k];
+        if (j < 0) return;
+        if (LOAD) p.x[b * npad + k] = r[j];
+        else r[j] = p.x[b * npad + k];
+    } else if (k < npad + m) {
+        const long i = k - npad;
+        if (LOAD) p.z[b * m + i] = r[n + i];
+        else r[n + i] = p.z[b * m + i];
+    } else if (k < npad + 2 * m) {
+        const long i = k - npad - m;
+        if (LOAD) p.y[b * m + i] = r[n + m + i];
+        else r[n + m + i] = p.y[b * m + i];
+    } else {
+        if (LOAD) p.status[b] = (int)r[n + 2 * m];
+        else r[n + 2 * m] = (double)p.status[b];
+    }
+}
+template <bool LOAD>
+static hipError_t launch_solution_record(const KParams& p, long B, double* rec, hipStream_t st) {
+    const long total = B * ((long)p.npad + 2L * p.m + 1);
+    hipLaunchKernelGGL(k_solution_record<LOAD>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p, B, rec);
+    return hipGetLastError();
+}
+hipError_t launch_save_solution(const KParams& p, long B, double* rec, hipStream_t st) {
+    return launch_solution_record<false>(p, B, rec, st);
+}
+hipError_t launch_load_solution(const KParams& p, long B, const double* rec, hipStream_t st) {
+    return launch_solution_record<true>(p, B, const_cast<double*>(rec), st);
+}
+
 // ------------------------------------------------------------------ order --
 // Dispatch order for the next solve on this workspace: longest previous solve first.
 // A batch larger than the resident slots (cfg 2: 1024 instances, 512 two-wave

@@ -286,16 +286,21 @@ __device__ void linearise_one(const VehicleK& k, const double* xin, const double
 }
 
 // update_dynamics_model (vehicle_models.py:343-477): one explicit-Euler step of the
-// nonlinear model from the guarded state
-__device__ void euler_step(const VehicleK& k, const double* xin, const double* uin, double* xn) {
+// nonlinear model from the guarded state.  euler_step<T> starts at a GUARDED (x, u), as
+// continuous_model does: double for k_incr_shift, Dual for k_incr_shift_vjp.
+template <class T>
+__device__ __forceinline__ void euler_step(const VehicleK& k, const T* x, const T* u, T* xn) {
+    const Tyre<T> t = tyre_forces<T>(k, x, u);
+    T f[6];
+    dynamics(k, x, u, t, f);
+    for (int i = 0; i < 6; ++i) xn[i] = x[i] + f[i] * k.dt;
+}
+__device__ void euler_step_guarded(const VehicleK& k, const double* xin, const double* uin, double* xn) {
     double x[6], u[2];
     for (int i = 0; i < 6; ++i) x[i] = xin[i];
     u[0] = uin[0]; u[1] = uin[1];
     low_speed_guard(x, u);
-    const Tyre<double> t = tyre_forces<double>(k, x, u);
-    double f[6];
-    dynamics(k, x, u, t, f);
-    for (int i = 0; i < 6; ++i) xn[i] = x[i] + f[i] * k.dt;
+    euler_step<double>(k, x, u, xn);
 }
 
 // ---------------------------------------------------------- kinematic bicycle --
@@ -884,10 +889,128 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
     double xN[6], uN[2], xe[6];
     for (int i = 0; i < 6; ++i) xN[i] = s[N * nxa + i];
     for (int j = 0; j < 2; ++j) uN[j] = s[(N - 1) * nxa + nx + j];
-    euler_step(vk, xN, uN, xe);
+    euler_step_guarded(vk, xN, uN, xe);
     for (int i = 0; i < nx; ++i) pb[N * nxa + i] = xe[i];
     for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = pb[(N - 1) * nxa + nx + j];
     for (int j = 0; j < nu; ++j) db[N * nu + j] = db[(N - 1) * nu + j];
+}
+
+// VJP of euler_step_guarded, of the forward as it computes (k_linearise_vjp's rules): the guard
+// first, then euler_step over duals in (yaw, vx, vy, r, steer, accel), seed 0 where the guard put a
+// constant; w (6) the cotangent of the new state -> gx (6), gu (2).  X and Y pass with derivative 1.
+__device__ void euler_step_vjp(const VehicleK& k, const double* xin, const double* uin, const double* w, double* gx,
+                               double* gu) {
+    double xg[6], ug[2];
+    for (int i = 0; i < 6; ++i) xg[i] = xin[i];
+    ug[0] = uin[0]; ug[1] = uin[1];
+    const double vx_in = xg[3];
+    low_speed_guard(xg, ug);
+    const bool lat = !(vx_in > -0.5 && vx_in < 0.5), lon = !(vx_in > -0.3 && vx_in < 0.3);
+    const Dual xd[6] = {Dual(xg[0]),          Dual(xg[1]),         Dual(xg[2], 0, true),
+                        Dual(xg[3], 1, lon), Dual(xg[4], 2, lat), Dual(xg[5], 3, lat)};
+    const Dual ud[2] = {Dual(ug[0], 4, lat), Dual(ug[1], 5, true)};
+    Dual xe[6];
+    euler_step<Dual>(k, xd, ud, xe);
+    double g[Dual::ND];
+    for (int q = 0; q < Dual::ND; ++q) g[q] = 0.0;
+    for (int i = 0; i < 6; ++i)
+        for (int q = 0; q < Dual::ND; ++q) g[q] += w[i] * xe[i].d[q];
+    gx[0] = w[0];
+    gx[1] = w[1];
+    gx[2] = g[0];
+    gx[3] = lon ? g[1] : 0.0;
+    gx[4] = lat ? g[2] : 0.0;
+    gx[5] = lat ? g[3] : 0.0;
+    gu[0] = lat ? g[4] : 0.0;
+    gu[1] = g[5];
+}
+
+// The transpose of k_incr_shift as it computes.  One thread per (vehicle, output row), rows =
+// the N+1 state rows of gsol (8 wide), its N increment rows (2 wide) and one row for the model
+// and state outputs (gAd0, gBd0, ggd0, gxt): every output element has one writer, consecutive
+// threads write consecutive rows of gsol, and no thread walks the horizon.  (One thread per
+// element would evaluate the dual Euler step eight times per vehicle; this form does it twice,
+// in rows N-1 and N, and one thread per vehicle -- the forward's shape -- writes n strided
+// doubles from one lane.)  Cotangents gxt (B,8), gpred (B,N+1,8), gpdu (B,N+1,2) of the NEW xt,
+// pred, pdu, each null = zero; xt the value from BEFORE the step.  With w = gxt + gpred[0]:
+//   plant step   gAd0 = w_x x',  gBd0 = w_x u',  ggd0 = w_x,  g u = w_u + Bd0' w_x  (u = u_prev + du_0),
+//                gxt = (Ad0' w_x, g u),  g du_0 = g u
+//   shift        g x~_k = gpred[k-1] (2 <= k <= N),  g du_k = gpdu[k-1] (1 <= k <= N-1);  du_{N-1} also
+//                takes gpdu[N-1] and gpdu[N], x~_N's inputs also gpred[N]'s, added in that order
+//   terminal     euler_step_vjp of gpred[N]'s state part: into x~_N's states and x~_{N-1}'s inputs
+__global__ __launch_bounds__(256) void k_incr_shift_vjp(VehicleK vk, IncrK L, long B, const double* __restrict__ sol,
+                                                        const double* __restrict__ Ad, const double* __restrict__ Bd,
+                                                        const double* __restrict__ xt, const double* __restrict__ gxt,
+                                                        const double* __restrict__ gpred,
+                                                        const double* __restrict__ gpdu, double* __restrict__ gsol,
+                                                        double* __restrict__ gAd0, double* __restrict__ gBd0,
+                                                        double* __restrict__ ggd0, double* __restrict__ gxt_o) {
+    const int N = L.N, n = L.n, rows = 2 * N + 2;
+    constexpr int nx = 6, nu = 2, nxa = 8;  // the entry point's check
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * rows) return;
+    const long b = t / rows;
+    const int row = (int)(t - b * rows);
+    const double* s = sol + b * n;
+    const double* gp = gpred ? gpred + b * (long)(N + 1) * nxa : nullptr;
+    const double* gd = gpdu ? gpdu + b * (long)(N + 1) * nu : nullptr;
+    if (row <= N) {  // g x~_row
+        if (!gsol) return;
+        const int k = row;
+        double g[nxa];
+        for (int i = 0; i < nxa; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nxa + i] : 0.0;
+        if (k == N && gp)
+            for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gp[N * nxa + nx + j];
+        if ((k == N || k == N - 1) && gp) {
+            double ge[nx], gue[nu];
+            euler_step_vjp(vk, s + N * nxa, s + (N - 1) * nxa + nx, gp + N * nxa, ge, gue);
+            if (k == N)
+                for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+            if (k == N - 1)
+                for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gue[j];
+        }
+        for (int i = 0; i < nxa; ++i) gsol[b * n + k * nxa + i] = g[i];
+        return;
+    }
+    // w, the cotangent of the stepped x~, and g u: what the rows below share
+    const double* B0 = Bd + b * (long)N * nx * nu;
+    double w[nxa], gu[nu];
+    for (int i = 0; i < nxa; ++i) w[i] = (gxt ? gxt[b * nxa + i] : 0.0) + (gp ? gp[i] : 0.0);
+    for (int j = 0; j < nu; ++j) {
+        double acc = 0.0;
+        for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
+        gu[j] = w[nx + j] + acc;
+    }
+    if (row <= 2 * N) {  // g du_k
+        if (!gsol) return;
+        const int k = row - (N + 1);
+        for (int j = 0; j < nu; ++j) {
+            double g = k == 0 ? gu[j] : (gd ? gd[(k - 1) * nu + j] : 0.0);
+            if (k == N - 1 && gd) g = (g + gd[(N - 1) * nu + j]) + gd[N * nu + j];
+            gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+        }
+        return;
+    }
+    // the model row
+    const double* A0 = Ad + b * (long)N * nx * nx;
+    const double* xb = xt + b * nxa;
+    double uu[nu];
+    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + s[(N + 1) * nxa + j];
+    for (int i = 0; i < nx; ++i) {
+        if (gAd0)
+            for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
+        if (gBd0)
+            for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = w[i] * uu[j];
+        if (ggd0) ggd0[b * nx + i] = w[i];
+    }
+    if (gxt_o) {
+        for (int j = 0; j < nx; ++j) {
+            double acc = 0.0;
+            for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
+            gxt_o[b * nxa + j] = acc;
+        }
+        for (int j = 0; j < nu; ++j) gxt_o[b * nxa + nx + j] = gu[j];
+    }
 }
 
 // Plant step and in-place horizon shift that mpc_incre_kine_func.simulate (:385-387, :403-428) and
@@ -1760,6 +1883,22 @@ int mpcqp_incr_shift_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh
     if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
     return launch(L->dev, stream, B, 128, k_incr_shift, vehicle_constants(*veh), incr_k(*L), B, dsol, dAd, dBd, dgd,
                   dxt, dpred, dpdu);
+}
+
+int mpcqp_incr_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh, int64_t B, const double* dsol,
+                                const double* dAd, const double* dBd, const double* dgd, const double* dxt_before,
+                                const double* dgxt, const double* dgpred, const double* dgpdu, double* dgsol,
+                                double* dgAd0, double* dgBd0, double* dggd0, double* dgxt_before, void* stream) {
+    (void)dgd;  // the step is affine in gd: its VJP does not read it
+    if (!L || !veh || !dsol || !dAd || !dBd || !dxt_before || B < 0)
+        return set_error(MPCQP_EINVAL, "incr_shift_vjp: bad arguments");
+    if (L->nx != 6 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "incr_shift_vjp: the plant model is the 6-state dynamic bicycle (nx 6, nu 2)");
+    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgxt_before)) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_incr_shift_vjp, vehicle_constants(*veh), incr_k(*L), B,
+                  dsol, dAd, dBd, dxt_before, dgxt, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before);
 }
 
 int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,

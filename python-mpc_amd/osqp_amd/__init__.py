@@ -139,6 +139,8 @@ def lib():
     L.mpcqp_solve_device.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mpcqp_adjoint_device.argtypes = [vp, C.c_int32] + [vp] * 13
     L.mpcqp_adjoint_batch.argtypes = [vp, C.c_int32] + [dp] * 9 + [_P(C.c_int8), dp, i32p]
+    L.mpcqp_save_solution_device.argtypes = [vp, vp, vp]
+    L.mpcqp_load_solution_device.argtypes = [vp, vp, vp]
     L.mpcqp_synchronize.argtypes = [vp]
     L.mpcqp_set_shared_matrices.argtypes = [vp, C.c_int32]
     L.mpcqp_set_one_shot.argtypes = [vp, C.c_int32]
@@ -658,6 +660,7 @@ class DeviceBatch:
         P, A = canonical_data(P, A)
         self.n, self.m, self.B = P.shape[0], A.shape[0], int(B)
         self.nnzP, self.nnzA = P.nnz, A.nnz
+        self.device = int(device)
         self._pattern = (np.ascontiguousarray(P.indptr, np.int32), np.ascontiguousarray(P.indices, np.int32),
                          np.ascontiguousarray(A.indptr, np.int32), np.ascontiguousarray(A.indices, np.int32))
         Pp, Pi, Ap, Ai = self._pattern
@@ -773,6 +776,37 @@ class DeviceBatch:
                                           self._ptr(o.gPx), self._ptr(o.gAx), self._ptr(o.act), self._ptr(o.ares),
                                           self._ptr(o.astat), stream), "adjoint_device")
         return o
+
+    @property
+    def record_width(self):
+        """Doubles per instance of a solution record: n + 2m + 1."""
+        return self.n + 2 * self.m + 1
+
+    def _record(self, t, name):
+        import torch
+        shp = (self.B, self.record_width)
+        if tuple(t.shape) != shp or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name}: the record must be a contiguous float64 tensor of shape {shp}")
+        return t
+
+    def save_solution(self, out=None, stream=None):
+        """The last solve's solution record (mpcqp_save_solution_device): a (B, n + 2m + 1) float64
+        tensor holding what adjoint() reads of the solve -- the scaled iterates and the status.
+        ``out``: a tensor to write it to (else allocated on the handle's device)."""
+        import torch
+        if out is None:
+            out = torch.empty((self.B, self.record_width), dtype=torch.float64,
+                              device=torch.device("cuda", self.device))
+        _check(lib().mpcqp_save_solution_device(self._h.ptr, self._ptr(self._record(out, "save_solution")), stream),
+               "save_solution_device")
+        return out
+
+    def load_solution(self, record, stream=None):
+        """Put a record of save_solution back (mpcqp_load_solution_device).  After setup() of the
+        data and settings the recorded solve had, adjoint() then returns what it returned right
+        after that solve, bit for bit."""
+        _check(lib().mpcqp_load_solution_device(self._h.ptr, self._ptr(self._record(record, "load_solution")),
+                                                stream), "load_solution_device")
 
     def one_shot(self, on=True):
         """mpcqp_set_one_shot: setup_solve keeps no workspace state (the scaled problem, the G

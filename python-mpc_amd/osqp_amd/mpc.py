@@ -645,6 +645,158 @@ def linearise_dynamics_vjp(veh: VehicleParams, x, u, gAd=None, gBd=None, ggd=Non
     return gx.reshape(lead + (6,)), gu.reshape(lead + (2,))
 
 
+# ------------------------------------------ the dynamic closed loop's tail and its VJP --
+def _fn(name, a):
+    """sin / cos / atan of an ndarray or a _Dual."""
+    return getattr(a, name)() if isinstance(a, _Dual) else getattr(np, {"atan": "arctan"}.get(name, name))(a)
+
+
+def _atan2(y, x):
+    return _Dual.atan2(y, x) if isinstance(x, _Dual) else np.arctan2(y, x)
+
+
+def _low_speed_guard(x, u):
+    """mpc_device.hip's low_speed_guard on copies of x (M, 6), u (M, 2); also the two regions
+    as k_linearise_vjp names them: lat / lon False where vy, r, steer / vx became constants."""
+    x, u = np.array(x, float, copy=True), np.array(u, float, copy=True)
+    vx_in = x[:, 3].copy()
+    g1 = (vx_in >= 0) & (vx_in < 0.5)
+    g2 = (vx_in > -0.5) & (vx_in < 0)
+    g = g1 | g2
+    x[g, 4] = 0.0; x[g, 5] = 0.0; u[g, 0] = 0.0
+    x[g1 & (vx_in < 0.3), 3] = 0.3
+    x[g2 & (vx_in > -0.3), 3] = -0.3
+    return x, u, ~((vx_in > -0.5) & (vx_in < 0.5)), ~((vx_in > -0.3) & (vx_in < 0.3))
+
+
+def _euler_step(veh: VehicleParams, x, u):
+    """mpc_device.hip's euler_step<T> from a GUARDED point: x, u lists of six / two ndarrays or
+    _Duals -> the six components of x + dt f(x, u) (tyre_forces, dynamics, operation by operation)."""
+    (Bf, Cf, Df), (Br, Cr, Dr) = veh.pacejka()
+    m, Iz, lf, lr, dt = veh.m, veh.Iz, veh.l_f, veh.l_r, veh.dt
+    cda, roll = veh.roh * veh.C_d * veh.A_f, veh.C_roll * m * 9.81
+    yaw, vx, vy, r = x[2:]
+    st, acc = u
+    af = -_atan2(lf * r + vy, vx) + st
+    ar = -_atan2(-lr * r + vy, vx)
+    Fyf = Df * _fn("sin", Cf * _fn("atan", Bf * af))
+    Fyr = Dr * _fn("sin", Cr * _fn("atan", Br * ar))
+    sg = np.sign(vx.v if isinstance(vx, _Dual) else vx)
+    Fx = m * acc - 0.5 * cda * vx * vx * sg - roll * sg
+    cy, sy, cs, ss = _fn("cos", yaw), _fn("sin", yaw), _fn("cos", st), _fn("sin", st)
+    f = [vx * cy - vy * sy, vy * cy + vx * sy, r,
+         1. / m * (Fx * cs - Fyf * ss + m * vy * r),
+         1. / m * (Fx * ss + Fyr + Fyf * cs - m * vx * r),
+         1. / Iz * (Fx * lf * ss + Fyf * lf * cs - Fyr * lr)]
+    return [x[i] + f[i] * dt for i in range(6)]
+
+
+def _shift_args(N, sol, Ad0, Bd0, xt):
+    sol, xt = np.asarray(sol, float), np.asarray(xt, float)
+    lead = xt.shape[:-1]
+    S = sol.reshape(-1, sol.shape[-1])
+    M = S.shape[0]
+    return (lead, M, S[:, :(N + 1) * 8].reshape(M, N + 1, 8), S[:, (N + 1) * 8:].reshape(M, N, 2),
+            np.asarray(Ad0, float).reshape(M, 6, 6), np.asarray(Bd0, float).reshape(M, 6, 2), xt.reshape(M, 8))
+
+
+def incr_shift(veh: VehicleParams, N, sol, Ad0, Bd0, gd0, xt):
+    """Plant step and horizon shift of mpc_dynamics.main (:578-617) -- mpc_device.hip::k_incr_shift
+    (mpcqp_incr_shift_device) in numpy, operation by operation, for one vehicle or a batch.
+
+    sol (..., (N+1) 8 + N 2) = (x~_0..x~_N, du_0..du_{N-1}); Ad0 (..., 6, 6), Bd0 (..., 6, 2),
+    gd0 (..., 6) stage 0 of the linearisation; xt (..., 8) = x~ as the step started.  Returns
+    (xt', pred', pdu'): xt' = ((Ad0 x + Bd0 u) + gd0, u) with u = u_prev + du_0; pred' (..., N+1, 8)
+    = (xt', x~_2..x~_N, (euler_step(x_N, u_{N-1}), u_N)) -- u_k the input part of x~_k, the Euler
+    step update_dynamics_model from the guarded point --; pdu' (..., N+1, 2) = (du_1..du_{N-1},
+    du_{N-1}, du_{N-1})."""
+    lead, M, X, D, A0, B0, x0 = _shift_args(N, sol, Ad0, Bd0, xt)
+    g0 = np.asarray(gd0, float).reshape(M, 6)
+    uu = x0[:, 6:] + D[:, 0]
+    xn = np.empty((M, 8))
+    for i in range(6):  # plant_step's association
+        acc = np.zeros(M)
+        for j in range(6):
+            acc = acc + A0[:, i, j] * x0[:, j]
+        bu = np.zeros(M)
+        for j in range(2):
+            bu = bu + B0[:, i, j] * uu[:, j]
+        xn[:, i] = (acc + bu) + g0[:, i]
+    xn[:, 6:] = uu
+    pred, pdu = np.empty((M, N + 1, 8)), np.empty((M, N + 1, 2))
+    pred[:, 0] = xn
+    pred[:, 1:N] = X[:, 2:N + 1]
+    pdu[:, 0:N - 1] = D[:, 1:N]
+    pdu[:, N - 1] = pdu[:, N] = D[:, N - 1]
+    xg, ug, _, _ = _low_speed_guard(X[:, N, :6], X[:, N - 1, 6:])
+    xe = _euler_step(veh, [xg[:, i] for i in range(6)], [ug[:, 0], ug[:, 1]])
+    pred[:, N, :6] = np.stack(xe, axis=1)
+    pred[:, N, 6:] = pred[:, N - 1, 6:]
+    return xn.reshape(lead + (8,)), pred.reshape(lead + (N + 1, 8)), pdu.reshape(lead + (N + 1, 2))
+
+
+def incr_shift_vjp(veh: VehicleParams, N, sol, Ad0, Bd0, xt, gxt=None, gpred=None, gpdu=None):
+    """The VJP of incr_shift in the order of mpc_device.hip's k_incr_shift_vjp
+    (mpcqp_incr_shift_vjp_device): cotangents gxt (..., 8), gpred (..., N+1, 8), gpdu (..., N+1, 2)
+    of (xt', pred', pdu') (None = zero); xt the value from BEFORE the step.  Returns (gsol, gAd0,
+    gBd0, ggd0, gxt_before) with the shapes of (sol, Ad0, Bd0, gd0, xt).
+
+    The transpose of the forward as it computes.  The plant step is bilinear: with w = gxt +
+    gpred[0] the cotangent of xt', gAd0 = w_x x', gBd0 = w_x u', ggd0 = w_x, the cotangent of u is
+    w_u + Bd0' w_x (it goes to xt's input part and to du_0), gxt_before's state part Ad0' w_x.
+    The shift is copies: x~_k (2 <= k <= N) takes gpred[k-1], du_k (1 <= k <= N-1) gpdu[k-1];
+    du_{N-1} also takes gpdu[N-1] and gpdu[N], x~_N's input part also gpred[N]'s, added in the
+    order of the output index.  x~_0 and x~_1 get zero but for x~_{N-1}'s input part, which is the
+    Euler step's control.  The terminal state is euler_step over forward-mode duals in (yaw, vx,
+    vy, r, steer, accel) at the guarded point, seeds 0 where the guard put a constant (so those
+    entries get exactly nothing from it), its tangents contracted with gpred[N]'s state part; X and
+    Y pass through it with derivative 1."""
+    lead, M, X, D, A0, B0, x0 = _shift_args(N, sol, Ad0, Bd0, xt)
+    zero = lambda g, tail: np.zeros((M,) + tail) if g is None else np.asarray(g, float).reshape((M,) + tail)
+    gxt, gpred, gpdu = zero(gxt, (8,)), zero(gpred, (N + 1, 8)), zero(gpdu, (N + 1, 2))
+    w = gxt + gpred[:, 0]
+    uu = x0[:, 6:] + D[:, 0]
+    gA0 = w[:, :6, None] * x0[:, None, :6]
+    gB0 = w[:, :6, None] * uu[:, None, :]
+    gg0 = w[:, :6].copy()
+    gx0 = np.empty((M, 8))
+    for j in range(6):
+        acc = np.zeros(M)
+        for i in range(6):
+            acc = acc + A0[:, i, j] * w[:, i]
+        gx0[:, j] = acc
+    for j in range(2):
+        acc = np.zeros(M)
+        for i in range(6):
+            acc = acc + B0[:, i, j] * w[:, i]
+        gx0[:, 6 + j] = w[:, 6 + j] + acc
+    gX, gD = np.zeros((M, N + 1, 8)), np.zeros((M, N, 2))
+    gX[:, 2:N + 1] = gpred[:, 1:N]
+    gD[:, 0] = gx0[:, 6:]
+    gD[:, 1:N] = gpdu[:, 0:N - 1]
+    gD[:, N - 1] = (gD[:, N - 1] + gpdu[:, N - 1]) + gpdu[:, N]
+    gX[:, N, 6:] = gX[:, N, 6:] + gpred[:, N, 6:]
+    # the terminal Euler step
+    xg, ug, lat, lon = _low_speed_guard(X[:, N, :6], X[:, N - 1, 6:])
+    const = lambda v: _Dual(v, np.zeros(v.shape + (6,)))
+    xd = [const(xg[:, 0]), const(xg[:, 1]), _Dual.input(xg[:, 2], 0, True), _Dual.input(xg[:, 3], 1, lon),
+          _Dual.input(xg[:, 4], 2, lat), _Dual.input(xg[:, 5], 3, lat)]
+    ud = [_Dual.input(ug[:, 0], 4, lat), _Dual.input(ug[:, 1], 5, True)]
+    xe = _euler_step(veh, xd, ud)
+    we = gpred[:, N, :6]
+    g = np.zeros((M, 6))
+    for i in range(6):
+        g = g + we[:, i, None] * xe[i].d
+    ge = np.stack([we[:, 0], we[:, 1], g[:, 0], np.where(lon, g[:, 1], 0.0), np.where(lat, g[:, 2], 0.0),
+                   np.where(lat, g[:, 3], 0.0)], axis=1)
+    gX[:, N, :6] = gX[:, N, :6] + ge
+    gX[:, N - 1, 6] = gX[:, N - 1, 6] + np.where(lat, g[:, 4], 0.0)
+    gX[:, N - 1, 7] = gX[:, N - 1, 7] + g[:, 5]
+    gsol = np.concatenate([gX.reshape(M, -1), gD.reshape(M, -1)], axis=1)
+    return (gsol.reshape(lead + (gsol.shape[1],)), gA0.reshape(lead + (6, 6)), gB0.reshape(lead + (6, 2)),
+            gg0.reshape(lead + (6,)), gx0.reshape(lead + (8,)))
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),

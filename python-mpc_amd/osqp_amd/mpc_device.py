@@ -82,6 +82,7 @@ def _bind():
     L.mpcqp_incr_layout_free.restype = None
     L.mpcqp_reference_search_device.argtypes = [i64, i32, i32, i32, vp, vp, vp, d, vp, i32, vp]
     L.mpcqp_incr_shift_device.argtypes = [vp, _P(Vehicle), i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpcqp_incr_shift_vjp_device.argtypes = [vp, _P(Vehicle), i64] + [vp] * 14
     L.mpcqp_incr_warm_shift_device.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, i32, vp]
     L.mpcqp_affine_create.argtypes = [i32, vp, i32, i32, vp, vp, vp, i32, _P(vp)]
     L.mpcqp_affine_apply_device.argtypes = [vp, i64, vp, i32, vp, vp, vp, vp, vp]
@@ -580,6 +581,68 @@ def reference_search(path_x, path_y, pred, dt):
                                            float(dt), _p(Xr), pred.device.index or 0, _stream(torch, pred.device)),
            "reference_search")
     return Xr
+
+
+def _shift_in(t, shape, name):
+    import torch
+    if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_cuda:
+        raise ValueError(f"{name} must be a float64 device tensor of shape {shape}")
+    return t.contiguous()
+
+
+def incr_shift(layout, veh: Vehicle, sol, Ad, Bd, gd, xt):
+    """Plant step and horizon shift of mpc_dynamics.main (mpcqp_incr_shift_device) as a function:
+    sol (B, n), Ad (B, N, 6, 6), Bd (B, N, 6, 2), gd (B, N, 6) (stage 0 is read), xt (B, 8) ->
+    (xt', pred', pdu') = new tensors (B, 8), (B, N+1, 8), (B, N+1, 2); nothing is written in place."""
+    import torch
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd, gd = _shift_in(Ad, (B, N, 6, 6), "Ad"), _shift_in(Bd, (B, N, 6, 2), "Bd"), _shift_in(gd, (B, N, 6), "gd")
+    xt1 = _shift_in(xt, (B, 8), "xt").clone()
+    pred = torch.empty((B, N + 1, 8), dtype=torch.float64, device=sol.device)
+    pdu = torch.empty((B, N + 1, 2), dtype=torch.float64, device=sol.device)
+    _check(_bind().mpcqp_incr_shift_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(xt1),
+                                           _p(pred), _p(pdu), _stream(torch, sol.device)), "incr_shift")
+    return xt1, pred, pdu
+
+
+SHIFT_VJP_OUTPUTS = ("gsol", "gAd0", "gBd0", "ggd0", "gxt")
+
+
+def incr_shift_vjp(layout, veh: Vehicle, sol, Ad, Bd, xt, gxt=None, gpred=None, gpdu=None, want=None, out=None):
+    """The transpose of incr_shift (mpcqp_incr_shift_vjp_device; mpcqp.h has the formulas).  sol, Ad,
+    Bd as the forward took them, xt the value from BEFORE the step; cotangents gxt (B, 8), gpred
+    (B, N+1, 8), gpdu (B, N+1, 2) of the new xt, pred, pdu: contiguous float64 device tensors, None
+    = zero.  want: the outputs to form, of SHIFT_VJP_OUTPUTS (default all); out: {name: tensor} to
+    write into.  Returns a namespace with gsol (B, n), gAd0 (B, 6, 6), gBd0 (B, 6, 2), ggd0 (B, 6)
+    -- the stage-0 model's, to be added into stage 0 -- and gxt (B, 8), None where not wanted."""
+    import torch
+    from types import SimpleNamespace
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd = _shift_in(Ad, (B, N, 6, 6), "Ad"), _shift_in(Bd, (B, N, 6, 2), "Bd")
+    xt = _shift_in(xt, (B, 8), "xt")
+    for t, shape, k in ((gxt, (B, 8), "gxt"), (gpred, (B, N + 1, 8), "gpred"), (gpdu, (B, N + 1, 2), "gpdu")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"incr_shift_vjp: {k} must be a contiguous float64 tensor of shape {shape}")
+    shapes = dict(gsol=(B, layout.n), gAd0=(B, 6, 6), gBd0=(B, 6, 2), ggd0=(B, 6), gxt=(B, 8))
+    want = list(SHIFT_VJP_OUTPUTS) if want is None else list(want)
+    bad = sorted(set(want) - set(shapes))
+    if bad:
+        raise ValueError(f"incr_shift_vjp: unknown output(s) {', '.join(bad)}")
+    o = SimpleNamespace(**{k: None for k in shapes})
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shapes[k], dtype=torch.float64, device=sol.device)
+        elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"incr_shift_vjp: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
+        setattr(o, k, t)
+    _check(_bind().mpcqp_incr_shift_vjp_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), None, _p(xt),
+                                               _po(gxt), _po(gpred), _po(gpdu),
+                                               *(_po(getattr(o, k)) for k in SHIFT_VJP_OUTPUTS),
+                                               _stream(torch, sol.device)), "incr_shift_vjp")
+    return o
 
 
 def warm_shift(N, nxa, nu, x, y=None):

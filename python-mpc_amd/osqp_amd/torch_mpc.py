@@ -11,6 +11,7 @@ DESIGN.md §15):
   ltv_assemble(layout, Ad, Bd, gd, x0, Xr, ...)         -> Ax, q, l, u [, Px]
   incr_assemble(layout, Ad, Bd, gd, xt0, Xr, ...)       -> Ax, q, l, u [, Px]
   affine_assemble(assembler, theta, regime)             -> q, l, u
+  incr_shift(layout, veh, sol, Ad, Bd, gd, xt)          -> xt', pred', pdu'
 
 and ``MPCLayer`` composes the assembly with one ``QPLayer``: (Ad, Bd, gd, x0, Xr[, weights]) ->
 (X, U, y), so that d u_0 / d x0 and d loss / d Q are one backward call on the device.  Every call
@@ -19,14 +20,18 @@ Gradients are formed only for the inputs that require them.
 
 With ``linearise_dynamics`` the closed loop of mpc_dynamics.main is differentiable end to end: its
 plant step is Ad_0 x + Bd_0 u + gd_0 and its shift copies stages of the solution, both plain torch
-operations between one MPCLayer per control step.
+operations between one MPCLayer per control step.  ``DynamicRollout`` differentiates
+T steps of that loop -- terminal Euler step included -- on ONE solver handle: the forward keeps a
+tape of small solution records, the backward sets each step up again, loads its record and runs the
+adjoint.
 """
 from __future__ import annotations
 
 from . import mpc_device as md
 from .torch_qp import QPLayer
 
-__all__ = ["linearise_kinematics", "linearise_dynamics", "ltv_assemble", "incr_assemble", "affine_assemble", "MPCLayer"]
+__all__ = ["linearise_kinematics", "linearise_dynamics", "ltv_assemble", "incr_assemble", "affine_assemble",
+           "incr_shift", "MPCLayer", "DynamicRollout"]
 
 _FN = None
 
@@ -117,7 +122,58 @@ def _functions():
                 gt = torch.cat([gt, gt.new_zeros((ctx.shape[0], ctx.shape[1] - a.nparam))], dim=1)
             return None, gt, None
 
-    _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine)
+    class IncrShift(torch.autograd.Function):
+        """inputs (layout, veh, sol, Ad, Bd, gd, xt)"""
+
+        @staticmethod
+        def forward(ctx, layout, veh, sol, Ad, Bd, gd, xt):
+            sol, Ad, Bd, gd, xt = (_c(t) for t in (sol, Ad, Bd, gd, xt))
+            ctx.layout, ctx.veh = layout, veh
+            ctx.save_for_backward(sol, Ad, Bd, xt)
+            ctx.set_materialize_grads(False)
+            return md.incr_shift(layout, veh, sol, Ad, Bd, gd, xt)
+
+        @staticmethod
+        def backward(ctx, gxt, gpred, gpdu):
+            if gxt is None and gpred is None and gpdu is None:
+                return (None,) * 7
+            sol, Ad, Bd, xt = ctx.saved_tensors
+            need = ctx.needs_input_grad[2:]  # (sol, Ad, Bd, gd, xt)
+            want = [k for k, n in zip(md.SHIFT_VJP_OUTPUTS, need) if n]
+            g = md.incr_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, xt, _c(gxt), _c(gpred), _c(gpdu), want=want)
+
+            def stage0(t, like_tail):  # the model outputs are stage 0's
+                if t is None:
+                    return None
+                full = t.new_zeros((t.shape[0], ctx.layout.N) + like_tail)
+                full[:, 0] = t
+                return full
+
+            return (None, None, g.gsol, stage0(g.gAd0, (6, 6)), stage0(g.gBd0, (6, 2)), stage0(g.ggd0, (6,)), g.gxt)
+
+    class Rollout(torch.autograd.Function):
+        """inputs (roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w)"""
+
+        @staticmethod
+        def forward(ctx, roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w):
+            xt0, pred0, Xr, Q, QN, R = (_c(t) for t in (xt0, pred0, Xr, Q, QN, R))
+            weights = (Q, QN, R) if use_w else None
+            ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
+            ctx.set_materialize_grads(False)
+            XT, DU0, pred, ctx.tape = roll._on_stream(lambda: roll._forward(xt0, pred0, T, Xr, path, weights))
+            return XT, DU0, pred
+
+        @staticmethod
+        def backward(ctx, gXT, gDU0, gpred):
+            if gXT is None and gDU0 is None and gpred is None:
+                return (None,) * 10
+            roll = ctx.roll
+            need = dict(zip(("xt0", "pred0", "Xr", "Q", "QN", "R"), ctx.needs_input_grad[3:9]))
+            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, _c(gXT), _c(gDU0),
+                                                       _c(gpred), need))
+            return (None, None, None, g["xt0"], g["pred0"], g["Xr"], g["Q"], g["QN"], g["R"], None)
+
+    _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine, IncrShift=IncrShift, Rollout=Rollout)
     return _FN
 
 
@@ -163,6 +219,15 @@ def affine_assemble(assembler, theta, regime=None):
     return _functions().Affine.apply(assembler, theta, regime)
 
 
+def incr_shift(layout, veh, sol, Ad, Bd, gd, xt):
+    """mpc_device.incr_shift -- the plant step, the horizon shift and the terminal Euler step of
+    mpc_dynamics.main's loop -- differentiable in sol, Ad, Bd, gd and xt (mpc_device.incr_shift_vjp):
+    (xt', pred', pdu').  Only stage 0 of Ad, Bd, gd is read, and only it gets a gradient."""
+    if layout._kind != "incr":
+        raise ValueError("incr_shift needs an IncrementalLayout")
+    return _functions().IncrShift.apply(layout, veh, sol, Ad, Bd, gd, xt)
+
+
 class MPCLayer:
     """One MPC step of either layout as a differentiable map
     ``layer(Ad, Bd, gd, x0, Xr, weights=None, xlo=None, xhi=None) -> (X, U, y)``:
@@ -201,3 +266,175 @@ class MPCLayer:
         x, y = self.qp(Px, Ax, q, l, u)
         ns = (L.N + 1) * L.nxa
         return x[:, :ns].reshape(self.B, L.N + 1, L.nxa), x[:, ns:].reshape(self.B, L.N, L.nu), y
+
+
+class DynamicRollout:
+    """T steps of the dynamic closed loop (mpc_device.DynamicMPC's step) as ONE differentiable map on
+    ONE solver handle:
+
+        roll = DynamicRollout(layout, B, veh, device=0, strict=True, warm_start=False, **settings)
+        XT, DU0, pred_T = roll(xt0, pred0, T, Xr=None, path=None, weights=None)
+
+    xt0 (B, 8) the augmented state, pred0 (B, N+1, 8) the predicted horizon the first step
+    linearises at; XT (B, T+1, 8) the states with XT[:, 0] = xt0, DU0 (B, T, 2) each step's du_0,
+    pred_T (B, N+1, 8) the horizon after the last step.  Each step: the reference -- searched on
+    ``path`` = (path_x, path_y) device tensors (reference_search) or the given ``Xr`` (T, B, 6, N+1)
+    --, the linearisation of stages 0..N-1 of pred, the assembly (``weights`` = (Q, QN, R) of the
+    call, each None: the layout's own), setup, with ``warm_start`` the previous solution shifted one
+    stage, the solve, and incr_shift.  With weights None and a path, XT equals DynamicMPC's xt step
+    for step, bit for bit.
+
+    The forward keeps, per step, xt and pred from before the step, the solution and its record
+    (DeviceBatch.save_solution): (N+2) 8 + 2n + 2m + 1 doubles per instance, owned by the autograd
+    context, so several rollouts of one object can be alive at once.  The backward walks the steps
+    in reverse: it rebuilds the step's QP from the tape, runs setup + load_solution, the shift's VJP,
+    ONE adjoint call (seed: the shift's gsol plus the step's own du_0 cotangent), the assembly's
+    and the linearisation's VJPs, and accumulates into the cotangents of (xt, pred).  The searched
+    reference is piecewise constant and carries no gradient; a given Xr gets its own.  Gradients go
+    to xt0, pred0, Q, QN, R (summed over the batch) and Xr, each formed only when required.
+
+    ``status``, ``iters`` (T, B) hold the last forward's solves; after a backward they are that
+    rollout's, with ``astat`` (T, B), ``ares`` (T, B) and ``act`` (T, B, m) of its adjoint calls.
+    ``strict`` is QPLayer's rule: backward raises when an instance's astat is not 1 at some step;
+    with strict=False such an instance gets zero gradients in every input and the weight sums
+    leave it out.  ``settings`` are DeviceBatch's."""
+
+    def __init__(self, layout, B, veh, device=0, strict=True, warm_start=False, **settings):
+        import torch
+        from . import DeviceBatch
+        if layout._kind != "incr" or (layout.nx, layout.nu) != (6, 2):
+            raise ValueError("DynamicRollout needs an IncrementalLayout of the dynamic bicycle (nx 6, nu 2)")
+        self.torch, self.layout, self.veh = torch, layout, veh
+        self.B, self.N = int(B), layout.N
+        self.dev = torch.device("cuda", int(device))
+        self.strict, self.shift_warm = bool(strict), bool(warm_start)
+        P, A, _, _ = layout.pattern()
+        settings.pop("verbose", None)
+        self.batch = DeviceBatch(P, A, self.B, device=int(device), **settings)
+        self.Px = torch.from_numpy(P.data.copy()).to(self.dev)[None, :].repeat(self.B, 1).contiguous()
+        self.stream = torch.cuda.Stream(self.dev)
+        self.status = self.iters = self.astat = self.ares = self.act = None
+        self._fn = _functions().Rollout
+
+    def tape_doubles_per_instance(self):
+        """Doubles the tape holds per step and instance: xt, pred, sol and the record."""
+        L = self.layout
+        return 8 + (L.N + 1) * 8 + L.n + self.batch.record_width
+
+    def __call__(self, xt0, pred0, T, Xr=None, path=None, weights=None):
+        torch, B, N = self.torch, self.B, self.N
+        T = int(T)
+        if T < 1:
+            raise ValueError("DynamicRollout: T must be at least 1")
+        if (Xr is None) == (path is None):
+            raise ValueError("DynamicRollout: give either Xr (T, B, 6, N+1) or path = (path_x, path_y)")
+        for t, shape, k in ((xt0, (B, 8), "xt0"), (pred0, (B, N + 1, 8), "pred0"), (Xr, (T, B, 6, N + 1), "Xr")):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.dev):
+                raise ValueError(f"DynamicRollout: {k} must be a float64 tensor of shape {shape} on {self.dev}")
+        if path is not None:
+            path = tuple(_c(p) for p in path)
+        Q, QN, R, use_w = _split_weights(weights)
+        return self._fn.apply(self, T, path, xt0, pred0, Xr, Q, QN, R, use_w)
+
+    def _on_stream(self, fn):
+        """fn() on the rollout's stream, ordered after the caller's current stream; the caller's
+        stream is ordered after it (mpc_device._ClosedLoop's rule)."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            out = fn()
+        caller.wait_stream(self.stream)
+        return out
+
+    def _problem(self, xt, pred, Xr_t, path, weights):
+        """One step's reference, linearisation and QP values from (xt, pred), as DynamicMPC._step."""
+        N, L = self.N, self.layout
+        Xr = md.reference_search(path[0], path[1], pred, self.veh.dt) if Xr_t is None else Xr_t
+        Ad, Bd, gd = md.linearise(self.veh, pred[:, :N, :6], pred[:, :N, 6:])
+        out = L.assemble(Ad, Bd, gd, xt, Xr, weights=weights)
+        Px = self.Px if weights is None else out[4][None, :].repeat(self.B, 1)
+        return Xr, Ad, Bd, gd, Px, out[:4]
+
+    def _forward(self, xt, pred, T, Xr, path, weights):
+        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
+        st = md._stream(torch, self.dev)  # self.stream
+        kw = dict(dtype=torch.float64, device=self.dev)
+        XT, DU0 = torch.empty((B, T + 1, 8), **kw), torch.empty((B, T, 2), **kw)
+        status = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        iters = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        XT[:, 0] = xt
+        tape, y, nd = [], None, (N + 1) * 8
+        for t in range(T):
+            _, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(xt, pred, None if Xr is None else Xr[t], path, weights)
+            b.setup(Px, Ax, q, l, u, stream=st)
+            if self.shift_warm and t > 0:
+                b.warm_start(*md.warm_shift(N, 8, 2, tape[-1][2], y), stream=st)
+            sol, y = torch.empty((B, L.n), **kw), torch.empty((B, L.m), **kw)
+            b.solve(sol, y, status[t], iters[t], stream=st)
+            rec = b.save_solution(torch.empty((B, b.record_width), **kw), stream=st)
+            tape.append((xt, pred, sol, rec))
+            xt, pred, _ = md.incr_shift(L, self.veh, sol, Ad, Bd, gd, xt)
+            XT[:, t + 1] = xt
+            DU0[:, t] = sol[:, nd:nd + 2]
+        self.status, self.iters = status, iters
+        return XT, DU0, pred, dict(steps=tape, status=status, iters=iters)
+
+    def _backward(self, tape, Xr, path, weights, gXT, gDU0, gpred, need):
+        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
+        st = md._stream(torch, self.dev)
+        steps = tape["steps"]
+        T, nd = len(steps), (N + 1) * 8
+        kw = dict(dtype=torch.float64, device=self.dev)
+        astat = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        ares = torch.empty((T, B), **kw)
+        act = torch.empty((T, B, L.m), dtype=torch.int8, device=self.dev)
+        wnames = [k for k in ("Q", "QN", "R") if weights is not None and need[k]]
+        gw = {k: torch.zeros((B,) + ((2, 2) if k == "R" else (6, 6)), **kw) for k in wnames}
+        gXr = torch.zeros((T, B, 6, N + 1), **kw) if Xr is not None and need["Xr"] else None
+        want = ["gAd", "gBd", "ggd", "gx0"] + ["gXr"] * (gXr is not None) + ["g" + k for k in wnames]
+        g_xt = gXT[:, T].clone() if gXT is not None else torch.zeros((B, 8), **kw)
+        g_pred = gpred
+        for t in reversed(range(T)):
+            xt, pred, sol, rec = steps[t]
+            Xr_t, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(xt, pred, None if Xr is None else Xr[t], path, weights)
+            b.setup(Px, Ax, q, l, u, stream=st)
+            b.load_solution(rec, stream=st)
+            sh = md.incr_shift_vjp(L, self.veh, sol, Ad, Bd, xt, g_xt, g_pred, None)
+            if gDU0 is not None:
+                sh.gsol[:, nd:nd + 2] += gDU0[:, t]
+            a = b.adjoint(sh.gsol, None, act=act[t], ares=ares[t], astat=astat[t], stream=st)
+            v = L.assemble_vjp(a.gAx, a.gq, a.gl, a.gu, gPx=a.gPx if wnames else None, Xr=Xr_t,
+                               weights=None if weights is None else (weights[0], weights[1], None), want=want)
+            v.gAd[:, 0] += sh.gAd0
+            v.gBd[:, 0] += sh.gBd0
+            v.ggd[:, 0] += sh.ggd0
+            gx, gu = md.linearise_vjp(self.veh, pred[:, :N, :6], pred[:, :N, 6:], v.gAd, v.gBd, v.ggd)
+            g_pred = torch.zeros((B, N + 1, 8), **kw)
+            g_pred[:, :N, :6] = gx
+            g_pred[:, :N, 6:] = gu
+            g_xt = sh.gxt + v.gx0
+            if gXT is not None:
+                g_xt += gXT[:, t]
+            for k in wnames:
+                gw[k] += getattr(v, "g" + k)
+            if gXr is not None:
+                gXr[t] = v.gXr
+        self.status, self.iters = tape["status"], tape["iters"]
+        self.astat, self.ares, self.act = astat, ares, act
+        bad = (astat != 1).any(0)
+        if bool(bad.any()):
+            if self.strict:
+                idx = bad.nonzero().flatten().tolist()
+                raise RuntimeError(f"DynamicRollout: no reliable gradient for instance(s) {idx[:8]} (astat per step "
+                                   f"{astat[:, bad].T.tolist()[:8]}; strict=False gives them zero gradients)")
+            zero = lambda g: None if g is None else torch.where(bad.view((-1,) + (1,) * (g.dim() - 1)), 0.0, g)
+            g_xt, g_pred = zero(g_xt), zero(g_pred)
+            gw = {k: zero(g) for k, g in gw.items()}
+            if gXr is not None:
+                gXr = torch.where(bad.view(1, -1, 1, 1), 0.0, gXr)
+        out = dict(xt0=g_xt if need["xt0"] else None, pred0=g_pred if need["pred0"] else None, Xr=gXr,
+                   Q=None, QN=None, R=None)
+        for k in wnames:
+            out[k] = gw[k].sum(0)
+        return out

@@ -23,18 +23,20 @@ def _function():
             x, y = layer._solve(Px, Ax, q, l, u)
             ctx.layer = layer
             ctx.generation = layer.generation
+            # record=True: the context owns what a later backward rebuilds the solve from
+            ctx.tape = layer._tape() if layer.record else None
             ctx.set_materialize_grads(False)
             return x, y
 
         @staticmethod
         def backward(ctx, gx, gy):
             layer = ctx.layer
-            if ctx.generation != layer.generation:
+            if ctx.tape is None and ctx.generation != layer.generation:
                 raise RuntimeError("QPLayer: backward after another forward of the same layer (its batch holds "
                                    "the later solve); use one layer per solve that is differentiated")
             if gx is None and gy is None:
                 return (None,) * 6
-            g = layer._adjoint(gx, gy)
+            g = layer._adjoint(gx, gy, ctx.tape)
             need = ctx.needs_input_grad  # (layer, Px, Ax, q, l, u)
             out = (g.gPx, g.gAx, g.gq, g.gl, g.gu)
             return (None,) + tuple(t if need[k + 1] else None for k, t in enumerate(out))
@@ -53,17 +55,23 @@ class QPLayer:
     (``astat`` != 1: not solved, or the adjoint solve's residual above 1e-8 -- a singular active
     set); with strict=False those instances get zero gradients instead.
     A layer holds one solve at a time: backward raises RuntimeError once the layer has run
-    another forward.  Gradients are formed only for the inputs that require them.
+    another forward.  With ``record=True`` every forward keeps the solve's solution record
+    (DeviceBatch.save_solution, n + 2m + 1 doubles per instance) and its five inputs in the autograd
+    context, and the backward runs setup + load_solution + adjoint: a backward after later forwards
+    of the same layer is then valid and returns the same bits.  Gradients are formed only for the
+    inputs that require them.
     """
 
-    def __init__(self, P_pattern, A_pattern, B, device=0, strict=True, **settings):
+    def __init__(self, P_pattern, A_pattern, B, device=0, strict=True, record=False, **settings):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", int(device))
         self.batch = DeviceBatch(P_pattern, A_pattern, B, device=int(device), **settings)
         self.B, self.n, self.m = self.batch.B, self.batch.n, self.batch.m
         self.strict = bool(strict)
+        self.record = bool(record)
         self.generation = 0
+        self._last = None
         self.stream = torch.cuda.Stream(self.dev)
         self.status = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
         self.iters = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
@@ -102,18 +110,34 @@ class QPLayer:
         x = torch.empty((B, n), dtype=torch.float64, device=self.dev)
         y = torch.empty((B, m), dtype=torch.float64, device=self.dev)
         s = self.stream.cuda_stream
+        rec = torch.empty((B, b.record_width), dtype=torch.float64, device=self.dev) if self.record else None
 
         def run():
             b.setup(Px, Ax, q, l, u, stream=s)
             b.solve(x, y, self.status, self.iters, stream=s)
+            if rec is not None:
+                b.save_solution(rec, stream=s)
 
         self._on_stream(run)
+        self._last = (Px, Ax, q, l, u, rec) if self.record else None
         return x, y
 
-    def _adjoint(self, gx, gy):
+    def _tape(self):
+        """The last forward's inputs as the setup took them, and its solution record."""
+        return self._last
+
+    def _adjoint(self, gx, gy, tape=None):
         gx = None if gx is None else gx.contiguous()
         gy = None if gy is None else gy.contiguous()
-        g = self._on_stream(lambda: self.batch.adjoint(gx, gy, stream=self.stream.cuda_stream))
+        s = self.stream.cuda_stream
+
+        def run():
+            if tape is not None:
+                self.batch.setup(*tape[:5], stream=s)
+                self.batch.load_solution(tape[5], stream=s)
+            return self.batch.adjoint(gx, gy, stream=s)
+
+        g = self._on_stream(run)
         self.astat, self.ares = g.astat, g.ares
         bad = g.astat != 1
         if bool(bad.any()):
