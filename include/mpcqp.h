@@ -571,6 +571,51 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout *L, const mpcqp_kin_vehicl
                                int32_t *dskipped, int32_t *dsteps_taken, double *dtraj, int32_t traj_cap,
                                int32_t *dtraj_len, void *stream);
 
+/* The transposes of the two kinematic tails as they compute, for a layout with
+ * nx 4, nu 2.  dmode[b] (int32[B]; NULL: 0 for every vehicle) says what the forward did:
+ *   0  the vehicle was stepped;
+ *   1  the forward left it untouched (mpcqp_kin_shift_device: done[b] was already set;
+ *      mpcqp_kin_ltv_shift_device: status[b] != 1): dgsol and the model outputs are exactly zero
+ *      and the state's cotangent passes through (dgxt_before = dgxt, dgx_before = dgx);
+ *   2  mpcqp_kin_shift_device only: the vehicle met the stop rule on this step (finish_cnt went
+ *      past 15), so pred / pred_du hold the unpacked solution and xt did not move:
+ *      g x~_k = dgpred[k] for all k, g du_k = dgpdu[k], du_{N-1} also takes dgpdu[N],
+ *      dgxt_before = dgxt, the model outputs are zero.
+ * Left to the caller: the cotangent of the PREVIOUS pred / pred_du (pred_x, pred_u and u for the
+ * LTV tail), which is dgpred / dgpdu (dgpred_x, dgpred_u, dgu) in mode 1 and zero in modes 0 and 2;
+ * these calls do not write it.
+ *
+ * mpcqp_kin_shift_vjp_device, mode 0, with w = dgxt + dgpred[0] and u = u_prev + du_0:
+ *   dgAd0[b*16] = w_x x',  dgBd0[b*8] = w_x u',  dggd0[b*4] = w_x,  g u = w_u + Bd0' w_x,
+ *   dgxt_before[b*6] = (Ad0' w_x, g u),  g du_0 = g u;
+ *   g x~_k = dgpred[k-1] (2 <= k <= N),  g du_k = dgpdu[k-1] (1 <= k <= N-1),  du_{N-1} also takes
+ *   dgpdu[N-1] and dgpdu[N], in that order;  x~_0 and x~_1 get nothing;
+ *   the forward's terminal state is (update_kinematics_model(x_N, u_N), u_N) of x~_N's own two
+ *   parts, so x~_N also takes dgpred[N]'s input part and the closed-form transpose of the update
+ *   applied to dgpred[N]'s state part.
+ * mpcqp_kin_ltv_shift_vjp_device, mode 0, with w = dgx + dgpred_x[0]:
+ *   dgAd0 = w x',  dgBd0 = w U_0',  dggd0 = w,  dgx_before[b*4] = Ad0' w,  g U_0 = Bd0' w + dgu
+ *   (the forward does not read the old u);  g S_k = dgpred_x[k-1] (2 <= k <= N),  g U_k =
+ *   dgpred_u[k-1] (1 <= k <= N-1),  U_{N-1} also takes dgpred_u[N-1] and dgpred_u[N];  the terminal
+ *   update is of (S_N, U_{N-1}): its transpose of dgpred_x[N] goes into S_N and U_{N-1}.
+ * dsol, dAd, dBd as the forward took them (stage 0 of dAd / dBd is read; dgd is not read and may
+ * be NULL); dxt_before / dx_before is the state from BEFORE the step.  Each cotangent may be NULL
+ * (zero), each output may be NULL (not written).  One thread per (vehicle, output row), one writer
+ * per element, no atomics: a repeated call returns the same bits.  MPCQP_EINVAL "kin_shift_vjp: bad
+ * arguments" / "kin_ltv_shift_vjp: bad arguments" (a NULL layout, vehicle, dsol, dAd, dBd or
+ * state-before, B < 0) and MPCQP_EUNSUPPORTED (a layout that is not nx 4, nu 2) before any device
+ * call; B == 0 or no output asked for succeeds without one. */
+int mpcqp_kin_shift_vjp_device(const mpcqp_incr_layout *L, const mpcqp_kin_vehicle *veh, int64_t B, const double *dsol,
+                               const double *dAd, const double *dBd, const double *dgd, const double *dxt_before,
+                               const int32_t *dmode, const double *dgxt, const double *dgpred, const double *dgpdu,
+                               double *dgsol, double *dgAd0, double *dgBd0, double *dggd0, double *dgxt_before,
+                               void *stream);
+int mpcqp_kin_ltv_shift_vjp_device(const mpcqp_ltv_layout *L, const mpcqp_kin_vehicle *veh, int64_t B,
+                                   const double *dsol, const double *dAd, const double *dBd, const double *dx_before,
+                                   const int32_t *dmode, const double *dgx, const double *dgu, const double *dgpred_x,
+                                   const double *dgpred_u, double *dgsol, double *dgAd0, double *dgBd0, double *dggd0,
+                                   double *dgx_before, void *stream);
+
 /* ======================================================================
  * A bank of paths with a per-vehicle selection, and the two closed loops built on the layouts
  * above that remain in Control/MPC: mpc_increment_kinematics_pred_matrix.main (:281-476, the

@@ -340,6 +340,22 @@ __device__ __forceinline__ void kin_update(const mpcqp_kin_vehicle& k, const dou
     xn[3] = yaw + v1 / (k.l_f + k.l_r) * tan(u[0]) * k.dt;
 }
 
+// The transpose of kin_update in closed form: w (4) the cotangent of the new state -> gx (4) of
+// (X, Y, v, yaw), gu (2) of (steer, accel).  v enters yaw's row through v1 = v + accel dt.
+__device__ __forceinline__ void kin_update_vjp(const mpcqp_kin_vehicle& k, const double* x, const double* u,
+                                               const double* w, double* gx, double* gu) {
+    const double v = x[2], yaw = x[3], st = u[0];
+    const double dt = k.dt, wb = k.l_f + k.l_r;
+    const double v1 = v + u[1] * dt;
+    const double cy = cos(yaw), sy = sin(yaw), ts = tan(st), cs = cos(st);
+    gx[0] = w[0];
+    gx[1] = w[1];
+    gx[2] = ((w[0] * cy * dt + w[1] * sy * dt) + w[2]) + w[3] * ts * dt / wb;
+    gx[3] = (-w[0] * v * sy * dt + w[1] * v * cy * dt) + w[3];
+    gu[0] = w[3] * v1 * dt / (wb * (cs * cs));
+    gu[1] = w[2] * dt + w[3] * dt * dt * ts / wb;
+}
+
 // -------------------------------------------------------------------- models --
 // What differs between the two bicycles where a kernel is written once over the model: the
 // state width, the constants (which select the linearise_one overload), the state that holds
@@ -1192,6 +1208,225 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     if (steps_taken) steps_taken[b] += 1;
 }
 
+// The transposes of the two kinematic tails as they compute, in k_incr_shift_vjp's
+// thread mapping: one thread per (vehicle, output row), rows = the N+1 state rows of gsol, its N
+// input rows and one row for the model and state outputs; one writer per output element, no
+// atomics, no thread walks the horizon.  mode (null = 0 everywhere) says what the forward did with
+// the vehicle: 0 stepped; 1 left untouched (done was set / status != solved): gsol and the model
+// outputs are zero and the state's cotangent passes through; 2 (k_kin_shift only) met the stop rule
+// on this step: pred / pdu took the unpacked solution, xt did not move.  The cotangent of the
+// PREVIOUS horizon (gpred / gpdu in mode 1, zero otherwise) is the caller's to form.
+
+// k_kin_shift / k_lane_tail (kin_incr_step_shift).  With w = gxt + gpred[0], mode 0:
+//   plant step   gAd0 = w_x x',  gBd0 = w_x u',  ggd0 = w_x,  g u = w_u + Bd0' w_x  (u = u_prev + du_0),
+//                gxt = (Ad0' w_x, g u),  g du_0 = g u
+//   shift        g x~_k = gpred[k-1] (2 <= k <= N),  g du_k = gpdu[k-1] (1 <= k <= N-1);  du_{N-1} also
+//                takes gpdu[N-1] and gpdu[N], added in that order
+//   terminal     pred[N] = (kin_update(x_N, u_N), u_N): x~_N also takes gpred[N]'s input part, then
+//                kin_update_vjp of gpred[N]'s state part in both its parts
+// mode 2: g x~_k = gpred[k], g du_k = gpdu[k], du_{N-1} also gpdu[N].
+__global__ __launch_bounds__(256) void k_kin_shift_vjp(mpcqp_kin_vehicle vk, IncrK L, long B,
+                                                       const double* __restrict__ sol, const double* __restrict__ Ad,
+                                                       const double* __restrict__ Bd, const double* __restrict__ xt,
+                                                       const int* __restrict__ dmode, const double* __restrict__ gxt,
+                                                       const double* __restrict__ gpred,
+                                                       const double* __restrict__ gpdu, double* __restrict__ gsol,
+                                                       double* __restrict__ gAd0, double* __restrict__ gBd0,
+                                                       double* __restrict__ ggd0, double* __restrict__ gxt_o) {
+    const int N = L.N, n = L.n, rows = 2 * N + 2;
+    constexpr int nx = 4, nu = 2, nxa = 6;  // the entry point's check
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * rows) return;
+    const long b = t / rows;
+    const int row = (int)(t - b * rows);
+    const int mode = dmode ? dmode[b] : 0;
+    const double* s = sol + b * n;
+    const double* gp = gpred ? gpred + b * (long)(N + 1) * nxa : nullptr;
+    const double* gd = gpdu ? gpdu + b * (long)(N + 1) * nu : nullptr;
+    if (row <= N) {  // g x~_row
+        if (!gsol) return;
+        const int k = row;
+        double g[nxa];
+        if (mode != 0) {
+            for (int i = 0; i < nxa; ++i) g[i] = (mode == 2 && gp) ? gp[k * nxa + i] : 0.0;
+        } else {
+            for (int i = 0; i < nxa; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nxa + i] : 0.0;
+            if (k == N && gp) {
+                double ge[nx], gue[nu];
+                kin_update_vjp(vk, s + N * nxa, s + N * nxa + nx, gp + N * nxa, ge, gue);
+                for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+                for (int j = 0; j < nu; ++j) g[nx + j] = (g[nx + j] + gp[N * nxa + nx + j]) + gue[j];
+            }
+        }
+        for (int i = 0; i < nxa; ++i) gsol[b * n + k * nxa + i] = g[i];
+        return;
+    }
+    if (mode != 0) {  // nothing went through the plant step
+        if (row <= 2 * N) {
+            if (!gsol) return;
+            const int k = row - (N + 1);
+            for (int j = 0; j < nu; ++j) {
+                double g = (mode == 2 && gd) ? gd[k * nu + j] : 0.0;
+                if (mode == 2 && gd && k == N - 1) g = g + gd[N * nu + j];
+                gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+            }
+            return;
+        }
+        for (int i = 0; i < nx; ++i) {
+            if (gAd0)
+                for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = 0.0;
+            if (gBd0)
+                for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = 0.0;
+            if (ggd0) ggd0[b * nx + i] = 0.0;
+        }
+        if (gxt_o)
+            for (int i = 0; i < nxa; ++i) gxt_o[b * nxa + i] = gxt ? gxt[b * nxa + i] : 0.0;
+        return;
+    }
+    // w, the cotangent of the stepped x~, and g u: what the rows below share
+    const double* B0 = Bd + b * (long)N * nx * nu;
+    double w[nxa], gu[nu];
+    for (int i = 0; i < nxa; ++i) w[i] = (gxt ? gxt[b * nxa + i] : 0.0) + (gp ? gp[i] : 0.0);
+    for (int j = 0; j < nu; ++j) {
+        double acc = 0.0;
+        for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
+        gu[j] = w[nx + j] + acc;
+    }
+    if (row <= 2 * N) {  // g du_k
+        if (!gsol) return;
+        const int k = row - (N + 1);
+        for (int j = 0; j < nu; ++j) {
+            double g = k == 0 ? gu[j] : (gd ? gd[(k - 1) * nu + j] : 0.0);
+            if (k == N - 1 && gd) g = (g + gd[(N - 1) * nu + j]) + gd[N * nu + j];
+            gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+        }
+        return;
+    }
+    // the model row
+    const double* A0 = Ad + b * (long)N * nx * nx;
+    const double* xb = xt + b * nxa;
+    double uu[nu];
+    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + s[(N + 1) * nxa + j];
+    for (int i = 0; i < nx; ++i) {
+        if (gAd0)
+            for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
+        if (gBd0)
+            for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = w[i] * uu[j];
+        if (ggd0) ggd0[b * nx + i] = w[i];
+    }
+    if (gxt_o) {
+        for (int j = 0; j < nx; ++j) {
+            double acc = 0.0;
+            for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
+            gxt_o[b * nxa + j] = acc;
+        }
+        for (int j = 0; j < nu; ++j) gxt_o[b * nxa + nx + j] = gu[j];
+    }
+}
+
+// k_kin_ltv_shift's executed branch: sol = (S_0..S_N, U_0..U_{N-1}), cotangents gx (B,4), gu (B,2),
+// gpx (B,N+1,4), gpu (B,N+1,2) of the NEW x, u, pred_x, pred_u.  With w = gx + gpx[0], mode 0:
+//   plant step   gAd0 = w x',  gBd0 = w U_0',  ggd0 = w,  gx_before = Ad0' w,  g U_0 = Bd0' w + gu
+//                (the old u is not read by the forward)
+//   shift        g S_k = gpx[k-1] (2 <= k <= N),  g U_k = gpu[k-1] (1 <= k <= N-1);  U_{N-1} also takes
+//                gpu[N-1] and gpu[N], added in that order
+//   terminal     pred_x[N] = kin_update(S_N, U_{N-1}): kin_update_vjp of gpx[N] into S_N and, last,
+//                into U_{N-1} (at N = 2 that is U_1, which is all of the above at once)
+__global__ __launch_bounds__(256) void k_kin_ltv_shift_vjp(mpcqp_kin_vehicle vk, int N, int n, long B,
+                                                           const double* __restrict__ sol,
+                                                           const double* __restrict__ Ad,
+                                                           const double* __restrict__ Bd, const double* __restrict__ x,
+                                                           const int* __restrict__ dmode, const double* __restrict__ gx,
+                                                           const double* __restrict__ gu, const double* __restrict__ gpx,
+                                                           const double* __restrict__ gpu, double* __restrict__ gsol,
+                                                           double* __restrict__ gAd0, double* __restrict__ gBd0,
+                                                           double* __restrict__ ggd0, double* __restrict__ gx_o) {
+    const int rows = 2 * N + 2;
+    constexpr int nx = 4, nu = 2;  // the entry point's check
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * rows) return;
+    const long b = t / rows;
+    const int row = (int)(t - b * rows);
+    const bool skip = dmode && dmode[b] != 0;
+    const double* S = sol + b * n;
+    const double* U = S + (N + 1) * nx;
+    const double* gp = gpx ? gpx + b * (long)(N + 1) * nx : nullptr;
+    const double* gq = gpu ? gpu + b * (long)(N + 1) * nu : nullptr;
+    if (row <= 2 * N && skip) {  // the solution was not used
+        if (!gsol) return;
+        if (row <= N)
+            for (int i = 0; i < nx; ++i) gsol[b * n + row * nx + i] = 0.0;
+        else
+            for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nx + (row - (N + 1)) * nu + j] = 0.0;
+        return;
+    }
+    if (row <= N) {  // g S_row
+        if (!gsol) return;
+        const int k = row;
+        double g[nx];
+        for (int i = 0; i < nx; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nx + i] : 0.0;
+        if (k == N && gp) {
+            double ge[nx], gue[nu];
+            kin_update_vjp(vk, S + N * nx, U + (N - 1) * nu, gp + N * nx, ge, gue);
+            for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+        }
+        for (int i = 0; i < nx; ++i) gsol[b * n + k * nx + i] = g[i];
+        return;
+    }
+    double w[nx];
+    for (int i = 0; i < nx; ++i) w[i] = (gx ? gx[b * nx + i] : 0.0) + (gp ? gp[i] : 0.0);
+    if (row <= 2 * N) {  // g U_k
+        if (!gsol) return;
+        const int k = row - (N + 1);
+        const double* B0 = Bd + b * (long)N * nx * nu;
+        double g[nu];
+        for (int j = 0; j < nu; ++j) {
+            if (k == 0) {
+                double acc = 0.0;
+                for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
+                g[j] = acc + (gu ? gu[b * nu + j] : 0.0);
+            } else {
+                g[j] = gq ? gq[(k - 1) * nu + j] : 0.0;
+            }
+            if (k == N - 1 && gq) g[j] = (g[j] + gq[(N - 1) * nu + j]) + gq[N * nu + j];
+        }
+        if (k == N - 1 && gp) {
+            double ge[nx], gue[nu];
+            kin_update_vjp(vk, S + N * nx, U + (N - 1) * nu, gp + N * nx, ge, gue);
+            for (int j = 0; j < nu; ++j) g[j] = g[j] + gue[j];
+        }
+        for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nx + k * nu + j] = g[j];
+        return;
+    }
+    // the model row
+    if (skip) {
+        for (int i = 0; i < nx; ++i) {
+            if (gAd0)
+                for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = 0.0;
+            if (gBd0)
+                for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = 0.0;
+            if (ggd0) ggd0[b * nx + i] = 0.0;
+            if (gx_o) gx_o[b * nx + i] = gx ? gx[b * nx + i] : 0.0;
+        }
+        return;
+    }
+    const double* A0 = Ad + b * (long)N * nx * nx;
+    const double* xb = x + b * nx;
+    for (int i = 0; i < nx; ++i) {
+        if (gAd0)
+            for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
+        if (gBd0)
+            for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = w[i] * U[j];
+        if (ggd0) ggd0[b * nx + i] = w[i];
+    }
+    if (gx_o)
+        for (int j = 0; j < nx; ++j) {
+            double acc = 0.0;
+            for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
+            gx_o[b * nx + j] = acc;
+        }
+}
+
 // Tail of mpc_kinematics.main's loop (:397-456), per vehicle.  One model (the linearisation at
 // the current (x, u)) serves every stage, so Ad / Bd / gd are read at stage 0 of the (B, N, ..)
 // lists the assembly took.  A vehicle whose status is not `solved` is skipped whole (:398-402).
@@ -1938,6 +2173,38 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicl
     if (B == 0) return 0;
     return launch(L->dev, stream, B, 128, k_kin_ltv_shift, *veh, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
                   dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
+}
+
+int mpcqp_kin_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
+                               const double* dAd, const double* dBd, const double* dgd, const double* dxt_before,
+                               const int32_t* dmode, const double* dgxt, const double* dgpred, const double* dgpdu,
+                               double* dgsol, double* dgAd0, double* dgBd0, double* dggd0, double* dgxt_before,
+                               void* stream) {
+    (void)dgd;  // the step is affine in gd: its VJP does not read it
+    if (!L || !veh || !dsol || !dAd || !dBd || !dxt_before || B < 0)
+        return set_error(MPCQP_EINVAL, "kin_shift_vjp: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_shift_vjp: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgxt_before)) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_kin_shift_vjp, *veh, incr_k(*L), B, dsol, dAd, dBd,
+                  dxt_before, dmode, dgxt, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before);
+}
+
+int mpcqp_kin_ltv_shift_vjp_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
+                                   const double* dsol, const double* dAd, const double* dBd, const double* dx_before,
+                                   const int32_t* dmode, const double* dgx, const double* dgu, const double* dgpred_x,
+                                   const double* dgpred_u, double* dgsol, double* dgAd0, double* dgBd0, double* dggd0,
+                                   double* dgx_before, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dx_before || B < 0)
+        return set_error(MPCQP_EINVAL, "kin_ltv_shift_vjp: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_ltv_shift_vjp: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgx_before)) return 0;
+    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_kin_ltv_shift_vjp, *veh, L->N, L->n, B, dsol, dAd, dBd,
+                  dx_before, dmode, dgx, dgu, dgpred_x, dgpred_u, dgsol, dgAd0, dgBd0, dggd0, dgx_before);
 }
 
 int mpcqp_kin_reference_search_paths_device(int64_t B, int32_t N, int32_t nxa, int32_t npaths, int32_t npath,

@@ -797,6 +797,211 @@ def incr_shift_vjp(veh: VehicleParams, N, sol, Ad0, Bd0, xt, gxt=None, gpred=Non
             gg0.reshape(lead + (6,)), gx0.reshape(lead + (8,)))
 
 
+# ------------------------------------------- the kinematic tails and their VJPs --
+def kin_update_vjp(l_f, l_r, dt, x, u, w):
+    """The transpose of kin_update in closed form (mpc_device.hip::kin_update_vjp): x (.., 4), u
+    (.., 2) the point, w (.., 4) the cotangent of the new state -> (gx (.., 4), gu (.., 2)).  v
+    enters yaw's row through v1 = v + accel dt, which the reference forms first."""
+    x, u, w = np.asarray(x, float), np.asarray(u, float), np.asarray(w, float)
+    v, yaw, st = x[..., 2], x[..., 3], u[..., 0]
+    wb = l_f + l_r
+    v1 = v + u[..., 1] * dt
+    cy, sy, ts, cs = np.cos(yaw), np.sin(yaw), np.tan(st), np.cos(st)
+    w0, w1, w2, w3 = (w[..., i] for i in range(4))
+    gx = np.stack([w0, w1,
+                   ((w0 * cy * dt + w1 * sy * dt) + w2) + w3 * ts * dt / wb,
+                   (-w0 * v * sy * dt + w1 * v * cy * dt) + w3], axis=-1)
+    gu = np.stack([w3 * v1 * dt / (wb * (cs * cs)), w2 * dt + w3 * dt * dt * ts / wb], axis=-1)
+    return gx, gu
+
+
+def _kin_tail_args(N, nxa, sol, Ad0, Bd0, x, mode):
+    sol, x = np.asarray(sol, float), np.asarray(x, float)
+    lead = x.shape[:-1]
+    S = sol.reshape(-1, sol.shape[-1])
+    M = S.shape[0]
+    mode = np.zeros(M, int) if mode is None else np.broadcast_to(np.asarray(mode, int).reshape(-1), (M,))
+    return (lead, M, S[:, :(N + 1) * nxa].reshape(M, N + 1, nxa), S[:, (N + 1) * nxa:].reshape(M, N, 2),
+            np.asarray(Ad0, float).reshape(M, 4, 4), np.asarray(Bd0, float).reshape(M, 4, 2), x.reshape(M, nxa), mode)
+
+
+def _plant_step4(A0, B0, g0, x, uu):
+    """plant_step's association: (sum_j A0[i, j] x[j] + sum_j B0[i, j] u[j]) + g0[i]."""
+    M = x.shape[0]
+    xn = np.empty((M, 4))
+    for i in range(4):
+        acc = np.zeros(M)
+        for j in range(4):
+            acc = acc + A0[:, i, j] * x[:, j]
+        bu = np.zeros(M)
+        for j in range(2):
+            bu = bu + B0[:, i, j] * uu[:, j]
+        xn[:, i] = (acc + bu) + g0[:, i]
+    return xn
+
+
+def _plant_step4_vjp(A0, B0, w):
+    """(Ad0' w, Bd0' w) in the kernels' order of summation."""
+    M = w.shape[0]
+    ga, gb = np.empty((M, 4)), np.empty((M, 2))
+    for j in range(4):
+        acc = np.zeros(M)
+        for i in range(4):
+            acc = acc + A0[:, i, j] * w[:, i]
+        ga[:, j] = acc
+    for j in range(2):
+        acc = np.zeros(M)
+        for i in range(4):
+            acc = acc + B0[:, i, j] * w[:, i]
+        gb[:, j] = acc
+    return ga, gb
+
+
+def _cot(g, M, tail):
+    return np.zeros((M,) + tail) if g is None else np.asarray(g, float).reshape((M,) + tail)
+
+
+def kin_incr_shift(veh, N, sol, Ad0, Bd0, gd0, xt, mode=None, pred=None, pdu=None):
+    """The plant step and in-place horizon shift that simulate (mpc_incre_kine_func.py:385-428) and
+    mpc_increment_kinematics_pred_matrix.main (:442-472) share -- mpc_device.hip::kin_incr_step_shift
+    in numpy, operation by operation, for one vehicle or a batch, with the masks of k_kin_shift.
+
+    veh = (l_f, l_r, dt); sol (..., (N+1) 6 + N 2) = (x~_0..x~_N, du_0..du_{N-1}); Ad0 (..., 4, 4),
+    Bd0 (..., 4, 2), gd0 (..., 4) stage 0 of the linearisation; xt (..., 6) = x~ as the step started.
+    Returns (xt', pred', pdu').  mode 0 (the default): xt' = ((Ad0 x + Bd0 u) + gd0, u) with u =
+    u_prev + du_0; pred' (..., N+1, 6) = (xt', x~_2..x~_N, (kin_update(x_N, u_N), u_N)); pdu'
+    (..., N+1, 2) = (du_1..du_{N-1}, du_{N-1}, du_{N-1}).  mode 1 (done was set): xt and the given
+    pred, pdu come back as they are.  mode 2 (the stop rule fired on this step): xt stays, pred' is
+    the unpacked (x~_0..x~_N), pdu' = (du_0..du_{N-1}, du_{N-1})."""
+    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 6, sol, Ad0, Bd0, xt, mode)
+    g0 = np.asarray(gd0, float).reshape(M, 4)
+    uu = x0[:, 4:] + D[:, 0]
+    xn = np.concatenate([_plant_step4(A0, B0, g0, x0[:, :4], uu), uu], axis=1)
+    pn, dn = np.empty((M, N + 1, 6)), np.empty((M, N + 1, 2))
+    pn[:, 0] = xn
+    pn[:, 1:N] = X[:, 2:N + 1]
+    dn[:, 0:N - 1] = D[:, 1:N]
+    dn[:, N - 1] = dn[:, N] = D[:, N - 1]
+    pn[:, N, :4] = kin_update(*veh, X[:, N, :4], X[:, N, 4:])
+    pn[:, N, 4:] = X[:, N, 4:]
+    m2 = mode == 2
+    xn[m2], pn[m2], dn[m2] = x0[m2], X[m2], np.concatenate([D[m2], D[m2, -1:]], axis=1)
+    m1 = mode == 1
+    if m1.any():
+        xn[m1] = x0[m1]
+        pn[m1] = np.asarray(pred, float).reshape(M, N + 1, 6)[m1]
+        dn[m1] = np.asarray(pdu, float).reshape(M, N + 1, 2)[m1]
+    return xn.reshape(lead + (6,)), pn.reshape(lead + (N + 1, 6)), dn.reshape(lead + (N + 1, 2))
+
+
+def kin_incr_shift_vjp(veh, N, sol, Ad0, Bd0, xt, gxt=None, gpred=None, gpdu=None, mode=None):
+    """The VJP of kin_incr_shift in the order of mpc_device.hip's k_kin_shift_vjp
+    (mpcqp_kin_shift_vjp_device): cotangents gxt (..., 6), gpred (..., N+1, 6), gpdu (..., N+1, 2)
+    of (xt', pred', pdu') (None = zero); xt the value from BEFORE the step.  Returns (gsol, gAd0,
+    gBd0, ggd0, gxt_before) with the shapes of (sol, Ad0, Bd0, gd0, xt).
+
+    mode 0, with w = gxt + gpred[0]: gAd0 = w_x x', gBd0 = w_x u', ggd0 = w_x, the cotangent of u is
+    w_u + Bd0' w_x (to xt's input part and to du_0), gxt_before's state part Ad0' w_x; x~_k
+    (2 <= k <= N) takes gpred[k-1], du_k (1 <= k <= N-1) gpdu[k-1], du_{N-1} also gpdu[N-1] and
+    gpdu[N] in that order; x~_N also takes gpred[N]'s input part and then kin_update_vjp of
+    gpred[N]'s state part at (x_N, u_N), its own two parts.  mode 1: everything zero, gxt_before =
+    gxt.  mode 2: x~_k takes gpred[k], du_k gpdu[k], du_{N-1} also gpdu[N]; gxt_before = gxt, the
+    model outputs zero.  The cotangent of the previous pred / pdu (gpred / gpdu in mode 1, else
+    zero) is not formed here."""
+    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 6, sol, Ad0, Bd0, xt, mode)
+    gxt, gpred, gpdu = _cot(gxt, M, (6,)), _cot(gpred, M, (N + 1, 6)), _cot(gpdu, M, (N + 1, 2))
+    w = gxt + gpred[:, 0]
+    uu = x0[:, 4:] + D[:, 0]
+    gA0 = w[:, :4, None] * x0[:, None, :4]
+    gB0 = w[:, :4, None] * uu[:, None, :]
+    gg0 = w[:, :4].copy()
+    ga, gb = _plant_step4_vjp(A0, B0, w[:, :4])
+    gx0 = np.concatenate([ga, w[:, 4:] + gb], axis=1)
+    gX, gD = np.zeros((M, N + 1, 6)), np.zeros((M, N, 2))
+    gX[:, 2:N + 1] = gpred[:, 1:N]
+    gD[:, 0] = gx0[:, 4:]
+    gD[:, 1:N] = gpdu[:, 0:N - 1]
+    gD[:, N - 1] = (gD[:, N - 1] + gpdu[:, N - 1]) + gpdu[:, N]
+    ge, gue = kin_update_vjp(*veh, X[:, N, :4], X[:, N, 4:], gpred[:, N, :4])
+    gX[:, N, :4] = gX[:, N, :4] + ge
+    gX[:, N, 4:] = (gX[:, N, 4:] + gpred[:, N, 4:]) + gue
+    m2 = mode == 2
+    gX[m2] = gpred[m2]
+    gD[m2] = gpdu[m2, :N]
+    gD[m2, N - 1] = gD[m2, N - 1] + gpdu[m2, N]
+    m1 = mode == 1
+    gX[m1], gD[m1] = 0.0, 0.0
+    off = mode != 0
+    gA0[off], gB0[off], gg0[off], gx0[off] = 0.0, 0.0, 0.0, gxt[off]
+    gsol = np.concatenate([gX.reshape(M, -1), gD.reshape(M, -1)], axis=1)
+    return (gsol.reshape(lead + (gsol.shape[1],)), gA0.reshape(lead + (4, 4)), gB0.reshape(lead + (4, 2)),
+            gg0.reshape(lead + (4,)), gx0.reshape(lead + (6,)))
+
+
+def kin_ltv_shift(veh, N, sol, Ad0, Bd0, gd0, x, mode=None, u=None, pred_x=None, pred_u=None):
+    """The tail of mpc_kinematics_pred_matrix.main's loop (:534-563) -- mpc_device.hip::
+    k_kin_ltv_shift in numpy, operation by operation, for one vehicle or a batch.
+
+    veh = (l_f, l_r, dt); sol (..., (N+1) 4 + N 2) = (S_0..S_N, U_0..U_{N-1}); Ad0, Bd0, gd0 stage 0
+    of the linearisation; x (..., 4) the state as the step started.  Returns (x', u', pred_x',
+    pred_u'): x' = (Ad0 x + Bd0 U_0) + gd0, u' = U_0, pred_x' (..., N+1, 4) = (x', S_2..S_N,
+    kin_update(S_N, U_{N-1})) -- the terminal control is stage N-1's --, pred_u' (..., N+1, 2) =
+    (U_1..U_{N-1}, U_{N-1}, U_{N-1}).  mode 1 (status != solved): the given x, u, pred_x, pred_u
+    come back as they are."""
+    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, sol, Ad0, Bd0, x, mode)
+    g0 = np.asarray(gd0, float).reshape(M, 4)
+    xn = _plant_step4(A0, B0, g0, x0, U[:, 0])
+    un = U[:, 0].copy()
+    px, pu = np.empty((M, N + 1, 4)), np.empty((M, N + 1, 2))
+    px[:, 0] = xn
+    px[:, 1:N] = S[:, 2:N + 1]
+    px[:, N] = kin_update(*veh, S[:, N], U[:, N - 1])
+    pu[:, 0:N - 1] = U[:, 1:N]
+    pu[:, N - 1] = pu[:, N] = U[:, N - 1]
+    m1 = mode != 0
+    if m1.any():
+        xn[m1] = x0[m1]
+        un[m1] = np.asarray(u, float).reshape(M, 2)[m1]
+        px[m1] = np.asarray(pred_x, float).reshape(M, N + 1, 4)[m1]
+        pu[m1] = np.asarray(pred_u, float).reshape(M, N + 1, 2)[m1]
+    return (xn.reshape(lead + (4,)), un.reshape(lead + (2,)), px.reshape(lead + (N + 1, 4)),
+            pu.reshape(lead + (N + 1, 2)))
+
+
+def kin_ltv_shift_vjp(veh, N, sol, Ad0, Bd0, x, gx=None, gu=None, gpred_x=None, gpred_u=None, mode=None):
+    """The VJP of kin_ltv_shift in the order of mpc_device.hip's k_kin_ltv_shift_vjp
+    (mpcqp_kin_ltv_shift_vjp_device): cotangents gx (..., 4), gu (..., 2), gpred_x (..., N+1, 4),
+    gpred_u (..., N+1, 2) of (x', u', pred_x', pred_u') (None = zero); x from BEFORE the step.
+    Returns (gsol, gAd0, gBd0, ggd0, gx_before).
+
+    mode 0, with w = gx + gpred_x[0]: gAd0 = w x', gBd0 = w U_0', ggd0 = w, gx_before = Ad0' w,
+    g U_0 = Bd0' w + gu; S_k (2 <= k <= N) takes gpred_x[k-1], U_k (1 <= k <= N-1) gpred_u[k-1],
+    U_{N-1} also gpred_u[N-1] and gpred_u[N] in that order; kin_update_vjp of gpred_x[N] at
+    (S_N, U_{N-1}) goes into S_N and, last, into U_{N-1}.  mode 1: everything zero, gx_before = gx;
+    the cotangent of the previous u, pred_x, pred_u (gu, gpred_x, gpred_u) is not formed here."""
+    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, sol, Ad0, Bd0, x, mode)
+    gx, gu = _cot(gx, M, (4,)), _cot(gu, M, (2,))
+    gpx, gpu = _cot(gpred_x, M, (N + 1, 4)), _cot(gpred_u, M, (N + 1, 2))
+    w = gx + gpx[:, 0]
+    gA0 = w[:, :, None] * x0[:, None, :]
+    gB0 = w[:, :, None] * U[:, 0][:, None, :]
+    gg0 = w.copy()
+    gxb, gb = _plant_step4_vjp(A0, B0, w)
+    gS, gU = np.zeros((M, N + 1, 4)), np.zeros((M, N, 2))
+    gS[:, 2:N + 1] = gpx[:, 1:N]
+    gU[:, 0] = gb + gu
+    gU[:, 1:N] = gpu[:, 0:N - 1]
+    gU[:, N - 1] = (gU[:, N - 1] + gpu[:, N - 1]) + gpu[:, N]
+    ge, gue = kin_update_vjp(*veh, S[:, N], U[:, N - 1], gpx[:, N])
+    gS[:, N] = gS[:, N] + ge
+    gU[:, N - 1] = gU[:, N - 1] + gue
+    off = mode != 0
+    gS[off], gU[off], gA0[off], gB0[off], gg0[off], gxb[off] = 0.0, 0.0, 0.0, 0.0, 0.0, gx[off]
+    gsol = np.concatenate([gS.reshape(M, -1), gU.reshape(M, -1)], axis=1)
+    return (gsol.reshape(lead + (gsol.shape[1],)), gA0.reshape(lead + (4, 4)), gB0.reshape(lead + (4, 2)),
+            gg0.reshape(lead + (4,)), gxb.reshape(lead + (4,)))
+
+
 # ------------------------------------------------------------ batch generators --
 CONFIGS = {
     1: dict(name="slack-single-N20", layout="slack", N=20, B=1),

@@ -92,6 +92,7 @@ def _bind():
                                              vp]
     L.mpcqp_kin_reference_search_device.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, vp, d, vp, i32, vp]
     L.mpcqp_kin_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 11 + [i32, vp, vp]
+    L.mpcqp_kin_shift_vjp_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 15
     L.mpcqp_ltv_layout_create.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, _P(vp)]
     L.mpcqp_ltv_layout_dims.argtypes = [vp, _P(i32), _P(i32), _P(i32), _P(i32)]
     L.mpcqp_ltv_layout_pattern.argtypes = [vp] * 9
@@ -100,6 +101,7 @@ def _bind():
     L.mpcqp_ltv_layout_free.restype = None
     L.mpcqp_kin_rollout_device.argtypes = [_P(KinVehicle), i64, i32, vp, vp, vp, vp, i32, vp]
     L.mpcqp_kin_ltv_shift_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 12 + [i32, vp, vp]
+    L.mpcqp_kin_ltv_shift_vjp_device.argtypes = [vp, _P(KinVehicle), i64] + [vp] * 15
     L.mpcqp_lti_step_device.argtypes = [i64, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp,
                                         vp, vp, i32, vp, i32, vp]
     L.mpcqp_kin_reference_search_paths_device.argtypes = [i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, d, vp, i32,
@@ -856,6 +858,146 @@ def reference_search_kin(path_x, path_y, path_yaw, set_speed, pred, dt):
                                                _p(set_speed), _p(pred), float(dt), _p(Xr), pred.device.index or 0,
                                                _stream(torch, pred.device)), "kin_reference_search")
     return Xr
+
+
+def _mode_in(mode, B, what):
+    import torch
+    if mode is not None and (tuple(mode.shape) != (B,) or mode.dtype != torch.int32 or not mode.is_cuda):
+        raise ValueError(f"{what} must be an int32 device tensor of shape ({B},)")
+    return None if mode is None else mode.contiguous()
+
+
+def kin_shift(layout, veh: KinVehicle, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt=None, done=None):
+    """The tail of simulate's loop (mpcqp_kin_shift_device, no trajectory record) as a function:
+    sol (B, n), Ad (B, N, 4, 4), Bd (B, N, 4, 2), gd (B, N, 4) (stage 0 is read), Xr (B, 4, N+1), xt
+    (B, 6), pred (B, N+1, 6), pdu (B, N+1, 2), finish_cnt / done int32 (B,) (None: zeros) ->
+    (xt', pred', pdu', finish_cnt', done', mode), all new tensors; nothing is written in place.
+    mode (B,) int32 is what kin_shift_vjp needs to know: 1 where done was already set (the vehicle
+    was left untouched), 2 where this step set it (the stop rule: pred', pdu' are the unpacked
+    solution, xt' = xt), 0 where the vehicle was stepped."""
+    import torch
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd, gd = _shift_in(Ad, (B, N, 4, 4), "Ad"), _shift_in(Bd, (B, N, 4, 2), "Bd"), _shift_in(gd, (B, N, 4), "gd")
+    Xr = _shift_in(Xr, (B, 4, N + 1), "Xr")
+    xt1 = _shift_in(xt, (B, 6), "xt").clone()
+    pred1 = _shift_in(pred, (B, N + 1, 6), "pred").clone()
+    pdu1 = _shift_in(pdu, (B, N + 1, 2), "pdu").clone()
+    ikw = dict(dtype=torch.int32, device=sol.device)
+    cnt1 = torch.zeros(B, **ikw) if finish_cnt is None else finish_cnt.to(**ikw).clone()
+    done0 = torch.zeros(B, **ikw) if done is None else done.to(**ikw).contiguous()
+    done1 = done0.clone()
+    _check(_bind().mpcqp_kin_shift_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(Xr), _p(xt1),
+                                          _p(pred1), _p(pdu1), _p(cnt1), _p(done1), None, 0, None,
+                                          _stream(torch, sol.device)), "kin_shift")
+    mode = torch.where(done0 != 0, 1, torch.where(done1 != 0, 2, 0)).to(torch.int32)
+    return xt1, pred1, pdu1, cnt1, done1, mode
+
+
+def kin_ltv_shift(layout, veh: KinVehicle, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
+    """The tail of mpc_kinematics_pred_matrix.main's loop (mpcqp_kin_ltv_shift_device, no trajectory
+    record) as a function: sol (B, n), status (B,) int32 or None (all solved), Ad, Bd, gd as for
+    kin_shift, x (B, 4), u (B, 2), pred_x (B, N+1, 4), pred_u (B, N+1, 2) -> (x', u', pred_x',
+    pred_u', mode), all new tensors.  mode (B,) int32 = (status != 1): a skipped vehicle keeps x, u,
+    pred_x, pred_u bit for bit."""
+    import torch
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd, gd = _shift_in(Ad, (B, N, 4, 4), "Ad"), _shift_in(Bd, (B, N, 4, 2), "Bd"), _shift_in(gd, (B, N, 4), "gd")
+    x1, u1 = _shift_in(x, (B, 4), "x").clone(), _shift_in(u, (B, 2), "u").clone()
+    px1 = _shift_in(pred_x, (B, N + 1, 4), "pred_x").clone()
+    pu1 = _shift_in(pred_u, (B, N + 1, 2), "pred_u").clone()
+    ikw = dict(dtype=torch.int32, device=sol.device)
+    if status is None:
+        mode = torch.zeros(B, **ikw)
+    else:
+        status = _mode_in(status, B, "kin_ltv_shift: status")
+        mode = (status != 1).to(torch.int32)
+    skipped = torch.zeros(B, **ikw)
+    _check(_bind().mpcqp_kin_ltv_shift_device(layout._h, C.byref(veh), B, _p(sol), _po(status), _p(Ad), _p(Bd), _p(gd),
+                                              _p(x1), _p(u1), _p(px1), _p(pu1), _p(skipped), None, None, 0, None,
+                                              _stream(torch, sol.device)), "kin_ltv_shift")
+    return x1, u1, px1, pu1, mode
+
+
+def _kin_tail_vjp(name, symbol, layout, veh, B, head, mode, cots, shapes, outputs, want, out, prev):
+    """What kin_shift_vjp and kin_ltv_shift_vjp share: cotangent / output checks, the call, and the
+    pass-through cotangents of the previous horizon (`prev`: output name -> cotangent name)."""
+    import torch
+    from types import SimpleNamespace
+    dev = head[0].device
+    for k, t, shape in cots:
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shape}")
+    want = list(outputs) if want is None else list(want)
+    bad = sorted(set(want) - set(outputs))
+    if bad:
+        raise ValueError(f"{name}: unknown output(s) {', '.join(bad)}")
+    o = SimpleNamespace(**{k: None for k in outputs})
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shapes[k], dtype=torch.float64, device=dev)
+        elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
+        setattr(o, k, t)
+    _check(getattr(_bind(), symbol)(layout._h, C.byref(veh), B, *(_po(t) for t in head), _po(mode),
+                                    *(_po(t) for _, t, _ in cots), *(_po(getattr(o, k)) for k in outputs),
+                                    _stream(torch, dev)), name)
+    given = {k: t for k, t, _ in cots}
+    for k_out, k_cot in prev.items():
+        g = given[k_cot]
+        if g is None:
+            setattr(o, k_out, None)
+        elif mode is None:
+            setattr(o, k_out, torch.zeros_like(g))
+        else:
+            setattr(o, k_out, torch.where((mode == 1).view((-1,) + (1,) * (g.dim() - 1)), g, 0.0))
+    return o
+
+
+KIN_LTV_SHIFT_VJP_OUTPUTS = ("gsol", "gAd0", "gBd0", "ggd0", "gx")
+
+
+def kin_shift_vjp(layout, veh: KinVehicle, sol, Ad, Bd, xt, mode=None, gxt=None, gpred=None, gpdu=None, want=None,
+                  out=None):
+    """The transpose of kin_shift (mpcqp_kin_shift_vjp_device; mpcqp.h has the formulas and the
+    modes).  sol, Ad, Bd as the forward took them, xt the value from BEFORE the step, mode kin_shift's
+    (None: every vehicle stepped); cotangents gxt (B, 6), gpred (B, N+1, 6), gpdu (B, N+1, 2) of the
+    new xt, pred, pdu: contiguous float64 device tensors, None = zero.  want / out as for
+    incr_shift_vjp, over SHIFT_VJP_OUTPUTS.  Returns a namespace with gsol (B, n), gAd0 (B, 4, 4),
+    gBd0 (B, 4, 2), ggd0 (B, 4), gxt (B, 6), and the cotangents of the PREVIOUS pred and pdu, which
+    the kernel leaves to the caller: gpred_prev, gpdu_prev = the given cotangent where mode is 1,
+    zero elsewhere (None for a None cotangent)."""
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd = _shift_in(Ad, (B, N, 4, 4), "Ad"), _shift_in(Bd, (B, N, 4, 2), "Bd")
+    xt = _shift_in(xt, (B, 6), "xt")
+    mode = _mode_in(mode, B, "kin_shift_vjp: mode")
+    shapes = dict(gsol=(B, layout.n), gAd0=(B, 4, 4), gBd0=(B, 4, 2), ggd0=(B, 4), gxt=(B, 6))
+    return _kin_tail_vjp("kin_shift_vjp", "mpcqp_kin_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, None, xt), mode,
+                         (("gxt", gxt, (B, 6)), ("gpred", gpred, (B, N + 1, 6)), ("gpdu", gpdu, (B, N + 1, 2))),
+                         shapes, SHIFT_VJP_OUTPUTS, want, out, dict(gpred_prev="gpred", gpdu_prev="gpdu"))
+
+
+def kin_ltv_shift_vjp(layout, veh: KinVehicle, sol, Ad, Bd, x, mode=None, gx=None, gu=None, gpred_x=None,
+                      gpred_u=None, want=None, out=None):
+    """The transpose of kin_ltv_shift (mpcqp_kin_ltv_shift_vjp_device).  x the state from BEFORE the
+    step, mode kin_ltv_shift's; cotangents gx (B, 4), gu (B, 2), gpred_x (B, N+1, 4), gpred_u
+    (B, N+1, 2) of the new x, u, pred_x, pred_u, None = zero.  Outputs KIN_LTV_SHIFT_VJP_OUTPUTS:
+    gsol (B, n), gAd0 (B, 4, 4), gBd0 (B, 4, 2), ggd0 (B, 4), gx (B, 4); and the caller's part, the
+    cotangents of the PREVIOUS u, pred_x, pred_u: gu_prev, gpred_x_prev, gpred_u_prev = the given
+    cotangent where mode is 1, zero elsewhere (None for a None cotangent)."""
+    B, N = sol.shape[0], layout.N
+    sol = _shift_in(sol, (B, layout.n), "sol")
+    Ad, Bd = _shift_in(Ad, (B, N, 4, 4), "Ad"), _shift_in(Bd, (B, N, 4, 2), "Bd")
+    x = _shift_in(x, (B, 4), "x")
+    mode = _mode_in(mode, B, "kin_ltv_shift_vjp: mode")
+    shapes = dict(gsol=(B, layout.n), gAd0=(B, 4, 4), gBd0=(B, 4, 2), ggd0=(B, 4), gx=(B, 4))
+    return _kin_tail_vjp("kin_ltv_shift_vjp", "mpcqp_kin_ltv_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, x), mode,
+                         (("gx", gx, (B, 4)), ("gu", gu, (B, 2)), ("gpred_x", gpred_x, (B, N + 1, 4)),
+                          ("gpred_u", gpred_u, (B, N + 1, 2))), shapes, KIN_LTV_SHIFT_VJP_OUTPUTS, want, out,
+                         dict(gu_prev="gu", gpred_x_prev="gpred_x", gpred_u_prev="gpred_u"))
 
 
 class KinematicMPC(_ClosedLoop):

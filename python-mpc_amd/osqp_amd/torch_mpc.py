@@ -12,6 +12,10 @@ DESIGN.md §15):
   incr_assemble(layout, Ad, Bd, gd, xt0, Xr, ...)       -> Ax, q, l, u [, Px]
   affine_assemble(assembler, theta, regime)             -> q, l, u
   incr_shift(layout, veh, sol, Ad, Bd, gd, xt)          -> xt', pred', pdu'
+  kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)
+                                                        -> xt', pred', pdu', finish_cnt', done', mode
+  kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)
+                                                        -> x', u', pred_x', pred_u', mode
 
 and ``MPCLayer`` composes the assembly with one ``QPLayer``: (Ad, Bd, gd, x0, Xr[, weights]) ->
 (X, U, y), so that d u_0 / d x0 and d loss / d Q are one backward call on the device.  Every call
@@ -23,7 +27,9 @@ plant step is Ad_0 x + Bd_0 u + gd_0 and its shift copies stages of the solution
 operations between one MPCLayer per control step.  ``DynamicRollout`` differentiates
 T steps of that loop -- terminal Euler step included -- on ONE solver handle: the forward keeps a
 tape of small solution records, the backward sets each step up again, loads its record and runs the
-adjoint.
+adjoint.  ``KinematicRollout`` and ``KinematicLTVRollout`` are the same body over the
+two kinematic loops (KinematicMPC, KinematicLTVMPC), whose tails carry the stop rule's and the skip
+rule's masks.
 """
 from __future__ import annotations
 
@@ -31,7 +37,8 @@ from . import mpc_device as md
 from .torch_qp import QPLayer
 
 __all__ = ["linearise_kinematics", "linearise_dynamics", "ltv_assemble", "incr_assemble", "affine_assemble",
-           "incr_shift", "MPCLayer", "DynamicRollout"]
+           "incr_shift", "kin_shift", "kin_ltv_shift", "MPCLayer", "DynamicRollout", "KinematicRollout",
+           "KinematicLTVRollout"]
 
 _FN = None
 
@@ -151,8 +158,69 @@ def _functions():
 
             return (None, None, g.gsol, stage0(g.gAd0, (6, 6)), stage0(g.gBd0, (6, 2)), stage0(g.ggd0, (6,)), g.gxt)
 
+    def stage0(t, N):  # the tails read the model of stage 0 only: its cotangent, zero in the others
+        if t is None:
+            return None
+        full = t.new_zeros((t.shape[0], N) + tuple(t.shape[1:]))
+        full[:, 0] = t
+        return full
+
+    class KinShift(torch.autograd.Function):
+        """inputs (layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)"""
+
+        @staticmethod
+        def forward(ctx, layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done):
+            sol, Ad, Bd, gd, Xr, xt, pred, pdu = (_c(t) for t in (sol, Ad, Bd, gd, Xr, xt, pred, pdu))
+            xt1, pred1, pdu1, cnt1, done1, mode = md.kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu,
+                                                               finish_cnt, done)
+            ctx.layout, ctx.veh = layout, veh
+            ctx.save_for_backward(sol, Ad, Bd, xt, mode)
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(cnt1, done1, mode)
+            return xt1, pred1, pdu1, cnt1, done1, mode
+
+        @staticmethod
+        def backward(ctx, gxt, gpred, gpdu, *_):
+            if gxt is None and gpred is None and gpdu is None:
+                return (None,) * 12
+            sol, Ad, Bd, xt, mode = ctx.saved_tensors
+            need = ctx.needs_input_grad
+            want = [k for k, n in zip(md.SHIFT_VJP_OUTPUTS, (need[2], need[3], need[4], need[5], need[7])) if n]
+            g = md.kin_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, xt, mode, _c(gxt), _c(gpred), _c(gpdu), want=want)
+            N = ctx.layout.N
+            return (None, None, g.gsol, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), None, g.gxt,
+                    g.gpred_prev if need[8] else None, g.gpdu_prev if need[9] else None, None, None)
+
+    class KinLTVShift(torch.autograd.Function):
+        """inputs (layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)"""
+
+        @staticmethod
+        def forward(ctx, layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
+            sol, Ad, Bd, gd, x, u, pred_x, pred_u = (_c(t) for t in (sol, Ad, Bd, gd, x, u, pred_x, pred_u))
+            x1, u1, px1, pu1, mode = md.kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)
+            ctx.layout, ctx.veh = layout, veh
+            ctx.save_for_backward(sol, Ad, Bd, x, mode)
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(mode)
+            return x1, u1, px1, pu1, mode
+
+        @staticmethod
+        def backward(ctx, gx, gu, gpx, gpu, *_):
+            if gx is None and gu is None and gpx is None and gpu is None:
+                return (None,) * 11
+            sol, Ad, Bd, x, mode = ctx.saved_tensors
+            need = ctx.needs_input_grad
+            want = [k for k, n in zip(md.KIN_LTV_SHIFT_VJP_OUTPUTS, (need[2], need[4], need[5], need[6], need[7])) if n]
+            g = md.kin_ltv_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, x, mode, _c(gx), _c(gu), _c(gpx), _c(gpu),
+                                     want=want)
+            N = ctx.layout.N
+            return (None, None, g.gsol, None, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), g.gx,
+                    g.gu_prev if need[8] else None, g.gpred_x_prev if need[9] else None,
+                    g.gpred_u_prev if need[10] else None)
+
     class Rollout(torch.autograd.Function):
-        """inputs (roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w)"""
+        """inputs (roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w): the rollouts of the incremental
+        layout, whose state and horizon are one tensor each"""
 
         @staticmethod
         def forward(ctx, roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w):
@@ -160,7 +228,8 @@ def _functions():
             weights = (Q, QN, R) if use_w else None
             ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
             ctx.set_materialize_grads(False)
-            XT, DU0, pred, ctx.tape = roll._on_stream(lambda: roll._forward(xt0, pred0, T, Xr, path, weights))
+            (XT,), DU0, (pred,), ctx.tape = roll._on_stream(lambda: roll._forward((xt0,), (pred0,), T, Xr, path,
+                                                                                   weights))
             return XT, DU0, pred
 
         @staticmethod
@@ -169,11 +238,38 @@ def _functions():
                 return (None,) * 10
             roll = ctx.roll
             need = dict(zip(("xt0", "pred0", "Xr", "Q", "QN", "R"), ctx.needs_input_grad[3:9]))
-            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, _c(gXT), _c(gDU0),
-                                                       _c(gpred), need))
-            return (None, None, None, g["xt0"], g["pred0"], g["Xr"], g["Q"], g["QN"], g["R"], None)
+            need["state"], need["hor"] = (need["xt0"],), (need["pred0"],)
+            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, (_c(gXT),), _c(gDU0),
+                                                       (_c(gpred),), need))
+            return (None, None, None, g["state"][0], g["hor"][0], g["Xr"], g["Q"], g["QN"], g["R"], None)
 
-    _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine, IncrShift=IncrShift, Rollout=Rollout)
+    class RolloutLTV(torch.autograd.Function):
+        """inputs (roll, T, path, x0, u0, pred_x0, pred_u0, Xr, Q, QN, R, use_w): the LTV layout's
+        rollout, whose state is (x, u) and whose horizon is (pred_x, pred_u)"""
+
+        @staticmethod
+        def forward(ctx, roll, T, path, x0, u0, px0, pu0, Xr, Q, QN, R, use_w):
+            x0, u0, px0, pu0, Xr, Q, QN, R = (_c(t) for t in (x0, u0, px0, pu0, Xr, Q, QN, R))
+            weights = (Q, QN, R) if use_w else None
+            ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
+            ctx.set_materialize_grads(False)
+            (X, U), _, (px, pu), ctx.tape = roll._on_stream(lambda: roll._forward((x0, u0), (px0, pu0), T, Xr, path,
+                                                                                  weights))
+            return X, U, px, pu
+
+        @staticmethod
+        def backward(ctx, gX, gU, gpx, gpu):
+            if gX is None and gU is None and gpx is None and gpu is None:
+                return (None,) * 12
+            roll = ctx.roll
+            n = ctx.needs_input_grad
+            need = dict(state=(n[3], n[4]), hor=(n[5], n[6]), Xr=n[7], Q=n[8], QN=n[9], R=n[10])
+            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, (_c(gX), _c(gU)), None,
+                                                       (_c(gpx), _c(gpu)), need))
+            return (None, None, None, *g["state"], *g["hor"], g["Xr"], g["Q"], g["QN"], g["R"], None)
+
+    _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine, IncrShift=IncrShift,
+                          KinShift=KinShift, KinLTVShift=KinLTVShift, Rollout=Rollout, RolloutLTV=RolloutLTV)
     return _FN
 
 
@@ -228,6 +324,28 @@ def incr_shift(layout, veh, sol, Ad, Bd, gd, xt):
     return _functions().IncrShift.apply(layout, veh, sol, Ad, Bd, gd, xt)
 
 
+def kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt=None, done=None):
+    """mpc_device.kin_shift -- the tail of simulate's loop on the kinematic bicycle: stop rule, plant
+    step, horizon shift, terminal update_kinematics_model step -- differentiable in sol, Ad, Bd, gd,
+    xt, pred and pdu (mpc_device.kin_shift_vjp): (xt', pred', pdu', finish_cnt', done', mode).  Only
+    stage 0 of Ad, Bd, gd is read.  pred and pdu get a gradient only where the vehicle was already
+    done (mode 1: they pass through); Xr only steers the stop rule and gets none."""
+    if layout._kind != "incr":
+        raise ValueError("kin_shift needs an IncrementalLayout")
+    return _functions().KinShift.apply(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)
+
+
+def kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
+    """mpc_device.kin_ltv_shift -- the tail of mpc_kinematics_pred_matrix.main's loop: skip rule,
+    plant step, horizon shift, terminal update_kinematics_model step -- differentiable in sol, Ad,
+    Bd, gd, x, u, pred_x and pred_u (mpc_device.kin_ltv_shift_vjp): (x', u', pred_x', pred_u', mode).
+    u, pred_x and pred_u get a gradient only where the vehicle was skipped (status != 1: they pass
+    through)."""
+    if layout._kind != "ltv":
+        raise ValueError("kin_ltv_shift needs an LTVLayout")
+    return _functions().KinLTVShift.apply(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)
+
+
 class MPCLayer:
     """One MPC step of either layout as a differentiable map
     ``layer(Ad, Bd, gd, x0, Xr, weights=None, xlo=None, xhi=None) -> (X, U, y)``:
@@ -268,7 +386,180 @@ class MPCLayer:
         return x[:, :ns].reshape(self.B, L.N + 1, L.nxa), x[:, ns:].reshape(self.B, L.N, L.nu), y
 
 
-class DynamicRollout:
+class _Rollout:
+    """What the rollouts share: T control steps on ONE DeviceBatch with a tape of solution records,
+    and the backward that walks it in reverse.  The loop's state and its
+    predicted horizon are tuples of tensors of widths ``_STATE`` and ``_HOR`` (per stage).  A subclass
+    states its ``_NAME``, ``_LAYOUT`` = (kind, nx, nu, words), ``_FN`` and the model-specific parts:
+
+      _problem(state, hor, Xr_t, path, weights)  -> Xr, Ad, Bd, gd, Px, (Ax, q, l, u)
+      _shift(sol, status, Ad, Bd, gd, Xr, state, hor, aux) -> state', hor', mode, aux'
+      _shift_vjp(sol, Ad, Bd, state, mode, g_state, g_hor) -> (namespace with gsol, gAd0, gBd0, ggd0),
+                                                   [cotangents of the state before], [of the previous
+                                                   horizon through the tail's masks] or None
+      _linearise_vjp(hor, gAd, gBd, ggd)         -> [cotangents of the horizon]
+      _exempt(mode)                              -> (B,) bool of the vehicles whose solution the step
+                                                   did not use, or None
+
+    ``_DU0``: the outputs include each step's first input rows of the solution, whose cotangent is
+    added to the adjoint's seed.  ``aux`` is what the tail carries besides state and horizon."""
+
+    _DU0 = True
+
+    def __init__(self, layout, B, veh, device=0, strict=True, warm_start=False, **settings):
+        import torch
+        from . import DeviceBatch
+        kind, nx, nu, words = self._LAYOUT
+        if layout._kind != kind or (layout.nx, layout.nu) != (nx, nu):
+            raise ValueError(f"{self._NAME} needs {words} (nx {nx}, nu {nu})")
+        self.torch, self.layout, self.veh = torch, layout, veh
+        self.B, self.N = int(B), layout.N
+        self.dev = torch.device("cuda", int(device))
+        self.strict, self.shift_warm = bool(strict), bool(warm_start)
+        P, A, _, _ = layout.pattern()
+        settings.pop("verbose", None)
+        self.batch = DeviceBatch(P, A, self.B, device=int(device), **settings)
+        self.Px = torch.from_numpy(P.data.copy()).to(self.dev)[None, :].repeat(self.B, 1).contiguous()
+        self.stream = torch.cuda.Stream(self.dev)
+        self.status = self.iters = self.astat = self.ares = self.act = self.mode = None
+        self._fn = getattr(_functions(), self._FN)
+
+    def tape_doubles_per_instance(self):
+        """Doubles the tape holds per step and instance: the state, the horizon, sol and the record
+        (a loop with masks keeps one int32 mode per step and instance besides)."""
+        L = self.layout
+        return sum(self._STATE) + (L.N + 1) * sum(self._HOR) + L.n + self.batch.record_width
+
+    def _check_call(self, T, Xr, path, tensors, path_words):
+        torch, B, N = self.torch, self.B, self.N
+        if T < 1:
+            raise ValueError(f"{self._NAME}: T must be at least 1")
+        nx = self.layout.nx
+        if (Xr is None) == (path is None):
+            raise ValueError(f"{self._NAME}: give either Xr (T, B, {nx}, N+1) or path = {path_words}")
+        for t, shape, k in tensors + ((Xr, (T, B, nx, N + 1), "Xr"),):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.dev):
+                raise ValueError(f"{self._NAME}: {k} must be a float64 tensor of shape {shape} on {self.dev}")
+
+    def _on_stream(self, fn):
+        """fn() on the rollout's stream, ordered after the caller's current stream; the caller's
+        stream is ordered after it (mpc_device._ClosedLoop's rule)."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            out = fn()
+        caller.wait_stream(self.stream)
+        return out
+
+    def _aux0(self):
+        return None
+
+    def _exempt(self, mode):
+        return None
+
+    def _forward(self, state, hor, T, Xr, path, weights):
+        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
+        st = md._stream(torch, self.dev)  # self.stream
+        kw = dict(dtype=torch.float64, device=self.dev)
+        trajs = [torch.empty((B, T + 1, w), **kw) for w in self._STATE]
+        DU0 = torch.empty((B, T, L.nu), **kw) if self._DU0 else None
+        status = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        iters = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        for X, s in zip(trajs, state):
+            X[:, 0] = s
+        tape, y, nd, aux = [], None, (N + 1) * L.nxa, self._aux0()
+        for t in range(T):
+            Xr_t, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(state, hor, None if Xr is None else Xr[t], path,
+                                                                weights)
+            b.setup(Px, Ax, q, l, u, stream=st)
+            if self.shift_warm and t > 0:
+                b.warm_start(*md.warm_shift(N, L.nxa, L.nu, tape[-1][2], y), stream=st)
+            sol, y = torch.empty((B, L.n), **kw), torch.empty((B, L.m), **kw)
+            b.solve(sol, y, status[t], iters[t], stream=st)
+            rec = b.save_solution(torch.empty((B, b.record_width), **kw), stream=st)
+            state1, hor1, mode, aux = self._shift(sol, status[t], Ad, Bd, gd, Xr_t, state, hor, aux)
+            tape.append((state, hor, sol, rec, mode))
+            state, hor = state1, hor1
+            for X, s in zip(trajs, state):
+                X[:, t + 1] = s
+            if DU0 is not None:
+                DU0[:, t] = sol[:, nd:nd + L.nu]
+        self.status, self.iters = status, iters
+        if tape[0][4] is not None:
+            self.mode = torch.stack([s[4] for s in tape])
+        return trajs, DU0, hor, dict(steps=tape, status=status, iters=iters)
+
+    def _backward(self, tape, Xr, path, weights, gtraj, gDU0, ghor, need):
+        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
+        st = md._stream(torch, self.dev)
+        steps = tape["steps"]
+        T, nd, nx, nu = len(steps), (N + 1) * L.nxa, L.nx, L.nu
+        kw = dict(dtype=torch.float64, device=self.dev)
+        astat = torch.empty((T, B), dtype=torch.int32, device=self.dev)
+        ares = torch.empty((T, B), **kw)
+        act = torch.empty((T, B, L.m), dtype=torch.int8, device=self.dev)
+        exempt = torch.zeros((T, B), dtype=torch.bool, device=self.dev)
+        wnames = [k for k in ("Q", "QN", "R") if weights is not None and need[k]]
+        gw = {k: torch.zeros((B,) + ((nu, nu) if k == "R" else (nx, nx)), **kw) for k in wnames}
+        gXr = torch.zeros((T, B, nx, N + 1), **kw) if Xr is not None and need["Xr"] else None
+        want = ["gAd", "gBd", "ggd", "gx0"] + ["gXr"] * (gXr is not None) + ["g" + k for k in wnames]
+        g_state = [g[:, T].clone() if g is not None else torch.zeros((B, w), **kw) for g, w in zip(gtraj, self._STATE)]
+        g_hor = list(ghor)
+        for t in reversed(range(T)):
+            state, hor, sol, rec, mode = steps[t]
+            Xr_t, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(state, hor, None if Xr is None else Xr[t], path,
+                                                                weights)
+            b.setup(Px, Ax, q, l, u, stream=st)
+            b.load_solution(rec, stream=st)
+            sh, g_before, g_hor_prev = self._shift_vjp(sol, Ad, Bd, state, mode, g_state, g_hor)
+            if gDU0 is not None:
+                sh.gsol[:, nd:nd + nu] += gDU0[:, t]
+            a = b.adjoint(sh.gsol, None, act=act[t], ares=ares[t], astat=astat[t], stream=st)
+            v = L.assemble_vjp(a.gAx, a.gq, a.gl, a.gu, gPx=a.gPx if wnames else None, Xr=Xr_t,
+                               weights=None if weights is None else (weights[0], weights[1], None), want=want)
+            v.gAd[:, 0] += sh.gAd0
+            v.gBd[:, 0] += sh.gBd0
+            v.ggd[:, 0] += sh.ggd0
+            skip = self._exempt(mode)
+            if skip is not None:  # the step did not use these solutions: nothing flows through their solves
+                exempt[t] = skip
+                for k in want:
+                    g = getattr(v, k)
+                    g.masked_fill_(skip.view((-1,) + (1,) * (g.dim() - 1)), 0.0)
+            g_hor = self._linearise_vjp(hor, v.gAd, v.gBd, v.ggd)
+            if g_hor_prev is not None:
+                g_hor = [g if p is None else g + p for g, p in zip(g_hor, g_hor_prev)]
+            g_state = list(g_before)
+            g_state[0] = g_state[0] + v.gx0
+            for i, g in enumerate(gtraj):
+                if g is not None:
+                    g_state[i] += g[:, t]
+            for k in wnames:
+                gw[k] += getattr(v, "g" + k)
+            if gXr is not None:
+                gXr[t] = v.gXr
+        self.status, self.iters = tape["status"], tape["iters"]
+        self.astat, self.ares, self.act = astat, ares, act
+        bad = ((astat != 1) & ~exempt).any(0)
+        if bool(bad.any()):
+            if self.strict:
+                idx = bad.nonzero().flatten().tolist()
+                raise RuntimeError(f"{self._NAME}: no reliable gradient for instance(s) {idx[:8]} (astat per step "
+                                   f"{astat[:, bad].T.tolist()[:8]}; strict=False gives them zero gradients)")
+            zero = lambda g: None if g is None else torch.where(bad.view((-1,) + (1,) * (g.dim() - 1)), 0.0, g)
+            g_state, g_hor = [zero(g) for g in g_state], [zero(g) for g in g_hor]
+            gw = {k: zero(g) for k, g in gw.items()}
+            if gXr is not None:
+                gXr = torch.where(bad.view(1, -1, 1, 1), 0.0, gXr)
+        out = dict(state=[g if n else None for g, n in zip(g_state, need["state"])],
+                   hor=[g if n else None for g, n in zip(g_hor, need["hor"])], Xr=gXr, Q=None, QN=None, R=None)
+        for k in wnames:
+            out[k] = gw[k].sum(0)
+        return out
+
+
+class DynamicRollout(_Rollout):
     """T steps of the dynamic closed loop (mpc_device.DynamicMPC's step) as ONE differentiable map on
     ONE solver handle:
 
@@ -299,142 +590,167 @@ class DynamicRollout:
     with strict=False such an instance gets zero gradients in every input and the weight sums
     leave it out.  ``settings`` are DeviceBatch's."""
 
-    def __init__(self, layout, B, veh, device=0, strict=True, warm_start=False, **settings):
-        import torch
-        from . import DeviceBatch
-        if layout._kind != "incr" or (layout.nx, layout.nu) != (6, 2):
-            raise ValueError("DynamicRollout needs an IncrementalLayout of the dynamic bicycle (nx 6, nu 2)")
-        self.torch, self.layout, self.veh = torch, layout, veh
-        self.B, self.N = int(B), layout.N
-        self.dev = torch.device("cuda", int(device))
-        self.strict, self.shift_warm = bool(strict), bool(warm_start)
-        P, A, _, _ = layout.pattern()
-        settings.pop("verbose", None)
-        self.batch = DeviceBatch(P, A, self.B, device=int(device), **settings)
-        self.Px = torch.from_numpy(P.data.copy()).to(self.dev)[None, :].repeat(self.B, 1).contiguous()
-        self.stream = torch.cuda.Stream(self.dev)
-        self.status = self.iters = self.astat = self.ares = self.act = None
-        self._fn = _functions().Rollout
-
-    def tape_doubles_per_instance(self):
-        """Doubles the tape holds per step and instance: xt, pred, sol and the record."""
-        L = self.layout
-        return 8 + (L.N + 1) * 8 + L.n + self.batch.record_width
+    _NAME, _FN = "DynamicRollout", "Rollout"
+    _LAYOUT = ("incr", 6, 2, "an IncrementalLayout of the dynamic bicycle")
+    _STATE, _HOR = (8,), (8,)
 
     def __call__(self, xt0, pred0, T, Xr=None, path=None, weights=None):
-        torch, B, N = self.torch, self.B, self.N
-        T = int(T)
-        if T < 1:
-            raise ValueError("DynamicRollout: T must be at least 1")
-        if (Xr is None) == (path is None):
-            raise ValueError("DynamicRollout: give either Xr (T, B, 6, N+1) or path = (path_x, path_y)")
-        for t, shape, k in ((xt0, (B, 8), "xt0"), (pred0, (B, N + 1, 8), "pred0"), (Xr, (T, B, 6, N + 1), "Xr")):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.dev):
-                raise ValueError(f"DynamicRollout: {k} must be a float64 tensor of shape {shape} on {self.dev}")
+        B, N, T = self.B, self.N, int(T)
+        self._check_call(T, Xr, path, ((xt0, (B, 8), "xt0"), (pred0, (B, N + 1, 8), "pred0")), "(path_x, path_y)")
         if path is not None:
             path = tuple(_c(p) for p in path)
         Q, QN, R, use_w = _split_weights(weights)
         return self._fn.apply(self, T, path, xt0, pred0, Xr, Q, QN, R, use_w)
 
-    def _on_stream(self, fn):
-        """fn() on the rollout's stream, ordered after the caller's current stream; the caller's
-        stream is ordered after it (mpc_device._ClosedLoop's rule)."""
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            out = fn()
-        caller.wait_stream(self.stream)
-        return out
-
-    def _problem(self, xt, pred, Xr_t, path, weights):
+    def _problem(self, state, hor, Xr_t, path, weights):
         """One step's reference, linearisation and QP values from (xt, pred), as DynamicMPC._step."""
-        N, L = self.N, self.layout
+        N, L, (xt,), (pred,) = self.N, self.layout, state, hor
         Xr = md.reference_search(path[0], path[1], pred, self.veh.dt) if Xr_t is None else Xr_t
         Ad, Bd, gd = md.linearise(self.veh, pred[:, :N, :6], pred[:, :N, 6:])
         out = L.assemble(Ad, Bd, gd, xt, Xr, weights=weights)
         Px = self.Px if weights is None else out[4][None, :].repeat(self.B, 1)
         return Xr, Ad, Bd, gd, Px, out[:4]
 
-    def _forward(self, xt, pred, T, Xr, path, weights):
-        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
-        st = md._stream(torch, self.dev)  # self.stream
-        kw = dict(dtype=torch.float64, device=self.dev)
-        XT, DU0 = torch.empty((B, T + 1, 8), **kw), torch.empty((B, T, 2), **kw)
-        status = torch.empty((T, B), dtype=torch.int32, device=self.dev)
-        iters = torch.empty((T, B), dtype=torch.int32, device=self.dev)
-        XT[:, 0] = xt
-        tape, y, nd = [], None, (N + 1) * 8
-        for t in range(T):
-            _, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(xt, pred, None if Xr is None else Xr[t], path, weights)
-            b.setup(Px, Ax, q, l, u, stream=st)
-            if self.shift_warm and t > 0:
-                b.warm_start(*md.warm_shift(N, 8, 2, tape[-1][2], y), stream=st)
-            sol, y = torch.empty((B, L.n), **kw), torch.empty((B, L.m), **kw)
-            b.solve(sol, y, status[t], iters[t], stream=st)
-            rec = b.save_solution(torch.empty((B, b.record_width), **kw), stream=st)
-            tape.append((xt, pred, sol, rec))
-            xt, pred, _ = md.incr_shift(L, self.veh, sol, Ad, Bd, gd, xt)
-            XT[:, t + 1] = xt
-            DU0[:, t] = sol[:, nd:nd + 2]
-        self.status, self.iters = status, iters
-        return XT, DU0, pred, dict(steps=tape, status=status, iters=iters)
+    def _shift(self, sol, status, Ad, Bd, gd, Xr, state, hor, aux):
+        xt, pred, _ = md.incr_shift(self.layout, self.veh, sol, Ad, Bd, gd, state[0])
+        return (xt,), (pred,), None, aux
 
-    def _backward(self, tape, Xr, path, weights, gXT, gDU0, gpred, need):
-        torch, B, N, L, b = self.torch, self.B, self.N, self.layout, self.batch
-        st = md._stream(torch, self.dev)
-        steps = tape["steps"]
-        T, nd = len(steps), (N + 1) * 8
-        kw = dict(dtype=torch.float64, device=self.dev)
-        astat = torch.empty((T, B), dtype=torch.int32, device=self.dev)
-        ares = torch.empty((T, B), **kw)
-        act = torch.empty((T, B, L.m), dtype=torch.int8, device=self.dev)
-        wnames = [k for k in ("Q", "QN", "R") if weights is not None and need[k]]
-        gw = {k: torch.zeros((B,) + ((2, 2) if k == "R" else (6, 6)), **kw) for k in wnames}
-        gXr = torch.zeros((T, B, 6, N + 1), **kw) if Xr is not None and need["Xr"] else None
-        want = ["gAd", "gBd", "ggd", "gx0"] + ["gXr"] * (gXr is not None) + ["g" + k for k in wnames]
-        g_xt = gXT[:, T].clone() if gXT is not None else torch.zeros((B, 8), **kw)
-        g_pred = gpred
-        for t in reversed(range(T)):
-            xt, pred, sol, rec = steps[t]
-            Xr_t, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(xt, pred, None if Xr is None else Xr[t], path, weights)
-            b.setup(Px, Ax, q, l, u, stream=st)
-            b.load_solution(rec, stream=st)
-            sh = md.incr_shift_vjp(L, self.veh, sol, Ad, Bd, xt, g_xt, g_pred, None)
-            if gDU0 is not None:
-                sh.gsol[:, nd:nd + 2] += gDU0[:, t]
-            a = b.adjoint(sh.gsol, None, act=act[t], ares=ares[t], astat=astat[t], stream=st)
-            v = L.assemble_vjp(a.gAx, a.gq, a.gl, a.gu, gPx=a.gPx if wnames else None, Xr=Xr_t,
-                               weights=None if weights is None else (weights[0], weights[1], None), want=want)
-            v.gAd[:, 0] += sh.gAd0
-            v.gBd[:, 0] += sh.gBd0
-            v.ggd[:, 0] += sh.ggd0
-            gx, gu = md.linearise_vjp(self.veh, pred[:, :N, :6], pred[:, :N, 6:], v.gAd, v.gBd, v.ggd)
-            g_pred = torch.zeros((B, N + 1, 8), **kw)
-            g_pred[:, :N, :6] = gx
-            g_pred[:, :N, 6:] = gu
-            g_xt = sh.gxt + v.gx0
-            if gXT is not None:
-                g_xt += gXT[:, t]
-            for k in wnames:
-                gw[k] += getattr(v, "g" + k)
-            if gXr is not None:
-                gXr[t] = v.gXr
-        self.status, self.iters = tape["status"], tape["iters"]
-        self.astat, self.ares, self.act = astat, ares, act
-        bad = (astat != 1).any(0)
-        if bool(bad.any()):
-            if self.strict:
-                idx = bad.nonzero().flatten().tolist()
-                raise RuntimeError(f"DynamicRollout: no reliable gradient for instance(s) {idx[:8]} (astat per step "
-                                   f"{astat[:, bad].T.tolist()[:8]}; strict=False gives them zero gradients)")
-            zero = lambda g: None if g is None else torch.where(bad.view((-1,) + (1,) * (g.dim() - 1)), 0.0, g)
-            g_xt, g_pred = zero(g_xt), zero(g_pred)
-            gw = {k: zero(g) for k, g in gw.items()}
-            if gXr is not None:
-                gXr = torch.where(bad.view(1, -1, 1, 1), 0.0, gXr)
-        out = dict(xt0=g_xt if need["xt0"] else None, pred0=g_pred if need["pred0"] else None, Xr=gXr,
-                   Q=None, QN=None, R=None)
-        for k in wnames:
-            out[k] = gw[k].sum(0)
+    def _shift_vjp(self, sol, Ad, Bd, state, mode, g_state, g_hor):
+        sh = md.incr_shift_vjp(self.layout, self.veh, sol, Ad, Bd, state[0], g_state[0], g_hor[0], None)
+        return sh, [sh.gxt], None
+
+    def _linearise_vjp(self, hor, gAd, gBd, ggd):
+        N, (pred,) = self.N, hor
+        gx, gu = md.linearise_vjp(self.veh, pred[:, :N, :6], pred[:, :N, 6:], gAd, gBd, ggd)
+        g = pred.new_zeros((self.B, N + 1, 8))
+        g[:, :N, :6] = gx
+        g[:, :N, 6:] = gu
+        return [g]
+
+
+def _incr_kin_problem(self, state, hor, Xr_t, path, weights):
+    """KinematicMPC._step's reference, linearisation and QP values; with the (x, pred_x, pred_u) of
+    the LTV loop, KinematicLTVMPC._step's."""
+    N, L = self.N, self.layout
+    if L._kind == "incr":
+        x0, xs, us = state[0], hor[0][:, :, :4], hor[0][:, :, 4:]
+    else:
+        x0, xs, us = state[0], hor[0], hor[1]
+    Xr = md.reference_search_kin(path[0], path[1], path[2], path[3], hor[0], self.veh.dt) if Xr_t is None else Xr_t
+    Ad, Bd, gd = md.linearise_kinematics(self.veh, xs[:, :N], us[:, :N])
+    out = L.assemble(Ad, Bd, gd, x0, Xr, weights=weights)
+    Px = self.Px if weights is None else out[4][None, :].repeat(self.B, 1)
+    return Xr, Ad, Bd, gd, Px, out[:4]
+
+
+class KinematicRollout(_Rollout):
+    """T steps of the kinematic closed loop (mpc_device.KinematicMPC's step; its tail is also
+    LaneChangeMPC's) as ONE differentiable map on ONE solver handle, as DynamicRollout:
+
+        roll = KinematicRollout(layout, B, veh, device=0, strict=True, warm_start=False, **settings)
+        XT, DU0, pred_T = roll(xt0, pred0, T, Xr=None, path=None, set_speed=None, weights=None)
+
+    xt0 (B, 6) = (X, Y, v, yaw, steer, accel), pred0 (B, N+1, 6); XT (B, T+1, 6), DU0 (B, T, 2),
+    pred_T (B, N+1, 6).  The reference is searched on ``path`` = (path_x, path_y, path_yaw) with
+    ``set_speed`` (B,) (default: xt0's v, as KinematicMPC) or given as ``Xr`` (T, B, 4, N+1).  The
+    forward runs the loop's own tail (mpc_device.kin_shift), stop rule included, with finish_cnt and
+    done starting at zero; ``done`` (T, B) and ``mode`` (T, B) of the last forward stay on the object.
+    A vehicle that no longer moves is still solved: DU0[:, t] is that solve's du_0, and its cotangent
+    goes through that step's adjoint like any other.  The backward is DynamicRollout's with
+    mpc_device.kin_shift_vjp and linearise_kinematics_vjp."""
+
+    _NAME, _FN = "KinematicRollout", "Rollout"
+    _LAYOUT = ("incr", 4, 2, "an IncrementalLayout of the kinematic bicycle")
+    _STATE, _HOR = (6,), (6,)
+    _problem = _incr_kin_problem
+
+    def __call__(self, xt0, pred0, T, Xr=None, path=None, set_speed=None, weights=None):
+        B, N, T = self.B, self.N, int(T)
+        self._check_call(T, Xr, path, ((xt0, (B, 6), "xt0"), (pred0, (B, N + 1, 6), "pred0"),
+                                       (set_speed, (B,), "set_speed")), "(path_x, path_y, path_yaw)")
+        if path is not None:
+            speed = xt0[:, 2] if set_speed is None else set_speed
+            path = tuple(_c(p) for p in path) + (_c(speed),)
+        Q, QN, R, use_w = _split_weights(weights)
+        return self._fn.apply(self, T, path, xt0, pred0, Xr, Q, QN, R, use_w)
+
+    def _aux0(self):
+        torch, B = self.torch, self.B
+        ikw = dict(dtype=torch.int32, device=self.dev)
+        return (torch.zeros((B, self.N + 1, 2), dtype=torch.float64, device=self.dev), torch.zeros(B, **ikw),
+                torch.zeros(B, **ikw))
+
+    def _shift(self, sol, status, Ad, Bd, gd, Xr, state, hor, aux):
+        xt, pred, pdu, cnt, done, mode = md.kin_shift(self.layout, self.veh, sol, Ad, Bd, gd, Xr, state[0], hor[0],
+                                                      *aux)
+        return (xt,), (pred,), mode, (pdu, cnt, done)
+
+    def _forward(self, state, hor, T, Xr, path, weights):
+        out = super()._forward(state, hor, T, Xr, path, weights)
+        self.done = (self.mode != 0).to(self.torch.int32)
         return out
+
+    def _shift_vjp(self, sol, Ad, Bd, state, mode, g_state, g_hor):
+        sh = md.kin_shift_vjp(self.layout, self.veh, sol, Ad, Bd, state[0], mode, g_state[0], g_hor[0], None)
+        return sh, [sh.gxt], [sh.gpred_prev]
+
+    def _linearise_vjp(self, hor, gAd, gBd, ggd):
+        N, (pred,) = self.N, hor
+        gx, gu = md.linearise_kinematics_vjp(self.veh, pred[:, :N, :4], pred[:, :N, 4:], gAd, gBd, ggd)
+        g = pred.new_zeros((self.B, N + 1, 6))
+        g[:, :N, :4] = gx
+        g[:, :N, 4:] = gu
+        return [g]
+
+
+class KinematicLTVRollout(_Rollout):
+    """T steps of the direct-input kinematic closed loop (mpc_device.KinematicLTVMPC's step) as ONE
+    differentiable map on ONE solver handle:
+
+        roll = KinematicLTVRollout(layout, B, veh, device=0, strict=True, warm_start=False, **settings)
+        X, U, pred_x_T, pred_u_T = roll(x0, u0, pred_x0, pred_u0, T, Xr=None, path=None, weights=None)
+
+    x0 (B, 4), u0 (B, 2), pred_x0 (B, N+1, 4), pred_u0 (B, N+1, 2); X (B, T+1, 4), U (B, T+1, 2) with
+    U[:, 0] = u0 and U[:, t+1] the control held after step t.  The reference is searched on ``path``
+    = (path_x, path_y) (set speed 10, path yaw 0, as KinematicLTVMPC) or given as ``Xr``
+    (T, B, 4, N+1).  The tail is mpc_device.kin_ltv_shift with its skip rule: a vehicle whose solve
+    did not end `solved` keeps x, u, pred_x, pred_u bit for bit (``mode`` (T, B) of the last forward
+    stays on the object).  In the backward such a (step, vehicle) pair seeds its adjoint with zero,
+    passes its cotangents through unchanged and is exempt from the ``strict`` rule -- its solution was
+    not used; ``strict`` otherwise follows DynamicRollout's rule."""
+
+    _NAME, _FN, _DU0 = "KinematicLTVRollout", "RolloutLTV", False
+    _LAYOUT = ("ltv", 4, 2, "an LTVLayout of the kinematic bicycle")
+    _STATE, _HOR = (4, 2), (4, 2)
+    _problem = _incr_kin_problem
+    SET_SPEED = md.KinematicLTVMPC.SET_SPEED
+
+    def __call__(self, x0, u0, pred_x0, pred_u0, T, Xr=None, path=None, weights=None):
+        torch, B, N, T = self.torch, self.B, self.N, int(T)
+        self._check_call(T, Xr, path, ((x0, (B, 4), "x0"), (u0, (B, 2), "u0"), (pred_x0, (B, N + 1, 4), "pred_x0"),
+                                       (pred_u0, (B, N + 1, 2), "pred_u0")), "(path_x, path_y)")
+        if path is not None:
+            px, py = (_c(p) for p in path)
+            path = (px, py, torch.zeros_like(px), torch.full((B,), self.SET_SPEED, dtype=torch.float64, device=self.dev))
+        Q, QN, R, use_w = _split_weights(weights)
+        return self._fn.apply(self, T, path, x0, u0, pred_x0, pred_u0, Xr, Q, QN, R, use_w)
+
+    def _shift(self, sol, status, Ad, Bd, gd, Xr, state, hor, aux):
+        x, u, px, pu, mode = md.kin_ltv_shift(self.layout, self.veh, sol, status, Ad, Bd, gd, *state, *hor)
+        return (x, u), (px, pu), mode, aux
+
+    def _exempt(self, mode):
+        return mode != 0
+
+    def _shift_vjp(self, sol, Ad, Bd, state, mode, g_state, g_hor):
+        sh = md.kin_ltv_shift_vjp(self.layout, self.veh, sol, Ad, Bd, state[0], mode, g_state[0], g_state[1],
+                                  g_hor[0], g_hor[1])
+        return sh, [sh.gx, sh.gu_prev], [sh.gpred_x_prev, sh.gpred_u_prev]
+
+    def _linearise_vjp(self, hor, gAd, gBd, ggd):
+        N, (px, pu) = self.N, hor
+        gx, gu = md.linearise_kinematics_vjp(self.veh, px[:, :N], pu[:, :N], gAd, gBd, ggd)
+        gpx, gpu = px.new_zeros(px.shape), pu.new_zeros(pu.shape)
+        gpx[:, :N] = gx
+        gpu[:, :N] = gu
+        return [gpx, gpu]
