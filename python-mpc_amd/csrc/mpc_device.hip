@@ -287,7 +287,7 @@ __device__ void linearise_one(const VehicleK& k, const double* xin, const double
 
 // update_dynamics_model (vehicle_models.py:343-477): one explicit-Euler step of the
 // nonlinear model from the guarded state.  euler_step<T> starts at a GUARDED (x, u), as
-// continuous_model does: double for k_incr_shift, Dual for k_incr_shift_vjp.
+// continuous_model does: double for k_incr_shift, Dual for its transpose (euler_step_vjp).
 template <class T>
 __device__ __forceinline__ void euler_step(const VehicleK& k, const T* x, const T* u, T* xn) {
     const Tyre<T> t = tyre_forces<T>(k, x, u);
@@ -941,94 +941,6 @@ __device__ void euler_step_vjp(const VehicleK& k, const double* xin, const doubl
     gu[1] = g[5];
 }
 
-// The transpose of k_incr_shift as it computes.  One thread per (vehicle, output row), rows =
-// the N+1 state rows of gsol (8 wide), its N increment rows (2 wide) and one row for the model
-// and state outputs (gAd0, gBd0, ggd0, gxt): every output element has one writer, consecutive
-// threads write consecutive rows of gsol, and no thread walks the horizon.  (One thread per
-// element would evaluate the dual Euler step eight times per vehicle; this form does it twice,
-// in rows N-1 and N, and one thread per vehicle -- the forward's shape -- writes n strided
-// doubles from one lane.)  Cotangents gxt (B,8), gpred (B,N+1,8), gpdu (B,N+1,2) of the NEW xt,
-// pred, pdu, each null = zero; xt the value from BEFORE the step.  With w = gxt + gpred[0]:
-//   plant step   gAd0 = w_x x',  gBd0 = w_x u',  ggd0 = w_x,  g u = w_u + Bd0' w_x  (u = u_prev + du_0),
-//                gxt = (Ad0' w_x, g u),  g du_0 = g u
-//   shift        g x~_k = gpred[k-1] (2 <= k <= N),  g du_k = gpdu[k-1] (1 <= k <= N-1);  du_{N-1} also
-//                takes gpdu[N-1] and gpdu[N], x~_N's inputs also gpred[N]'s, added in that order
-//   terminal     euler_step_vjp of gpred[N]'s state part: into x~_N's states and x~_{N-1}'s inputs
-__global__ __launch_bounds__(256) void k_incr_shift_vjp(VehicleK vk, IncrK L, long B, const double* __restrict__ sol,
-                                                        const double* __restrict__ Ad, const double* __restrict__ Bd,
-                                                        const double* __restrict__ xt, const double* __restrict__ gxt,
-                                                        const double* __restrict__ gpred,
-                                                        const double* __restrict__ gpdu, double* __restrict__ gsol,
-                                                        double* __restrict__ gAd0, double* __restrict__ gBd0,
-                                                        double* __restrict__ ggd0, double* __restrict__ gxt_o) {
-    const int N = L.N, n = L.n, rows = 2 * N + 2;
-    constexpr int nx = 6, nu = 2, nxa = 8;  // the entry point's check
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * rows) return;
-    const long b = t / rows;
-    const int row = (int)(t - b * rows);
-    const double* s = sol + b * n;
-    const double* gp = gpred ? gpred + b * (long)(N + 1) * nxa : nullptr;
-    const double* gd = gpdu ? gpdu + b * (long)(N + 1) * nu : nullptr;
-    if (row <= N) {  // g x~_row
-        if (!gsol) return;
-        const int k = row;
-        double g[nxa];
-        for (int i = 0; i < nxa; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nxa + i] : 0.0;
-        if (k == N && gp)
-            for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gp[N * nxa + nx + j];
-        if ((k == N || k == N - 1) && gp) {
-            double ge[nx], gue[nu];
-            euler_step_vjp(vk, s + N * nxa, s + (N - 1) * nxa + nx, gp + N * nxa, ge, gue);
-            if (k == N)
-                for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
-            if (k == N - 1)
-                for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gue[j];
-        }
-        for (int i = 0; i < nxa; ++i) gsol[b * n + k * nxa + i] = g[i];
-        return;
-    }
-    // w, the cotangent of the stepped x~, and g u: what the rows below share
-    const double* B0 = Bd + b * (long)N * nx * nu;
-    double w[nxa], gu[nu];
-    for (int i = 0; i < nxa; ++i) w[i] = (gxt ? gxt[b * nxa + i] : 0.0) + (gp ? gp[i] : 0.0);
-    for (int j = 0; j < nu; ++j) {
-        double acc = 0.0;
-        for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
-        gu[j] = w[nx + j] + acc;
-    }
-    if (row <= 2 * N) {  // g du_k
-        if (!gsol) return;
-        const int k = row - (N + 1);
-        for (int j = 0; j < nu; ++j) {
-            double g = k == 0 ? gu[j] : (gd ? gd[(k - 1) * nu + j] : 0.0);
-            if (k == N - 1 && gd) g = (g + gd[(N - 1) * nu + j]) + gd[N * nu + j];
-            gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
-        }
-        return;
-    }
-    // the model row
-    const double* A0 = Ad + b * (long)N * nx * nx;
-    const double* xb = xt + b * nxa;
-    double uu[nu];
-    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + s[(N + 1) * nxa + j];
-    for (int i = 0; i < nx; ++i) {
-        if (gAd0)
-            for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
-        if (gBd0)
-            for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = w[i] * uu[j];
-        if (ggd0) ggd0[b * nx + i] = w[i];
-    }
-    if (gxt_o) {
-        for (int j = 0; j < nx; ++j) {
-            double acc = 0.0;
-            for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
-            gxt_o[b * nxa + j] = acc;
-        }
-        for (int j = 0; j < nu; ++j) gxt_o[b * nxa + nx + j] = gu[j];
-    }
-}
-
 // Plant step and in-place horizon shift that mpc_incre_kine_func.simulate (:385-387, :403-428) and
 // mpc_increment_kinematics_pred_matrix.main (:442-472) share word for word, for one vehicle:
 // s = (x~_0..x~_N, du_0..du_{N-1}) the solution, A0 / B0 / g0 stage 0 of the linearisation,
@@ -1208,38 +1120,106 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     if (steps_taken) steps_taken[b] += 1;
 }
 
-// The transposes of the two kinematic tails as they compute, in k_incr_shift_vjp's
-// thread mapping: one thread per (vehicle, output row), rows = the N+1 state rows of gsol, its N
-// input rows and one row for the model and state outputs; one writer per output element, no
-// atomics, no thread walks the horizon.  mode (null = 0 everywhere) says what the forward did with
-// the vehicle: 0 stepped; 1 left untouched (done was set / status != solved): gsol and the model
-// outputs are zero and the state's cotangent passes through; 2 (k_kin_shift only) met the stop rule
-// on this step: pred / pdu took the unpacked solution, xt did not move.  The cotangent of the
-// PREVIOUS horizon (gpred / gpdu in mode 1, zero otherwise) is the caller's to form.
+// The transposes of the differentiable loop tails as they compute, written once
+// over a Tail.  One thread per (vehicle, output row), rows = the N+1 state rows of gsol (nxa wide),
+// its N input rows (nu wide) and one row for the model and state outputs (gAd0, gBd0, ggd0, gxt):
+// every output element has one writer, consecutive threads write consecutive rows of gsol, no
+// atomics, and no thread walks the horizon.  (One thread per element would evaluate the terminal
+// step's transpose nxa times per vehicle; this form does it in the one or two rows it lands in, and
+// one thread per vehicle -- the forward's shape -- writes n strided doubles from one lane.)
+// sol = (x~_0..x~_N, v_0..v_{N-1}), x~ the state (augmented by the applied input where the loop is
+// incremental) and v the loop's input variable; xt the value from BEFORE the step.  Cotangents gxt
+// (B,nxa), gu (B,nu; direct input only), gpred (B,N+1,nxa), gpdu (B,N+1,nu) of the NEW xt, u, pred,
+// pdu, each null = zero; every output may be null.  With w = gxt + gpred[0], mode 0:
+//   plant step   gAd0 = w_x x',  gBd0 = w_x u',  ggd0 = w_x,  gxt = Ad0' w_x (state part);
+//                incremental (u = u_prev + v_0):  g u = w_u + Bd0' w_x,  gxt's input part = g v_0 = g u
+//                direct (u = v_0; the old u is not read by the forward):  g v_0 = Bd0' w_x + gu
+//   shift        g x~_k = gpred[k-1] (2 <= k <= N),  g v_k = gpdu[k-1] (1 <= k <= N-1);  v_{N-1} also
+//                takes gpdu[N-1] and gpdu[N], added in that order; incremental: pred[N]'s input part is
+//                x~_N's, which takes gpred[N]'s
+//   terminal     Tail::terminal, the transpose of the step that formed pred[N]'s state part, added
+//                last into the rows it touches
+// mode (null = 0 everywhere; a Tail with modes = 1 has none) says what the forward did with the
+// vehicle: 0 stepped; 1 left untouched (done was set / status != solved): gsol and the model outputs
+// are zero and the state's cotangent passes through; 2 (modes = 3 only) met the stop rule on this
+// step: pred / pdu took the unpacked solution (g x~_k = gpred[k], g v_k = gpdu[k], v_{N-1} also
+// gpdu[N]), xt did not move.  The cotangent of the PREVIOUS horizon (gpred / gpdu in mode 1, zero
+// otherwise) is the caller's to form.
+//
+// A Tail states the widths, whether the input is incremental, how many modes it knows, and
+// terminal(vk, N, s, wN, row, g): wN = gpred[N], g the cotangent of output row `row` of gsol
+// (row <= N: x~_row, else v_{row-N-1}).
 
-// k_kin_shift / k_lane_tail (kin_incr_step_shift).  With w = gxt + gpred[0], mode 0:
-//   plant step   gAd0 = w_x x',  gBd0 = w_x u',  ggd0 = w_x,  g u = w_u + Bd0' w_x  (u = u_prev + du_0),
-//                gxt = (Ad0' w_x, g u),  g du_0 = g u
-//   shift        g x~_k = gpred[k-1] (2 <= k <= N),  g du_k = gpdu[k-1] (1 <= k <= N-1);  du_{N-1} also
-//                takes gpdu[N-1] and gpdu[N], added in that order
-//   terminal     pred[N] = (kin_update(x_N, u_N), u_N): x~_N also takes gpred[N]'s input part, then
-//                kin_update_vjp of gpred[N]'s state part in both its parts
-// mode 2: g x~_k = gpred[k], g du_k = gpdu[k], du_{N-1} also gpdu[N].
-__global__ __launch_bounds__(256) void k_kin_shift_vjp(mpcqp_kin_vehicle vk, IncrK L, long B,
-                                                       const double* __restrict__ sol, const double* __restrict__ Ad,
-                                                       const double* __restrict__ Bd, const double* __restrict__ xt,
-                                                       const int* __restrict__ dmode, const double* __restrict__ gxt,
-                                                       const double* __restrict__ gpred,
-                                                       const double* __restrict__ gpdu, double* __restrict__ gsol,
-                                                       double* __restrict__ gAd0, double* __restrict__ gBd0,
-                                                       double* __restrict__ ggd0, double* __restrict__ gxt_o) {
-    const int N = L.N, n = L.n, rows = 2 * N + 2;
-    constexpr int nx = 4, nu = 2, nxa = 6;  // the entry point's check
+// k_incr_shift: pred[N] = (euler_step_guarded(x_N, u_{N-1}), u_N): euler_step_vjp into x~_N's
+// states and x~_{N-1}'s inputs.  The dual Euler step runs twice per vehicle, in rows N-1 and N.
+struct DynamicIncrTail {
+    using K = VehicleK;
+    static constexpr int nx = 6, nu = 2, nxa = 8, modes = 1;
+    static constexpr bool incremental = true;
+    static constexpr const char* model = "6-state dynamic";
+    static __device__ void terminal(const K& vk, int N, const double* s, const double* wN, int row, double* g) {
+        if (row != N && row != N - 1) return;
+        double ge[nx], gue[nu];
+        euler_step_vjp(vk, s + N * nxa, s + (N - 1) * nxa + nx, wN, ge, gue);
+        if (row == N)
+            for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+        if (row == N - 1)
+            for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gue[j];
+    }
+};
+
+// k_kin_shift / k_lane_tail (kin_incr_step_shift): pred[N] = (kin_update(x_N, u_N), u_N):
+// kin_update_vjp into x~_N in both its parts, the input part after gpred[N]'s.
+struct KinIncrTail {
+    using K = mpcqp_kin_vehicle;
+    static constexpr int nx = 4, nu = 2, nxa = 6, modes = 3;
+    static constexpr bool incremental = true;
+    static constexpr const char* model = "4-state kinematic";
+    static __device__ void terminal(const K& vk, int N, const double* s, const double* wN, int row, double* g) {
+        if (row != N) return;
+        double ge[nx], gue[nu];
+        kin_update_vjp(vk, s + N * nxa, s + N * nxa + nx, wN, ge, gue);
+        for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+        for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gue[j];
+    }
+};
+
+// k_kin_ltv_shift's executed branch, sol = (S_0..S_N, U_0..U_{N-1}): pred_x[N] = kin_update(S_N,
+// U_{N-1}): kin_update_vjp into S_N and into U_{N-1} (at N = 2 that is U_1, which takes the shift's
+// triple sum and this at once).
+struct KinLtvTail {
+    using K = mpcqp_kin_vehicle;
+    static constexpr int nx = 4, nu = 2, nxa = 4, modes = 2;
+    static constexpr bool incremental = false;
+    static constexpr const char* model = "4-state kinematic";
+    static __device__ void terminal(const K& vk, int N, const double* s, const double* wN, int row, double* g) {
+        if (row != N && row != 2 * N) return;
+        double ge[nx], gue[nu];
+        kin_update_vjp(vk, s + N * nx, s + (N + 1) * nx + (N - 1) * nu, wN, ge, gue);
+        if (row == N)
+            for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
+        else
+            for (int j = 0; j < nu; ++j) g[j] = g[j] + gue[j];
+    }
+};
+
+template <class Tail>
+__global__ __launch_bounds__(256) void k_tail_vjp(typename Tail::K vk, int N, int n, long B,
+                                                  const double* __restrict__ sol, const double* __restrict__ Ad,
+                                                  const double* __restrict__ Bd, const double* __restrict__ xt,
+                                                  const int* __restrict__ dmode, const double* __restrict__ gxt,
+                                                  const double* __restrict__ gu, const double* __restrict__ gpred,
+                                                  const double* __restrict__ gpdu, double* __restrict__ gsol,
+                                                  double* __restrict__ gAd0, double* __restrict__ gBd0,
+                                                  double* __restrict__ ggd0, double* __restrict__ gxt_o) {
+    constexpr int nx = Tail::nx, nu = Tail::nu, nxa = Tail::nxa;  // the entry point's check
+    constexpr bool stops = Tail::modes == 3;
+    const int rows = 2 * N + 2;
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * rows) return;
     const long b = t / rows;
     const int row = (int)(t - b * rows);
-    const int mode = dmode ? dmode[b] : 0;
+    const int mode = (Tail::modes > 1 && dmode) ? dmode[b] : 0;
     const double* s = sol + b * n;
     const double* gp = gpred ? gpred + b * (long)(N + 1) * nxa : nullptr;
     const double* gd = gpdu ? gpdu + b * (long)(N + 1) * nu : nullptr;
@@ -1248,65 +1228,73 @@ __global__ __launch_bounds__(256) void k_kin_shift_vjp(mpcqp_kin_vehicle vk, Inc
         const int k = row;
         double g[nxa];
         if (mode != 0) {
-            for (int i = 0; i < nxa; ++i) g[i] = (mode == 2 && gp) ? gp[k * nxa + i] : 0.0;
+            for (int i = 0; i < nxa; ++i) g[i] = (stops && mode == 2 && gp) ? gp[k * nxa + i] : 0.0;
         } else {
             for (int i = 0; i < nxa; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nxa + i] : 0.0;
-            if (k == N && gp) {
-                double ge[nx], gue[nu];
-                kin_update_vjp(vk, s + N * nxa, s + N * nxa + nx, gp + N * nxa, ge, gue);
-                for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
-                for (int j = 0; j < nu; ++j) g[nx + j] = (g[nx + j] + gp[N * nxa + nx + j]) + gue[j];
-            }
+            if constexpr (Tail::incremental)
+                if (k == N && gp)
+                    for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gp[N * nxa + nx + j];
+            if (gp) Tail::terminal(vk, N, s, gp + N * nxa, row, g);
         }
         for (int i = 0; i < nxa; ++i) gsol[b * n + k * nxa + i] = g[i];
         return;
     }
-    if (mode != 0) {  // nothing went through the plant step
-        if (row <= 2 * N) {
-            if (!gsol) return;
-            const int k = row - (N + 1);
-            for (int j = 0; j < nu; ++j) {
-                double g = (mode == 2 && gd) ? gd[k * nu + j] : 0.0;
-                if (mode == 2 && gd && k == N - 1) g = g + gd[N * nu + j];
-                gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+    if constexpr (Tail::modes > 1)
+        if (mode != 0) {  // nothing went through the plant step
+            if (row <= 2 * N) {
+                if (!gsol) return;
+                const int k = row - (N + 1);
+                for (int j = 0; j < nu; ++j) {
+                    double g = (stops && mode == 2 && gd) ? gd[k * nu + j] : 0.0;
+                    if (stops && mode == 2 && gd && k == N - 1) g = g + gd[N * nu + j];
+                    gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+                }
+                return;
             }
+            for (int i = 0; i < nx; ++i) {
+                if (gAd0)
+                    for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = 0.0;
+                if (gBd0)
+                    for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = 0.0;
+                if (ggd0) ggd0[b * nx + i] = 0.0;
+            }
+            if (gxt_o)
+                for (int i = 0; i < nxa; ++i) gxt_o[b * nxa + i] = gxt ? gxt[b * nxa + i] : 0.0;
             return;
         }
-        for (int i = 0; i < nx; ++i) {
-            if (gAd0)
-                for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = 0.0;
-            if (gBd0)
-                for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = 0.0;
-            if (ggd0) ggd0[b * nx + i] = 0.0;
-        }
-        if (gxt_o)
-            for (int i = 0; i < nxa; ++i) gxt_o[b * nxa + i] = gxt ? gxt[b * nxa + i] : 0.0;
-        return;
-    }
-    // w, the cotangent of the stepped x~, and g u: what the rows below share
+    // w, the cotangent of the stepped x~, and that of the first input: what the rows below share
     const double* B0 = Bd + b * (long)N * nx * nu;
-    double w[nxa], gu[nu];
+    double w[nxa], gv0[nu];
     for (int i = 0; i < nxa; ++i) w[i] = (gxt ? gxt[b * nxa + i] : 0.0) + (gp ? gp[i] : 0.0);
-    for (int j = 0; j < nu; ++j) {
+    const auto first_input = [&](int j) {  // g v_0
         double acc = 0.0;
         for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
-        gu[j] = w[nx + j] + acc;
-    }
-    if (row <= 2 * N) {  // g du_k
+        if constexpr (Tail::incremental) return w[nx + j] + acc;
+        else return acc + (gu ? gu[b * nu + j] : 0.0);
+    };
+    // incremental: input row 0 and the model row read it, and forming it in every row measured
+    // faster than doing so under their branches; direct: input row 0 alone forms it
+    if constexpr (Tail::incremental)
+        for (int j = 0; j < nu; ++j) gv0[j] = first_input(j);
+    if (row <= 2 * N) {  // g v_k
         if (!gsol) return;
         const int k = row - (N + 1);
+        double g[nu];
         for (int j = 0; j < nu; ++j) {
-            double g = k == 0 ? gu[j] : (gd ? gd[(k - 1) * nu + j] : 0.0);
-            if (k == N - 1 && gd) g = (g + gd[(N - 1) * nu + j]) + gd[N * nu + j];
-            gsol[b * n + (N + 1) * nxa + k * nu + j] = g;
+            if (k == 0) g[j] = Tail::incremental ? gv0[j] : first_input(j);
+            else g[j] = gd ? gd[(k - 1) * nu + j] : 0.0;
+            if (k == N - 1 && gd) g[j] = (g[j] + gd[(N - 1) * nu + j]) + gd[N * nu + j];
         }
+        if (gp) Tail::terminal(vk, N, s, gp + N * nxa, row, g);
+        for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nxa + k * nu + j] = g[j];
         return;
     }
     // the model row
     const double* A0 = Ad + b * (long)N * nx * nx;
     const double* xb = xt + b * nxa;
     double uu[nu];
-    for (int j = 0; j < nu; ++j) uu[j] = xb[nx + j] + s[(N + 1) * nxa + j];
+    for (int j = 0; j < nu; ++j)
+        uu[j] = Tail::incremental ? xb[nx + j] + s[(N + 1) * nxa + j] : s[(N + 1) * nxa + j];
     for (int i = 0; i < nx; ++i) {
         if (gAd0)
             for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
@@ -1320,112 +1308,11 @@ __global__ __launch_bounds__(256) void k_kin_shift_vjp(mpcqp_kin_vehicle vk, Inc
             for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
             gxt_o[b * nxa + j] = acc;
         }
-        for (int j = 0; j < nu; ++j) gxt_o[b * nxa + nx + j] = gu[j];
+        if constexpr (Tail::incremental)
+            for (int j = 0; j < nu; ++j) gxt_o[b * nxa + nx + j] = gv0[j];
     }
 }
 
-// k_kin_ltv_shift's executed branch: sol = (S_0..S_N, U_0..U_{N-1}), cotangents gx (B,4), gu (B,2),
-// gpx (B,N+1,4), gpu (B,N+1,2) of the NEW x, u, pred_x, pred_u.  With w = gx + gpx[0], mode 0:
-//   plant step   gAd0 = w x',  gBd0 = w U_0',  ggd0 = w,  gx_before = Ad0' w,  g U_0 = Bd0' w + gu
-//                (the old u is not read by the forward)
-//   shift        g S_k = gpx[k-1] (2 <= k <= N),  g U_k = gpu[k-1] (1 <= k <= N-1);  U_{N-1} also takes
-//                gpu[N-1] and gpu[N], added in that order
-//   terminal     pred_x[N] = kin_update(S_N, U_{N-1}): kin_update_vjp of gpx[N] into S_N and, last,
-//                into U_{N-1} (at N = 2 that is U_1, which is all of the above at once)
-__global__ __launch_bounds__(256) void k_kin_ltv_shift_vjp(mpcqp_kin_vehicle vk, int N, int n, long B,
-                                                           const double* __restrict__ sol,
-                                                           const double* __restrict__ Ad,
-                                                           const double* __restrict__ Bd, const double* __restrict__ x,
-                                                           const int* __restrict__ dmode, const double* __restrict__ gx,
-                                                           const double* __restrict__ gu, const double* __restrict__ gpx,
-                                                           const double* __restrict__ gpu, double* __restrict__ gsol,
-                                                           double* __restrict__ gAd0, double* __restrict__ gBd0,
-                                                           double* __restrict__ ggd0, double* __restrict__ gx_o) {
-    const int rows = 2 * N + 2;
-    constexpr int nx = 4, nu = 2;  // the entry point's check
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * rows) return;
-    const long b = t / rows;
-    const int row = (int)(t - b * rows);
-    const bool skip = dmode && dmode[b] != 0;
-    const double* S = sol + b * n;
-    const double* U = S + (N + 1) * nx;
-    const double* gp = gpx ? gpx + b * (long)(N + 1) * nx : nullptr;
-    const double* gq = gpu ? gpu + b * (long)(N + 1) * nu : nullptr;
-    if (row <= 2 * N && skip) {  // the solution was not used
-        if (!gsol) return;
-        if (row <= N)
-            for (int i = 0; i < nx; ++i) gsol[b * n + row * nx + i] = 0.0;
-        else
-            for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nx + (row - (N + 1)) * nu + j] = 0.0;
-        return;
-    }
-    if (row <= N) {  // g S_row
-        if (!gsol) return;
-        const int k = row;
-        double g[nx];
-        for (int i = 0; i < nx; ++i) g[i] = (k >= 2 && gp) ? gp[(k - 1) * nx + i] : 0.0;
-        if (k == N && gp) {
-            double ge[nx], gue[nu];
-            kin_update_vjp(vk, S + N * nx, U + (N - 1) * nu, gp + N * nx, ge, gue);
-            for (int i = 0; i < nx; ++i) g[i] = g[i] + ge[i];
-        }
-        for (int i = 0; i < nx; ++i) gsol[b * n + k * nx + i] = g[i];
-        return;
-    }
-    double w[nx];
-    for (int i = 0; i < nx; ++i) w[i] = (gx ? gx[b * nx + i] : 0.0) + (gp ? gp[i] : 0.0);
-    if (row <= 2 * N) {  // g U_k
-        if (!gsol) return;
-        const int k = row - (N + 1);
-        const double* B0 = Bd + b * (long)N * nx * nu;
-        double g[nu];
-        for (int j = 0; j < nu; ++j) {
-            if (k == 0) {
-                double acc = 0.0;
-                for (int i = 0; i < nx; ++i) acc += B0[i * nu + j] * w[i];
-                g[j] = acc + (gu ? gu[b * nu + j] : 0.0);
-            } else {
-                g[j] = gq ? gq[(k - 1) * nu + j] : 0.0;
-            }
-            if (k == N - 1 && gq) g[j] = (g[j] + gq[(N - 1) * nu + j]) + gq[N * nu + j];
-        }
-        if (k == N - 1 && gp) {
-            double ge[nx], gue[nu];
-            kin_update_vjp(vk, S + N * nx, U + (N - 1) * nu, gp + N * nx, ge, gue);
-            for (int j = 0; j < nu; ++j) g[j] = g[j] + gue[j];
-        }
-        for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nx + k * nu + j] = g[j];
-        return;
-    }
-    // the model row
-    if (skip) {
-        for (int i = 0; i < nx; ++i) {
-            if (gAd0)
-                for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = 0.0;
-            if (gBd0)
-                for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = 0.0;
-            if (ggd0) ggd0[b * nx + i] = 0.0;
-            if (gx_o) gx_o[b * nx + i] = gx ? gx[b * nx + i] : 0.0;
-        }
-        return;
-    }
-    const double* A0 = Ad + b * (long)N * nx * nx;
-    const double* xb = x + b * nx;
-    for (int i = 0; i < nx; ++i) {
-        if (gAd0)
-            for (int j = 0; j < nx; ++j) gAd0[b * nx * nx + i * nx + j] = w[i] * xb[j];
-        if (gBd0)
-            for (int j = 0; j < nu; ++j) gBd0[b * nx * nu + i * nu + j] = w[i] * U[j];
-        if (ggd0) ggd0[b * nx + i] = w[i];
-    }
-    if (gx_o)
-        for (int j = 0; j < nx; ++j) {
-            double acc = 0.0;
-            for (int i = 0; i < nx; ++i) acc += A0[i * nx + j] * w[i];
-            gx_o[b * nx + j] = acc;
-        }
-}
 
 // Tail of mpc_kinematics.main's loop (:397-456), per vehicle.  One model (the linearisation at
 // the current (x, u)) serves every stage, so Ad / Bd / gd are read at stage 0 of the (B, N, ..)
@@ -1840,6 +1727,23 @@ int linearise_device(const char* what, const V* veh, int64_t B, int32_t N, const
                   u_sk, dAd, dBd, dgd);
 }
 
+// dmode: null where the Tail has no modes; dgu: the direct-input Tail's, else null.  Every
+// cotangent and every output may be null.
+template <class Tail, class V>
+int tail_vjp_device(const char* what, const IncrLayout* L, const V* veh, int64_t B, const double* dsol,
+                    const double* dAd, const double* dBd, const double* dx_before, const int32_t* dmode,
+                    const double* dgx, const double* dgu, const double* dgpred, const double* dgpdu, double* dgsol,
+                    double* dgAd0, double* dgBd0, double* dggd0, double* dgx_before, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dx_before || B < 0)
+        return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (L->nx != Tail::nx || L->nu != Tail::nu)
+        return set_error(MPCQP_EUNSUPPORTED, "%s: the plant model is the %s bicycle (nx %d, nu %d)", what, Tail::model,
+                         Tail::nx, Tail::nu);
+    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgx_before)) return 0;
+    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_tail_vjp<Tail>, vehicle_constants(*veh), L->N, L->n, B,
+                  dsol, dAd, dBd, dx_before, dmode, dgx, dgu, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgx_before);
+}
+
 // dpath_yaw, dset_speed: the kinematic reference's (its entry point checks them), else null
 template <class M>
 int reference_device(const char* what, int64_t B, int32_t N, int32_t nxa, int32_t npath, const double* dpath_x,
@@ -2125,15 +2029,8 @@ int mpcqp_incr_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_vehicle*
                                 const double* dgxt, const double* dgpred, const double* dgpdu, double* dgsol,
                                 double* dgAd0, double* dgBd0, double* dggd0, double* dgxt_before, void* stream) {
     (void)dgd;  // the step is affine in gd: its VJP does not read it
-    if (!L || !veh || !dsol || !dAd || !dBd || !dxt_before || B < 0)
-        return set_error(MPCQP_EINVAL, "incr_shift_vjp: bad arguments");
-    if (L->nx != 6 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "incr_shift_vjp: the plant model is the 6-state dynamic bicycle (nx 6, nu 2)");
-    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgxt_before)) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_incr_shift_vjp, vehicle_constants(*veh), incr_k(*L), B,
-                  dsol, dAd, dBd, dxt_before, dgxt, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before);
+    return tail_vjp_device<DynamicIncrTail>("incr_shift_vjp", L, veh, B, dsol, dAd, dBd, dxt_before, nullptr, dgxt,
+                                            nullptr, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before, stream);
 }
 
 int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
@@ -2181,15 +2078,8 @@ int mpcqp_kin_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehic
                                double* dgsol, double* dgAd0, double* dgBd0, double* dggd0, double* dgxt_before,
                                void* stream) {
     (void)dgd;  // the step is affine in gd: its VJP does not read it
-    if (!L || !veh || !dsol || !dAd || !dBd || !dxt_before || B < 0)
-        return set_error(MPCQP_EINVAL, "kin_shift_vjp: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "kin_shift_vjp: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgxt_before)) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_kin_shift_vjp, *veh, incr_k(*L), B, dsol, dAd, dBd,
-                  dxt_before, dmode, dgxt, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before);
+    return tail_vjp_device<KinIncrTail>("kin_shift_vjp", L, veh, B, dsol, dAd, dBd, dxt_before, dmode, dgxt, nullptr,
+                                        dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before, stream);
 }
 
 int mpcqp_kin_ltv_shift_vjp_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
@@ -2197,14 +2087,8 @@ int mpcqp_kin_ltv_shift_vjp_device(const mpcqp_ltv_layout* L, const mpcqp_kin_ve
                                    const int32_t* dmode, const double* dgx, const double* dgu, const double* dgpred_x,
                                    const double* dgpred_u, double* dgsol, double* dgAd0, double* dgBd0, double* dggd0,
                                    double* dgx_before, void* stream) {
-    if (!L || !veh || !dsol || !dAd || !dBd || !dx_before || B < 0)
-        return set_error(MPCQP_EINVAL, "kin_ltv_shift_vjp: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "kin_ltv_shift_vjp: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgx_before)) return 0;
-    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_kin_ltv_shift_vjp, *veh, L->N, L->n, B, dsol, dAd, dBd,
-                  dx_before, dmode, dgx, dgu, dgpred_x, dgpred_u, dgsol, dgAd0, dgBd0, dggd0, dgx_before);
+    return tail_vjp_device<KinLtvTail>("kin_ltv_shift_vjp", L, veh, B, dsol, dAd, dBd, dx_before, dmode, dgx, dgu,
+                                       dgpred_x, dgpred_u, dgsol, dgAd0, dgBd0, dggd0, dgx_before, stream);
 }
 
 int mpcqp_kin_reference_search_paths_device(int64_t B, int32_t N, int32_t nxa, int32_t npaths, int32_t npath,

@@ -691,13 +691,51 @@ def _euler_step(veh: VehicleParams, x, u):
     return [x[i] + f[i] * dt for i in range(6)]
 
 
-def _shift_args(N, sol, Ad0, Bd0, xt):
-    sol, xt = np.asarray(sol, float), np.asarray(xt, float)
-    lead = xt.shape[:-1]
+def _kin_tail_args(N, nx, nxa, sol, Ad0, Bd0, x, mode=None):
+    sol, x = np.asarray(sol, float), np.asarray(x, float)
+    lead = x.shape[:-1]
     S = sol.reshape(-1, sol.shape[-1])
     M = S.shape[0]
-    return (lead, M, S[:, :(N + 1) * 8].reshape(M, N + 1, 8), S[:, (N + 1) * 8:].reshape(M, N, 2),
-            np.asarray(Ad0, float).reshape(M, 6, 6), np.asarray(Bd0, float).reshape(M, 6, 2), xt.reshape(M, 8))
+    mode = np.zeros(M, int) if mode is None else np.broadcast_to(np.asarray(mode, int).reshape(-1), (M,))
+    return (lead, M, S[:, :(N + 1) * nxa].reshape(M, N + 1, nxa), S[:, (N + 1) * nxa:].reshape(M, N, 2),
+            np.asarray(Ad0, float).reshape(M, nx, nx), np.asarray(Bd0, float).reshape(M, nx, 2), x.reshape(M, nxa),
+            mode)
+
+
+def _plant_step(A0, B0, g0, x, uu):
+    """plant_step's association: (sum_j A0[i, j] x[j] + sum_j B0[i, j] u[j]) + g0[i]."""
+    M, nx, nu = x.shape[0], A0.shape[1], B0.shape[2]
+    xn = np.empty((M, nx))
+    for i in range(nx):
+        acc = np.zeros(M)
+        for j in range(nx):
+            acc = acc + A0[:, i, j] * x[:, j]
+        bu = np.zeros(M)
+        for j in range(nu):
+            bu = bu + B0[:, i, j] * uu[:, j]
+        xn[:, i] = (acc + bu) + g0[:, i]
+    return xn
+
+
+def _plant_step_vjp(A0, B0, w):
+    """(Ad0' w, Bd0' w) in the kernel's order of summation."""
+    M, nx, nu = w.shape[0], A0.shape[1], B0.shape[2]
+    ga, gb = np.empty((M, nx)), np.empty((M, nu))
+    for j in range(nx):
+        acc = np.zeros(M)
+        for i in range(nx):
+            acc = acc + A0[:, i, j] * w[:, i]
+        ga[:, j] = acc
+    for j in range(nu):
+        acc = np.zeros(M)
+        for i in range(nx):
+            acc = acc + B0[:, i, j] * w[:, i]
+        gb[:, j] = acc
+    return ga, gb
+
+
+def _cot(g, M, tail):
+    return np.zeros((M,) + tail) if g is None else np.asarray(g, float).reshape((M,) + tail)
 
 
 def incr_shift(veh: VehicleParams, N, sol, Ad0, Bd0, gd0, xt):
@@ -710,19 +748,10 @@ def incr_shift(veh: VehicleParams, N, sol, Ad0, Bd0, gd0, xt):
     = (xt', x~_2..x~_N, (euler_step(x_N, u_{N-1}), u_N)) -- u_k the input part of x~_k, the Euler
     step update_dynamics_model from the guarded point --; pdu' (..., N+1, 2) = (du_1..du_{N-1},
     du_{N-1}, du_{N-1})."""
-    lead, M, X, D, A0, B0, x0 = _shift_args(N, sol, Ad0, Bd0, xt)
+    lead, M, X, D, A0, B0, x0, _ = _kin_tail_args(N, 6, 8, sol, Ad0, Bd0, xt)
     g0 = np.asarray(gd0, float).reshape(M, 6)
     uu = x0[:, 6:] + D[:, 0]
-    xn = np.empty((M, 8))
-    for i in range(6):  # plant_step's association
-        acc = np.zeros(M)
-        for j in range(6):
-            acc = acc + A0[:, i, j] * x0[:, j]
-        bu = np.zeros(M)
-        for j in range(2):
-            bu = bu + B0[:, i, j] * uu[:, j]
-        xn[:, i] = (acc + bu) + g0[:, i]
-    xn[:, 6:] = uu
+    xn = np.concatenate([_plant_step(A0, B0, g0, x0[:, :6], uu), uu], axis=1)
     pred, pdu = np.empty((M, N + 1, 8)), np.empty((M, N + 1, 2))
     pred[:, 0] = xn
     pred[:, 1:N] = X[:, 2:N + 1]
@@ -736,7 +765,7 @@ def incr_shift(veh: VehicleParams, N, sol, Ad0, Bd0, gd0, xt):
 
 
 def incr_shift_vjp(veh: VehicleParams, N, sol, Ad0, Bd0, xt, gxt=None, gpred=None, gpdu=None):
-    """The VJP of incr_shift in the order of mpc_device.hip's k_incr_shift_vjp
+    """The VJP of incr_shift in the order of mpc_device.hip's k_tail_vjp<DynamicIncrTail>
     (mpcqp_incr_shift_vjp_device): cotangents gxt (..., 8), gpred (..., N+1, 8), gpdu (..., N+1, 2)
     of (xt', pred', pdu') (None = zero); xt the value from BEFORE the step.  Returns (gsol, gAd0,
     gBd0, ggd0, gxt_before) with the shapes of (sol, Ad0, Bd0, gd0, xt).
@@ -751,25 +780,15 @@ def incr_shift_vjp(veh: VehicleParams, N, sol, Ad0, Bd0, xt, gxt=None, gpred=Non
     vy, r, steer, accel) at the guarded point, seeds 0 where the guard put a constant (so those
     entries get exactly nothing from it), its tangents contracted with gpred[N]'s state part; X and
     Y pass through it with derivative 1."""
-    lead, M, X, D, A0, B0, x0 = _shift_args(N, sol, Ad0, Bd0, xt)
-    zero = lambda g, tail: np.zeros((M,) + tail) if g is None else np.asarray(g, float).reshape((M,) + tail)
-    gxt, gpred, gpdu = zero(gxt, (8,)), zero(gpred, (N + 1, 8)), zero(gpdu, (N + 1, 2))
+    lead, M, X, D, A0, B0, x0, _ = _kin_tail_args(N, 6, 8, sol, Ad0, Bd0, xt)
+    gxt, gpred, gpdu = _cot(gxt, M, (8,)), _cot(gpred, M, (N + 1, 8)), _cot(gpdu, M, (N + 1, 2))
     w = gxt + gpred[:, 0]
     uu = x0[:, 6:] + D[:, 0]
     gA0 = w[:, :6, None] * x0[:, None, :6]
     gB0 = w[:, :6, None] * uu[:, None, :]
     gg0 = w[:, :6].copy()
-    gx0 = np.empty((M, 8))
-    for j in range(6):
-        acc = np.zeros(M)
-        for i in range(6):
-            acc = acc + A0[:, i, j] * w[:, i]
-        gx0[:, j] = acc
-    for j in range(2):
-        acc = np.zeros(M)
-        for i in range(6):
-            acc = acc + B0[:, i, j] * w[:, i]
-        gx0[:, 6 + j] = w[:, 6 + j] + acc
+    ga, gb = _plant_step_vjp(A0, B0, w[:, :6])
+    gx0 = np.concatenate([ga, w[:, 6:] + gb], axis=1)
     gX, gD = np.zeros((M, N + 1, 8)), np.zeros((M, N, 2))
     gX[:, 2:N + 1] = gpred[:, 1:N]
     gD[:, 0] = gx0[:, 6:]
@@ -815,52 +834,6 @@ def kin_update_vjp(l_f, l_r, dt, x, u, w):
     return gx, gu
 
 
-def _kin_tail_args(N, nxa, sol, Ad0, Bd0, x, mode):
-    sol, x = np.asarray(sol, float), np.asarray(x, float)
-    lead = x.shape[:-1]
-    S = sol.reshape(-1, sol.shape[-1])
-    M = S.shape[0]
-    mode = np.zeros(M, int) if mode is None else np.broadcast_to(np.asarray(mode, int).reshape(-1), (M,))
-    return (lead, M, S[:, :(N + 1) * nxa].reshape(M, N + 1, nxa), S[:, (N + 1) * nxa:].reshape(M, N, 2),
-            np.asarray(Ad0, float).reshape(M, 4, 4), np.asarray(Bd0, float).reshape(M, 4, 2), x.reshape(M, nxa), mode)
-
-
-def _plant_step4(A0, B0, g0, x, uu):
-    """plant_step's association: (sum_j A0[i, j] x[j] + sum_j B0[i, j] u[j]) + g0[i]."""
-    M = x.shape[0]
-    xn = np.empty((M, 4))
-    for i in range(4):
-        acc = np.zeros(M)
-        for j in range(4):
-            acc = acc + A0[:, i, j] * x[:, j]
-        bu = np.zeros(M)
-        for j in range(2):
-            bu = bu + B0[:, i, j] * uu[:, j]
-        xn[:, i] = (acc + bu) + g0[:, i]
-    return xn
-
-
-def _plant_step4_vjp(A0, B0, w):
-    """(Ad0' w, Bd0' w) in the kernels' order of summation."""
-    M = w.shape[0]
-    ga, gb = np.empty((M, 4)), np.empty((M, 2))
-    for j in range(4):
-        acc = np.zeros(M)
-        for i in range(4):
-            acc = acc + A0[:, i, j] * w[:, i]
-        ga[:, j] = acc
-    for j in range(2):
-        acc = np.zeros(M)
-        for i in range(4):
-            acc = acc + B0[:, i, j] * w[:, i]
-        gb[:, j] = acc
-    return ga, gb
-
-
-def _cot(g, M, tail):
-    return np.zeros((M,) + tail) if g is None else np.asarray(g, float).reshape((M,) + tail)
-
-
 def kin_incr_shift(veh, N, sol, Ad0, Bd0, gd0, xt, mode=None, pred=None, pdu=None):
     """The plant step and in-place horizon shift that simulate (mpc_incre_kine_func.py:385-428) and
     mpc_increment_kinematics_pred_matrix.main (:442-472) share -- mpc_device.hip::kin_incr_step_shift
@@ -873,10 +846,10 @@ def kin_incr_shift(veh, N, sol, Ad0, Bd0, gd0, xt, mode=None, pred=None, pdu=Non
     (..., N+1, 2) = (du_1..du_{N-1}, du_{N-1}, du_{N-1}).  mode 1 (done was set): xt and the given
     pred, pdu come back as they are.  mode 2 (the stop rule fired on this step): xt stays, pred' is
     the unpacked (x~_0..x~_N), pdu' = (du_0..du_{N-1}, du_{N-1})."""
-    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 6, sol, Ad0, Bd0, xt, mode)
+    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 4, 6, sol, Ad0, Bd0, xt, mode)
     g0 = np.asarray(gd0, float).reshape(M, 4)
     uu = x0[:, 4:] + D[:, 0]
-    xn = np.concatenate([_plant_step4(A0, B0, g0, x0[:, :4], uu), uu], axis=1)
+    xn = np.concatenate([_plant_step(A0, B0, g0, x0[:, :4], uu), uu], axis=1)
     pn, dn = np.empty((M, N + 1, 6)), np.empty((M, N + 1, 2))
     pn[:, 0] = xn
     pn[:, 1:N] = X[:, 2:N + 1]
@@ -895,7 +868,7 @@ def kin_incr_shift(veh, N, sol, Ad0, Bd0, gd0, xt, mode=None, pred=None, pdu=Non
 
 
 def kin_incr_shift_vjp(veh, N, sol, Ad0, Bd0, xt, gxt=None, gpred=None, gpdu=None, mode=None):
-    """The VJP of kin_incr_shift in the order of mpc_device.hip's k_kin_shift_vjp
+    """The VJP of kin_incr_shift in the order of mpc_device.hip's k_tail_vjp<KinIncrTail>
     (mpcqp_kin_shift_vjp_device): cotangents gxt (..., 6), gpred (..., N+1, 6), gpdu (..., N+1, 2)
     of (xt', pred', pdu') (None = zero); xt the value from BEFORE the step.  Returns (gsol, gAd0,
     gBd0, ggd0, gxt_before) with the shapes of (sol, Ad0, Bd0, gd0, xt).
@@ -908,14 +881,14 @@ def kin_incr_shift_vjp(veh, N, sol, Ad0, Bd0, xt, gxt=None, gpred=None, gpdu=Non
     gxt.  mode 2: x~_k takes gpred[k], du_k gpdu[k], du_{N-1} also gpdu[N]; gxt_before = gxt, the
     model outputs zero.  The cotangent of the previous pred / pdu (gpred / gpdu in mode 1, else
     zero) is not formed here."""
-    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 6, sol, Ad0, Bd0, xt, mode)
+    lead, M, X, D, A0, B0, x0, mode = _kin_tail_args(N, 4, 6, sol, Ad0, Bd0, xt, mode)
     gxt, gpred, gpdu = _cot(gxt, M, (6,)), _cot(gpred, M, (N + 1, 6)), _cot(gpdu, M, (N + 1, 2))
     w = gxt + gpred[:, 0]
     uu = x0[:, 4:] + D[:, 0]
     gA0 = w[:, :4, None] * x0[:, None, :4]
     gB0 = w[:, :4, None] * uu[:, None, :]
     gg0 = w[:, :4].copy()
-    ga, gb = _plant_step4_vjp(A0, B0, w[:, :4])
+    ga, gb = _plant_step_vjp(A0, B0, w[:, :4])
     gx0 = np.concatenate([ga, w[:, 4:] + gb], axis=1)
     gX, gD = np.zeros((M, N + 1, 6)), np.zeros((M, N, 2))
     gX[:, 2:N + 1] = gpred[:, 1:N]
@@ -948,9 +921,9 @@ def kin_ltv_shift(veh, N, sol, Ad0, Bd0, gd0, x, mode=None, u=None, pred_x=None,
     kin_update(S_N, U_{N-1})) -- the terminal control is stage N-1's --, pred_u' (..., N+1, 2) =
     (U_1..U_{N-1}, U_{N-1}, U_{N-1}).  mode 1 (status != solved): the given x, u, pred_x, pred_u
     come back as they are."""
-    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, sol, Ad0, Bd0, x, mode)
+    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, 4, sol, Ad0, Bd0, x, mode)
     g0 = np.asarray(gd0, float).reshape(M, 4)
-    xn = _plant_step4(A0, B0, g0, x0, U[:, 0])
+    xn = _plant_step(A0, B0, g0, x0, U[:, 0])
     un = U[:, 0].copy()
     px, pu = np.empty((M, N + 1, 4)), np.empty((M, N + 1, 2))
     px[:, 0] = xn
@@ -969,7 +942,7 @@ def kin_ltv_shift(veh, N, sol, Ad0, Bd0, gd0, x, mode=None, u=None, pred_x=None,
 
 
 def kin_ltv_shift_vjp(veh, N, sol, Ad0, Bd0, x, gx=None, gu=None, gpred_x=None, gpred_u=None, mode=None):
-    """The VJP of kin_ltv_shift in the order of mpc_device.hip's k_kin_ltv_shift_vjp
+    """The VJP of kin_ltv_shift in the order of mpc_device.hip's k_tail_vjp<KinLtvTail>
     (mpcqp_kin_ltv_shift_vjp_device): cotangents gx (..., 4), gu (..., 2), gpred_x (..., N+1, 4),
     gpred_u (..., N+1, 2) of (x', u', pred_x', pred_u') (None = zero); x from BEFORE the step.
     Returns (gsol, gAd0, gBd0, ggd0, gx_before).
@@ -979,14 +952,14 @@ def kin_ltv_shift_vjp(veh, N, sol, Ad0, Bd0, x, gx=None, gu=None, gpred_x=None, 
     U_{N-1} also gpred_u[N-1] and gpred_u[N] in that order; kin_update_vjp of gpred_x[N] at
     (S_N, U_{N-1}) goes into S_N and, last, into U_{N-1}.  mode 1: everything zero, gx_before = gx;
     the cotangent of the previous u, pred_x, pred_u (gu, gpred_x, gpred_u) is not formed here."""
-    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, sol, Ad0, Bd0, x, mode)
+    lead, M, S, U, A0, B0, x0, mode = _kin_tail_args(N, 4, 4, sol, Ad0, Bd0, x, mode)
     gx, gu = _cot(gx, M, (4,)), _cot(gu, M, (2,))
     gpx, gpu = _cot(gpred_x, M, (N + 1, 4)), _cot(gpred_u, M, (N + 1, 2))
     w = gx + gpx[:, 0]
     gA0 = w[:, :, None] * x0[:, None, :]
     gB0 = w[:, :, None] * U[:, 0][:, None, :]
     gg0 = w.copy()
-    gxb, gb = _plant_step4_vjp(A0, B0, w)
+    gxb, gb = _plant_step_vjp(A0, B0, w)
     gS, gU = np.zeros((M, N + 1, 4)), np.zeros((M, N, 2))
     gS[:, 2:N + 1] = gpx[:, 1:N]
     gU[:, 0] = gb + gu

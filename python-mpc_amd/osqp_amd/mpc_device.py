@@ -608,6 +608,43 @@ def incr_shift(layout, veh: Vehicle, sol, Ad, Bd, gd, xt):
     return xt1, pred, pdu
 
 
+def _tail_vjp(name, symbol, layout, veh, B, head, cots, shapes, outputs, want, out, mode=None, prev=()):
+    """What the tails' VJPs share: cotangent / output checks, the call (`head`: the entry point's
+    arguments between B and the cotangents), and the pass-through cotangents of the previous horizon
+    (`prev`: output name -> cotangent name, by `mode`)."""
+    import torch
+    from types import SimpleNamespace
+    dev = head[0].device
+    for k, t, shape in cots:
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shape}")
+    want = list(outputs) if want is None else list(want)
+    bad = sorted(set(want) - set(outputs))
+    if bad:
+        raise ValueError(f"{name}: unknown output(s) {', '.join(bad)}")
+    o = SimpleNamespace(**{k: None for k in outputs})
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shapes[k], dtype=torch.float64, device=dev)
+        elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
+        setattr(o, k, t)
+    _check(getattr(_bind(), symbol)(layout._h, C.byref(veh), B, *(_po(t) for t in head),
+                                    *(_po(t) for _, t, _ in cots), *(_po(getattr(o, k)) for k in outputs),
+                                    _stream(torch, dev)), name)
+    given = {k: t for k, t, _ in cots}
+    for k_out, k_cot in dict(prev).items():
+        g = given[k_cot]
+        if g is None:
+            setattr(o, k_out, None)
+        elif mode is None:
+            setattr(o, k_out, torch.zeros_like(g))
+        else:
+            setattr(o, k_out, torch.where((mode == 1).view((-1,) + (1,) * (g.dim() - 1)), g, 0.0))
+    return o
+
+
 SHIFT_VJP_OUTPUTS = ("gsol", "gAd0", "gBd0", "ggd0", "gxt")
 
 
@@ -618,33 +655,14 @@ def incr_shift_vjp(layout, veh: Vehicle, sol, Ad, Bd, xt, gxt=None, gpred=None, 
     = zero.  want: the outputs to form, of SHIFT_VJP_OUTPUTS (default all); out: {name: tensor} to
     write into.  Returns a namespace with gsol (B, n), gAd0 (B, 6, 6), gBd0 (B, 6, 2), ggd0 (B, 6)
     -- the stage-0 model's, to be added into stage 0 -- and gxt (B, 8), None where not wanted."""
-    import torch
-    from types import SimpleNamespace
     B, N = sol.shape[0], layout.N
     sol = _shift_in(sol, (B, layout.n), "sol")
     Ad, Bd = _shift_in(Ad, (B, N, 6, 6), "Ad"), _shift_in(Bd, (B, N, 6, 2), "Bd")
     xt = _shift_in(xt, (B, 8), "xt")
-    for t, shape, k in ((gxt, (B, 8), "gxt"), (gpred, (B, N + 1, 8), "gpred"), (gpdu, (B, N + 1, 2), "gpdu")):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise ValueError(f"incr_shift_vjp: {k} must be a contiguous float64 tensor of shape {shape}")
     shapes = dict(gsol=(B, layout.n), gAd0=(B, 6, 6), gBd0=(B, 6, 2), ggd0=(B, 6), gxt=(B, 8))
-    want = list(SHIFT_VJP_OUTPUTS) if want is None else list(want)
-    bad = sorted(set(want) - set(shapes))
-    if bad:
-        raise ValueError(f"incr_shift_vjp: unknown output(s) {', '.join(bad)}")
-    o = SimpleNamespace(**{k: None for k in shapes})
-    for k in want:
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shapes[k], dtype=torch.float64, device=sol.device)
-        elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
-            raise ValueError(f"incr_shift_vjp: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
-        setattr(o, k, t)
-    _check(_bind().mpcqp_incr_shift_vjp_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), None, _p(xt),
-                                               _po(gxt), _po(gpred), _po(gpdu),
-                                               *(_po(getattr(o, k)) for k in SHIFT_VJP_OUTPUTS),
-                                               _stream(torch, sol.device)), "incr_shift_vjp")
-    return o
+    return _tail_vjp("incr_shift_vjp", "mpcqp_incr_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, None, xt),
+                     (("gxt", gxt, (B, 8)), ("gpred", gpred, (B, N + 1, 8)), ("gpdu", gpdu, (B, N + 1, 2))),
+                     shapes, SHIFT_VJP_OUTPUTS, want, out)
 
 
 def warm_shift(N, nxa, nu, x, y=None):
@@ -920,42 +938,6 @@ def kin_ltv_shift(layout, veh: KinVehicle, sol, status, Ad, Bd, gd, x, u, pred_x
     return x1, u1, px1, pu1, mode
 
 
-def _kin_tail_vjp(name, symbol, layout, veh, B, head, mode, cots, shapes, outputs, want, out, prev):
-    """What kin_shift_vjp and kin_ltv_shift_vjp share: cotangent / output checks, the call, and the
-    pass-through cotangents of the previous horizon (`prev`: output name -> cotangent name)."""
-    import torch
-    from types import SimpleNamespace
-    dev = head[0].device
-    for k, t, shape in cots:
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shape}")
-    want = list(outputs) if want is None else list(want)
-    bad = sorted(set(want) - set(outputs))
-    if bad:
-        raise ValueError(f"{name}: unknown output(s) {', '.join(bad)}")
-    o = SimpleNamespace(**{k: None for k in outputs})
-    for k in want:
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shapes[k], dtype=torch.float64, device=dev)
-        elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
-            raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
-        setattr(o, k, t)
-    _check(getattr(_bind(), symbol)(layout._h, C.byref(veh), B, *(_po(t) for t in head), _po(mode),
-                                    *(_po(t) for _, t, _ in cots), *(_po(getattr(o, k)) for k in outputs),
-                                    _stream(torch, dev)), name)
-    given = {k: t for k, t, _ in cots}
-    for k_out, k_cot in prev.items():
-        g = given[k_cot]
-        if g is None:
-            setattr(o, k_out, None)
-        elif mode is None:
-            setattr(o, k_out, torch.zeros_like(g))
-        else:
-            setattr(o, k_out, torch.where((mode == 1).view((-1,) + (1,) * (g.dim() - 1)), g, 0.0))
-    return o
-
-
 KIN_LTV_SHIFT_VJP_OUTPUTS = ("gsol", "gAd0", "gBd0", "ggd0", "gx")
 
 
@@ -975,9 +957,9 @@ def kin_shift_vjp(layout, veh: KinVehicle, sol, Ad, Bd, xt, mode=None, gxt=None,
     xt = _shift_in(xt, (B, 6), "xt")
     mode = _mode_in(mode, B, "kin_shift_vjp: mode")
     shapes = dict(gsol=(B, layout.n), gAd0=(B, 4, 4), gBd0=(B, 4, 2), ggd0=(B, 4), gxt=(B, 6))
-    return _kin_tail_vjp("kin_shift_vjp", "mpcqp_kin_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, None, xt), mode,
-                         (("gxt", gxt, (B, 6)), ("gpred", gpred, (B, N + 1, 6)), ("gpdu", gpdu, (B, N + 1, 2))),
-                         shapes, SHIFT_VJP_OUTPUTS, want, out, dict(gpred_prev="gpred", gpdu_prev="gpdu"))
+    return _tail_vjp("kin_shift_vjp", "mpcqp_kin_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, None, xt, mode),
+                     (("gxt", gxt, (B, 6)), ("gpred", gpred, (B, N + 1, 6)), ("gpdu", gpdu, (B, N + 1, 2))),
+                     shapes, SHIFT_VJP_OUTPUTS, want, out, mode, dict(gpred_prev="gpred", gpdu_prev="gpdu"))
 
 
 def kin_ltv_shift_vjp(layout, veh: KinVehicle, sol, Ad, Bd, x, mode=None, gx=None, gu=None, gpred_x=None,
@@ -994,10 +976,10 @@ def kin_ltv_shift_vjp(layout, veh: KinVehicle, sol, Ad, Bd, x, mode=None, gx=Non
     x = _shift_in(x, (B, 4), "x")
     mode = _mode_in(mode, B, "kin_ltv_shift_vjp: mode")
     shapes = dict(gsol=(B, layout.n), gAd0=(B, 4, 4), gBd0=(B, 4, 2), ggd0=(B, 4), gx=(B, 4))
-    return _kin_tail_vjp("kin_ltv_shift_vjp", "mpcqp_kin_ltv_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, x), mode,
-                         (("gx", gx, (B, 4)), ("gu", gu, (B, 2)), ("gpred_x", gpred_x, (B, N + 1, 4)),
-                          ("gpred_u", gpred_u, (B, N + 1, 2))), shapes, KIN_LTV_SHIFT_VJP_OUTPUTS, want, out,
-                         dict(gu_prev="gu", gpred_x_prev="gpred_x", gpred_u_prev="gpred_u"))
+    return _tail_vjp("kin_ltv_shift_vjp", "mpcqp_kin_ltv_shift_vjp_device", layout, veh, B, (sol, Ad, Bd, x, mode),
+                     (("gx", gx, (B, 4)), ("gu", gu, (B, 2)), ("gpred_x", gpred_x, (B, N + 1, 4)),
+                      ("gpred_u", gpred_u, (B, N + 1, 2))), shapes, KIN_LTV_SHIFT_VJP_OUTPUTS, want, out, mode,
+                     dict(gu_prev="gu", gpred_x_prev="gpred_x", gpred_u_prev="gpred_u"))
 
 
 class KinematicMPC(_ClosedLoop):

@@ -129,6 +129,13 @@ def _functions():
                 gt = torch.cat([gt, gt.new_zeros((ctx.shape[0], ctx.shape[1] - a.nparam))], dim=1)
             return None, gt, None
 
+    def stage0(t, N):  # the tails read the model of stage 0 only: its cotangent, zero in the others
+        if t is None:
+            return None
+        full = t.new_zeros((t.shape[0], N) + tuple(t.shape[1:]))
+        full[:, 0] = t
+        return full
+
     class IncrShift(torch.autograd.Function):
         """inputs (layout, veh, sol, Ad, Bd, gd, xt)"""
 
@@ -148,22 +155,8 @@ def _functions():
             need = ctx.needs_input_grad[2:]  # (sol, Ad, Bd, gd, xt)
             want = [k for k, n in zip(md.SHIFT_VJP_OUTPUTS, need) if n]
             g = md.incr_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, xt, _c(gxt), _c(gpred), _c(gpdu), want=want)
-
-            def stage0(t, like_tail):  # the model outputs are stage 0's
-                if t is None:
-                    return None
-                full = t.new_zeros((t.shape[0], ctx.layout.N) + like_tail)
-                full[:, 0] = t
-                return full
-
-            return (None, None, g.gsol, stage0(g.gAd0, (6, 6)), stage0(g.gBd0, (6, 2)), stage0(g.ggd0, (6,)), g.gxt)
-
-    def stage0(t, N):  # the tails read the model of stage 0 only: its cotangent, zero in the others
-        if t is None:
-            return None
-        full = t.new_zeros((t.shape[0], N) + tuple(t.shape[1:]))
-        full[:, 0] = t
-        return full
+            N = ctx.layout.N
+            return (None, None, g.gsol, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), g.gxt)
 
     class KinShift(torch.autograd.Function):
         """inputs (layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)"""
@@ -219,57 +212,37 @@ def _functions():
                     g.gpred_u_prev if need[10] else None)
 
     class Rollout(torch.autograd.Function):
-        """inputs (roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w): the rollouts of the incremental
-        layout, whose state and horizon are one tensor each"""
+        """inputs (roll, T, path, use_w, *state, *hor, Xr, Q, QN, R), the state and the horizon as many
+        tensors as roll._STATE and roll._HOR say; outputs (*trajectories, [DU0,] *horizon)"""
 
         @staticmethod
-        def forward(ctx, roll, T, path, xt0, pred0, Xr, Q, QN, R, use_w):
-            xt0, pred0, Xr, Q, QN, R = (_c(t) for t in (xt0, pred0, Xr, Q, QN, R))
+        def forward(ctx, roll, T, path, use_w, *tensors):
+            tensors = tuple(_c(t) for t in tensors)
+            ns, nh = len(roll._STATE), len(roll._HOR)
+            Xr, Q, QN, R = tensors[ns + nh:]
             weights = (Q, QN, R) if use_w else None
             ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
             ctx.set_materialize_grads(False)
-            (XT,), DU0, (pred,), ctx.tape = roll._on_stream(lambda: roll._forward((xt0,), (pred0,), T, Xr, path,
-                                                                                   weights))
-            return XT, DU0, pred
+            trajs, DU0, hor, ctx.tape = roll._on_stream(lambda: roll._forward(tensors[:ns], tensors[ns:ns + nh], T, Xr,
+                                                                              path, weights))
+            return (*trajs, *((DU0,) if roll._DU0 else ()), *hor)
 
         @staticmethod
-        def backward(ctx, gXT, gDU0, gpred):
-            if gXT is None and gDU0 is None and gpred is None:
-                return (None,) * 10
+        def backward(ctx, *cots):
             roll = ctx.roll
-            need = dict(zip(("xt0", "pred0", "Xr", "Q", "QN", "R"), ctx.needs_input_grad[3:9]))
-            need["state"], need["hor"] = (need["xt0"],), (need["pred0"],)
-            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, (_c(gXT),), _c(gDU0),
-                                                       (_c(gpred),), need))
-            return (None, None, None, g["state"][0], g["hor"][0], g["Xr"], g["Q"], g["QN"], g["R"], None)
-
-    class RolloutLTV(torch.autograd.Function):
-        """inputs (roll, T, path, x0, u0, pred_x0, pred_u0, Xr, Q, QN, R, use_w): the LTV layout's
-        rollout, whose state is (x, u) and whose horizon is (pred_x, pred_u)"""
-
-        @staticmethod
-        def forward(ctx, roll, T, path, x0, u0, px0, pu0, Xr, Q, QN, R, use_w):
-            x0, u0, px0, pu0, Xr, Q, QN, R = (_c(t) for t in (x0, u0, px0, pu0, Xr, Q, QN, R))
-            weights = (Q, QN, R) if use_w else None
-            ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
-            ctx.set_materialize_grads(False)
-            (X, U), _, (px, pu), ctx.tape = roll._on_stream(lambda: roll._forward((x0, u0), (px0, pu0), T, Xr, path,
-                                                                                  weights))
-            return X, U, px, pu
-
-        @staticmethod
-        def backward(ctx, gX, gU, gpx, gpu):
-            if gX is None and gU is None and gpx is None and gpu is None:
-                return (None,) * 12
-            roll = ctx.roll
-            n = ctx.needs_input_grad
-            need = dict(state=(n[3], n[4]), hor=(n[5], n[6]), Xr=n[7], Q=n[8], QN=n[9], R=n[10])
-            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, (_c(gX), _c(gU)), None,
-                                                       (_c(gpx), _c(gpu)), need))
-            return (None, None, None, *g["state"], *g["hor"], g["Xr"], g["Q"], g["QN"], g["R"], None)
+            ns, nh = len(roll._STATE), len(roll._HOR)
+            if all(g is None for g in cots):
+                return (None,) * (8 + ns + nh)
+            cots = tuple(_c(g) for g in cots)
+            n = ctx.needs_input_grad[4:]
+            need = dict(state=n[:ns], hor=n[ns:ns + nh], Xr=n[-4], Q=n[-3], QN=n[-2], R=n[-1])
+            gDU0 = cots[ns] if roll._DU0 else None
+            g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, cots[:ns], gDU0,
+                                                       cots[len(cots) - nh:], need))
+            return (None, None, None, None, *g["state"], *g["hor"], g["Xr"], g["Q"], g["QN"], g["R"])
 
     _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine, IncrShift=IncrShift,
-                          KinShift=KinShift, KinLTVShift=KinLTVShift, Rollout=Rollout, RolloutLTV=RolloutLTV)
+                          KinShift=KinShift, KinLTVShift=KinLTVShift, Rollout=Rollout)
     return _FN
 
 
@@ -390,7 +363,7 @@ class _Rollout:
     """What the rollouts share: T control steps on ONE DeviceBatch with a tape of solution records,
     and the backward that walks it in reverse.  The loop's state and its
     predicted horizon are tuples of tensors of widths ``_STATE`` and ``_HOR`` (per stage).  A subclass
-    states its ``_NAME``, ``_LAYOUT`` = (kind, nx, nu, words), ``_FN`` and the model-specific parts:
+    states its ``_NAME``, ``_LAYOUT`` = (kind, nx, nu, words) and the model-specific parts:
 
       _problem(state, hor, Xr_t, path, weights)  -> Xr, Ad, Bd, gd, Px, (Ax, q, l, u)
       _shift(sol, status, Ad, Bd, gd, Xr, state, hor, aux) -> state', hor', mode, aux'
@@ -422,7 +395,6 @@ class _Rollout:
         self.Px = torch.from_numpy(P.data.copy()).to(self.dev)[None, :].repeat(self.B, 1).contiguous()
         self.stream = torch.cuda.Stream(self.dev)
         self.status = self.iters = self.astat = self.ares = self.act = self.mode = None
-        self._fn = getattr(_functions(), self._FN)
 
     def tape_doubles_per_instance(self):
         """Doubles the tape holds per step and instance: the state, the horizon, sol and the record
@@ -440,6 +412,11 @@ class _Rollout:
         for t, shape, k in tensors + ((Xr, (T, B, nx, N + 1), "Xr"),):
             if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.dev):
                 raise ValueError(f"{self._NAME}: {k} must be a float64 tensor of shape {shape} on {self.dev}")
+
+    def _apply(self, T, path, weights, *tensors):
+        """The rollout as one autograd node; tensors = (*state, *hor, Xr)."""
+        Q, QN, R, use_w = _split_weights(weights)
+        return _functions().Rollout.apply(self, T, path, use_w, *tensors, Q, QN, R)
 
     def _on_stream(self, fn):
         """fn() on the rollout's stream, ordered after the caller's current stream; the caller's
@@ -590,7 +567,7 @@ class DynamicRollout(_Rollout):
     with strict=False such an instance gets zero gradients in every input and the weight sums
     leave it out.  ``settings`` are DeviceBatch's."""
 
-    _NAME, _FN = "DynamicRollout", "Rollout"
+    _NAME = "DynamicRollout"
     _LAYOUT = ("incr", 6, 2, "an IncrementalLayout of the dynamic bicycle")
     _STATE, _HOR = (8,), (8,)
 
@@ -599,8 +576,7 @@ class DynamicRollout(_Rollout):
         self._check_call(T, Xr, path, ((xt0, (B, 8), "xt0"), (pred0, (B, N + 1, 8), "pred0")), "(path_x, path_y)")
         if path is not None:
             path = tuple(_c(p) for p in path)
-        Q, QN, R, use_w = _split_weights(weights)
-        return self._fn.apply(self, T, path, xt0, pred0, Xr, Q, QN, R, use_w)
+        return self._apply(T, path, weights, xt0, pred0, Xr)
 
     def _problem(self, state, hor, Xr_t, path, weights):
         """One step's reference, linearisation and QP values from (xt, pred), as DynamicMPC._step."""
@@ -659,7 +635,7 @@ class KinematicRollout(_Rollout):
     goes through that step's adjoint like any other.  The backward is DynamicRollout's with
     mpc_device.kin_shift_vjp and linearise_kinematics_vjp."""
 
-    _NAME, _FN = "KinematicRollout", "Rollout"
+    _NAME = "KinematicRollout"
     _LAYOUT = ("incr", 4, 2, "an IncrementalLayout of the kinematic bicycle")
     _STATE, _HOR = (6,), (6,)
     _problem = _incr_kin_problem
@@ -671,8 +647,7 @@ class KinematicRollout(_Rollout):
         if path is not None:
             speed = xt0[:, 2] if set_speed is None else set_speed
             path = tuple(_c(p) for p in path) + (_c(speed),)
-        Q, QN, R, use_w = _split_weights(weights)
-        return self._fn.apply(self, T, path, xt0, pred0, Xr, Q, QN, R, use_w)
+        return self._apply(T, path, weights, xt0, pred0, Xr)
 
     def _aux0(self):
         torch, B = self.torch, self.B
@@ -719,7 +694,7 @@ class KinematicLTVRollout(_Rollout):
     passes its cotangents through unchanged and is exempt from the ``strict`` rule -- its solution was
     not used; ``strict`` otherwise follows DynamicRollout's rule."""
 
-    _NAME, _FN, _DU0 = "KinematicLTVRollout", "RolloutLTV", False
+    _NAME, _DU0 = "KinematicLTVRollout", False
     _LAYOUT = ("ltv", 4, 2, "an LTVLayout of the kinematic bicycle")
     _STATE, _HOR = (4, 2), (4, 2)
     _problem = _incr_kin_problem
@@ -732,8 +707,7 @@ class KinematicLTVRollout(_Rollout):
         if path is not None:
             px, py = (_c(p) for p in path)
             path = (px, py, torch.zeros_like(px), torch.full((B,), self.SET_SPEED, dtype=torch.float64, device=self.dev))
-        Q, QN, R, use_w = _split_weights(weights)
-        return self._fn.apply(self, T, path, x0, u0, pred_x0, pred_u0, Xr, Q, QN, R, use_w)
+        return self._apply(T, path, weights, x0, u0, pred_x0, pred_u0, Xr)
 
     def _shift(self, sol, status, Ad, Bd, gd, Xr, state, hor, aux):
         x, u, px, pu, mode = md.kin_ltv_shift(self.layout, self.veh, sol, status, Ad, Bd, gd, *state, *hor)

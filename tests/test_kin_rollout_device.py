@@ -1,5 +1,5 @@
 """The kinematic closed loops differentiated on one solver handle (include/mpcqp.h):
-k_kin_shift_vjp and k_kin_ltv_shift_vjp against their numpy statements, masks included; the torch
+k_tail_vjp<KinIncrTail> and <KinLtvTail> against their numpy statements, masks included; the torch
 tails against the wrappers; torch_mpc.KinematicRollout / KinematicLTVRollout -- forward against
 KinematicMPC / KinematicLTVMPC, the masks end to end, backward against a chain of two recording
 MPCLayers with the torch tail between them and against central differences.

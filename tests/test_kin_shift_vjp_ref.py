@@ -1,6 +1,6 @@
 """osqp_amd.mpc.kin_incr_shift / kin_ltv_shift and their VJPs, the numpy statements of the two
 kinematic tails (kin_incr_step_shift under k_kin_shift and k_lane_tail; k_kin_ltv_shift) and of
-k_kin_shift_vjp / k_kin_ltv_shift_vjp: the forwards against the reference's own
+k_tail_vjp<KinIncrTail> / <KinLtvTail>: the forwards against the reference's own
 steps (tests/golden/kin_sim_n40.npz, kinltv_sim_n3.npz) and against mpc.lane_tail, the VJPs against
 central differences of the forwards, the masks' copies and zeros exactly.
 

@@ -1,5 +1,5 @@
 """Closed-loop rollouts differentiated on one solver handle (include/mpcqp.h): the
-solution record's round trip, QPLayer(record=True), k_incr_shift_vjp against its numpy statement,
+solution record's round trip, QPLayer(record=True), k_tail_vjp<DynamicIncrTail> against its numpy statement,
 and torch_mpc.DynamicRollout -- forward against DynamicMPC, backward against the chain of
 MPCLayers of tests/test_dyn_vjp_device.py and against central differences.
 

@@ -1,5 +1,5 @@
 """osqp_amd.mpc.incr_shift and incr_shift_vjp, the numpy statements of k_incr_shift and
-k_incr_shift_vjp: the forward against the reference's own three steps
+k_tail_vjp<DynamicIncrTail>: the forward against the reference's own three steps
 (tests/golden/dyn_main_n30.npz), the VJP against central differences of the forward.
 
 The tail of the loop is linear or bilinear in everything but the six inputs of the terminal Euler
