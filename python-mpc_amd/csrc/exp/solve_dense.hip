@@ -39,8 +39,9 @@
 // and Control/MPC/mpc_kinematics.py:196; oracle/osqp_oracle.c restates it).
 #include <hip/hip_runtime.h>
 
-#include "solve_phases.h"
-#include "wave_util.h"
+#include "../solve_phases.h"
+#include "../wave_util.h"
+#include "exp.h"
 
 namespace mpcqp {
 

@@ -34,13 +34,14 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "setup_r.h"
-#include "solve_phases.h"
-#include "wave_util.h"
+#include "../setup_r.h"
+#include "../solve_phases.h"
+#include "../wave_util.h"
+#include "exp.h"
 
 namespace mpcqp {
 
-#ifdef MPCQP_EXPERIMENTAL  // measured and not taken: the experimental builds only
+// measured and not taken: the experimental builds only
 constexpr int TH = 512;    // threads per instance
 constexpr int HSEG = 14;   // columns per segment (two per block of <= 28 real columns)
 constexpr int HSTR = 18;   // doubles between segments in the rhs layout (bank-spread)
@@ -656,7 +657,5 @@ hipError_t launch_setup_solve_heavy(const KParams& p, long B, const double* Px, 
     hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(TH), lds, st, p, Px, Ax, q, l, u, xo, yo);
     return hipGetLastError();
 }
-
-#endif  // MPCQP_EXPERIMENTAL
 
 }  // namespace mpcqp

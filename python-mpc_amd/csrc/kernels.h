@@ -1,4 +1,5 @@
-// kernels.h -- device-side interface shared by kernels.hip and api.hip.
+// kernels.h -- device-side interface shared by the kernel sources and api.hip: the parameter
+// block, the launch functions and the solve variants' descriptor (struct Variant).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +9,6 @@ namespace mpcqp {
 
 constexpr int kThreads = 256;
 constexpr int kThreadsBig = 512;  // solve_big.hip (long horizons)
-constexpr int kDenseR = 104;      // solve_dense.hip: register row length of M^{-1} (variables per QP)
 constexpr int kProfSlots = 24;  // factor, rhs, bt_solve, update, checks, tail, total cycles, total 100 MHz ticks,
                                 // factor split: assembly, F/S products, Gauss-Jordan, block epilogue,
                                 // solve split (wave kernels): phase A, phase B, phase C, spare,
@@ -38,7 +38,7 @@ struct KParams {
     int ifok;         // the interface form of the two-sided solve fits (solve_big.hip::iface_solve):
                       // amax, bmax <= 16 and the meeting block's top rows and window disjoint
     int bsz01, bsz23; // largest of blocks 0 and 1 / 2 and 3 (real columns; nb = 4 plans)
-    int variant;  // solve-kernel instantiation (solve.hip: launch_solve)
+    int variant;  // solve-kernel instantiation (solve.hip: the table of struct Variant below)
     int mode;     // factor storage of that variant (solve.hip: factorize)
     // plan
     const int *pad_var, *acsc_ptr, *acsc_row, *acsc_v, *acsr_ptr, *acsr_col, *acsr_v;
@@ -159,6 +159,34 @@ hipError_t launch_copy16(const double* src, double* dst, long n, hipStream_t st,
 constexpr long kDenseRowDoubles = 256L * 54;
 bool dense_w4_on();  // solve_wave.hip: experimental build and MPCQP_DENSE_W4=1
 inline long dense_rows_doubles(int nb, int ne) { return nb == 4 && ne == 0 && dense_w4_on() ? kDenseRowDoubles : 0; }
+// What a solve launch runs: the variant's kernel, workgroup size and dynamic LDS.  A launch
+// function given a non-null ref only fills it in (no launch).
+struct KernelRef {
+    const void* fn;
+    int threads;
+    size_t lds;
+};
+// One solve-kernel variant (KParams::variant, MPCQP_VARIANT).  solve.hip keeps the table of
+// them, indexed by id, and nothing else interprets a variant number; the experimental
+// builds add the variants of exp/variants.hip to it.
+struct Variant {
+    int id;
+    int threads;  // workgroup size: threads per QP
+    int mode;     // what factorize stores for the variant (KParams::mode)
+    bool order;   // the kernel sorts the next dispatch order in its last workgroup (KParams::done)
+    bool elim;    // handles plans with eliminated variables (KParams::ne)
+    bool (*fits)(const KParams& p);   // the exact precondition of the variant's instantiations
+    size_t (*lds)(const KParams& p);  // what its kernel allocates
+    hipError_t (*launch)(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                         KernelRef* ref);
+    // setup + solve of the same inputs where the variant owns a fused launch (polish included), or null
+    hipError_t (*setup_solve)(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                              const double* l, const double* u, double* xo, double* yo, hipStream_t st, int one_shot);
+};
+constexpr int kVariantIds = 20;
+const Variant* variant_of(int id);  // null: this build has no such variant
+// the experimental builds' entries (exp/variants.hip); returns their count
+int exp_variants(const Variant** list);
 int solve_variant(const KParams& p);  // -1: no instantiation fits the plan
 int solve_mode(int variant);
 int solve_threads(int variant);  // workgroup size of the variant's kernel
@@ -176,20 +204,9 @@ hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const 
 // own (two workgroups per CU still fit), 3 the G blocks straight into the solve's LDS copy
 // (factorize_w4_gl); *lds = its dynamic LDS bytes
 int one_shot_form(const KParams& p, size_t* lds = nullptr);
-// What a solve launch runs: the variant's kernel, workgroup size and dynamic LDS.  The
-// launch_solve_* functions given a non-null ref only fill it in (no launch).
-struct KernelRef {
-    const void* fn;
-    int threads;
-    size_t lds;
-};
 // resident workgroups of the variant's kernel per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 int solve_blocks_per_cu(const KParams& p);
-// dense-inverse kernel (solve_dense.hip), variant 16, and its LDS bytes
-hipError_t launch_solve_dense(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
-                        KernelRef* ref = nullptr);
-size_t lds_dense_bytes(const KParams& p);
-size_t lds_w2_bytes(const KParams& p);  // solve_wave.hip, variant 10
+size_t lds_w2_bytes(const KParams& p);  // solve_wave.hip: the two- and four-wave kernels
 // solution polishing (OSQP 0.6 polish.c) after the solve; launch_solve runs it when p.polish
 hipError_t launch_polish(const KParams& p, long B, double* xo, double* yo, hipStream_t st);
 // Gradients of the solution map (adjoint.hip::k_adjoint; mpcqp_adjoint_device): the seeds and
@@ -210,19 +227,24 @@ hipError_t launch_adjoint(const KParams& p, long B, const AdjointIO& io, hipStre
 // all k_adjoint reads of a finished solve.  One kernel each way, one thread per workspace element.
 hipError_t launch_save_solution(const KParams& p, long B, double* rec, hipStream_t st);
 hipError_t launch_load_solution(const KParams& p, long B, const double* rec, hipStream_t st);
-// one-wave-per-QP kernel (solve_wave.hip), variants 8 and 9
-hipError_t launch_solve_wave(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
-                        KernelRef* ref = nullptr);
-// one 512-thread workgroup per QP, alone on its CU, the dense-inverse solve held in registers
-// (solve_heavy.hip, variant 19): the latency form for a batch's predicted-slowest instances
-bool heavy_fits(const KParams& p);
-size_t heavy_lds(const KParams& p);
-hipError_t launch_solve_heavy(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+// The variants' launch functions outside solve.hip.  Two-wave and four-wave kernels
+// (solve_wave.hip), with their fused setup + solve launches
+hipError_t launch_solve_w2(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                           KernelRef* ref = nullptr);
+hipError_t launch_solve_w4(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                           KernelRef* ref = nullptr);
+hipError_t launch_setup_solve_w2(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                                 const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                                 int one_shot);
+hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                                 const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                                 int one_shot);
+// 512-thread long-horizon kernel (solve_big.hip): the instantiations for nb <= 12, 18, 24
+hipError_t launch_solve_big12(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
                               KernelRef* ref = nullptr);
-hipError_t launch_setup_solve_heavy(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
-                                    const double* l, const double* u, double* xo, double* yo, hipStream_t st);
-// 512-thread long-horizon kernel (solve_big.hip), variants 11-13
-hipError_t launch_solve_big(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
-                        KernelRef* ref = nullptr);
+hipError_t launch_solve_big18(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                              KernelRef* ref = nullptr);
+hipError_t launch_solve_big24(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                              KernelRef* ref = nullptr);
 
 }  // namespace mpcqp

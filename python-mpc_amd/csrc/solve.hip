@@ -637,20 +637,9 @@ hipError_t launch_polish(const KParams& p, long B, double* xo, double* yo, hipSt
 // ------------------------------------------------------------ launcher --
 size_t lds_solve_bytes(const KParams& p) { return lds_base_bytes(p); }
 
-size_t lds_kernel_bytes(const KParams& p) {
-#ifdef MPCQP_EXPERIMENTAL
-    if (p.variant == 16) return lds_dense_bytes(p);
-#endif
-    if (p.variant == 10 || p.variant == 17) return lds_w2_bytes(p);
-#ifdef MPCQP_EXPERIMENTAL
-    if (p.variant == 19) return heavy_lds(p);
-#endif
-    return (p.variant >= 11 && p.variant <= 15) ? lds_solve_bytes_big(p) : lds_solve_bytes(p);
-}
-
 template <int NB, int A, int K, int CS, int RS, int W, bool TRI = false>
-static hipError_t go(const KParams& p, long B, double* xo, double* yo, int fo, hipStream_t st, size_t lds,
-                     KernelRef* ref) {
+static hipError_t go(const KParams& p, long B, double* xo, double* yo, int fo, hipStream_t st, KernelRef* ref) {
+    const size_t lds = lds_solve_bytes(p);
     auto k = k_solve<NB, A, K, CS, RS, W, TRI>;
     if (ref) { *ref = {(const void*)k, T, lds}; return hipSuccess; }
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -659,136 +648,115 @@ static hipError_t go(const KParams& p, long B, double* xo, double* yo, int fo, h
     return hipGetLastError();
 }
 
-// Instantiations: NB = register-resident factor blocks (0: tiles read from the
+// ---- the solve variants (kernels.h, struct Variant) ----
+static int cs(const KParams& p) { return (p.npad + T - 1) / T; }  // columns / rows per thread of k_solve
+static int rs(const KParams& p) { return (p.m + T - 1) / T; }
+
+// the long-horizon kernel's instantiations: v = 11, 12, 13 for nb <= 12, 18, 24
+template <int v>
+static bool fits_big(const KParams& p) {
+    const int nbm = v == 11 ? 12 : v == 12 ? 18 : 24, csm = v == 11 ? 1 : 2, rsm = v == 13 ? 3 : 2;
+    const int csb = (p.npad + kThreadsBig - 1) / kThreadsBig, rsb = (p.m + kThreadsBig - 1) / kThreadsBig;
+    return p.nb > 4 && p.nb <= nbm && p.amax <= 16 && p.bmax <= 16 && p.gk <= 8 && csb <= csm && rsb <= rsm &&
+           lds_solve_bytes_big(p) <= 160 * 1024;
+}
+
+// four waves, two workgroups per CU (two waves per SIMD): up to 80 KB of LDS each
+static bool fits_w4(const KParams& p) {
+    // with eliminated columns: one per upper-half lane (npad <= 256, the fused setup's one
+    // column per thread), at most two A nonzeros each (the rhs list LE), three A values per
+    // thread in the fused setup
+    KParams q2 = p;
+    q2.mode = 2;  // the LDS carve of mode 2 (fits may run before KParams::mode is set)
+    // (and column lists of up to 8 entries: the slack layout's u_prev columns have 7)
+    const bool el = p.ne > 0;
+    return p.nb == 4 && p.amax <= 8 && p.gkr <= 6 && p.gkc <= (el ? 8 : 6) && p.pk <= 4 && p.m <= 256 &&
+           p.npad <= (el ? 256 : 128) && p.nnzA <= (el ? 768 : 512) && p.nnzP <= 256 &&
+           (!el || (p.ecnt <= 2 && p.ne <= 128)) && lds_w2_bytes(q2) <= 80 * 1024;
+}
+
+// The production variants: the only place their numbers are interpreted.  k_solve's
+// instantiations (0-7): NB = register-resident factor blocks (0: tiles read from the
 // workspace), A = coupling rows of F_k, K = gather-list length, CS / RS = columns /
 // rows per thread, W = waves per SIMD the register budget is sized for (variants 0, 1, 7
 // were sized for 4 and spilled 47 / 161 / 39 VGPRs at the occupancy of 2 they ran at
-// anyway; sized for 2 they spill 0 / 19 / 0, round 3), TRI =
-// three-phase solve.  variant_fits() is the exact precondition of each.
+// anyway; sized for 2 they spill 0 / 19 / 0, round 3), TRI = three-phase solve.
+// Columns: id, threads, mode (2: G blocks, 1: register sweep, 3: two-sided factor of
+// solve_big.hip, 0: workspace tiles), order, elim, fits, lds, launch, setup_solve.
+#define FITS(...) [](const KParams& p) -> bool { return __VA_ARGS__; }
+static const Variant kVariants[] = {
+    {0, T, 2, false, false, FITS(p.nb == 4 && p.amax <= 8 && p.gk <= 6 && cs(p) <= 1 && rs(p) <= 1), lds_solve_bytes,
+     go<4, 8, 6, 1, 1, 2, true>, nullptr},
+    {1, T, 1, false, false, FITS(p.nb == 8 && p.amax <= 8 && p.gk <= 8 && cs(p) <= 1 && rs(p) <= 1), lds_solve_bytes,
+     go<8, 8, 8, 1, 1, 2>, nullptr},
+    {2, T, 1, false, false, FITS(p.nb == 8 && p.amax <= 16 && p.gk <= 8 && cs(p) <= 1 && rs(p) <= 1), lds_solve_bytes,
+     go<8, 16, 8, 1, 1, 2>, nullptr},
+    {3, T, 1, false, false, FITS(p.nb == 8 && p.amax <= 16 && p.gk <= 8 && cs(p) <= 1 && rs(p) <= 2), lds_solve_bytes,
+     go<8, 16, 8, 1, 2, 2>, nullptr},
+    {4, T, 0, false, false, FITS(p.gk <= 8 && cs(p) <= 2 && rs(p) <= 4), lds_solve_bytes, go<0, 32, 8, 2, 4, 2>,
+     nullptr},
+    {5, T, 0, false, false, FITS(p.gk <= 8 && cs(p) <= 4 && rs(p) <= 4), lds_solve_bytes, go<0, 32, 8, 4, 4, 2>,
+     nullptr},
+    {6, T, 0, false, false, FITS(p.gk <= 16 && cs(p) <= 8 && rs(p) <= 8), lds_solve_bytes, go<0, 32, 16, 8, 8, 1>,
+     nullptr},
+    {7, T, 1, false, false, FITS(p.nb == 4 && p.amax <= 8 && p.gk <= 6 && cs(p) <= 1 && rs(p) <= 1), lds_solve_bytes,
+     go<4, 8, 6, 1, 1, 2, false>, nullptr},
+    // two workgroups per CU (one wave per SIMD): up to 80 KB of LDS each
+    {10, 128, 2, true, false,
+     FITS(p.nb == 4 && p.amax <= 8 && p.gk <= 6 && p.pk <= 4 && p.m <= 2 * 128 && lds_w2_bytes(p) <= 80 * 1024),
+     lds_w2_bytes, launch_solve_w2, launch_setup_solve_w2},
+    {11, kThreadsBig, 3, false, false, fits_big<11>, lds_solve_bytes_big, launch_solve_big12, nullptr},
+    {12, kThreadsBig, 3, false, false, fits_big<12>, lds_solve_bytes_big, launch_solve_big18, nullptr},
+    {13, kThreadsBig, 3, false, false, fits_big<13>, lds_solve_bytes_big, launch_solve_big24, nullptr},
+    // the only variant for plans with eliminated variables
+    {17, 256, 2, true, true, fits_w4, lds_w2_bytes, launch_solve_w4, launch_setup_solve_w4},
+};
+#undef FITS
+// what solve_variant tries, in order (7 and the experimental variants: MPCQP_VARIANT only)
+static const int kPreference[] = {17, 10, 0, 1, 2, 3, 11, 12, 13, 4, 5, 6};
+
+const Variant* variant_of(int id) {
+    static const struct Table {
+        const Variant* at[kVariantIds] = {};
+        Table() {
+            for (const Variant& v : kVariants) at[v.id] = &v;
+#ifdef MPCQP_EXPERIMENTAL  // measured and not taken: exp/variants.hip
+            const Variant* x = nullptr;
+            for (int i = 0, n = exp_variants(&x); i < n; ++i) at[x[i].id] = &x[i];
+#endif
+        }
+    } table;
+    return id >= 0 && id < kVariantIds ? table.at[id] : nullptr;
+}
+
 bool variant_fits(const KParams& p, int v) {
-    const int cs = (p.npad + T - 1) / T, rs = (p.m + T - 1) / T;
-    if (p.ne && v != 17) return false;  // eliminated variables: the four-wave kernel only
-#ifndef MPCQP_EXPERIMENTAL
-    // measured and not taken: one-wave 8 / 9, two-wave two-sided 14,
-    // 256-thread twisted 15, dense inverse 16, eight-wave 18, one-instance-per-CU dense 19 -- only
-    // in the exp / diagnostic builds (MPCQP_BUILD=exp)
-    if (v == 8 || v == 9 || v == 14 || v == 15 || v == 16 || v == 18 || v == 19) return false;
-#endif
-    switch (v) {
-        case 0: case 7: return p.nb == 4 && p.amax <= 8 && p.gk <= 6 && cs <= 1 && rs <= 1;
-        case 1: return p.nb == 8 && p.amax <= 8 && p.gk <= 8 && cs <= 1 && rs <= 1;
-        case 2: return p.nb == 8 && p.amax <= 16 && p.gk <= 8 && cs <= 1 && rs <= 1;
-        case 3: return p.nb == 8 && p.amax <= 16 && p.gk <= 8 && cs <= 1 && rs <= 2;
-        case 4: return p.gk <= 8 && cs <= 2 && rs <= 4;
-        case 5: return p.gk <= 8 && cs <= 4 && rs <= 4;
-        case 6: return p.gk <= 16 && cs <= 8 && rs <= 8;
-        // the one-wave kernels' rows i = lane + 64 s, s < RS, must cover exactly the padded rows
-        // (solve_mpad): RS = 3 for 128 < m <= 192, RS = 4 for 192 < m <= 256
-        case 8: return p.nb == 4 && p.amax <= 8 && p.gk <= 6 && solve_mpad(p.m) == 3 * 64 && lds_solve_bytes(p) < 65536;
-        case 9: return p.nb == 4 && p.amax <= 8 && p.gk <= 8 && solve_mpad(p.m) == 4 * 64 && lds_solve_bytes(p) < 65536;
-        case 10:  // two workgroups per CU (one wave per SIMD): up to 80 KB of LDS each
-            return p.nb == 4 && p.amax <= 8 && p.gk <= 6 && p.pk <= 4 && p.m <= 2 * 128 && lds_w2_bytes(p) <= 80 * 1024;
-        case 11: case 12: case 13: {
-            const int nbm = v == 11 ? 12 : v == 12 ? 18 : 24, csm = v == 11 ? 1 : 2, rsm = v == 13 ? 3 : 2;
-            const int csb = (p.npad + kThreadsBig - 1) / kThreadsBig, rsb = (p.m + kThreadsBig - 1) / kThreadsBig;
-            return p.nb > 4 && p.nb <= nbm && p.amax <= 16 && p.bmax <= 16 && p.gk <= 8 && csb <= csm && rsb <= rsm &&
-                   lds_solve_bytes_big(p) <= 160 * 1024;
-        }
-        case 15: {  // 256 threads, one wave per SIMD (twisted_solve4): nb <= 18
-            const int csb = (p.npad + 255) / 256, rsb = (p.m + 255) / 256;
-            return p.nb > 4 && p.nb <= 18 && p.amax <= 16 && p.bmax <= 16 && p.gk <= 8 && csb <= 3 && rsb <= 4 &&
-                   lds_solve_bytes_big(p) <= 160 * 1024;
-        }
-        case 14:
-            return p.nb > 4 && p.nb <= 8 && p.amax <= 16 && p.bmax <= 16 && p.gk <= 8 && p.npad <= 256 &&
-                   p.m <= 256 && lds_solve_bytes_big(p) <= 160 * 1024;
-        case 17: {  // four waves, two workgroups per CU (two waves per SIMD): up to 80 KB of LDS each
-            // with eliminated columns: one per upper-half lane (npad <= 256, the fused setup's one
-            // column per thread), at most two A nonzeros each (the rhs list LE), three A values per
-            // thread in the fused setup
-            KParams q2 = p;
-            q2.mode = 2;  // the LDS carve of mode 2 (fits may run before KParams::mode is set)
-            // (and column lists of up to 8 entries: the slack layout's u_prev columns have 7)
-            const bool el = p.ne > 0;
-            return p.nb == 4 && p.amax <= 8 && p.gkr <= 6 && p.gkc <= (el ? 8 : 6) && p.pk <= 4 && p.m <= 256 &&
-                   p.npad <= (el ? 256 : 128) && p.nnzA <= (el ? 768 : 512) && p.nnzP <= 256 &&
-                   (!el || (p.ecnt <= 2 && p.ne <= 128)) && lds_w2_bytes(q2) <= 80 * 1024;
-        }
-        case 18: {  // eight waves, one workgroup per CU; the gather lists pack 16-bit LDS addresses
-            KParams q2 = p;
-            q2.mode = 2;  // the LDS carve of mode 2 (fits may run before KParams::mode is set)
-            const long mp = solve_mpad(p.m), packed = 8L * (al2(p.nnzA + 1) + al2(p.nnzP + 1) + 4 * mp + 4L * p.npad);
-            return p.nb == 8 && p.amax <= 12 && p.gk <= 8 && p.pk <= 8 && p.m <= 512 && p.npad <= 256 &&
-                   packed < 65536 && lds_solve_bytes(q2) <= 160 * 1024;
-        }
-#ifdef MPCQP_EXPERIMENTAL
-        case 19: return heavy_fits(p);  // one 512-thread workgroup per QP (solve_heavy.hip)
-        case 16:  // dense inverse: one variable per lane pair of a 256-thread workgroup, packed LDS addresses
-            return p.n <= kDenseR && p.npad <= 128 && p.gk <= 6 && p.pk <= 4 && p.m <= 2 * 128 &&
-                   lds_dense_bytes(p) < 65536;
-#endif
-        default: return false;
-    }
+    const Variant* d = variant_of(v);
+    return d && (!p.ne || d->elim) && d->fits(p);
 }
 
 int solve_variant(const KParams& p) {
-    static const int order[] = {17, 10, 0, 1, 2, 3, 11, 12, 13, 4, 5, 6};  // 8, 9, 14, 16, 18, 19: MPCQP_VARIANT only
-    for (int v : order)
+    for (int v : kPreference)
         if (variant_fits(p, v)) return v;
     return -1;
 }
 
 int solve_threads(int variant) {
-    switch (variant) {
-        case 8: case 9: return 64;
-        case 10: return 128;
-        case 11: case 12: case 13: return kThreadsBig;
-        case 14: return 128;
-        case 15: return 256;
-        case 16: return 256;
-        case 17: return 256;
-        case 18: return 512;
-        case 19: return 512;
-        default: return T;
-    }
+    const Variant* d = variant_of(variant);
+    return d ? d->threads : T;
 }
-
-int solve_mode(int variant) {  // what factorize stores for the variant (KParams::mode)
-    switch (variant) {
-        case 0: case 8: case 9: case 10: case 17: case 18: case 19: return 2;
-        case 1: case 2: case 3: case 7: case 16: return 1;  // (16: no factor stored; dx aliases rb)
-        case 11: case 12: case 13: case 14: case 15: return 3;  // two-sided factor (solve_big.hip)
-        default: return 0;
-    }
+int solve_mode(int variant) {
+    const Variant* d = variant_of(variant);
+    return d ? d->mode : 0;
+}
+size_t lds_kernel_bytes(const KParams& p) {
+    const Variant* d = variant_of(p.variant);
+    return d ? d->lds(p) : lds_solve_bytes(p);
 }
 
 static hipError_t launch_solve_only(const KParams& p, long B, double* xo, double* yo, int factor_only,
                                     hipStream_t st, KernelRef* ref = nullptr) {
-    const size_t lds = lds_solve_bytes(p);
-    switch (p.variant) {
-        case 0: return go<4, 8, 6, 1, 1, 2, true>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 1: return go<8, 8, 8, 1, 1, 2>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 2: return go<8, 16, 8, 1, 1, 2>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 3: return go<8, 16, 8, 1, 2, 2>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 4: return go<0, 32, 8, 2, 4, 2>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 5: return go<0, 32, 8, 4, 4, 2>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 6: return go<0, 32, 16, 8, 8, 1>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 7: return go<4, 8, 6, 1, 1, 2, false>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 8: case 9: case 10: case 17: case 18: return launch_solve_wave(p, B, xo, yo, factor_only, st, ref);
-#ifdef MPCQP_EXPERIMENTAL
-        case 19: {
-            if (!factor_only) return launch_solve_heavy(p, B, xo, yo, 0, st, ref);
-            KParams q = p;  // setup()'s convexity factorisation: the four-wave kernel's (the same factor)
-            q.variant = 17;
-            return launch_solve_wave(q, B, xo, yo, factor_only, st, ref);
-        }
-#endif
-#ifdef MPCQP_EXPERIMENTAL
-        case 16: return launch_solve_dense(p, B, xo, yo, factor_only, st, ref);
-#endif
-        case 11: case 12: case 13: case 14: case 15: return launch_solve_big(p, B, xo, yo, factor_only, st, ref);
-        default: return hipErrorInvalidValue;
-    }
+    const Variant* d = variant_of(p.variant);
+    return d ? d->launch(p, B, xo, yo, factor_only, st, ref) : hipErrorInvalidValue;
 }
 
 int solve_blocks_per_cu(const KParams& p) {
@@ -804,6 +772,16 @@ hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int fa
     hipError_t e = launch_solve_only(p, B, xo, yo, factor_only, st);
     if (e != hipSuccess || factor_only || !p.polish) return e;
     return launch_polish(p, B, xo, yo, st);
+}
+
+// setup + solve of the same inputs: the variant's fused launch, else the two kernels
+hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                              const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                              int one_shot) {
+    const Variant* d = variant_of(p.variant);
+    if (d && d->setup_solve) return d->setup_solve(p, B, Px, Ax, q, l, u, xo, yo, st, one_shot);
+    hipError_t e = launch_setup(p, B, Px, Ax, q, l, u, st);
+    return e != hipSuccess ? e : launch_solve(p, B, xo, yo, 0, st);
 }
 
 }  // namespace mpcqp

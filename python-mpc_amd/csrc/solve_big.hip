@@ -943,7 +943,7 @@ __device__ __forceinline__ void twisted_solve(const TwoSided<SL>& R, const KP& p
 
 // ---------------------------------------------------------------------------
 // The forms measured and not taken (variants 14 / 15, the interface form) live in
-// solve_big_exp.h, built into the experimental builds only; k_solve_b names them in branches the
+// exp/solve_big_exp.h, built into the experimental builds only; k_solve_b names them in branches the
 // production instantiations discard.
 template <int SL> struct TwoSided4;
 template <int SL> struct TwoSidedQ;
@@ -960,7 +960,7 @@ template <int NS>
 __device__ void wave_twisted_solve(const TwoSidedW<NS>& R, const KParams& p, const double* Fc, const double* Gc,
                                    const int* toffL, double* rb, double* xt, double* cor, long long* pacc);
 #ifdef MPCQP_EXPERIMENTAL
-#include "solve_big_exp.h"
+#include "exp/solve_big_exp.h"
 #endif
 
 // doubles of the F / G region: F_k rows (k = 1..p), G_k tail rows (k = p..nb-2), and
@@ -1071,19 +1071,29 @@ static hipError_t go_b(const KParams& p, long B, double* xo, double* yo, int fo,
     return hipGetLastError();
 }
 
-hipError_t launch_solve_big(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
-                            KernelRef* ref) {
-    switch (p.variant) {
-        case 11: return go_b<512, 6, 8, 1, 2>(p, B, xo, yo, factor_only, st, ref);   // nb <= 12
-        case 12: return go_b<512, 9, 8, 2, 2>(p, B, xo, yo, factor_only, st, ref);   // nb <= 18
-        case 13: return go_b<512, 12, 8, 2, 3>(p, B, xo, yo, factor_only, st, ref);  // nb <= 24
-#ifdef MPCQP_EXPERIMENTAL
-        // 256 threads, one wave per SIMD (twisted_solve4): measured and not taken
-        case 15: return go_b<256, 9, 8, 3, 4>(p, B, xo, yo, factor_only, st, ref);   // nb <= 18
-        case 14: return go_b<128, 4, 8, 2, 2>(p, B, xo, yo, factor_only, st, ref);   // nb <= 8, two waves
-#endif
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_solve_big12(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                              KernelRef* ref) {
+    return go_b<512, 6, 8, 1, 2>(p, B, xo, yo, factor_only, st, ref);  // nb <= 12
 }
+hipError_t launch_solve_big18(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                              KernelRef* ref) {
+    return go_b<512, 9, 8, 2, 2>(p, B, xo, yo, factor_only, st, ref);  // nb <= 18
+}
+hipError_t launch_solve_big24(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                              KernelRef* ref) {
+    return go_b<512, 12, 8, 2, 3>(p, B, xo, yo, factor_only, st, ref);  // nb <= 24
+}
+#ifdef MPCQP_EXPERIMENTAL
+// measured and not taken (exp/variants.hip): 256 threads, one wave per SIMD
+// (twisted_solve4), nb <= 18; two waves, nb <= 8
+hipError_t launch_solve_big18_256(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                                  KernelRef* ref) {
+    return go_b<256, 9, 8, 3, 4>(p, B, xo, yo, factor_only, st, ref);
+}
+hipError_t launch_solve_big8_w2(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                                KernelRef* ref) {
+    return go_b<128, 4, 8, 2, 2>(p, B, xo, yo, factor_only, st, ref);
+}
+#endif
 
 }  // namespace mpcqp

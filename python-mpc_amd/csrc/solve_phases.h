@@ -627,7 +627,7 @@ __device__ __forceinline__ bool factorize_w2(const KP& p, SLds& L, const double 
 // k assembles D_k and pre-pivots it (block 0: the whole inverse), all four at once --
 // then the same k = 1..3 chain (F_k, the corner, the G blocks, wave 0's corner pivots).
 // The critical path of stage 1 is one block's pivots instead of two.  Same outputs.
-// TT = 512 (solve_heavy.hip, the one-instance-per-CU kernel): waves 0-3 run stage 1 and the
+// TT = 512 (exp/solve_heavy.hip, the one-instance-per-CU kernel): waves 0-3 run stage 1 and the
 // chain exactly as with 256 threads, waves 4-7 join the F / G products (the same sums per
 // output element: the factor is bit-identical to the 256-thread one).
 // SWZ (the one-shot kernel, solve_w4_body): the S_k^{-1} tiles in Sg have tile_at<true>'s layout
@@ -860,7 +860,7 @@ __device__ __forceinline__ bool factorize_w4_gl(const KP& p, SLds& L, const doub
 
 __host__ __device__ inline double* w8_gpair(double* Fg, double* Hg, int amax, int q);  // (below)
 
-// The eight-wave kernel's factorisation (solve_wave.hip::k_solve_w8, variant 18: mode 2,
+// The eight-wave kernel's factorisation (exp/solve_wave8.hip::k_solve_w8, variant 18: mode 2,
 // nb = 8, amax <= 12; TT = 512): factorize_w4 with eight blocks -- stage 1 pre-pivots all
 // eight at once (wave k: block k), then the k = 1..7 chain: F_k = E_k S_{k-1}^{-1}
 // (G_{k,k-1} = -F_k), wave 0 forms the corner and pivots it (gj_seg<2>, rolled: amax may

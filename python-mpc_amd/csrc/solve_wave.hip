@@ -1,31 +1,8 @@
-// solve_wave.hip -- the ADMM kernel with ONE 64-lane wavefront per QP instance.
-//
-// Why a wave and not a workgroup: one ADMM iteration of a cfg-2 QP (SURVEY.md §8,
-// n = 104, m = 188) is ~7 kFLOP of dependent phases (rhs gather, block solve, row
-// update).  Spread over a 256-thread workgroup (solve.hip) every phase boundary
-// is an s_barrier between four waves and the iteration costs ~7,000 cycles, almost
-// all of it barrier and LDS round trips.  Inside a single wave the phases are
-// ordered by the wave's own instruction stream: the compiler drops s_barrier for a
-// 64-thread workgroup (it emits only the LDS waitcnt), so a phase boundary costs one
-// LDS round trip, and each wave is an independent QP that the four SIMDs of a CU
-// run side by side.
-//
-// Work decomposition (NB <= 4 blocks of S = 32 variables, amax <= 8 coupling rows):
-//   lane = (h, r) = (lane / 32, lane % 32) owns the padded columns
-//     pc_e = kb_e * 32 + r,  kb_0 = h, kb_1 = 3 - h   (blocks {0,3} / {1,2}: balanced
-//     phase-C work), with x, x_prev, q and its column gather lists in registers;
-//   constraint rows i = lane + 64 s (s < RS) with y, z, their row gather lists;
-//   the factor, in the three-phase form K^{-1} = L^{-T} D^{-1} L^{-1}
-//   (solve_phases.h::factorize, mode 2):
-//     SB[e][c] = S_{kb_e}^{-1}[r][c]                        (phase B, 64 doubles)
-//     GA[q][e] = G_q[lane / 8][4 (lane % 8) + e]            (phase A, pair q = k(k-1)/2 + j)
-//     GC[s][q] = G_{j_s, kb_s}[q][r]                        (phase C, transposed use)
-// One iteration:
-//   rhs   b = sigma x - q + A'(rho z - y)                   -> rb   (LDS)
-//   A     c_k = sum_{j<k} G_kj b_j   (8-lane DPP sums)      -> cor  (LDS)
-//   B     t_k = S_k^{-1} (b_k + c_k)                        -> tv   (LDS)
-//   C     x~_k = t_k + sum_{j>k} G_jk' t_j                  -> xt   (LDS)
-//   rows  z~ = A x~, relaxation, projection, y update, w = rho z - y -> w (LDS)
+// solve_wave.hip -- the ADMM kernels with one wavefront per block of the QP: the two-wave
+// kernel (variant 10: a 128-thread workgroup per QP, each wave two blocks) and the four-wave
+// kernel (variant 17: a 256-thread workgroup, one block per wave), each with its fused
+// setup + solve form.  The one-wave and eight-wave kernels they grew out of and after were
+// measured and not taken: exp/solve_wave1.hip, exp/solve_wave8.hip (the experimental builds).
 // Reference semantics as solve.hip (OSQP 0.6 osqp_solve, behind
 // vehicle_lateral_mpc_slack_increment.py:248 / Control/MPC/mpc_dynamics.py:396).
 #include <hip/hip_runtime.h>
@@ -39,372 +16,6 @@
 #include "wave_util.h"
 
 namespace mpcqp {
-
-[[maybe_unused]] constexpr int TW = 64;
-
-#ifdef MPCQP_EXPERIMENTAL  // the one-wave kernels (variants 8, 9): make exp / MPCQP_BUILD=exp
-// S^{-1} rows of the lane's two blocks, SB[e][c] = S_{kb_e}^{-1}[r][c] (128 VGPRs)
-struct WaveFactor {
-    double SB[2][S];
-    __device__ __forceinline__ void load(const double* __restrict__ Sg) {
-        const int lane = threadIdx.x, h = lane >> 5, r = lane & 31;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const double* src = Sg + (long)(e ? 3 - h : h) * SS + r * S;
-#pragma unroll
-            for (int c = 0; c < S; ++c) SB[e][c] = src[c];
-        }
-    }
-};
-
-template <int K, int RS>
-__global__ __launch_bounds__(TW, 1) void k_solve_w(KParams p, double* __restrict__ xo, double* __restrict__ yo,
-                                                   int factor_only) {
-    const int lane = threadIdx.x;
-    const int h = lane >> 5, r = lane & 31, rr = lane >> 3, ch = lane & 7;
-    const int kb0 = h, kb1 = 3 - h;
-    constexpr int NB = 4, NP = NB * (NB - 1) / 2;  // exactly four blocks (solve.hip::variant_fits)
-    const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
-    SL2 C = carve(p);
-    SLds& L = C.L;
-    const double* Hg = p.H + b * (long)p.nb * SS;
-    const double* Sg = p.Si + b * (long)p.nb * SS;
-
-    if (p.err[b]) {  // invalid data (flagged by setup/update): NaN outputs
-        for (int j = lane; j < n; j += TW) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = lane; i < m; i += TW) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (lane == 0) fail_status(p, b);
-        return;
-    }
-
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (lane < 16) L.pacc[lane] = 0; }
-#define PH(k) if (prof && lane == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
-
-    const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
-    double rho = p.scal[b * 4 + 2];
-    const double sigma = p.sigma, alpha = p.alpha;
-    const bool warm = p.warm_start != 0;
-    for (int e = lane; e < nnzA; e += TW) L.Acsc[e] = p.Ax[b * nnzA + e];
-    if (lane == 0) L.Acsc[nnzA] = 0.0;  // the gather lists' padding slot
-    for (int v = lane; v < nnzP; v += TW) L.Pv[v] = p.Px[b * nnzP + v];
-    if (lane == 0) L.Pv[nnzP] = 0.0;
-    const int mp = solve_mpad(m);
-    for (int i = lane; i < mp; i += TW) {  // rows >= m: inert padding (l = u = 0, z = 0)
-        const bool in = i < m;
-        L.lo[i] = in ? p.l[b * m + i] : 0.0;
-        L.up[i] = in ? p.u[b * m + i] : 0.0;
-        L.ct[i] = in ? p.ct[b * m + i] : 0;
-        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
-    }
-    for (int pc = lane; pc < npad; pc += TW) {
-        L.qv[pc] = p.q[b * npad + pc];
-        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
-    }
-    if (lane < S) L.cor[lane] = 0.0;  // block 0 has no phase-A correction
-    if (lane < 16) L.res[lane] = 0.0;
-    if (lane < 4) L.flag[lane] = 0;
-
-    int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
-    bool can_check = false, need_factor = true;
-    PH(5)
-    // Runs of ADMM iterations up to the next termination / rho-adaptation point
-    // alternate with the out-of-line phases; the run state lives in registers and
-    // is re-derived from LDS and the workspace at every run start (nothing but
-    // scalars is live across a call).
-    for (;;) {
-        __syncthreads();
-        if (need_factor) {  // start, and after a rho change
-            need_factor = false;
-            // the factorisation scratch aliases ys (and dY, rb, xt, w): y waits in the
-            // workspace's y array (the warm-start input at the first factorisation)
-            if (iter > 0)
-                for (int i = lane; i < m; i += TW) p.y[b * m + i] = L.ys[i];
-            const bool ok = factorize_nl<TW>(p.self, b, rho);
-            if (!ok) {
-                if (iter == 0) {
-                    for (int j = lane; j < n; j += TW) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = lane; i < m; i += TW) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (lane == 0) fail_status(p, b);
-                    return;
-                }
-                status = MPCQP_NON_CVX_;
-                can_check = true;  // skip the final check_termination
-                break;
-            }
-            if (factor_only) return;
-            __syncthreads();
-            const bool have_y = iter > 0 || warm;
-            for (int i = lane; i < mp; i += TW) L.ys[i] = (have_y && i < m) ? p.y[b * m + i] : 0.0;
-            // G blocks -> LDS, rows padded to 8 with zeros: gl[pair][row < 8][32]
-            for (int o = lane; o < NP * 8 * S; o += TW) {
-                const int q = o >> 8, t = (o >> 5) & 7;
-                L.gl[o] = t < p.amax ? Hg[(long)q * p.amax * S + (o & 255)] : 0.0;
-            }
-            PH(0)
-        }
-        // ---- run state ----
-        WaveFactor RF;
-        RF.load(Sg);
-        int pcs[2];
-        bool cv[2];
-        double X[2], Q[2], DX[2];
-        // LDS byte addresses of the gathered arrays
-        const unsigned abase = lds_addr(L.Acsc), wbase = lds_addr(L.w), xbase = lds_addr(L.xt);
-        GatherW<K> cg[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int pc = (e ? kb1 : kb0) * S + r;  // < npad = 4 S
-            pcs[e] = pc;
-            cv[e] = p.pad_var[pc] >= 0;
-            X[e] = C.X[pc];
-            Q[e] = L.qv[pc];
-            DX[e] = 0.0;
-            cg[e].load(p.gcol + pc, npad, abase, wbase);
-        }
-        GatherW<K> rg[RS];
-        double y[RS], Z[RS], dy[RS], rv[RS], rvi[RS];
-        const double r_hi = RHO_EQ_OVER_RHO_INEQ * rho;
-#pragma unroll
-        for (int s = 0; s < RS; ++s) {
-            const int i = lane + s * TW;  // < mp
-            dy[s] = 0.0;
-            if (i < m) rg[s].load(p.grow + i, m, abase, xbase);
-            else rg[s].clear(abase + 8u * nnzA, xbase);
-            y[s] = L.ys[i];
-            Z[s] = C.Z[i];
-            const signed char cl = L.ct[i];  // OSQP rho_vec / rho_inv_vec of the row
-            rv[s] = cl < 0 ? RHO_MIN : (cl > 0 ? r_hi : rho);
-            rvi[s] = cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho);
-            L.w[i] = rv[s] * Z[s] - y[s];  // w = rho z_prev - y (rho may be new)
-        }
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
-        __syncthreads();
-        PH(5)
-        while (iter < stop_at) {
-            ++iter;
-            int opq = 0;
-            asm volatile("" : "+s"(opq));  // keeps per-lane LDS addresses out of the register budget
-            double* const rb = L.rb + opq;
-            double* const cor = L.cor + opq;
-            double* const tv = L.tv + opq;
-            double* const xt = L.xt + opq;
-            // rhs = sigma x_prev - q + A' (rho z_prev - y)
-            {
-                double av[2][K], wv[2][K];
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        av[e][k] = lds_at(cg[e].e[k] & 0xFFFFu);
-                        wv[e][k] = lds_at(cg[e].e[k] >> 16);
-                    }
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    double v = sigma * X[e] - Q[e];
-#pragma unroll
-                    for (int k = 0; k < K; ++k) v += av[e][k] * wv[e][k];
-                    rb[pcs[e]] = cv[e] ? v : 0.0;
-                }
-            }
-            __syncthreads();
-            PH(1)
-            // A: c_k = sum_{j<k} G_kj b_j on rows < 8: lane (rr, ch) takes columns
-            // [4 ch, 4 ch + 4) of every pair, 8-lane DPP sums over ch (every lane of
-            // the group holds the sum and writes it)
-            {
-                const double* gq = L.gl + opq + rr * S + 4 * ch;
-                double bj[NB - 1][4], ga[NP][4];
-#pragma unroll
-                for (int j = 0; j < NB - 1; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) bj[j][e] = rb[j * S + 4 * ch + e];
-#pragma unroll
-                for (int q = 0; q < NP; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ga[q][e] = gq[q * 8 * S + e];
-#pragma unroll
-                for (int k = 1; k < NB; ++k) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int j = 0; j < k; ++j)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc += ga[k * (k - 1) / 2 + j][e] * bj[j][e];
-                    cor[k * S + rr] = reduce8(acc);
-                }
-            }
-            __syncthreads();
-            // B: t_kb = S_kb^{-1} (b_kb + c_kb), one full row per lane and block
-            double t[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int kb = e ? kb1 : kb0;
-                const double* bv = rb + kb * S;
-                const double* cb = cor + kb * S;
-                double v[S], cc[8];
-#pragma unroll
-                for (int c = 0; c < S; ++c) v[c] = bv[c];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) cc[c] = cb[c];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) v[c] += cc[c];
-                double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int c = 0; c < S; ++c) a[c & 3] += RF.SB[e][c] * v[c];
-                t[e] = (a[0] + a[1]) + (a[2] + a[3]);
-            }
-            tv[kb0 * S + r] = t[0];
-            tv[kb1 * S + r] = t[1];
-            __syncthreads();
-            // C: x~_kb = t_kb + sum_{j>kb} G_{j,kb}' t_j  (t_j rows < 8); the lane's
-            // pairs: h = 0: (1,0) (2,0) (3,0);  h = 1: (2,1) (3,1) (3,2)
-            double xn[2];
-            {
-                double d[3], gv[3][8], tq[3][8];
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    const int j = s < 2 ? s + 1 + h : 3;
-                    const int kb = s < 2 ? h : 2 * h;
-                    const double* tj = tv + j * S;
-                    const double* gc = L.gl + opq + (j * (j - 1) / 2 + kb) * 8 * S + r;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) { gv[s][q] = gc[q * S]; tq[s][q] = tj[q]; }
-                }
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 8; q += 2) {
-                        a0 += gv[s][q] * tq[s][q];
-                        a1 += gv[s][q + 1] * tq[s][q + 1];
-                    }
-                    d[s] = a0 + a1;
-                }
-                xn[0] = t[0] + (d[0] + d[1]) + (h ? 0.0 : d[2]);
-                xn[1] = t[1] + (h ? d[2] : 0.0);
-            }
-            xt[kb0 * S + r] = xn[0];
-            xt[kb1 * S + r] = xn[1];
-            // x update (own columns, registers)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const double xnew = alpha * xn[e] + (1.0 - alpha) * X[e];
-                DX[e] = xnew - X[e];
-                X[e] = xnew;
-            }
-            __syncthreads();
-            PH(2)
-            // z~ = A x~ ; relaxed + projected z ; y ; next w   (padded rows stay 0)
-            double zts[RS];
-            {
-                double av[RS][K], xv[RS][K];
-#pragma unroll
-                for (int s = 0; s < RS; ++s)
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        av[s][k] = lds_at(rg[s].e[k] & 0xFFFFu);
-                        xv[s][k] = lds_at(rg[s].e[k] >> 16);
-                    }
-#pragma unroll
-                for (int s = 0; s < RS; ++s) {
-                    double v = av[s][0] * xv[s][0];
-#pragma unroll
-                    for (int k = 1; k < K; ++k) v += av[s][k] * xv[s][k];
-                    zts[s] = v;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < RS; ++s) {
-                const int i = lane + opq + s * TW;
-                const double zt = zts[s];
-                const double zr = alpha * zt + (1.0 - alpha) * Z[s];
-                const double zn = __builtin_fmin(__builtin_fmax(zr + rvi[s] * y[s], L.lo[i]), L.up[i]);
-                const double dd = rv[s] * (zr - zn);
-                Z[s] = zn;
-                dy[s] = dd;
-                y[s] += dd;
-                L.w[i] = rv[s] * zn - y[s];
-            }
-            __syncthreads();
-            PH(3)
-        }
-        // run state back to LDS for the out-of-line phases
-#pragma unroll
-        for (int e = 0; e < 2; ++e) { C.X[pcs[e]] = X[e]; L.dx[pcs[e]] = DX[e]; }
-#pragma unroll
-        for (int s = 0; s < RS; ++s) {
-            const int i = lane + s * TW;
-            L.ys[i] = y[s]; C.Z[i] = Z[s]; C.dY[i] = dy[s];
-        }
-        __syncthreads();
-        // ---- out-of-line phases (only scalars live across these calls) ----
-        can_check = p.check_term && (iter % p.check_term == 0);
-        const bool do_rho = p.adaptive_rho && p.rho_interval && (iter % p.rho_interval == 0);
-        if (!can_check && !do_rho) break;  // max_iter reached
-        update_info_nl<TW>(p.self, b, cinv);
-        info_iter = iter;
-        bool stop = false;
-        if (can_check) {
-            status = check_termination_nl<TW>(p.self, b, cval, cinv, 0);
-            stop = status != MPCQP_UNSOLVED_;
-        }
-        if (!stop && do_rho) {
-            Res R;
-            R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
-        }
-        __syncthreads();
-        PH(4)
-        if (stop || iter >= p.max_iter) break;
-    }
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<TW>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<TW>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<TW>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<TW>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<TW>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
-#ifdef MPCQP_PHASE_PROF
-    if (prof) {
-        __syncthreads();
-        PH(5)
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 12; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-        }
-    }
-#endif
-#undef PH
-}
-
-#endif  // MPCQP_EXPERIMENTAL
 
 // ---------------------------------------------------------------------------
 // Two-wave variant: one 128-thread workgroup (2 waves, on 2 SIMDs) per QP.
@@ -2051,505 +1662,6 @@ __global__ __launch_bounds__(T4, 2) void k_setup_solve_w4(KParams p, const doubl
 }
 
 
-#ifdef MPCQP_EXPERIMENTAL  // the eight-wave kernel (variant 18): make exp / MPCQP_BUILD=exp
-// ---------------------------------------------------------------------------
-// Eight-wave variant (variant 18, k_solve_w8): the four-wave kernel's iteration for nb = 8
-// plans (the slack-variable MPC, SURVEY.md configs[2]/[3]): one 512-thread workgroup per
-// QP, wave k owns block k (lane (h, r): row r of S_k^{-1}, columns [16 h, 16 h + 16)), one
-// workgroup per CU.  The 28 G blocks (rows < 12) and the eight S_k^{-1} tiles do not fit
-// in LDS together, so the tiles live only during the factorisation: S^{-1} stays in
-// registers for the whole solve and the G copy reuses the tiles' LDS (solve_phases.h::
-// w8_toff).  Phase A: 16 rows x 4 lanes of 8 columns per wave; phase C: up to four pairs
-// per half.  MPCQP_VARIANT=18.
-constexpr int T8 = 512;
-
-template <int K, int KPK>
-__device__ __forceinline__ void solve_w8_body(const KParams& p, double* __restrict__ xo, double* __restrict__ yo,
-                                              int factor_only) {
-    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int h = lane >> 5, r = lane & 31, rr = lane >> 2, ch = lane & 3;
-    constexpr int NB = 8, NP = NB * (NB - 1) / 2;  // exactly eight blocks (solve.hip::variant_fits)
-    constexpr int QR = 12, GR = 12;                 // G rows summed (amax <= 12) / per pair in gl
-    static_assert(K % 2 == 0, "the rhs splits the column list over the half-waves");
-    constexpr int KH = K / 2;                       // column-list entries per half in the rhs
-    const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
-    SL2 C = carve(p);
-    SLds& L = C.L;
-    double* const Hg = p.H + b * (long)p.nb * SS;
-    double* const Fg = p.F + b * (long)p.nb * SS;  // the G pairs past H's room (w8_gpair)
-    double* const Sg = L.SP + w8_toff(p.amax);                    // S_k^{-1} tiles (in V, past the factor scratch)
-    double* const red8 = L.SP + w8_roff(p.m, p.npad, p.amax);     // the inline check's reduction buffer
-
-    if (p.err[b]) {
-        for (int j = tid; j < n; j += T8) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += T8) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
-        return;
-    }
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
-    const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
-    double rho = p.scal[b * 4 + 2];
-    const double sigma = p.sigma, alpha = p.alpha;
-    const bool warm = p.warm_start != 0;
-    for (int e = tid; e < nnzA; e += T8) L.Acsc[e] = p.Ax[b * nnzA + e];
-    if (tid == 0) L.Acsc[nnzA] = 0.0;
-    for (int v = tid; v < nnzP; v += T8) L.Pv[v] = p.Px[b * nnzP + v];
-    if (tid == 0) L.Pv[nnzP] = 0.0;
-    const int mp = solve_mpad(m);
-    for (int i = tid; i < mp; i += T8) {
-        const bool in = i < m;
-        L.lo[i] = in ? p.l[b * m + i] : 0.0;
-        L.up[i] = in ? p.u[b * m + i] : 0.0;
-        L.ct[i] = in ? p.ct[b * m + i] : 0;
-        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
-    }
-    for (int pc = tid; pc < npad; pc += T8) {
-        L.qv[pc] = p.q[b * npad + pc];
-        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
-    }
-    if (tid < 16) L.cor[tid] = 0.0;        // c_0 = 0 (block 0 has no correction)
-    if (tid < 16) L.cor[128 + tid] = 0.0;  // the upper half's zero correction row (phase B)
-    if (tid < 16) L.res[tid] = 0.0;
-    if (tid < 4) L.flag[tid] = 0;
-
-    int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
-    bool can_check = false, need_factor = true;
-    const int pc = w * S + r;  // the lane's column (both halves; the lower half stores)
-    const bool low = h == 0;
-    const unsigned abase = lds_addr(L.Acsc), wbase = lds_addr(L.w), xbase = lds_addr(L.xt);
-    const unsigned Xbase = lds_addr(C.X);
-    bool cv = false;
-    double Dv = 1.0, Ev = 1.0;
-    GatherW<K> cg, rg;
-    GatherW<KPK> pg;
-    const int ri = min(tid, mp - 1);  // lanes past the padded rows repeat the inert last row
-    const bool rows_wave = w * 64 < mp;  // wave-uniform: waves wholly past the padded rows skip the rows
-    double SB[16];                    // row r of S_w^{-1}, columns [16 h, 16 h + 16): kept across runs
-#pragma unroll
-    for (int c = 0; c < 16; ++c) SB[c] = 0.0;
-    PH(5)
-    for (;;) {
-        __syncthreads();
-        if (need_factor) {
-            need_factor = false;
-            if (iter > 0) {
-                for (int i = tid; i < m; i += T8) p.y[b * m + i] = L.ys[i];
-                __syncthreads();  // every ys read is done before factorize_w4's E tiles overwrite it
-            }
-            const bool ok = factorize_nl<T8>(p.self, b, rho, Sg);
-            if (!ok) {
-                if (iter == 0) {
-                    for (int j = tid; j < n; j += T8) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = tid; i < m; i += T8) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (tid == 0) fail_status(p, b);
-                    return;
-                }
-                status = MPCQP_NON_CVX_;
-                can_check = true;
-                break;
-            }
-            if (factor_only) return;
-            __syncthreads();
-            {
-                const double* src = Sg + (long)w * SS + r * S + 16 * h;
-#pragma unroll
-                for (int c = 0; c < 16; c += 2) ld2(src + c, SB[c], SB[c + 1]);
-            }
-            __syncthreads();  // the tiles are in registers: the G copy overwrites them
-            const bool have_y = iter > 0 || warm;
-            for (int i = tid; i < mp; i += T8) L.ys[i] = (have_y && i < m) ? p.y[b * m + i] : 0.0;
-            for (int o = tid; o < (NP + 1) * GR * S; o += T8) {
-                const int q = o / (GR * S), t = (o >> 5) - q * GR;
-                L.gl[o] = (q < NP && t < p.amax) ? w8_gpair(Fg, Hg, p.amax, q)[t * S + (o & 31)] : 0.0;
-            }
-            cv = low && p.pad_var[pc] >= 0;
-            cg.load(p.gcol + pc, npad, abase, wbase);
-            pg.load(p.gpsym + pc, npad, lds_addr(L.Pv), Xbase);
-            Dv = p.D[b * npad + pc];
-            Ev = ri < m ? p.E[b * m + ri] : 1.0;
-            if (ri < m) rg.load(p.grow + ri, m, abase, xbase);  // by ri: duplicate lanes repeat its row
-            else rg.clear(abase + 8u * nnzA, xbase);
-            PH(0)
-        }
-        // ---- run state ----
-        double X = C.X[pc], DX = 0.0;
-        const double Q = L.qv[pc];
-        // phase-C slots: the pairs (j, w), j > w, alternate over the halves (the i-th to half
-        // i & 1); the wave runs NSW(w) slots, a half without a pair there reads the zero pair
-        constexpr int NS = (NB - 1 + 1) / 2;
-        const int nsw = (NB - w) >> 1;  // ceil((NB - 1 - w) / 2)
-        unsigned gslot[NS], tslot[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int j = w + 1 + 2 * s + h;
-            const bool v = j < NB;
-            gslot[s] = lds_addr(L.gl + (v ? j * (j - 1) / 2 + w : NP) * GR * S + r);
-            tslot[s] = lds_addr(L.tv + (v ? j : 0) * 16);
-        }
-        // the half's share of the column list (KH entries; the list is zero-padded to K)
-        GatherW<KH> ch2;
-#pragma unroll
-        for (int k = 0; k < KH; ++k) ch2.e[k] = h ? cg.e[k + KH] : cg.e[k];
-        const double r_hi = RHO_EQ_OVER_RHO_INEQ * rho;
-        double y = L.ys[ri], Z = C.Z[ri], dy = 0.0;
-        const signed char cl = L.ct[ri];
-        const double rv = cl < 0 ? RHO_MIN : (cl > 0 ? r_hi : rho);
-        const double rvi = cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho);
-        __syncthreads();
-        if (rows_wave) L.w[ri] = rv * Z - y;  // (lanes past the padded rows may hold a stale y)
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
-        __syncthreads();
-        PH(5)
-        double* const cw = L.cor + w * 16;                  // c_w rows < QR
-        const double* const cwh = L.cor + (h ? 128 : w * 16);  // the half's correction (upper half: zeros)
-        while (iter < stop_at) {
-            ++iter;
-            // rhs = sigma x_prev - q + A' (rho z_prev - y), column pc: the lower half sums
-            // the list's first KH entries, the upper half the rest, one permlane32 swap
-            {
-                double av[KH], wv[KH];
-#pragma unroll
-                for (int k = 0; k < KH; ++k) {
-                    av[k] = lds_at(ch2.e[k] & 0xFFFFu);
-                    wv[k] = lds_at(ch2.e[k] >> 16);
-                }
-                double v = low ? sigma * X - Q : 0.0;
-#pragma unroll
-                for (int k = 0; k < KH; ++k) v += av[k] * wv[k];
-                const unsigned vlo = (unsigned)__double2loint(v), vhi = (unsigned)__double2hiint(v);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(vlo, vlo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(vhi, vhi, false, false);
-                const double v0 = __hiloint2double((int)h2[0], (int)l2[0]);
-                const double v1 = __hiloint2double((int)h2[1], (int)l2[1]);
-                if (low) L.rb[pc] = cv ? v0 + v1 : 0.0;
-            }
-            __syncthreads();
-            PH(1)
-            // A: c_w = sum_{j<w} G_wj b_j (rows rr < QR: 16 rows x 4 lanes of 8 columns), wave w only
-            if (w > 0) {
-                const double* gq = L.gl + (w * (w - 1) / 2) * GR * S + min(rr, GR - 1) * S + 8 * ch;
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < NB - 1; ++j) {
-                    if (j < w) {
-                        double bj[8], ga[8];
-#pragma unroll
-                        for (int e = 0; e < 8; e += 2) {
-                            ld2(L.rb + j * S + 8 * ch + e, bj[e], bj[e + 1]);
-                            ld2(gq + j * GR * S + e, ga[e], ga[e + 1]);
-                        }
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) acc += ga[e] * bj[e];
-                    }
-                }
-                acc += dpp<0xB1>(acc);
-                acc += dpp<0x4E>(acc);
-                if (ch == 0 && rr < QR) cw[rr] = acc;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            PH(12)
-            // B: t_w[r] = S_w^{-1}[r] (b_w + c_w): half-row sums, permlane32 swap
-            double t;
-            {
-                constexpr int QE = (QR + 1) & ~1;  // c_w's nonzero rows (< amax), read in pairs
-                double v[16], cc[QE];
-#pragma unroll
-                for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, v[c], v[c + 1]);
-#pragma unroll
-                for (int c = 0; c < QE; c += 2) ld2(cwh + c, cc[c], cc[c + 1]);
-#pragma unroll
-                for (int c = 0; c < QR; ++c) v[c] += cc[c];
-                double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int c = 0; c < 16; ++c) a[c & 3] += SB[c] * v[c];
-                const double th = (a[0] + a[1]) + (a[2] + a[3]);
-                const unsigned lo = (unsigned)__double2loint(th), hi = (unsigned)__double2hiint(th);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                const double t0 = __hiloint2double((int)h2[0], (int)l2[0]);  // lower half's
-                const double t1 = __hiloint2double((int)h2[1], (int)l2[1]);  // upper half's
-                t = t0 + t1;
-                if (low && r < QR) L.tv[w * 16 + r] = t;
-            }
-            __syncthreads();
-            PH(13)
-            // C: x~_w[r] = t + sum_s G_{pair_s}[q][r] t_{j_s}[q]  (slots split over the halves;
-            // rows q < QR: the G blocks are zero from row amax on)
-            {
-                double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    if (s < nsw) {
-                        double gv[QR], tq[QR];
-#pragma unroll
-                        for (int q = 0; q < QR; ++q) gv[q] = lds_at(gslot[s] + q * S * 8);
-#pragma unroll
-                        for (int q = 0; q < QR; q += 2) lds_at2(tslot[s] + q * 8, tq[q], tq[q + 1]);
-#pragma unroll
-                        for (int q = 0; q < QR; q += 2) {
-                            a0 += gv[q] * tq[q];
-                            a1 += gv[q + 1] * tq[q + 1];
-                        }
-                    }
-                }
-                const double d = a0 + a1;
-                const unsigned lo = (unsigned)__double2loint(d), hi = (unsigned)__double2hiint(d);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                const double d0 = __hiloint2double((int)h2[0], (int)l2[0]);
-                const double d1 = __hiloint2double((int)h2[1], (int)l2[1]);
-                const double xn = t + (d0 + d1);
-                if (low) L.xt[pc] = xn;
-                const double xnew = alpha * xn + (1.0 - alpha) * X;
-                DX = xnew - X;
-                X = xnew;
-            }
-            __syncthreads();
-            PH(14)
-            // rows: z~ = A x~ ; relaxed + projected z ; y ; next w
-            if (rows_wave) {
-                double av[K], xv[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    av[k] = lds_at(rg.e[k] & 0xFFFFu);
-                    xv[k] = lds_at(rg.e[k] >> 16);
-                }
-                const double lo = L.lo[ri], up = L.up[ri];
-                double zt = av[0] * xv[0];
-#pragma unroll
-                for (int k = 1; k < K; ++k) zt += av[k] * xv[k];
-                const double zr = alpha * zt + (1.0 - alpha) * Z;
-                const double zn = __builtin_fmin(__builtin_fmax(zr + rvi * y, lo), up);
-                const double dd = rv * (zr - zn);
-                Z = zn;
-                dy = dd;
-                y += dd;
-                L.w[ri] = rv * zn - y;
-            }
-            __syncthreads();
-            PH(3)
-        }
-        // run state back to LDS
-        if (low) { C.X[pc] = X; L.dx[pc] = DX; }
-        if (rows_wave) { L.ys[ri] = y; C.Z[ri] = Z; C.dY[ri] = dy; }
-        __syncthreads();
-        can_check = p.check_term && (iter % p.check_term == 0);
-        const bool do_rho = p.adaptive_rho && p.rho_interval && (iter % p.rho_interval == 0);
-        if (!can_check && !do_rho) break;
-        info_iter = iter;
-        bool stop = false;
-        {
-            // inline update_info + check_termination (as solve_w2_body's), one row per thread
-            const bool unscale = p.scaling && !p.scaled_term;
-            const unsigned ysbase = lds_addr(L.ys), dYbase = lds_addr(C.dY), dxbase = lds_addr(L.dx);
-            double mx[17], sm[2] = {0.0, 0.0}, adx = 0.0;
-#pragma unroll
-            for (int k = 0; k < 17; ++k) mx[k] = 0.0;
-            {
-                const bool ok = tid < m;
-                double ax = 0.0, ad = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const unsigned e = rg.e[k], va = e >> 16;
-                    const double a = lds_at(e & 0xFFFFu);
-                    ax += a * lds_at(va - xbase + Xbase);
-                    ad += a * lds_at(va - xbase + dxbase);
-                }
-                adx = ad;
-                const double zi = Z, pr = ax - zi, ei = 1.0 / Ev;
-                const double lo = L.lo[ri], up = L.up[ri];
-                double d = dy;
-                if (up > OSQP_INFTY * MIN_SCALING) d = (lo < -OSQP_INFTY * MIN_SCALING) ? 0.0 : cmin(d, 0.0);
-                else if (lo < -OSQP_INFTY * MIN_SCALING) d = cmax(d, 0.0);
-                if (ok) {
-                    mx[0] = fabs(ei * pr);
-                    mx[2] = fabs(ei * zi);
-                    mx[3] = fabs(ei * ax);
-                    mx[7] = fabs(pr);
-                    mx[9] = fabs(zi);
-                    mx[10] = fabs(ax);
-                    mx[14] = fabs(unscale ? Ev * d : d);
-                    sm[0] = up * cmax(d, 0.0) + lo * cmin(d, 0.0);
-                    C.dY[ri] = d;
-                }
-            }
-            {  // the lane's column (lower half): P x, A' y, P dx, and the delta x norm
-                double px = 0.0, pdx = 0.0, aty = 0.0;
-#pragma unroll
-                for (int k = 0; k < KPK; ++k) {
-                    const unsigned e = pg.e[k], va = e >> 16;
-                    const double pv = lds_at(e & 0xFFFFu);
-                    px += pv * lds_at(va);
-                    pdx += pv * lds_at(va - Xbase + dxbase);
-                }
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const unsigned e = cg.e[k];
-                    aty += lds_at(e & 0xFFFFu) * lds_at((e >> 16) - wbase + ysbase);
-                }
-                if (cv) {
-                    const double d = (Q + px) + aty, di = 1.0 / Dv;
-                    mx[1] = fabs(di * d);
-                    mx[4] = fabs(di * Q);
-                    mx[5] = fabs(di * aty);
-                    mx[6] = fabs(di * px);
-                    mx[8] = fabs(d);
-                    mx[11] = fabs(Q);
-                    mx[12] = fabs(aty);
-                    mx[13] = fabs(px);
-                    mx[15] = fabs(unscale ? Dv * DX : DX);
-                    mx[16] = fabs(unscale ? pdx * di : pdx);
-                }
-            }
-            if (tid < npad && p.pad_var[tid] >= 0) sm[1] = L.qv[tid] * L.dx[tid];
-            block_max_sum_tr<T8, 17, 2>(mx, sm, red8);
-            Res R;
-            if (unscale) {
-                R.pri = mx[0]; R.dua = cinv * mx[1];
-                R.nz = mx[2]; R.nax = mx[3]; R.nq = mx[4]; R.naty = mx[5]; R.npx = mx[6];
-            } else {
-                R.pri = mx[7]; R.dua = mx[8];
-                R.nz = mx[9]; R.nax = mx[10]; R.nq = mx[11]; R.naty = mx[12]; R.npx = mx[13];
-            }
-            R.rpri = mx[7]; R.rdua = mx[8]; R.rz = mx[9]; R.rax = mx[10]; R.rq = mx[11]; R.raty = mx[12]; R.rpx = mx[13];
-            if (m == 0) R.pri = 0.0;
-            if (tid == 0) R.save(L.res);
-            if (can_check) {
-                int st = MPCQP_UNSOLVED_;
-                double obj = 0.0;
-                bool done = false;
-                if (R.pri > OSQP_INFTY || R.dua > OSQP_INFTY) {
-                    st = MPCQP_NON_CVX_;
-                    obj = __builtin_nan("");
-                    done = true;
-                } else {
-                    const bool prim_ok = m == 0 || R.pri < p.eps_abs + p.eps_rel * cmax(R.nz, R.nax);
-                    double mxd = cmax(cmax(R.nq, R.naty), R.npx);
-                    if (unscale) mxd *= cinv;
-                    const bool dual_ok = R.dua < p.eps_abs + p.eps_rel * mxd;
-                    bool prim_inf = false, dual_inf = false;
-                    if (!prim_ok || !dual_ok) {
-                        const double norm_dy = mx[14], norm_dx = mx[15], epi = p.eps_pinf, edi = p.eps_dinf;
-                        const double cs = unscale ? cval : 1.0;
-                        if (!prim_ok && m != 0 && norm_dy > epi && sm[0] < epi * norm_dy) {
-                            __syncthreads();
-                            double na[1] = {0.0};
-                            double a = 0.0;
-#pragma unroll
-                            for (int k = 0; k < K; ++k) {
-                                const unsigned e = cg.e[k];
-                                a += lds_at(e & 0xFFFFu) * lds_at((e >> 16) - wbase + dYbase);
-                            }
-                            if (cv) na[0] = fabs(unscale ? a * (1.0 / Dv) : a);
-                            block_max<T8, 1>(na, L.red);
-                            prim_inf = na[0] < epi * norm_dy;
-                        }
-                        if (!dual_ok && norm_dx > edi && sm[1] < cs * edi * norm_dx && mx[16] < cs * edi * norm_dx) {
-                            bool viol = false;
-                            if (tid < m) {
-                                const double ar = unscale ? adx * (1.0 / Ev) : adx;
-                                const double lo = L.lo[ri], up = L.up[ri];
-                                if ((up < OSQP_INFTY * MIN_SCALING && ar > edi * norm_dx) ||
-                                    (lo > -OSQP_INFTY * MIN_SCALING && ar < -edi * norm_dx))
-                                    viol = true;
-                            }
-                            dual_inf = !block_any<T8>(viol, L.flag);
-                        }
-                    }
-                    if (prim_ok && dual_ok) {
-                        st = MPCQP_SOLVED_;
-                        done = true;
-                    } else if (prim_inf) {
-                        st = MPCQP_PRIMAL_INFEASIBLE_;
-                        obj = OSQP_INFTY;
-                        if (tid == 0) L.flag[3] = unscale;
-                        done = true;
-                    } else if (dual_inf) {
-                        st = MPCQP_DUAL_INFEASIBLE_;
-                        obj = -OSQP_INFTY;
-                        if (tid == 0) L.flag[2] = unscale;
-                        done = true;
-                    }
-                }
-                __syncthreads();
-                if (done && tid == 0) { L.flag[1] = st; L.res[14] = obj; }
-                __syncthreads();
-                status = done ? st : MPCQP_UNSOLVED_;
-                stop = done;
-            }
-        }
-        if (!stop && do_rho) {
-            Res R;
-            R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
-        }
-        __syncthreads();
-        PH(4)
-        if (stop || iter >= p.max_iter) break;
-    }
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<T8>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<T8>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<T8>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<T8>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<T8>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
-#ifdef MPCQP_PHASE_PROF
-    if (prof) {
-        __syncthreads();
-        PH(5)
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 2] = L.pacc[12] + L.pacc[13] + L.pacc[14];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-            p.prof[b * kProfSlots + 15] = t0w;
-        }
-    }
-#endif
-#undef PH
-}
-
-template <int K, int KPK>
-__global__ __launch_bounds__(T8, 1) void k_solve_w8(KParams p, double* __restrict__ xo, double* __restrict__ yo,
-                                                    int factor_only) {
-    solve_w8_body<K, KPK>(p, xo, yo, factor_only);
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    order_epilogue<T8>(p, (int*)sm);
-}
-
-#endif  // MPCQP_EXPERIMENTAL
-
 // Host-side guard tying an instantiation's compile-time list lengths to the plan: gather
 // lists are kGS deep in memory (plan.cpp), so a shorter K never reads out of the list, but
 // it would drop A entries; K / KC: row / column gather lengths, KPK: P terms per column,
@@ -2580,16 +1692,9 @@ bool dense_w4_on() {
     return dense_w4_on() && p.ne == 0 && p.Kd && p.bsz01 <= 26 && p.bsz23 <= 28;
 }
 
-// the fused kernel's instantiation for the plan, or 0: variant 10 and the 128-thread
-// register-list setup shape (one padded column per thread, two rows, four A values)
-static int setup_solve_fits(const KParams& p) {
-    if (p.variant == 17) return p.pk <= 4;  // variant_fits(17) covers the rest (list lengths, nnzA <= 2 or 3 x T4)
-    return p.variant == 10 && p.npad <= T2 && p.m <= 2 * T2 && p.gk <= 6 && p.pk <= 4 && p.nnzA <= 4 * T2 &&
-           p.nnzP <= 2 * T2;
-}
-
 int one_shot_form(const KParams& p, size_t* lds) {
-    if (p.variant != 17 || p.polish || !setup_solve_fits(p)) return 0;
+    const Variant* d = variant_of(p.variant);  // the fused four-wave kernel's variants only
+    if (!d || d->setup_solve != launch_setup_solve_w4 || p.polish) return 0;
     const size_t base = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
     // (form 2: the G blocks and the y of a refactorisation, which the factorisation's E tiles
     // overwrite in the carve, after the S_k^{-1} tiles)
@@ -2605,9 +1710,11 @@ int one_shot_form(const KParams& p, size_t* lds) {
     return form;
 }
 
-hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
-                              const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                              int one_shot) {
+// the four-wave kernel's fused launch (variant_fits covers its preconditions: list lengths,
+// pk <= 4, nnzA <= 2 or 3 x T4)
+hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                                 const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                                 int one_shot) {
     size_t lds1 = 0;
     const int form = one_shot ? one_shot_form(p, &lds1) : 0;
     if (form) {
@@ -2632,34 +1739,34 @@ hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const 
         hipLaunchKernelGGL(k4, dim3((unsigned)B), dim3(T4), lds1, st, p, Px, Ax, q, l, u, xo, yo);
         return hipGetLastError();
     }
+    const size_t lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
+    // QR: rows of the G blocks phase C sums (the nonzero ones: amax)
+    // EL (eliminated columns, the slack layouts): three A values per setup thread
+    auto k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8>
+                   : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2> : k_setup_solve_w4<6, 4, 8, 6, 2>);
 #ifdef MPCQP_EXPERIMENTAL
-    if (p.variant == 19) {
-        hipError_t e = launch_setup_solve_heavy(p, B, Px, Ax, q, l, u, xo, yo, st);
-        return (e != hipSuccess || !p.polish) ? e : launch_polish(p, B, xo, yo, st);
-    }
+    if (!p.ne && p.amax <= 5 && dense_w4(p)) k4 = k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, true>;
 #endif
-    if (!setup_solve_fits(p)) {
+    hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k4, dim3((unsigned)B), dim3(T4), lds, st, p, Px, Ax, q, l, u, xo, yo);
+    e = hipGetLastError();
+    if (e != hipSuccess || !p.polish) return e;
+    return launch_polish(p, B, xo, yo, st);
+}
+
+// the two-wave kernel's fused launch where the 128-thread register-list setup shape holds (one
+// padded column per thread, two rows, four A values), else the two kernels
+hipError_t launch_setup_solve_w2(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
+                                 const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                                 int /*one_shot*/) {
+    if (!(p.npad <= T2 && p.m <= 2 * T2 && p.gk <= 6 && p.pk <= 4 && p.nnzA <= 4 * T2 && p.nnzP <= 2 * T2)) {
         hipError_t e = launch_setup(p, B, Px, Ax, q, l, u, st);
         return e != hipSuccess ? e : launch_solve(p, B, xo, yo, 0, st);
     }
     const size_t lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
-    if (p.variant == 17) {
-        // QR: rows of the G blocks phase C sums (the nonzero ones: amax)
-        // EL (eliminated columns, the slack layouts): three A values per setup thread
-        auto k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8>
-                       : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2> : k_setup_solve_w4<6, 4, 8, 6, 2>);
-#ifdef MPCQP_EXPERIMENTAL
-        if (!p.ne && p.amax <= 5 && dense_w4(p)) k4 = k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, true>;
-#endif
-        hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k4, dim3((unsigned)B), dim3(T4), lds, st, p, Px, Ax, q, l, u, xo, yo);
-        e = hipGetLastError();
-        if (e != hipSuccess || !p.polish) return e;
-        return launch_polish(p, B, xo, yo, st);
-    }
     auto k = p.gk1 <= 1 ? k_setup_solve_w2<6, 2, 4, 1, 6, 2, 4, 2> : k_setup_solve_w2<6, 2, 4, 6, 6, 2, 4, 2>;
     hipError_t e = lists_fit(p, 6, 6, 4, 1 << 30, 6);
     if (e != hipSuccess) return e;
@@ -2684,66 +1791,37 @@ static hipError_t go_w2(const KParams& p, long B, double* xo, double* yo, int fo
     return hipGetLastError();
 }
 
-#ifdef MPCQP_EXPERIMENTAL
-template <int K, int RS>
-static hipError_t go_w(const KParams& p, long B, double* xo, double* yo, int fo, hipStream_t st, size_t lds,
-                       KernelRef* ref) {
-    auto k = k_solve_w<K, RS>;
-    if (ref) { *ref = {(const void*)k, TW, lds}; return hipSuccess; }
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(TW), lds, st, p, xo, yo, fo);
-    return hipGetLastError();
-}
-#endif
-
 // the two-wave kernel's LDS: the carve plus the nb S_k^{-1} tiles
 size_t lds_w2_bytes(const KParams& p) {
     return 16 * ((lds_base_bytes(p) + 15) / 16) + sizeof(double) * (size_t)p.nb * SS;
 }
 
-// Wave-kernel instantiations (solve.hip::variant_fits gives their preconditions).
-hipError_t launch_solve_wave(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
-                             KernelRef* ref) {
-    [[maybe_unused]] const size_t lds = lds_solve_bytes(p);  // (the experimental variants')
-    switch (p.variant) {
+// The four-wave kernel's instantiations (solve.hip's table gives the preconditions).
+hipError_t launch_solve_w4(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                           KernelRef* ref) {
+    auto k = factor_only
+                 ? (p.ne ? k_solve_w4<6, 4, 8, true, 8, true>
+                         : (p.amax <= 5 ? k_solve_w4<6, 4, 5, false, 6, true> : k_solve_w4<6, 4, 8, false, 6, true>))
+                 : (p.ne ? k_solve_w4<6, 4, 8, true, 8>
+                         : (p.amax <= 5 ? k_solve_w4<6, 4, 5> : k_solve_w4<6, 4, 8>));
 #ifdef MPCQP_EXPERIMENTAL
-        case 8: return go_w<6, 3>(p, B, xo, yo, factor_only, st, lds, ref);
-        case 9: return go_w<8, 4>(p, B, xo, yo, factor_only, st, lds, ref);
+    if (!factor_only && !p.ne && p.amax <= 5 && dense_w4(p)) k = k_solve_w4<6, 4, 5, false, 6, false, true>;
 #endif
-        case 17: {
-            auto k = factor_only
-                         ? (p.ne ? k_solve_w4<6, 4, 8, true, 8, true>
-                                 : (p.amax <= 5 ? k_solve_w4<6, 4, 5, false, 6, true> : k_solve_w4<6, 4, 8, false, 6, true>))
-                         : (p.ne ? k_solve_w4<6, 4, 8, true, 8>
-                                 : (p.amax <= 5 ? k_solve_w4<6, 4, 5> : k_solve_w4<6, 4, 8>));
-#ifdef MPCQP_EXPERIMENTAL
-            if (!factor_only && !p.ne && p.amax <= 5 && dense_w4(p)) k = k_solve_w4<6, 4, 5, false, 6, false, true>;
-#endif
-            const size_t lds = lds_w2_bytes(p);
-            hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
-            if (e != hipSuccess) return e;
-            if (ref) { *ref = {(const void*)k, T4, lds}; return hipSuccess; }
-            e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(T4), lds, st, p, xo, yo, factor_only);
-            return hipGetLastError();
-        }
-#ifdef MPCQP_EXPERIMENTAL
-        case 18: {
-            auto k = k_solve_w8<8, 8>;
-            if (ref) { *ref = {(const void*)k, T8, lds}; return hipSuccess; }
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(T8), lds, st, p, xo, yo, factor_only);
-            return hipGetLastError();
-        }
-#endif
-        case 10:  // slot-1 rows (>= 128) with at most one nonzero (cfg 2's box rows): K1 = 1
-            return p.gk1 <= 1 ? go_w2<6, 2, 4, 1>(p, B, xo, yo, factor_only, st, lds_w2_bytes(p), ref)
-                              : go_w2<6, 2, 4, 6>(p, B, xo, yo, factor_only, st, lds_w2_bytes(p), ref);
-        default: return hipErrorInvalidValue;
-    }
+    const size_t lds = lds_w2_bytes(p);
+    hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
+    if (e != hipSuccess) return e;
+    if (ref) { *ref = {(const void*)k, T4, lds}; return hipSuccess; }
+    e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(T4), lds, st, p, xo, yo, factor_only);
+    return hipGetLastError();
+}
+
+// The two-wave kernel's: slot-1 rows (>= 128) with at most one nonzero (cfg 2's box rows): K1 = 1
+hipError_t launch_solve_w2(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
+                           KernelRef* ref) {
+    return p.gk1 <= 1 ? go_w2<6, 2, 4, 1>(p, B, xo, yo, factor_only, st, lds_w2_bytes(p), ref)
+                      : go_w2<6, 2, 4, 6>(p, B, xo, yo, factor_only, st, lds_w2_bytes(p), ref);
 }
 
 }  // namespace mpcqp

@@ -1,5 +1,5 @@
 // wave_util.h -- LDS addressing helpers shared by the wave-level solve kernels
-// (solve_wave.hip, solve_dense.hip): packed gather lists with absolute LDS byte
+// (solve_wave.hip, and exp/'s solve_wave1 / solve_wave8 / solve_dense / solve_heavy): packed gather lists with absolute LDS byte
 // addresses and 16-byte LDS reads.
 #pragma once
 #include <hip/hip_runtime.h>
