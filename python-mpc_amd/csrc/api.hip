@@ -146,11 +146,16 @@ int need_state(const mpcqp_handle* h, const char* what) {
     return 0;
 }
 
-template <class T>
-size_t carve(size_t& off, size_t count) {
+bool env_is(const char* name, char c) {  // a one-character switch in the environment
+    const char* e = getenv(name);
+    return e && e[0] == c;
+}
+
+// the next region of a block: 256-byte aligned
+size_t carve(size_t& off, size_t bytes) {
     off = (off + 255) & ~(size_t)255;
     size_t o = off;
-    off += count * sizeof(T);
+    off += bytes;
     return o;
 }
 
@@ -291,17 +296,20 @@ void pool_stream_release(Shard& s) {
 }
 
 int upload_plan(const Plan& pl, Shard& s) {
-    std::vector<const std::vector<int>*> parts = {
-        &pl.pad_var, &pl.acsc_ptr, &pl.acsc_row, &pl.acsc_v, &pl.acsr_ptr, &pl.acsr_col, &pl.acsr_v,
-        &pl.psym_ptr, &pl.psym_col, &pl.psym_v, &pl.p_r, &pl.p_c, &pl.a_r, &pl.a_c,
-        &pl.asm_blk_ptr, &pl.asm_tgt, &pl.tterm, &pl.acsr_pos, &pl.gcol, &pl.grow, &pl.gpsym, &pl.toff, &pl.bsize, &pl.tcnt,
-        &pl.eown, &pl.etterm, &pl.wide_cg, &pl.wide_pg, &pl.wide_rg, &pl.wide_as, &pl.wide_ps, &pl.csc_pos};
-    std::vector<size_t> offs;
+    KParams& k = s.kp;
+    struct Part { const std::vector<int>* v; const int** dst; };  // a plan array and its device pointer
+    const Part parts[] = {
+        {&pl.pad_var, &k.pad_var}, {&pl.acsc_ptr, &k.acsc_ptr}, {&pl.acsc_row, &k.acsc_row}, {&pl.acsc_v, &k.acsc_v},
+        {&pl.acsr_ptr, &k.acsr_ptr}, {&pl.acsr_col, &k.acsr_col}, {&pl.acsr_v, &k.acsr_v},
+        {&pl.psym_ptr, &k.psym_ptr}, {&pl.psym_col, &k.psym_col}, {&pl.psym_v, &k.psym_v},
+        {&pl.p_r, &k.p_r}, {&pl.p_c, &k.p_c}, {&pl.a_r, &k.a_r}, {&pl.a_c, &k.a_c},
+        {&pl.asm_blk_ptr, &k.asm_blk_ptr}, {&pl.asm_tgt, &k.asm_tgt}, {&pl.tterm, &k.tterm},
+        {&pl.acsr_pos, &k.acsr_pos}, {&pl.gcol, &k.gcol}, {&pl.grow, &k.grow}, {&pl.gpsym, &k.gpsym},
+        {&pl.toff, &k.toff}, {&pl.bsize, &k.bsize}, {&pl.tcnt, &k.tcnt}, {&pl.eown, &k.eown},
+        {&pl.etterm, &k.etterm}, {&pl.wide_cg, &k.wcg}, {&pl.wide_pg, &k.wpg}, {&pl.wide_rg, &k.wrg},
+        {&pl.wide_as, &k.was}, {&pl.wide_ps, &k.wps}, {&pl.csc_pos, &k.csc_pos}};
     size_t total = 0;
-    for (auto* v : parts) {
-        offs.push_back(total);
-        total += v->size() + 1;  // never allocate zero-length parts
-    }
+    for (auto& p : parts) total += p.v->size() + 1;  // never allocate zero-length parts
     s.dplan_bytes = total * sizeof(int);
     s.dplan_tag = pl.uid;
     bool have = false;  // a pooled copy of this very plan (a fresh handle of the same pattern)
@@ -309,48 +317,132 @@ int upload_plan(const Plan& pl, Shard& s) {
     if (!have) {  // (the flat image is built only when it is uploaded)
         std::vector<int> flat;
         flat.reserve(total);
-        for (auto* v : parts) {
-            flat.insert(flat.end(), v->begin(), v->end());
+        for (auto& p : parts) {
+            flat.insert(flat.end(), p.v->begin(), p.v->end());
             flat.push_back(0);
         }
         HIPCHK(hipMemcpy(s.dplan, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    const int** dst[] = {&s.kp.pad_var, &s.kp.acsc_ptr, &s.kp.acsc_row, &s.kp.acsc_v, &s.kp.acsr_ptr,
-                         &s.kp.acsr_col, &s.kp.acsr_v, &s.kp.psym_ptr, &s.kp.psym_col, &s.kp.psym_v,
-                         &s.kp.p_r, &s.kp.p_c, &s.kp.a_r, &s.kp.a_c, &s.kp.asm_blk_ptr, &s.kp.asm_tgt,
-                         &s.kp.tterm, &s.kp.acsr_pos,
-                         &s.kp.gcol, &s.kp.grow, &s.kp.gpsym, &s.kp.toff, &s.kp.bsize, &s.kp.tcnt,
-                         &s.kp.eown, &s.kp.etterm, &s.kp.wcg, &s.kp.wpg, &s.kp.wrg, &s.kp.was, &s.kp.wps,
-                         &s.kp.csc_pos};
-    for (size_t i = 0; i < parts.size(); ++i) *dst[i] = s.dplan + offs[i];
+    size_t off = 0;
+    for (auto& p : parts) {
+        *p.dst = s.dplan + off;
+        off += p.v->size() + 1;
+    }
     return 0;
 }
 
-size_t workspace_bytes(const Plan& pl, long B, bool with_io) {
-    size_t off = 0;
-    const long n = pl.n, m = pl.m, np = pl.npad, nb = pl.nb;
-    const long SS = (long)kS * kS;
-    carve<double>(off, B * pl.nnzP); carve<double>(off, B * pl.nnzA);
-    carve<double>(off, B * np); carve<double>(off, B * np);            // q, D
-    carve<double>(off, B * m); carve<double>(off, B * m); carve<double>(off, B * m);  // l u E
-    carve<double>(off, B * np); carve<double>(off, B * m); carve<double>(off, B * m); // x z y
-    carve<double>(off, B * 4);
-    carve<double>(off, B * nb * SS); carve<double>(off, B * nb * SS); carve<double>(off, B * nb * SS);
-    carve<double>(off, B * dense_rows_doubles(pl.nb, pl.ne));       // Kd
-    carve<double>(off, B * m); carve<double>(off, B * n);              // certificates
-    for (int i = 0; i < 4; ++i) carve<double>(off, B);
-    carve<signed char>(off, B * m);
-    for (int i = 0; i < 8; ++i) carve<int>(off, B);
-    carve<int>(off, 1);  // done (fused order epilogue)
-    carve<int>(off, 2);  // queue (k_solve_b's persistent form)
-    carve<long long>(off, B * kProfSlots);
-    carve<KParams>(off, 1);
-    if (with_io) {
-        carve<double>(off, B * pl.nnzP); carve<double>(off, B * pl.nnzA);
-        carve<double>(off, B * n); carve<double>(off, B * m); carve<double>(off, B * m);
-        carve<double>(off, B * n); carve<double>(off, B * m);
+// ---- the workspace (Shard::dws): one listing ----
+// Every region in carve order, each on a 256-byte boundary: the KParams / Shard pointer it is
+// carved into, its element size and count, and what a re-plan does with it.  workspace_bytes,
+// alloc_shard's carve and replan_plain's copies are passes over this listing.
+enum class Carry {
+    copy,    // moved verbatim
+    by_var,  // per column, padded order: old var_pad -> new var_pad, the padding set to Region::pad
+    by_csc,  // the scaled A values: old csc_pos -> new csc_pos
+    drop     // rebuilt by the next solve (the factor), restarted (the dispatch order) or the block's own
+};
+struct Region {
+    void* slot;  // the pointer member's address
+    size_t esz, count;
+    Carry carry;
+    double pad;
+    bool carved;  // false: counted in the size, but the pointer stays null and the carve skips it
+};
+void* region_ptr(const Region& r) {
+    void* p;
+    memcpy(&p, r.slot, sizeof p);
+    return p;
+}
+
+std::vector<Region> workspace_regions(const Plan& pl, long B, bool with_io, Shard& s) {
+    KParams& k = s.kp;
+    const size_t b = B, n = pl.n, m = pl.m, np = pl.npad, fac = (size_t)pl.nb * kS * kS;
+    const size_t kd = dense_rows_doubles(pl.nb, pl.ne);  // (zero in the production build)
+    std::vector<Region> r;
+    r.reserve(48);
+    auto add = [&](auto*& p, size_t count, Carry c, double pad = 0.0, bool carved = true) {
+        r.push_back({(void*)&p, sizeof(*p), count, c, pad, carved});
+    };
+    const Carry cp = Carry::copy, no = Carry::drop;
+    add(k.Px, b * pl.nnzP, cp); add(k.Ax, b * pl.nnzA, Carry::by_csc);
+    add(k.q, b * np, Carry::by_var, 0.0); add(k.D, b * np, Carry::by_var, 1.0);
+    add(k.l, b * m, cp); add(k.u, b * m, cp); add(k.E, b * m, cp);
+    add(k.x, b * np, Carry::by_var, 0.0); add(k.z, b * m, cp); add(k.y, b * m, cp);
+    add(k.scal, b * 4, cp);
+    add(k.F, b * fac, no); add(k.H, b * fac, no); add(k.Si, b * fac, no);
+    add(k.Kd, b * kd, no, 0.0, kd != 0);
+    add(k.dyc, b * m, cp); add(k.dxc, b * n, cp);  // certificates
+    add(k.obj, b, cp); add(k.pri, b, cp); add(k.dua, b, cp); add(k.rho_est, b, cp);
+    add(k.ct, b * m, cp);
+    // err right before status: check_setup reads both in one copy, from err to the end of status
+    add(k.err, b, cp); add(k.status, b, cp);
+    add(k.iter, b, cp); add(k.rho_upd, b, cp); add(k.pstat, b, cp);
+    add(k.ffresh, b, no);
+    add(k.order, b, no); add(k.pred, b, no);  // (alloc_shard fills order with the identity)
+    add(k.done, 1, no);   // (fused order epilogue; alloc_shard keeps it for some variants only)
+    add(k.queue, 2, no);  // (k_solve_b's persistent form)
+    add(k.prof, b * kProfSlots, no, 0.0, env_is("MPCQP_PHASE_PROF", '1'));  // (always counted)
+    add(k.self, 1, no);
+    if (with_io) {  // the host-pointer API's device inputs and outputs; the five inputs in one run
+        add(s.in_Px, b * pl.nnzP, cp); add(s.in_Ax, b * pl.nnzA, cp);
+        add(s.in_q, b * n, cp); add(s.in_l, b * m, cp); add(s.in_u, b * m, cp);
+        add(s.out_x, b * n, cp); add(s.out_y, b * m, cp);
     }
+    return r;
+}
+
+size_t workspace_bytes(const Plan& pl, long B, bool with_io) {
+    Shard none;
+    size_t off = 0;
+    for (const Region& r : workspace_regions(pl, B, with_io, none)) carve(off, r.esz * r.count);
     return off + 256;
+}
+
+// The settings a running handle may change (mpcqp_update_settings), as (KParams, mpcqp_settings)
+// member pairs.  rho_interval is not among them: OSQP resolves the automatic interval in
+// osqp_setup, so check_termination set later does not move it.
+template <class F>
+void each_mutable_setting(F&& f) {
+    using K = KParams;
+    using S = mpcqp_settings;
+    f(&K::alpha, &S::alpha); f(&K::eps_abs, &S::eps_abs); f(&K::eps_rel, &S::eps_rel);
+    f(&K::eps_pinf, &S::eps_prim_inf); f(&K::eps_dinf, &S::eps_dual_inf); f(&K::rho0, &S::rho);
+    f(&K::max_iter, &S::max_iter); f(&K::check_term, &S::check_termination); f(&K::warm_start, &S::warm_start);
+    f(&K::scaled_term, &S::scaled_termination); f(&K::polish, &S::polish);
+    f(&K::refine_iter, &S::polish_refine_iter); f(&K::delta, &S::delta);
+}
+void apply_settings(KParams& k, const mpcqp_settings& st) {
+    each_mutable_setting([&](auto kf, auto sf) { k.*kf = st.*sf; });
+}
+void carry_settings(KParams& to, const KParams& from) {  // (replan_plain)
+    each_mutable_setting([&](auto kf, auto) { to.*kf = from.*kf; });
+}
+
+// The solve variant of a plan's shape: the production choice (-1: no instantiation fits), the
+// MPCQP_VARIANT override (diagnostic: A/B timing) and the variant's mode.
+int pick_variant(KParams& k) {
+    k.variant = solve_variant(k);
+    if (const char* ev = getenv("MPCQP_VARIANT"); ev && *ev) {
+        const int v = atoi(ev);
+        if (!variant_fits(k, v)) return fail(MPCQP_EUNSUPPORTED, "MPCQP_VARIANT=%d does not fit this plan", v);
+        k.variant = v;
+    }
+    k.mode = k.variant >= 0 ? solve_mode(k.variant) : 0;
+    return 0;
+}
+
+// what mpcqp_get_plan_info and mpcqp_plan_preview report of a plan and its variant (k: shape,
+// variant and mode filled; null: no shard)
+void fill_plan_info(mpcqp_plan_info* info, int n, int m, const Plan& pl, const KParams* k) {
+    const bool have = k && k->variant >= 0;
+    info->n = n; info->m = m; info->nb = pl.nb; info->block = kS; info->npad = pl.npad;
+    info->max_level = pl.max_level;
+    info->lds_bytes_solve = have ? (int64_t)lds_kernel_bytes(*k) : 0;
+    info->bytes_per_instance = (int64_t)workspace_bytes(pl, 1, false);
+    info->amax = pl.amax; info->gather_k = pl.gather_k;
+    info->variant = k ? k->variant : -1;
+    info->threads_per_qp = have ? solve_threads(k->variant) : 0;
+    info->n_eliminated = pl.ne; info->plan_choice = pl.choice;
 }
 
 // sync: wait for the zeroing, the identity order and the parameter block before returning (the
@@ -363,8 +455,7 @@ int alloc_shard(mpcqp_handle* h, Shard& s, bool with_io, bool sync = true) {
     strace().mark("stream");
     if (int e = upload_plan(pl, s)) return e;
     strace().mark("plan upload");
-    const long B = s.B, n = pl.n, m = pl.m, np = pl.npad, nb = pl.nb;
-    const long SS = (long)kS * kS;
+    const long B = s.B;
     size_t total = workspace_bytes(pl, B, with_io);
     hipError_t e = pool_malloc(s.dev, total, &s.dws, false);
     if (e == hipSuccess) s.dws_bytes = total;
@@ -373,93 +464,40 @@ int alloc_shard(mpcqp_handle* h, Shard& s, bool with_io, bool sync = true) {
     strace().mark("workspace alloc");
     HIPCHK(hipMemsetAsync(s.dws, 0, total, s.stream));
     strace().mark("workspace memset");
-    char* base = (char*)s.dws;
-    size_t off = 0;
     KParams& k = s.kp;
-    k.Px = (double*)(base + carve<double>(off, B * pl.nnzP));
-    k.Ax = (double*)(base + carve<double>(off, B * pl.nnzA));
-    k.q = (double*)(base + carve<double>(off, B * np));
-    k.D = (double*)(base + carve<double>(off, B * np));
-    k.l = (double*)(base + carve<double>(off, B * m));
-    k.u = (double*)(base + carve<double>(off, B * m));
-    k.E = (double*)(base + carve<double>(off, B * m));
-    k.x = (double*)(base + carve<double>(off, B * np));
-    k.z = (double*)(base + carve<double>(off, B * m));
-    k.y = (double*)(base + carve<double>(off, B * m));
-    k.scal = (double*)(base + carve<double>(off, B * 4));
-    k.F = (double*)(base + carve<double>(off, B * nb * SS));
-    k.H = (double*)(base + carve<double>(off, B * nb * SS));
-    k.Si = (double*)(base + carve<double>(off, B * nb * SS));
-    k.Kd = dense_rows_doubles(pl.nb, pl.ne) ? (double*)(base + carve<double>(off, B * dense_rows_doubles(pl.nb, pl.ne)))
-                                            : nullptr;
-    k.dyc = (double*)(base + carve<double>(off, B * m));
-    k.dxc = (double*)(base + carve<double>(off, B * n));
-    k.obj = (double*)(base + carve<double>(off, B));
-    k.pri = (double*)(base + carve<double>(off, B));
-    k.dua = (double*)(base + carve<double>(off, B));
-    k.rho_est = (double*)(base + carve<double>(off, B));
-    k.ct = (signed char*)(base + carve<signed char>(off, B * m));
-    k.err = (int*)(base + carve<int>(off, B));  // (err right before status: check_setup reads both in one copy)
-    k.status = (int*)(base + carve<int>(off, B));
-    k.iter = (int*)(base + carve<int>(off, B));
-    k.rho_upd = (int*)(base + carve<int>(off, B));
-    k.pstat = (int*)(base + carve<int>(off, B));
-    k.ffresh = (int*)(base + carve<int>(off, B));  // zero from the memset above
-    k.reuse = !(getenv("MPCQP_FACTOR_REUSE") && getenv("MPCQP_FACTOR_REUSE")[0] == '0');
-    k.apart = !(getenv("MPCQP_MIDDLE_APART") && getenv("MPCQP_MIDDLE_APART")[0] == '0');
-    k.lchain = !(getenv("MPCQP_LDS_CHAIN") && getenv("MPCQP_LDS_CHAIN")[0] == '0');
-    {  // dispatch order (kernels.hip::k_order), identity until the first solve
-        int* ord = (int*)(base + carve<int>(off, B));
-        HIPCHK(launch_iota(ord, B, s.stream));
-        k.order = ord;
-        k.pred = (int*)(base + carve<int>(off, B));  // zero from the memset above
+    size_t off = 0;
+    for (const Region& r : workspace_regions(pl, B, with_io, s)) {
+        void* p = r.carved ? (char*)s.dws + carve(off, r.esz * r.count) : nullptr;
+        memcpy(r.slot, &p, sizeof p);
+    }
+    if (off > total)
+        return fail(MPCQP_EDEVICE, "workspace carve ends at %zu bytes, past the %zu bytes allocated", off, total);
+    k.reuse = !env_is("MPCQP_FACTOR_REUSE", '0');
+    k.apart = !env_is("MPCQP_MIDDLE_APART", '0');
+    k.lchain = !env_is("MPCQP_LDS_CHAIN", '0');
+    {  // dispatch order (kernels.hip::k_order), identity until the first solve; pred, done and
+       // queue are zero from the memset above
+        HIPCHK(launch_iota(const_cast<int*>(k.order), B, s.stream));
         const char* od = getenv("MPCQP_ORDER_DECAY");
         k.odecay = od ? std::max(0, std::min(8, atoi(od))) : 7;  // (tools/pred_sim.py, profiles/r6/dispatch.txt)
         strace().mark("order upload");
         if (const char* ev = getenv("MPCQP_DISPATCH"); ev && !strcmp(ev, "identity")) k.order = nullptr;  // A/B
     }
-    int* const done = (int*)(base + carve<int>(off, 1));  // zero from the memset above
-    k.queue = (int*)(base + carve<int>(off, 2));          // zero from the memset above
-    k.qpersist = !(getenv("MPCQP_PERSIST") && getenv("MPCQP_PERSIST")[0] == '0');
+    k.qpersist = !env_is("MPCQP_PERSIST", '0');
     k.persist = 0;
     k.qn = 0;
-    k.prof = nullptr;
-    if (const char* ev = getenv("MPCQP_PHASE_PROF"); ev && ev[0] == '1')
-        k.prof = (long long*)(base + carve<long long>(off, B * kProfSlots));
-    if (with_io) {
-        s.in_Px = (double*)(base + carve<double>(off, B * pl.nnzP));
-        s.in_Ax = (double*)(base + carve<double>(off, B * pl.nnzA));
-        s.in_q = (double*)(base + carve<double>(off, B * n));
-        s.in_l = (double*)(base + carve<double>(off, B * m));
-        s.in_u = (double*)(base + carve<double>(off, B * m));
-        s.out_x = (double*)(base + carve<double>(off, B * n));
-        s.out_y = (double*)(base + carve<double>(off, B * m));
-    }
     shape_params(pl, k);
     const mpcqp_settings& st = h->set;
-    k.sigma = st.sigma; k.alpha = st.alpha; k.eps_abs = st.eps_abs; k.eps_rel = st.eps_rel;
-    k.eps_pinf = st.eps_prim_inf; k.eps_dinf = st.eps_dual_inf; k.rho0 = st.rho;
-    k.rho_tol = st.adaptive_rho_tolerance;
-    k.max_iter = st.max_iter; k.scaling = st.scaling; k.check_term = st.check_termination;
-    k.warm_start = st.warm_start; k.adaptive_rho = st.adaptive_rho; k.scaled_term = st.scaled_termination;
-    k.polish = st.polish; k.refine_iter = st.polish_refine_iter; k.delta = st.delta;
+    apply_settings(k, st);  // ... and the ones fixed at setup:
+    k.sigma = st.sigma; k.rho_tol = st.adaptive_rho_tolerance; k.scaling = st.scaling; k.adaptive_rho = st.adaptive_rho;
     int interval = st.adaptive_rho_interval;
     if (st.adaptive_rho && interval == 0) interval = st.check_termination ? 4 * st.check_termination : 100;
     k.rho_interval = interval;
     if (solve_variant(k) < 0)
         return fail(MPCQP_EUNSUPPORTED, "problem shape outside the solve kernel's instantiations (n=%d m=%d)", pl.n, pl.m);
-    k.variant = solve_variant(k);
-    if (const char* ev = getenv("MPCQP_VARIANT"); ev && *ev) {  // diagnostic override (A/B timing)
-        const int v = atoi(ev);
-        if (!variant_fits(k, v)) return fail(MPCQP_EUNSUPPORTED, "MPCQP_VARIANT=%d does not fit this plan", v);
-        k.variant = v;
-    }
-    k.mode = solve_mode(k.variant);
+    if (int e = pick_variant(k)) return e;
     // some variants' kernels sort the next dispatch order in their last workgroup (MPCQP_ORDER_KERNEL=1: k_order)
-    k.done = nullptr;
-    if (variant_of(k.variant)->order && k.order &&
-        !(getenv("MPCQP_ORDER_KERNEL") && getenv("MPCQP_ORDER_KERNEL")[0] == '1'))
-        k.done = done;
+    if (!(variant_of(k.variant)->order && k.order && !env_is("MPCQP_ORDER_KERNEL", '1'))) k.done = nullptr;
     {  // resident solve workgroups: below this batch size the dispatch order is moot
         int ncu = 0;
         HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s.dev));
@@ -468,7 +506,6 @@ int alloc_shard(mpcqp_handle* h, Shard& s, bool with_io, bool sync = true) {
         k.slots = (long)ncu * occ;
     }
     strace().mark("variant + occupancy");
-    k.self = (const KParams*)(base + carve<KParams>(off, 1));
     // the zeroing, the identity order and the parameter block in stream order, one wait for
     // all three (callers then use the workspace from any stream or from the host)
     HIPCHK(hipMemcpyAsync((void*)k.self, &k, sizeof(KParams), hipMemcpyHostToDevice, s.stream));
@@ -711,38 +748,166 @@ int stream_leave(Shard& s, hipStream_t st) {
     return 0;
 }
 
-int check_err_flags(mpcqp_handle* h) {
-    for (auto& s : h->shards) {
-        std::vector<int> err(s.B);
-        HIPCHK(hipSetDevice(s.dev));
-        HIPCHK(hipMemcpy(err.data(), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-        for (long i = 0; i < s.B; ++i)
-            if (err[i]) return fail(MPCQP_EINVAL, "instance %ld: invalid data (l > u or NaN bounds)", s.b0 + i);
+// One call's work on one shard: body enqueues on st between stream_enter and stream_leave.
+// stream_leave runs on every return path -- work may be queued on st before a HIP call fails,
+// and the next call on another stream must still wait for it.  Inlined: no allocation, no lock.
+template <class F>
+int on_stream(Shard& s, hipStream_t st, F&& body) {
+    HIPCHK(hipSetDevice(s.dev));
+    if (int e = stream_enter(s, st)) return e;
+    if (const int rc = body()) {
+        const std::string why = g_err;  // body's error is the one reported
+        (void)stream_leave(s, st);
+        g_err = why;
+        return rc;
     }
+    return stream_leave(s, st);
+}
+
+// the first instance a setup / update kernel flagged (KParams::err), and the first one the
+// factor-only solve found non-convex
+int first_flagged(const int* err, long B, long b0) {
+    for (long i = 0; i < B; ++i)
+        if (err[i]) return fail(MPCQP_EINVAL, "instance %ld: invalid data (l > u or NaN bounds)", b0 + i);
+    return 0;
+}
+int first_nonconvex(const int* status, long B, long b0) {
+    for (long i = 0; i < B; ++i)
+        if (status[i] == MPCQP_NON_CVX_)
+            return fail(MPCQP_ENONCVX, "instance %ld: P is not convex (the KKT matrix is not quasi-definite)", b0 + i);
+    return 0;
+}
+int shard_err_flags(Shard& s) {  // (synchronous: a shard past kStageMax, or outside the staged calls)
+    std::vector<int> err(s.B);
+    HIPCHK(hipSetDevice(s.dev));
+    HIPCHK(hipMemcpy(err.data(), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost));
+    return first_flagged(err.data(), s.B, s.b0);
+}
+int check_err_flags(mpcqp_handle* h) {
+    for (auto& s : h->shards)
+        if (int e = shard_err_flags(s)) return e;
     return 0;
 }
 
-// The staging layout of one shard (Bs instances): x (Bs n), y (Bs m), obj, pri, dua, rho_est
-// (Bs each), the certificates dxc (Bs n) and dyc (Bs m) as doubles, then status, iter,
-// rho_upd, pstat (Bs each) as ints.  Shards past kStageMax bytes copy straight into the
-// caller's buffers as before (the large throughput batches, where the copies dominate).
+// ---- staging of the host-pointer API ----
+// A call's arrays as segments.  A small shard packs them into a pinned block (at Seg::off) and
+// moves them with one copy where the device side has the same layout (mirror), asynchronously
+// and with one synchronisation per call; a shard past kStageMax bytes copies each array
+// straight from / into the caller's memory as before (the large throughput batches, where the
+// copies dominate).
 constexpr size_t kStageMax = 16u << 20;
-size_t stage_bytes(const mpcqp_handle* h, long Bs) {
-    return sizeof(double) * (size_t)Bs * (2 * (size_t)h->n + 2 * (size_t)h->m + 4) + sizeof(int) * 4 * (size_t)Bs;
-}
-struct Stage {
-    double *x, *y, *obj, *pri, *dua, *rho_est, *dxc, *dyc;
-    int *status, *iter, *rho_upd, *pstat;
+enum class Dir { up, down };
+struct Seg {
+    void* host;  // the caller's array, all instances (null: not given)
+    void* dev;   // the shard's device array (down, null: zeros)
+    long per;    // elements per instance
+    int sz;      // element size
+    Dir dir;
+    size_t off;  // in the pinned block
 };
-Stage stage_of(const mpcqp_handle* h, const Shard& s) {
-    Stage g;
-    double* d = (double*)s.hstage;
-    const long Bs = s.B, n = h->n, m = h->m;
-    g.x = d; g.y = g.x + Bs * n; g.obj = g.y + Bs * m; g.pri = g.obj + Bs; g.dua = g.pri + Bs;
-    g.rho_est = g.dua + Bs; g.dxc = g.rho_est + Bs; g.dyc = g.dxc + Bs * n;
-    int* q = (int*)(g.dyc + Bs * m);
-    g.status = q; g.iter = q + Bs; g.rho_upd = q + 2 * Bs; g.pstat = q + 3 * Bs;
-    return g;
+size_t seg_bytes(const Seg& g, long Bs) { return (size_t)Bs * g.per * g.sz; }
+char* seg_host(const Seg& g, long b0) { return (char*)g.host + (size_t)b0 * g.per * g.sz; }
+
+// hb: the pinned block, null for direct copies; mirror: the device block laid out as hb, null
+// when the device arrays lie elsewhere (then one copy per segment, out of hb)
+int stage_up(Shard& s, const Seg* sg, size_t nseg, char* hb, void* mirror) {
+    size_t end = 0;
+    for (const Seg* g = sg; g != sg + nseg; ++g) {
+        if (g->dir != Dir::up || !g->host) continue;
+        const char* src = seg_host(*g, s.b0);
+        const size_t by = seg_bytes(*g, s.B);
+        if (hb) {
+            memcpy(hb + g->off, src, by);
+            src = hb + g->off;
+            end = g->off + by;
+        }
+        if (!hb || !mirror) HIPCHK(hipMemcpyAsync(g->dev, src, by, hipMemcpyHostToDevice, s.stream));
+    }
+    if (hb && mirror) HIPCHK(hipMemcpyAsync(mirror, hb, end, hipMemcpyHostToDevice, s.stream));
+    return 0;
+}
+int stage_down(Shard& s, const Seg* sg, size_t nseg, char* hb, const void* mirror, size_t bytes) {
+    if (hb) {
+        HIPCHK(hipMemcpyAsync(hb, mirror, bytes, hipMemcpyDeviceToHost, s.stream));
+        return 0;
+    }
+    for (const Seg* g = sg; g != sg + nseg; ++g)
+        if (g->dir == Dir::down && g->host)
+            HIPCHK(hipMemcpyAsync(seg_host(*g, s.b0), g->dev, seg_bytes(*g, s.B), hipMemcpyDeviceToHost, s.stream));
+    return 0;
+}
+void stage_unpack(const Shard& s, const Seg* sg, size_t nseg, const char* hb) {  // after the synchronisation
+    for (const Seg* g = sg; g != sg + nseg; ++g)
+        if (g->dir == Dir::down && g->host) memcpy(seg_host(*g, s.b0), hb + g->off, seg_bytes(*g, s.B));
+}
+
+// Shard::hin, the persistent pinned input block, serves three calls; whichever comes first
+// allocates it for all of them:
+//   mpcqp_setup_batch   the five inputs, laid out as in the workspace (input_span)
+//   check_setup         err and status in one copy (flag_span)
+//   mpcqp_update_batch  q, l, u back to back, then the error flags read back (update_bytes)
+size_t input_span(const mpcqp_handle* h, const Shard& s) {
+    return (size_t)((const char*)(s.in_u + s.B * h->m) - (const char*)s.in_Px);
+}
+size_t flag_span(const Shard& s) { return (size_t)((const char*)(s.kp.status + s.B) - (const char*)s.kp.err); }
+size_t update_bytes(const mpcqp_handle* h, long Bs) {
+    return sizeof(double) * (size_t)Bs * (h->n + 2 * h->m) + sizeof(int) * (size_t)Bs;
+}
+int need_hin(const mpcqp_handle* h, Shard& s) {
+    if (s.hin) return 0;
+    size_t by = std::max(update_bytes(h, s.B), flag_span(s));
+    if (input_span(h, s) <= kStageMax) by = std::max(by, input_span(h, s));
+    HIPCHK(pool_malloc(s.dev, by, (void**)&s.hin, true));
+    s.hin_bytes = by;
+    return 0;
+}
+
+// Everything a solve returns, one listing: the caller's array (ResultPtrs, null: not asked
+// for), the device array, elements per instance, element size.  The segments lie back to back
+// in this order in the shard's persistent pinned block hstage and its device twin dstage
+// (launch_gather), filled by mpcqp_solve_batch with one synchronisation; the info / certificate
+// / polish getters then read hstage (mpcqp_handle::staged).
+struct ResultPtrs {
+    void *x = nullptr, *y = nullptr, *obj = nullptr, *pri = nullptr, *dua = nullptr, *rho_est = nullptr,
+         *dxc = nullptr, *dyc = nullptr, *status = nullptr, *iter = nullptr, *rho_upd = nullptr, *pstat = nullptr;
+};
+struct Results {
+    Seg seg[kGatherMax];
+    size_t nseg, bytes;
+};
+Results result_segs(const mpcqp_handle* h, const Shard& s, const ResultPtrs& u) {
+    const long n = h->n, m = h->m;
+    const KParams& k = s.kp;
+    const Dir dn = Dir::down;
+    Results r{{{u.x, s.out_x, n, 8, dn, 0}, {u.y, s.out_y, m, 8, dn, 0},
+               {u.obj, k.obj, 1, 8, dn, 0}, {u.pri, k.pri, 1, 8, dn, 0}, {u.dua, k.dua, 1, 8, dn, 0},
+               {u.rho_est, k.rho_est, 1, 8, dn, 0}, {u.dxc, k.dxc, n, 8, dn, 0}, {u.dyc, k.dyc, m, 8, dn, 0},
+               {u.status, k.status, 1, 4, dn, 0}, {u.iter, k.iter, 1, 4, dn, 0}, {u.rho_upd, k.rho_upd, 1, 4, dn, 0},
+               {u.pstat, h->set.polish ? k.pstat : nullptr, 1, 4, dn, 0}},  // (no polish: zeros)
+              12, 0};
+    for (size_t i = 0; i < r.nseg; ++i) {
+        r.seg[i].off = r.bytes;
+        r.bytes += seg_bytes(r.seg[i], s.B);
+    }
+    return r;
+}
+// the getters: out of hstage after a staged solve, else one synchronous copy per array
+int read_results(mpcqp_handle* h, const ResultPtrs& u) {
+    for (auto& s : h->shards) {
+        if (!h->staged) HIPCHK(hipSetDevice(s.dev));
+        const Results r = result_segs(h, s, u);
+        if (h->staged) {
+            stage_unpack(s, r.seg, r.nseg, s.hstage);
+            continue;
+        }
+        for (size_t i = 0; i < r.nseg; ++i) {
+            const Seg& g = r.seg[i];
+            if (!g.host) continue;
+            if (g.dev) HIPCHK(hipMemcpy(seg_host(g, s.b0), g.dev, seg_bytes(g, s.B), hipMemcpyDeviceToHost));
+            else memset(seg_host(g, s.b0), 0, seg_bytes(g, s.B));
+        }
+    }
+    return 0;
 }
 
 // osqp_setup's convexity test (OSQP 0.6 init_linsys_solver: the quasi-definite KKT matrix
@@ -753,72 +918,57 @@ Stage stage_of(const mpcqp_handle* h, const Shard& s) {
 // The setup's invalid-data flags (check_err_flags) and osqp_setup's convexity test
 // (check_convex) behind the setup kernel with one synchronisation: the factor-only launch is
 // enqueued right after it, and both the flags and the statuses come back through the shard's
-// pinned staging (update()'s, allocated here) in stream order.  Invalid data is reported
-// first, as the two checks in turn would.
+// pinned input block in stream order.  Invalid data is reported first, as the two checks in
+// turn would.
 int check_setup(mpcqp_handle* h) {
-    const long n = h->n, m = h->m;
-    std::vector<int*> got(h->shards.size(), nullptr);
-    std::vector<std::vector<int>> host(h->shards.size());
-    std::vector<long> stoff(h->shards.size(), 0);  // status's offset from err in got[]
-    for (size_t si = 0; si < h->shards.size(); ++si) {
+    const size_t ns = h->shards.size();
+    std::vector<const int*> err(ns, nullptr), stat(ns, nullptr);
+    std::vector<std::vector<int>> host(ns);
+    for (size_t si = 0; si < ns; ++si) {
         Shard& s = h->shards[si];
-        HIPCHK(hipSetDevice(s.dev));
-        if (int e = stream_enter(s, s.stream)) return e;
-        HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 1, s.stream));
-        // err and status in one copy: the workspace carves err right before status
-        const size_t span = (size_t)((const char*)(s.kp.status + s.B) - (const char*)s.kp.err);
-        const size_t ib = std::max(span, sizeof(double) * (size_t)s.B * (n + 2 * m) + sizeof(int) * (size_t)s.B);
-        if (ib <= kStageMax) {
-            if (!s.hin) {
-                HIPCHK(pool_malloc(s.dev, ib, (void**)&s.hin, true));
-                s.hin_bytes = ib;
-            }
-            got[si] = (int*)s.hin;  // err (B), then status (B) at stoff[si]
-            HIPCHK(hipMemcpyAsync(got[si], s.kp.err, span, hipMemcpyDeviceToHost, s.stream));
-            stoff[si] = s.kp.status - s.kp.err;
-        }
-        if (int e = stream_leave(s, s.stream)) return e;
+        const int e = on_stream(s, s.stream, [&]() -> int {
+            HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 1, s.stream));
+            const size_t span = flag_span(s);
+            if (std::max(span, update_bytes(h, s.B)) > kStageMax) return 0;
+            if (int e = need_hin(h, s)) return e;
+            HIPCHK(hipMemcpyAsync(s.hin, s.kp.err, span, hipMemcpyDeviceToHost, s.stream));
+            err[si] = (const int*)s.hin;
+            stat[si] = err[si] + (s.kp.status - s.kp.err);
+            return 0;
+        });
+        if (e) return e;
     }
     if (int e = sync_all(h)) return e;
-    for (size_t si = 0; si < h->shards.size(); ++si) {
+    for (size_t si = 0; si < ns; ++si) {
         Shard& s = h->shards[si];
-        if (!got[si]) {
-            host[si].resize(2 * s.B);
-            HIPCHK(hipSetDevice(s.dev));
-            HIPCHK(hipMemcpy(host[si].data(), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(host[si].data() + s.B, s.kp.status, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-            got[si] = host[si].data();
-            stoff[si] = s.B;
-        }
+        if (err[si]) continue;
+        host[si].resize(2 * s.B);
+        HIPCHK(hipSetDevice(s.dev));
+        HIPCHK(hipMemcpy(host[si].data(), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(host[si].data() + s.B, s.kp.status, sizeof(int) * s.B, hipMemcpyDeviceToHost));
+        err[si] = host[si].data();
+        stat[si] = err[si] + s.B;
     }
-    for (size_t si = 0; si < h->shards.size(); ++si)
-        for (long i = 0; i < h->shards[si].B; ++i)
-            if (got[si][i])
-                return fail(MPCQP_EINVAL, "instance %ld: invalid data (l > u or NaN bounds)", h->shards[si].b0 + i);
-    for (size_t si = 0; si < h->shards.size(); ++si)
-        for (long i = 0; i < h->shards[si].B; ++i)
-            if (got[si][stoff[si] + i] == MPCQP_NON_CVX_)
-                return fail(MPCQP_ENONCVX, "instance %ld: P is not convex (the KKT matrix is not quasi-definite)",
-                            h->shards[si].b0 + i);
+    for (size_t si = 0; si < ns; ++si)
+        if (int e = first_flagged(err[si], h->shards[si].B, h->shards[si].b0)) return e;
+    for (size_t si = 0; si < ns; ++si)
+        if (int e = first_nonconvex(stat[si], h->shards[si].B, h->shards[si].b0)) return e;
     return 0;
 }
 
 int check_convex(mpcqp_handle* h) {
-    for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (int e = stream_enter(s, s.stream)) return e;
-        HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 1, s.stream));
-        if (int e = stream_leave(s, s.stream)) return e;
-    }
+    for (auto& s : h->shards)
+        if (int e = on_stream(s, s.stream, [&]() -> int {
+                HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 1, s.stream));
+                return 0;
+            }))
+            return e;
     if (int e = sync_all(h)) return e;
     for (auto& s : h->shards) {
         std::vector<int> st(s.B);
         HIPCHK(hipSetDevice(s.dev));
         HIPCHK(hipMemcpy(st.data(), s.kp.status, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-        for (long i = 0; i < s.B; ++i)
-            if (st[i] == MPCQP_NON_CVX_)
-                return fail(MPCQP_ENONCVX, "instance %ld: P is not convex (the KKT matrix is not quasi-definite)",
-                            s.b0 + i);
+        if (int e = first_nonconvex(st.data(), s.B, s.b0)) return e;
     }
     return 0;
 }
@@ -856,75 +1006,46 @@ int replan_plain(mpcqp_handle* h) {
     std::shared_ptr<const Plan> oldp = h->plan;
     const Plan& old = *oldp;
     h->plan = npl;
-    const long n = h->n, m = h->m, npo = old.npad, npn = h->plan->npad;
+    const long n = h->n;
+    // one region across, by the listing's rule for it (workspace_regions)
+    auto move = [&](const Region& a, const Region& b, long B) -> int {
+        double *src = (double*)region_ptr(a), *dst = (double*)region_ptr(b);
+        if (a.carry == Carry::drop || !a.count || !src || !dst) return 0;
+        if (a.carry == Carry::copy) {
+            HIPCHK(hipMemcpy(dst, src, a.esz * a.count, hipMemcpyDeviceToDevice));
+            return 0;
+        }
+        const long wo = (long)a.count / B, wn = (long)b.count / B;  // an instance's row, old and new
+        std::vector<double> ho(a.count), hn(b.count, b.pad);
+        if (hipMemcpy(ho.data(), src, sizeof(double) * a.count, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(MPCQP_EDEVICE, "re-plan: copy-out failed");
+        const bool var = a.carry == Carry::by_var;  // else the padded-CSC order of each plan
+        const std::vector<int>&from = var ? old.var_pad : old.csc_pos, &to = var ? npl->var_pad : npl->csc_pos;
+        const long cols = var ? n : wo;  // (k.Ax[e] = Ax[acsc_v[e]], kernels.hip::k_setup: user value v at csc_pos[v])
+        for (long i = 0; i < B; ++i)
+            for (long j = 0; j < cols; ++j) hn[i * wn + to[j]] = ho[i * wo + from[j]];
+        if (hipMemcpy(dst, hn.data(), sizeof(double) * b.count, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MPCQP_EDEVICE, "re-plan: copy-in failed");
+        return 0;
+    };
     std::vector<Shard> fresh;
+    fresh.reserve(h->shards.size());
     int rc = 0;
     for (auto& os : h->shards) {
         Shard s;
         s.dev = os.dev; s.b0 = os.b0; s.B = os.B;
         fresh.push_back(s);
-        if ((rc = alloc_shard(h, fresh.back(), os.in_Px != nullptr))) break;
         Shard& ns = fresh.back();
-        KParams &a = os.kp, &b = ns.kp;
-        b.mat_shared = a.mat_shared;
-        b.polish = a.polish; b.refine_iter = a.refine_iter; b.delta = a.delta;
-        b.alpha = a.alpha; b.eps_abs = a.eps_abs; b.eps_rel = a.eps_rel; b.eps_pinf = a.eps_pinf;
-        b.eps_dinf = a.eps_dinf; b.rho0 = a.rho0; b.max_iter = a.max_iter; b.check_term = a.check_term;
-        b.warm_start = a.warm_start; b.scaled_term = a.scaled_term;
-        const long B = s.B;
-        auto cp = [&](void* d, const void* src, size_t bytes) -> int {
-            if (bytes) HIPCHK(hipMemcpy(d, src, bytes, hipMemcpyDeviceToDevice));
-            return 0;
-        };
-        const size_t D8 = sizeof(double), I4 = sizeof(int);
-        if ((rc = cp(b.Px, a.Px, D8 * B * old.nnzP)) ||
-            (rc = cp(b.l, a.l, D8 * B * m)) || (rc = cp(b.u, a.u, D8 * B * m)) || (rc = cp(b.E, a.E, D8 * B * m)) ||
-            (rc = cp(b.z, a.z, D8 * B * m)) || (rc = cp(b.y, a.y, D8 * B * m)) || (rc = cp(b.scal, a.scal, D8 * B * 4)) ||
-            (rc = cp(b.dyc, a.dyc, D8 * B * m)) || (rc = cp(b.dxc, a.dxc, D8 * B * n)) ||
-            (rc = cp(b.obj, a.obj, D8 * B)) || (rc = cp(b.pri, a.pri, D8 * B)) || (rc = cp(b.dua, a.dua, D8 * B)) ||
-            (rc = cp(b.rho_est, a.rho_est, D8 * B)) || (rc = cp(b.ct, a.ct, (size_t)B * m)) ||
-            (rc = cp(b.status, a.status, I4 * B)) || (rc = cp(b.iter, a.iter, I4 * B)) ||
-            (rc = cp(b.rho_upd, a.rho_upd, I4 * B)) || (rc = cp(b.pstat, a.pstat, I4 * B)) ||
-            (rc = cp(b.err, a.err, I4 * B)))
-            break;
-        if (os.in_Px &&
-            ((rc = cp(ns.in_Px, os.in_Px, D8 * B * old.nnzP)) || (rc = cp(ns.in_Ax, os.in_Ax, D8 * B * old.nnzA)) ||
-             (rc = cp(ns.in_q, os.in_q, D8 * B * n)) || (rc = cp(ns.in_l, os.in_l, D8 * B * m)) ||
-             (rc = cp(ns.in_u, os.in_u, D8 * B * m)) || (rc = cp(ns.out_x, os.out_x, D8 * B * n)) ||
-             (rc = cp(ns.out_y, os.out_y, D8 * B * m))))
-            break;
-        // q, D, x: padded order -> the new padded order (padding: q = 0, D = 1, x = 0, as setup leaves it)
-        double* cols_old[3] = {a.q, a.D, a.x};
-        double* cols_new[3] = {b.q, b.D, b.x};
-        std::vector<double> ho((size_t)B * npo), hn((size_t)B * npn);
-        for (int t = 0; t < 3 && !rc; ++t) {
-            if (hipMemcpy(ho.data(), cols_old[t], D8 * B * npo, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(MPCQP_EDEVICE, "re-plan: copy-out failed");
-                break;
-            }
-            std::fill(hn.begin(), hn.end(), t == 1 ? 1.0 : 0.0);
-            for (long i = 0; i < B; ++i)
-                for (long j = 0; j < n; ++j) hn[i * npn + h->plan->var_pad[j]] = ho[i * npo + old.var_pad[j]];
-            if (hipMemcpy(cols_new[t], hn.data(), D8 * B * npn, hipMemcpyHostToDevice) != hipSuccess)
-                rc = fail(MPCQP_EDEVICE, "re-plan: copy-in failed");
-        }
-        // the scaled A values: the padded-CSC order of each plan (k.Ax[e] = Ax[acsc_v[e]],
-        // kernels.hip::k_setup), user value v at csc_pos[v]
-        if (!rc && old.nnzA > 0) {
-            const long nz = old.nnzA;
-            std::vector<double> ao((size_t)B * nz), an((size_t)B * nz);
-            if (hipMemcpy(ao.data(), a.Ax, D8 * B * nz, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(MPCQP_EDEVICE, "re-plan: copy-out failed");
-            } else {
-                for (long i = 0; i < B; ++i)
-                    for (long v = 0; v < nz; ++v) an[i * nz + h->plan->csc_pos[v]] = ao[i * nz + old.csc_pos[v]];
-                if (hipMemcpy(b.Ax, an.data(), D8 * B * nz, hipMemcpyHostToDevice) != hipSuccess)
-                    rc = fail(MPCQP_EDEVICE, "re-plan: copy-in failed");
-            }
-        }
+        const bool with_io = os.in_Px != nullptr;
+        if ((rc = alloc_shard(h, ns, with_io))) break;
+        ns.kp.mat_shared = os.kp.mat_shared;
+        carry_settings(ns.kp, os.kp);
+        const std::vector<Region> ra = workspace_regions(old, os.B, with_io, os),
+                                  rb = workspace_regions(*npl, ns.B, with_io, ns);
+        for (size_t i = 0; i < ra.size() && !rc; ++i) rc = move(ra[i], rb[i], os.B);
         if (rc) break;
         (void)hipSetDevice(ns.dev);
-        if (hipMemcpy((void*)b.self, &b, sizeof(KParams), hipMemcpyHostToDevice) != hipSuccess) {
+        if (hipMemcpy((void*)ns.kp.self, &ns.kp, sizeof(KParams), hipMemcpyHostToDevice) != hipSuccess) {
             rc = fail(MPCQP_EDEVICE, "re-plan: parameter copy failed");
             break;
         }
@@ -937,6 +1058,52 @@ int replan_plain(mpcqp_handle* h) {
     for (auto& s : h->shards) free_shard(s);
     h->shards.swap(fresh);
     h->staged = false;
+    return 0;
+}
+
+// ---- the *_device entry points ----
+int single_device(const mpcqp_handle* h) {
+    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    return 0;
+}
+// body(shard, stream) on the caller's stream (null: the handle's own), after the checks every
+// device call makes; the entry points with checks of their own go to on_stream themselves
+template <class F>
+int on_caller_stream(mpcqp_handle* h, void* stream, F&& body) {
+    Shard& s = h->shards[0];
+    const hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+    return on_stream(s, st, [&]() -> int { return body(s, st); });
+}
+// what: the entry point reads the workspace's state (need_state), null: it does not
+template <class F>
+int device_call(mpcqp_handle* h, void* stream, const char* what, F&& body) {
+    if (what)
+        if (int e = need_state(h, what)) return e;
+    if (int e = single_device(h)) return e;
+    h->staged = false;  // (device work: the staged results of the last solve are stale)
+    return on_caller_stream(h, stream, body);
+}
+
+// A launch between a fresh hipEvent pair, recorded in v, while `on` (collect: solve launches,
+// collect_setup: setup launches); last: the pair mpcqp_last_kernel_ms reads.  No event between
+// the kernels unless timing is on: every recorded event is a packet the command processor
+// completes between two launches (≈12 us per step measured on the cfg-2 bench, 2.33 -> 2.40 M
+// solves/s without them).
+template <class F>
+int timed_launch(bool on, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t st,
+                 std::pair<hipEvent_t, hipEvent_t>* last, F&& launch) {
+    if (on) {
+        hipEvent_t a, b;
+        HIPCHK(hipEventCreate(&a));
+        HIPCHK(hipEventCreate(&b));
+        HIPCHK(hipEventRecord(a, st));
+        v.push_back({a, b});
+    }
+    if (int e = launch()) return e;
+    if (on) {
+        HIPCHK(hipEventRecord(v.back().second, st));
+        if (last) *last = v.back();
+    }
     return 0;
 }
 
@@ -997,38 +1164,24 @@ int mpcqp_setup_batch(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi
     if (int e = make_handle(n, m, Pp, Pi, Ap, Ai, B, settings, devs, true, &h)) return e;
     if (int e = check_bounds_host(h, l, u, B)) { mpcqp_free(h); return e; }
     const Plan& pl = *h->plan;
+    // the five inputs lie one after another in the workspace (workspace_regions): a small shard
+    // stages them in pinned memory with the same layout and goes up in one copy (five pageable
+    // copies cost ~4 us each on a one-QP setup)
     auto upload = [&](Shard& s) -> int {
-        const long b0 = s.b0, Bs = s.B;
-        HIPCHK(hipSetDevice(s.dev));
-        // the five inputs lie one after another in the workspace (alloc_shard's carve): a small
-        // shard stages them in pinned memory with the same layout and goes up in one copy (five
-        // pageable copies cost ~4 us each on a one-QP setup)
-        const size_t span = (size_t)((const char*)(s.in_u + Bs * m) - (const char*)s.in_Px);
-        const size_t upd = sizeof(double) * (size_t)Bs * (n + 2 * m) + sizeof(int) * (size_t)Bs;  // (update's use)
-        if (span <= kStageMax) {
-            if (!s.hin) {
-                HIPCHK(pool_malloc(s.dev, std::max(span, upd), (void**)&s.hin, true));
-                s.hin_bytes = std::max(span, upd);
-            }
-            char* const hb = (char*)s.hin;
-            auto put = [&](const double* dst, const double* src, size_t cnt) {
-                memcpy(hb + ((const char*)dst - (const char*)s.in_Px), src, sizeof(double) * cnt);
-            };
-            put(s.in_Px, Px + b0 * pl.nnzP, (size_t)Bs * pl.nnzP);
-            put(s.in_Ax, Ax + b0 * pl.nnzA, (size_t)Bs * pl.nnzA);
-            put(s.in_q, q + b0 * n, (size_t)Bs * n);
-            put(s.in_l, l + b0 * m, (size_t)Bs * m);
-            put(s.in_u, u + b0 * m, (size_t)Bs * m);
-            HIPCHK(hipMemcpyAsync(s.in_Px, hb, span, hipMemcpyHostToDevice, s.stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(s.in_Px, Px + b0 * pl.nnzP, sizeof(double) * Bs * pl.nnzP, hipMemcpyHostToDevice, s.stream));
-            HIPCHK(hipMemcpyAsync(s.in_Ax, Ax + b0 * pl.nnzA, sizeof(double) * Bs * pl.nnzA, hipMemcpyHostToDevice, s.stream));
-            HIPCHK(hipMemcpyAsync(s.in_q, q + b0 * n, sizeof(double) * Bs * n, hipMemcpyHostToDevice, s.stream));
-            HIPCHK(hipMemcpyAsync(s.in_l, l + b0 * m, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-            HIPCHK(hipMemcpyAsync(s.in_u, u + b0 * m, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-        }
-        HIPCHK(launch_setup(s.kp, Bs, s.in_Px, s.in_Ax, s.in_q, s.in_l, s.in_u, s.stream));
-        return stream_leave(s, s.stream);
+        return on_stream(s, s.stream, [&]() -> int {
+            auto at = [&](const double* d) { return (size_t)((const char*)d - (const char*)s.in_Px); };
+            const Seg sg[] = {{(void*)Px, s.in_Px, pl.nnzP, 8, Dir::up, at(s.in_Px)},
+                              {(void*)Ax, s.in_Ax, pl.nnzA, 8, Dir::up, at(s.in_Ax)},
+                              {(void*)q, s.in_q, n, 8, Dir::up, at(s.in_q)},
+                              {(void*)l, s.in_l, m, 8, Dir::up, at(s.in_l)},
+                              {(void*)u, s.in_u, m, 8, Dir::up, at(s.in_u)}};
+            const bool staged = input_span(h, s) <= kStageMax;
+            if (staged)
+                if (int e = need_hin(h, s)) return e;
+            if (int e = stage_up(s, sg, 5, staged ? s.hin : nullptr, s.in_Px)) return e;
+            HIPCHK(launch_setup(s.kp, s.B, s.in_Px, s.in_Ax, s.in_q, s.in_l, s.in_u, s.stream));
+            return 0;
+        });
     };
     strace().mark("handle");
     for (auto& s : h->shards)
@@ -1048,57 +1201,32 @@ int mpcqp_update_batch(mpcqp_handle* h, const double* q, const double* l, const 
     if (l && u)
         if (int e = check_bounds_host(h, l, u, h->B)) return e;
     const long n = h->n, m = h->m;
-    // small shards go through pinned staging: the copies and the error flags' read-back are
-    // asynchronous and the call synchronises once (osqp's per-step update of one problem)
-    auto in_bytes = [&](long Bs) { return sizeof(double) * (size_t)Bs * (n + 2 * m) + sizeof(int) * (size_t)Bs; };
+    // small shards go through pinned staging (Shard::hin): the copies and the error flags'
+    // read-back are asynchronous and the call synchronises once (osqp's per-step update of one
+    // problem); the device arrays are not one run, so one copy per array either way.  In hin: q,
+    // l, u back to back, then the flags (update_bytes)
+    auto staged = [&](const Shard& s) { return update_bytes(h, s.B) <= kStageMax; };
+    auto at = [&](const Shard& s, long doubles) { return sizeof(double) * (size_t)s.B * doubles; };
+    auto flags = [&](const Shard& s) { return (int*)(s.hin + at(s, n + 2 * m)); };
     for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (int e = stream_enter(s, s.stream)) return e;
-        const long Bs = s.B;
-        if (in_bytes(Bs) <= kStageMax) {
-            if (!s.hin) {
-                HIPCHK(pool_malloc(s.dev, in_bytes(Bs), (void**)&s.hin, true));
-                s.hin_bytes = in_bytes(Bs);
-            }
-            double *hq = (double*)s.hin, *hl = hq + Bs * n, *hu = hl + Bs * m;
-            int* herr = (int*)(hu + Bs * m);
-            if (q) {
-                std::copy(q + s.b0 * n, q + (s.b0 + Bs) * n, hq);
-                HIPCHK(hipMemcpyAsync(s.in_q, hq, sizeof(double) * Bs * n, hipMemcpyHostToDevice, s.stream));
-            }
-            if (l) {
-                std::copy(l + s.b0 * m, l + (s.b0 + Bs) * m, hl);
-                HIPCHK(hipMemcpyAsync(s.in_l, hl, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-            }
-            if (u) {
-                std::copy(u + s.b0 * m, u + (s.b0 + Bs) * m, hu);
-                HIPCHK(hipMemcpyAsync(s.in_u, hu, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-            }
-            HIPCHK(launch_update(s.kp, Bs, q ? s.in_q : nullptr, l ? s.in_l : nullptr, u ? s.in_u : nullptr, s.stream));
-            if (l || u) HIPCHK(hipMemcpyAsync(herr, s.kp.err, sizeof(int) * Bs, hipMemcpyDeviceToHost, s.stream));
-        } else {
-            if (q) HIPCHK(hipMemcpyAsync(s.in_q, q + s.b0 * n, sizeof(double) * Bs * n, hipMemcpyHostToDevice, s.stream));
-            if (l) HIPCHK(hipMemcpyAsync(s.in_l, l + s.b0 * m, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-            if (u) HIPCHK(hipMemcpyAsync(s.in_u, u + s.b0 * m, sizeof(double) * Bs * m, hipMemcpyHostToDevice, s.stream));
-            HIPCHK(launch_update(s.kp, Bs, q ? s.in_q : nullptr, l ? s.in_l : nullptr, u ? s.in_u : nullptr, s.stream));
-        }
-        if (int e = stream_leave(s, s.stream)) return e;
+        const int rc = on_stream(s, s.stream, [&]() -> int {
+            const Seg sg[] = {{(void*)q, s.in_q, n, 8, Dir::up, at(s, 0)},
+                              {(void*)l, s.in_l, m, 8, Dir::up, at(s, n)},
+                              {(void*)u, s.in_u, m, 8, Dir::up, at(s, n + m)}};
+            if (staged(s))
+                if (int e = need_hin(h, s)) return e;
+            if (int e = stage_up(s, sg, 3, staged(s) ? s.hin : nullptr, nullptr)) return e;
+            HIPCHK(launch_update(s.kp, s.B, q ? s.in_q : nullptr, l ? s.in_l : nullptr, u ? s.in_u : nullptr, s.stream));
+            if (staged(s) && (l || u))
+                HIPCHK(hipMemcpyAsync(flags(s), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost, s.stream));
+            return 0;
+        });
+        if (rc) return rc;
     }
     if (int e = sync_all(h)) return e;
     if (!(l || u)) return 0;
-    for (auto& s : h->shards) {
-        if (in_bytes(s.B) > kStageMax) {
-            std::vector<int> err(s.B);
-            HIPCHK(hipSetDevice(s.dev));
-            HIPCHK(hipMemcpy(err.data(), s.kp.err, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-            for (long i = 0; i < s.B; ++i)
-                if (err[i]) return fail(MPCQP_EINVAL, "instance %ld: invalid data (l > u or NaN bounds)", s.b0 + i);
-        } else {
-            const int* herr = (const int*)((const double*)s.hin + s.B * (n + 2 * m));
-            for (long i = 0; i < s.B; ++i)
-                if (herr[i]) return fail(MPCQP_EINVAL, "instance %ld: invalid data (l > u or NaN bounds)", s.b0 + i);
-        }
-    }
+    for (auto& s : h->shards)
+        if (int e = staged(s) ? first_flagged(flags(s), s.B, s.b0) : shard_err_flags(s)) return e;
     return 0;
 }
 
@@ -1160,20 +1288,17 @@ int mpcqp_update_matrices_batch(mpcqp_handle* h, const double* Px, const int32_t
             for (int k = 0; k < nA; ++k) hv[Bs * nP + b * nA + k] = Ax[(s.b0 + b) * kA + acol[k]];
         }
         const size_t vbytes = sizeof(double) * hv.size(), ibytes = sizeof(int) * (size_t)(nP + nA);
-        auto step = [&]() -> int {
-            HIPCHK(hipSetDevice(s.dev));
+        err = on_stream(s, s.stream, [&]() -> int {
             HIPCHK(hipMalloc(&tmp[si], vbytes + ibytes + 16));
             double* dv = (double*)tmp[si];
             int* di = (int*)((char*)tmp[si] + vbytes);
-            if (int e = stream_enter(s, s.stream)) return e;
             if (vbytes) HIPCHK(hipMemcpyAsync(dv, hv.data(), vbytes, hipMemcpyHostToDevice, s.stream));
             if (nP) HIPCHK(hipMemcpyAsync(di, pdst.data(), sizeof(int) * nP, hipMemcpyHostToDevice, s.stream));
             if (nA) HIPCHK(hipMemcpyAsync(di + nP, adst.data(), sizeof(int) * nA, hipMemcpyHostToDevice, s.stream));
             HIPCHK(launch_update_mat(s.kp, Bs, s.in_Px, s.in_Ax, s.in_q, s.in_l, s.in_u, Px ? dv : nullptr, di, nP,
                                      Ax ? dv + Bs * nP : nullptr, di + nP, nA, s.stream));
-            return stream_leave(s, s.stream);
-        };
-        err = step();
+            return 0;
+        });
     }
     if (!err) err = sync_all(h);
     release();
@@ -1196,24 +1321,19 @@ int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s, int32_t set_
     const double rho = std::min(std::max(s->rho, 1e-6), 1e6);  // osqp_update_rho: RHO_MIN / RHO_MAX
     for (auto& sh : h->shards) {
         KParams& k = sh.kp;
-        k.alpha = s->alpha; k.eps_abs = s->eps_abs; k.eps_rel = s->eps_rel;
-        k.eps_pinf = s->eps_prim_inf; k.eps_dinf = s->eps_dual_inf; k.rho0 = s->rho;
-        k.max_iter = s->max_iter; k.check_term = s->check_termination; k.warm_start = s->warm_start;
-        k.scaled_term = s->scaled_termination; k.polish = s->polish; k.refine_iter = s->polish_refine_iter;
-        k.delta = s->delta;
-        // (rho_interval keeps the value setup resolved: OSQP resolves the automatic interval
-        // in osqp_setup, so check_termination set later does not move it)
-        HIPCHK(hipSetDevice(sh.dev));
-        if (int e = stream_enter(sh, sh.stream)) return e;
-        HIPCHK(hipMemcpyAsync((void*)k.self, &k, sizeof(KParams), hipMemcpyHostToDevice, sh.stream));
-        if (rho_changed) {  // every instance's current rho (scal[2]); the solve refactors with it
-            HIPCHK(hipMemsetAsync(k.ffresh, 0, sizeof(int) * sh.B, sh.stream));
-            std::vector<double> r(sh.B, rho);
-            HIPCHK(hipMemcpy2DAsync(k.scal + 2, 4 * sizeof(double), r.data(), sizeof(double), sizeof(double), sh.B,
-                                    hipMemcpyHostToDevice, sh.stream));
-            HIPCHK(hipStreamSynchronize(sh.stream));  // r is a host temporary
-        }
-        if (int e = stream_leave(sh, sh.stream)) return e;
+        apply_settings(k, *s);
+        const int rc = on_stream(sh, sh.stream, [&]() -> int {
+            HIPCHK(hipMemcpyAsync((void*)k.self, &k, sizeof(KParams), hipMemcpyHostToDevice, sh.stream));
+            if (rho_changed) {  // every instance's current rho (scal[2]); the solve refactors with it
+                HIPCHK(hipMemsetAsync(k.ffresh, 0, sizeof(int) * sh.B, sh.stream));
+                std::vector<double> r(sh.B, rho);
+                HIPCHK(hipMemcpy2DAsync(k.scal + 2, 4 * sizeof(double), r.data(), sizeof(double), sizeof(double), sh.B,
+                                        hipMemcpyHostToDevice, sh.stream));
+                HIPCHK(hipStreamSynchronize(sh.stream));  // r is a host temporary
+            }
+            return 0;
+        });
+        if (rc) return rc;
     }
     const int interval = h->set.adaptive_rho_interval;
     h->set = *s;
@@ -1227,12 +1347,13 @@ int mpcqp_warm_start_batch(mpcqp_handle* h, const double* x, const double* y) {
     h->staged = false;  // (device work: the staged results of the last solve are stale)
     const long n = h->n, m = h->m;
     for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (int e = stream_enter(s, s.stream)) return e;
-        if (x) HIPCHK(hipMemcpyAsync(s.out_x, x + s.b0 * n, sizeof(double) * s.B * n, hipMemcpyHostToDevice, s.stream));
-        if (y) HIPCHK(hipMemcpyAsync(s.out_y, y + s.b0 * m, sizeof(double) * s.B * m, hipMemcpyHostToDevice, s.stream));
-        HIPCHK(launch_warm(s.kp, s.B, x ? s.out_x : nullptr, y ? s.out_y : nullptr, s.stream));
-        if (int e = stream_leave(s, s.stream)) return e;
+        const int rc = on_stream(s, s.stream, [&]() -> int {
+            if (x) HIPCHK(hipMemcpyAsync(s.out_x, x + s.b0 * n, sizeof(double) * s.B * n, hipMemcpyHostToDevice, s.stream));
+            if (y) HIPCHK(hipMemcpyAsync(s.out_y, y + s.b0 * m, sizeof(double) * s.B * m, hipMemcpyHostToDevice, s.stream));
+            HIPCHK(launch_warm(s.kp, s.B, x ? s.out_x : nullptr, y ? s.out_y : nullptr, s.stream));
+            return 0;
+        });
+        if (rc) return rc;
         s.kp.warm_start = 1;
     }
     h->set.warm_start = 1;
@@ -1242,7 +1363,6 @@ int mpcqp_warm_start_batch(mpcqp_handle* h, const double* x, const double* y) {
 int mpcqp_solve_batch(mpcqp_handle* h, double* x, double* y, int32_t* status, int32_t* iters) {
     if (int e = need_state(h, "mpcqp_solve_batch")) return e;
     if (!h) return fail(MPCQP_EINVAL, "NULL handle");
-    const long n = h->n, m = h->m;
     // every shard's kernels are enqueued before any result is copied back: a copy into the
     // caller's (pageable) memory blocks the host until its shard is done, so copying inside
     // the launch loop would start shard d+1 only after shard d had finished
@@ -1250,72 +1370,51 @@ int mpcqp_solve_batch(mpcqp_handle* h, double* x, double* y, int32_t* status, in
     // packets cost a one-QP solve() ~5.5 us of its ~150 (cfg 2, same-box A/B, profiles/r6/lat_events_ab.txt)
     const bool evs = h->collect;
     for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (int e = stream_enter(s, s.stream)) return e;
-        if (evs) HIPCHK(hipEventRecord(s.ev0, s.stream));
-        HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 0, s.stream));
-        if (evs) HIPCHK(hipEventRecord(s.ev1, s.stream));
-        HIPCHK(launch_order(s.kp, s.B, s.stream));
-        if (int e = stream_leave(s, s.stream)) return e;
+        const int rc = on_stream(s, s.stream, [&]() -> int {
+            if (evs) HIPCHK(hipEventRecord(s.ev0, s.stream));
+            HIPCHK(launch_solve(s.kp, s.B, s.out_x, s.out_y, 0, s.stream));
+            if (evs) HIPCHK(hipEventRecord(s.ev1, s.stream));
+            HIPCHK(launch_order(s.kp, s.B, s.stream));
+            return 0;
+        });
+        if (rc) return rc;
     }
     // the host-side gather: each shard's slice of the caller's buffers, in shard order; a
     // small shard stages everything its solve returns in pinned memory (one synchronisation
-    // for the solve and the getters that follow it, instead of one per array)
+    // for the solve and the getters that follow it, instead of one per array): one gather
+    // kernel into the device twin of the staging layout, one copy down
+    ResultPtrs u;
+    u.x = x; u.y = y; u.status = status; u.iter = iters;
     bool all_staged = true;
     for (auto& s : h->shards) {
         HIPCHK(hipSetDevice(s.dev));
-        const size_t sb = stage_bytes(h, s.B);
-        if (sb <= kStageMax) {
+        const Results r = result_segs(h, s, u);
+        const bool staged = r.bytes <= kStageMax;
+        if (staged) {
             if (!s.hstage) {
-                HIPCHK(pool_malloc(s.dev, sb, (void**)&s.hstage, true));
-                s.hstage_bytes = sb;
+                HIPCHK(pool_malloc(s.dev, r.bytes, (void**)&s.hstage, true));
+                s.hstage_bytes = r.bytes;
             }
             if (!s.dstage) {
-                HIPCHK(pool_malloc(s.dev, sb, (void**)&s.dstage, false));
-                s.dstage_bytes = sb;
+                HIPCHK(pool_malloc(s.dev, r.bytes, (void**)&s.dstage, false));
+                s.dstage_bytes = r.bytes;
             }
-            const Stage g = stage_of(h, s);
-            const long Bs = s.B;
-            // one gather kernel into the device twin of the staging layout, one copy down
             GatherList gl{};
-            auto add = [&](const void* hdst, const void* src, long cnt, int sz) {
-                GatherSeg& e = gl.seg[gl.nseg++];
-                e.src = src;
-                e.off = (long)((const char*)hdst - s.hstage);
-                e.cnt = cnt;
-                e.sz = sz;
-                gl.most = std::max(gl.most, cnt);
-            };
-            add(g.x, s.out_x, Bs * n, 8);
-            add(g.y, s.out_y, Bs * m, 8);
-            add(g.obj, s.kp.obj, Bs, 8);
-            add(g.pri, s.kp.pri, Bs, 8);
-            add(g.dua, s.kp.dua, Bs, 8);
-            add(g.rho_est, s.kp.rho_est, Bs, 8);
-            add(g.dxc, s.kp.dxc, Bs * n, 8);
-            add(g.dyc, s.kp.dyc, Bs * m, 8);
-            add(g.status, s.kp.status, Bs, 4);
-            add(g.iter, s.kp.iter, Bs, 4);
-            add(g.rho_upd, s.kp.rho_upd, Bs, 4);
-            add(g.pstat, h->set.polish ? (const void*)s.kp.pstat : nullptr, Bs, 4);  // (no polish: zeros)
+            for (size_t i = 0; i < r.nseg; ++i) {
+                const Seg& g = r.seg[i];
+                gl.seg[gl.nseg++] = GatherSeg{g.dev, (long)g.off, s.B * g.per, g.sz};
+                gl.most = std::max(gl.most, s.B * g.per);
+            }
             HIPCHK(launch_gather(gl, s.dstage, s.stream));
-            HIPCHK(hipMemcpyAsync(s.hstage, s.dstage, sb, hipMemcpyDeviceToHost, s.stream));
         } else {
             all_staged = false;
-            if (x) HIPCHK(hipMemcpyAsync(x + s.b0 * n, s.out_x, sizeof(double) * s.B * n, hipMemcpyDeviceToHost, s.stream));
-            if (y) HIPCHK(hipMemcpyAsync(y + s.b0 * m, s.out_y, sizeof(double) * s.B * m, hipMemcpyDeviceToHost, s.stream));
-            if (status) HIPCHK(hipMemcpyAsync(status + s.b0, s.kp.status, sizeof(int) * s.B, hipMemcpyDeviceToHost, s.stream));
-            if (iters) HIPCHK(hipMemcpyAsync(iters + s.b0, s.kp.iter, sizeof(int) * s.B, hipMemcpyDeviceToHost, s.stream));
         }
+        if (int e = stage_down(s, r.seg, r.nseg, staged ? s.hstage : nullptr, s.dstage, r.bytes)) return e;
     }
     if (int e = sync_all(h)) return e;
     for (auto& s : h->shards) {
-        if (stage_bytes(h, s.B) > kStageMax) continue;
-        const Stage g = stage_of(h, s);
-        if (x) std::copy(g.x, g.x + s.B * n, x + s.b0 * n);
-        if (y) std::copy(g.y, g.y + s.B * m, y + s.b0 * m);
-        if (status) std::copy(g.status, g.status + s.B, status + s.b0);
-        if (iters) std::copy(g.iter, g.iter + s.B, iters + s.b0);
+        const Results r = result_segs(h, s, u);
+        if (r.bytes <= kStageMax) stage_unpack(s, r.seg, r.nseg, s.hstage);
     }
     h->staged = all_staged;
     h->solved = true;
@@ -1331,66 +1430,24 @@ int mpcqp_solve_batch(mpcqp_handle* h, double* x, double* y, int32_t* status, in
 int mpcqp_get_info_batch(mpcqp_handle* h, double* obj_val, double* pri_res, double* dua_res,
                          double* rho_estimate, int32_t* rho_updates) {
     if (!h) return fail(MPCQP_EINVAL, "NULL handle");
-    if (h->staged) {
-        for (auto& s : h->shards) {
-            const Stage g = stage_of(h, s);
-            if (obj_val) std::copy(g.obj, g.obj + s.B, obj_val + s.b0);
-            if (pri_res) std::copy(g.pri, g.pri + s.B, pri_res + s.b0);
-            if (dua_res) std::copy(g.dua, g.dua + s.B, dua_res + s.b0);
-            if (rho_estimate) std::copy(g.rho_est, g.rho_est + s.B, rho_estimate + s.b0);
-            if (rho_updates) std::copy(g.rho_upd, g.rho_upd + s.B, rho_updates + s.b0);
-        }
-        return 0;
-    }
-    for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (obj_val) HIPCHK(hipMemcpy(obj_val + s.b0, s.kp.obj, sizeof(double) * s.B, hipMemcpyDeviceToHost));
-        if (pri_res) HIPCHK(hipMemcpy(pri_res + s.b0, s.kp.pri, sizeof(double) * s.B, hipMemcpyDeviceToHost));
-        if (dua_res) HIPCHK(hipMemcpy(dua_res + s.b0, s.kp.dua, sizeof(double) * s.B, hipMemcpyDeviceToHost));
-        if (rho_estimate) HIPCHK(hipMemcpy(rho_estimate + s.b0, s.kp.rho_est, sizeof(double) * s.B, hipMemcpyDeviceToHost));
-        if (rho_updates) HIPCHK(hipMemcpy(rho_updates + s.b0, s.kp.rho_upd, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    ResultPtrs u;
+    u.obj = obj_val; u.pri = pri_res; u.dua = dua_res; u.rho_est = rho_estimate; u.rho_upd = rho_updates;
+    return read_results(h, u);
 }
 
 int mpcqp_get_polish_status(mpcqp_handle* h, int32_t* status_polish) {
     if (!h || !status_polish) return fail(MPCQP_EINVAL, "NULL argument");
-    if (h->staged) {
-        for (auto& s : h->shards) {
-            const Stage g = stage_of(h, s);
-            std::copy(g.pstat, g.pstat + s.B, status_polish + s.b0);
-        }
-        return 0;
-    }
-    for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (h->set.polish)
-            HIPCHK(hipMemcpy(status_polish + s.b0, s.kp.pstat, sizeof(int) * s.B, hipMemcpyDeviceToHost));
-        else
-            std::fill(status_polish + s.b0, status_polish + s.b0 + s.B, 0);
-    }
-    return 0;
+    ResultPtrs u;
+    u.pstat = status_polish;
+    return read_results(h, u);
 }
 
 int mpcqp_get_certificates(mpcqp_handle* h, double* prim_inf_cert, double* dual_inf_cert) {
     if (int e = need_state(h, "mpcqp_get_certificates")) return e;
     if (!h) return fail(MPCQP_EINVAL, "NULL handle");
-    if (h->staged) {
-        for (auto& s : h->shards) {
-            const Stage g = stage_of(h, s);
-            if (prim_inf_cert) std::copy(g.dyc, g.dyc + s.B * h->m, prim_inf_cert + s.b0 * h->m);
-            if (dual_inf_cert) std::copy(g.dxc, g.dxc + s.B * h->n, dual_inf_cert + s.b0 * h->n);
-        }
-        return 0;
-    }
-    for (auto& s : h->shards) {
-        HIPCHK(hipSetDevice(s.dev));
-        if (prim_inf_cert)
-            HIPCHK(hipMemcpy(prim_inf_cert + s.b0 * h->m, s.kp.dyc, sizeof(double) * s.B * h->m, hipMemcpyDeviceToHost));
-        if (dual_inf_cert)
-            HIPCHK(hipMemcpy(dual_inf_cert + s.b0 * h->n, s.kp.dxc, sizeof(double) * s.B * h->n, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    ResultPtrs u;
+    u.dyc = prim_inf_cert; u.dxc = dual_inf_cert;
+    return read_results(h, u);
 }
 
 int mpcqp_create(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, const int32_t* Ap,
@@ -1399,89 +1456,54 @@ int mpcqp_create(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, con
     return make_handle(n, m, Pp, Pi, Ap, Ai, B, settings, std::vector<int>{device}, false, out);
 }
 
-static hipStream_t pick(Shard& s, void* stream) { return stream ? (hipStream_t)stream : s.stream; }
-
-// on: the record this launch kind goes to is enabled (collect: solve launches,
-// collect_setup: setup launches)
-static int ev_begin(bool on, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t st) {
-    if (!on) return 0;
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    HIPCHK(hipEventRecord(a, st));
-    v.push_back({a, b});
-    return 0;
-}
-static int ev_end(bool on, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t st) {
-    if (!on || v.empty()) return 0;
-    HIPCHK(hipEventRecord(v.back().second, st));
-    return 0;
-}
-
+// A setup overwrites the workspace: state_gone holds from before the launch (one that fails
+// part-way leaves nothing a later call may read) until the setup is known to keep its state.
 int mpcqp_setup_device(mpcqp_handle* h, const double* dPx, const double* dAx, const double* dq,
                        const double* dl, const double* du, void* stream) {
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    if (h->collect_setup)
-        if (int e = ev_begin(h->collect_setup, h->ev_setup, st)) return e;
-    HIPCHK(launch_setup(s.kp, s.B, dPx, dAx, dq, dl, du, st));
-    if (h->collect_setup)
-        if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
-    h->state_gone = false;
-    h->solved = false;
-    h->has_setup = true;
-    return stream_leave(s, st);
+    return device_call(h, stream, nullptr, [&](Shard& s, hipStream_t st) -> int {
+        h->state_gone = true;
+        if (int e = timed_launch(h->collect_setup, h->ev_setup, st, nullptr,
+                                 [&]() -> int { HIPCHK(launch_setup(s.kp, s.B, dPx, dAx, dq, dl, du, st)); return 0; }))
+            return e;
+        h->state_gone = false;
+        h->solved = false;
+        h->has_setup = true;
+        return 0;
+    });
 }
 
 int mpcqp_update_device(mpcqp_handle* h, const double* dq, const double* dl, const double* du, void* stream) {
-    if (int e = need_state(h, "mpcqp_update_device")) return e;
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    HIPCHK(launch_update(s.kp, s.B, dq, dl, du, st));
-    return stream_leave(s, st);
+    return device_call(h, stream, "mpcqp_update_device", [&](Shard& s, hipStream_t st) -> int {
+        HIPCHK(launch_update(s.kp, s.B, dq, dl, du, st));
+        return 0;
+    });
 }
 
 int mpcqp_warm_start_device(mpcqp_handle* h, const double* dx, const double* dy, void* stream) {
-    if (int e = need_state(h, "mpcqp_warm_start_device")) return e;
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    HIPCHK(launch_warm(s.kp, s.B, dx, dy, st));
-    s.kp.warm_start = 1;
-    h->set.warm_start = 1;
-    return stream_leave(s, st);
+    return device_call(h, stream, "mpcqp_warm_start_device", [&](Shard& s, hipStream_t st) -> int {
+        HIPCHK(launch_warm(s.kp, s.B, dx, dy, st));
+        s.kp.warm_start = 1;
+        h->set.warm_start = 1;
+        return 0;
+    });
 }
 
 int mpcqp_setup_warm_device(mpcqp_handle* h, const double* dPx, const double* dAx, const double* dq,
                             const double* dl, const double* du, const double* dx0, const double* dy0, void* stream) {
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    if (h->collect_setup)
-        if (int e = ev_begin(h->collect_setup, h->ev_setup, st)) return e;
-    HIPCHK(launch_setup_warm(s.kp, s.B, dPx, dAx, dq, dl, du, dx0, dy0, st));
-    if (h->collect_setup)
-        if (int e = ev_end(h->collect_setup, h->ev_setup, st)) return e;
-    h->state_gone = false;
-    h->solved = false;
-    h->has_setup = true;
-    s.kp.warm_start = 1;
-    h->set.warm_start = 1;
-    return stream_leave(s, st);
+    return device_call(h, stream, nullptr, [&](Shard& s, hipStream_t st) -> int {
+        h->state_gone = true;
+        if (int e = timed_launch(h->collect_setup, h->ev_setup, st, nullptr, [&]() -> int {
+                HIPCHK(launch_setup_warm(s.kp, s.B, dPx, dAx, dq, dl, du, dx0, dy0, st));
+                return 0;
+            }))
+            return e;
+        h->state_gone = false;
+        h->solved = false;
+        h->has_setup = true;
+        s.kp.warm_start = 1;
+        h->set.warm_start = 1;
+        return 0;
+    });
 }
 
 int mpcqp_setup_warm_fused(const mpcqp_handle* h) {
@@ -1490,86 +1512,71 @@ int mpcqp_setup_warm_fused(const mpcqp_handle* h) {
 }
 
 int mpcqp_solve_device(mpcqp_handle* h, double* dx, double* dy, int32_t* dstatus, int32_t* diters, void* stream) {
-    if (int e = need_state(h, "mpcqp_solve_device")) return e;
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    // an event pair around the launch only while timing is on (mpcqp_setup_solve_device)
-    if (h->collect)
-        if (int e = ev_begin(h->collect, h->ev_solve, st)) return e;
-    KParams k = s.kp;  // the solve kernel writes status / iter into the caller's arrays as well
-    k.ostat = dstatus;
-    k.oiter = diters;
-    HIPCHK(launch_solve(k, s.B, dx, dy, 0, st));
-    if (h->collect) {
-        if (int e = ev_end(h->collect, h->ev_solve, st)) return e;
-        h->last_pair = h->ev_solve.back();
-    }
-    HIPCHK(launch_order(k, s.B, st));
-    h->timed = true;
-    h->solved = true;
-    return stream_leave(s, st);
+    return device_call(h, stream, "mpcqp_solve_device", [&](Shard& s, hipStream_t st) -> int {
+        KParams k = s.kp;  // the solve kernel writes status / iter into the caller's arrays as well
+        k.ostat = dstatus;
+        k.oiter = diters;
+        if (int e = timed_launch(h->collect, h->ev_solve, st, &h->last_pair,
+                                 [&]() -> int { HIPCHK(launch_solve(k, s.B, dx, dy, 0, st)); return 0; }))
+            return e;
+        HIPCHK(launch_order(k, s.B, st));
+        h->timed = true;
+        h->solved = true;
+        return 0;
+    });
 }
 
 int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* dAx, const double* dq,
                              const double* dl, const double* du, double* dx, double* dy, int32_t* dstatus,
                              int32_t* diters, void* stream) {
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    // no event between the kernels unless timing is on: every recorded event is a packet
-    // the command processor completes between two launches (≈12 us per step measured on
-    // the cfg-2 bench, 2.33 -> 2.40 M solves/s without them)
-    if (h->collect)
-        if (int e = ev_begin(h->collect, h->ev_solve, st)) return e;
-    KParams k = s.kp;
-    k.ostat = dstatus;
-    k.oiter = diters;
-    const bool one = h->one_shot && one_shot_form(k) > 0;
-    HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? (h->one_shot_lds ? 2 : 1) : 0));
-    h->state_gone = one;
-    h->has_setup = true;
-    if (h->collect) {
-        if (int e = ev_end(h->collect, h->ev_solve, st)) return e;
-        h->last_pair = h->ev_solve.back();
-    }
-    HIPCHK(launch_order(k, s.B, st));
-    h->timed = true;
-    h->solved = true;
-    return stream_leave(s, st);
+    return device_call(h, stream, nullptr, [&](Shard& s, hipStream_t st) -> int {
+        KParams k = s.kp;
+        k.ostat = dstatus;
+        k.oiter = diters;
+        const bool one = h->one_shot && one_shot_form(k) > 0;
+        h->state_gone = one;
+        if (int e = timed_launch(h->collect, h->ev_solve, st, &h->last_pair, [&]() -> int {
+                HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? (h->one_shot_lds ? 2 : 1) : 0));
+                return 0;
+            }))
+            return e;
+        h->has_setup = true;
+        HIPCHK(launch_order(k, s.B, st));
+        h->timed = true;
+        h->solved = true;
+        return 0;
+    });
 }
 
-// what both adjoint entry points check before any device work; a handle on an eliminated plan
-// moves to the plain plan (the adjoint system is factored over all of K, as polish's)
+// what the adjoint and solution-record entry points check before any device work: a finished
+// solve (need_solved) or at least a setup; a handle on an eliminated plan then moves to the plain
+// plan (the adjoint system is factored over all of K, as polish's)
+static int need_plain_state(mpcqp_handle* h, bool need_solved, const char* what) {
+    if (int e = need_state(h, what)) return e;
+    if (need_solved && !h->solved)
+        return fail(MPCQP_EINVAL, "%s: no solve has run on this handle's setup yet", what);
+    if (!need_solved && !h->has_setup) return fail(MPCQP_EINVAL, "%s: no setup has run on this handle yet", what);
+    if (h->plan->ne > 0)
+        if (int e = replan_plain(h)) return e;
+    return 0;
+}
 static int adjoint_enter(mpcqp_handle* h, int32_t nrhs, const void* gx, const void* gy, const char* what) {
     if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
     if (nrhs < 1) return fail(MPCQP_EINVAL, "%s: nrhs must be at least 1 (got %d)", what, (int)nrhs);
     if (!gx && !gy) return fail(MPCQP_EINVAL, "%s: both seeds are NULL", what);
-    if (int e = need_state(h, what)) return e;
-    if (!h->solved) return fail(MPCQP_EINVAL, "%s: no solve has run on this handle's setup yet", what);
-    if (h->plan->ne > 0)
-        if (int e = replan_plain(h)) return e;
-    return 0;
+    return need_plain_state(h, true, what);
 }
 
 int mpcqp_adjoint_device(mpcqp_handle* h, int32_t nrhs, const double* dgx, const double* dgy, double* drx,
                          double* dry, double* dgq, double* dgl, double* dgu, double* dgPx, double* dgAx,
                          int8_t* dact, double* dares, int32_t* dastat, void* stream) {
     if (int e = adjoint_enter(h, nrhs, dgx, dgy, "mpcqp_adjoint_device")) return e;
-    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    const AdjointIO io{nrhs, dgx, dgy, drx, dry, dgq, dgl, dgu, dgPx, dgAx, (signed char*)dact, dares, dastat};
-    HIPCHK(launch_adjoint(s.kp, s.B, io, st));
-    return stream_leave(s, st);
+    if (int e = single_device(h)) return e;
+    return on_caller_stream(h, stream, [&](Shard& s, hipStream_t st) -> int {
+        const AdjointIO io{nrhs, dgx, dgy, drx, dry, dgq, dgl, dgu, dgPx, dgAx, (signed char*)dact, dares, dastat};
+        HIPCHK(launch_adjoint(s.kp, s.B, io, st));
+        return 0;
+    });
 }
 
 int mpcqp_adjoint_batch(mpcqp_handle* h, int32_t nrhs, const double* gx, const double* gy, double* rx, double* ry,
@@ -1579,118 +1586,72 @@ int mpcqp_adjoint_batch(mpcqp_handle* h, int32_t nrhs, const double* gx, const d
     const long n = h->n, m = h->m, nP = h->plan->nnzP, nA = h->plan->nnzA, R = nrhs;
     // per shard one device block and (small shards) one pinned block of the same layout: the
     // seeds, then every output the caller asked for; freed (to the pool) after the call
-    struct Seg { const void* in; void* out; long per; int sz; size_t off; };  // per: elements per instance
-    struct Tmp { void* d = nullptr; char* hb = nullptr; size_t bytes = 0; };
+    struct Tmp { void* d = nullptr; char* hb = nullptr; size_t bytes = 0; std::vector<Seg> sg; };
     std::vector<Tmp> tmp(h->shards.size());
-    auto release = [&]() {
-        for (size_t i = 0; i < tmp.size(); ++i) {
-            pool_free(h->shards[i].dev, tmp[i].bytes, tmp[i].d, false);
-            pool_free(h->shards[i].dev, tmp[i].bytes, tmp[i].hb, true);
-        }
-    };
-    std::vector<std::vector<Seg>> segs(h->shards.size());
-    auto enqueue = [&](size_t si) -> int {
-        Shard& s = h->shards[si];
-        const long Bs = s.B;
-        std::vector<Seg>& sg = segs[si];
-        sg = {{gx, nullptr, R * n, 8, 0},  {gy, nullptr, R * m, 8, 0},  {nullptr, rx, R * n, 8, 0},
-              {nullptr, ry, R * m, 8, 0},  {nullptr, gq, R * n, 8, 0},  {nullptr, gl, R * m, 8, 0},
-              {nullptr, gu, R * m, 8, 0},  {nullptr, gPx, R * nP, 8, 0}, {nullptr, gAx, R * nA, 8, 0},
-              {nullptr, ares, R, 8, 0},    {nullptr, astat, 1, 4, 0},   {nullptr, act, m, 1, 0}};
-        size_t off = 0;
-        for (auto& g : sg) {
-            if (!g.in && !g.out) continue;
-            g.off = carve<char>(off, (size_t)Bs * g.per * g.sz);
-        }
-        Tmp& t = tmp[si];
-        t.bytes = off + 256;
-        HIPCHK(hipSetDevice(s.dev));
-        HIPCHK(pool_malloc(s.dev, t.bytes, &t.d, false));
-        if (t.bytes <= kStageMax) HIPCHK(pool_malloc(s.dev, t.bytes, (void**)&t.hb, true));
-        char* const db = (char*)t.d;
-        if (int e = stream_enter(s, s.stream)) return e;
-        if (t.hb) {  // the seeds lie first: one copy up
-            size_t up = 0;
-            for (auto& g : sg)
-                if (g.in) {
-                    const size_t by = (size_t)Bs * g.per * g.sz;
-                    memcpy(t.hb + g.off, (const char*)g.in + (size_t)s.b0 * g.per * g.sz, by);
-                    up = g.off + by;
-                }
-            HIPCHK(hipMemcpyAsync(db, t.hb, up, hipMemcpyHostToDevice, s.stream));
-        } else {
-            for (auto& g : sg)
-                if (g.in)
-                    HIPCHK(hipMemcpyAsync(db + g.off, (const char*)g.in + (size_t)s.b0 * g.per * g.sz,
-                                          (size_t)Bs * g.per * g.sz, hipMemcpyHostToDevice, s.stream));
-        }
-        auto dp = [&](int k) { return (sg[k].in || sg[k].out) ? db + sg[k].off : nullptr; };
-        const AdjointIO io{nrhs, (const double*)dp(0), (const double*)dp(1), (double*)dp(2), (double*)dp(3),
-                           (double*)dp(4), (double*)dp(5), (double*)dp(6), (double*)dp(7), (double*)dp(8),
-                           (signed char*)dp(11), (double*)dp(9), (int*)dp(10)};
-        HIPCHK(launch_adjoint(s.kp, Bs, io, s.stream));
-        if (t.hb) {
-            HIPCHK(hipMemcpyAsync(t.hb, db, off, hipMemcpyDeviceToHost, s.stream));
-        } else {
-            for (auto& g : sg)
-                if (g.out)
-                    HIPCHK(hipMemcpyAsync((char*)g.out + (size_t)s.b0 * g.per * g.sz, db + g.off,
-                                          (size_t)Bs * g.per * g.sz, hipMemcpyDeviceToHost, s.stream));
-        }
-        return stream_leave(s, s.stream);
+    auto enqueue = [&](Shard& s, Tmp& t) -> int {
+        t.sg = {{(void*)gx, nullptr, R * n, 8, Dir::up, 0}, {(void*)gy, nullptr, R * m, 8, Dir::up, 0},
+                {rx, nullptr, R * n, 8, Dir::down, 0},      {ry, nullptr, R * m, 8, Dir::down, 0},
+                {gq, nullptr, R * n, 8, Dir::down, 0},      {gl, nullptr, R * m, 8, Dir::down, 0},
+                {gu, nullptr, R * m, 8, Dir::down, 0},      {gPx, nullptr, R * nP, 8, Dir::down, 0},
+                {gAx, nullptr, R * nA, 8, Dir::down, 0},    {ares, nullptr, R, 8, Dir::down, 0},
+                {astat, nullptr, 1, 4, Dir::down, 0},       {act, nullptr, m, 1, Dir::down, 0}};
+        size_t end = 0;
+        for (Seg& g : t.sg)
+            if (g.host) g.off = carve(end, seg_bytes(g, s.B));
+        t.bytes = end + 256;
+        return on_stream(s, s.stream, [&]() -> int {
+            HIPCHK(pool_malloc(s.dev, t.bytes, &t.d, false));
+            if (t.bytes <= kStageMax) HIPCHK(pool_malloc(s.dev, t.bytes, (void**)&t.hb, true));
+            for (Seg& g : t.sg)
+                if (g.host) g.dev = (char*)t.d + g.off;
+            if (int e = stage_up(s, t.sg.data(), t.sg.size(), t.hb, t.d)) return e;  // the seeds lie first
+            auto dp = [&](int k) { return t.sg[k].dev; };
+            const AdjointIO io{nrhs, (const double*)dp(0), (const double*)dp(1), (double*)dp(2), (double*)dp(3),
+                               (double*)dp(4), (double*)dp(5), (double*)dp(6), (double*)dp(7), (double*)dp(8),
+                               (signed char*)dp(11), (double*)dp(9), (int*)dp(10)};
+            HIPCHK(launch_adjoint(s.kp, s.B, io, s.stream));
+            return stage_down(s, t.sg.data(), t.sg.size(), t.hb, t.d, end);
+        });
     };
     int err = 0;
-    for (size_t si = 0; si < h->shards.size() && !err; ++si) err = enqueue(si);
+    for (size_t si = 0; si < h->shards.size() && !err; ++si) err = enqueue(h->shards[si], tmp[si]);
     if (int e = sync_all(h); e && !err) err = e;  // (also on an error: no block goes back to the pool in use)
-    if (!err)
-        for (size_t si = 0; si < h->shards.size(); ++si) {
-            if (!tmp[si].hb) continue;
-            const Shard& s = h->shards[si];
-            for (auto& g : segs[si])
-                if (g.out)
-                    memcpy((char*)g.out + (size_t)s.b0 * g.per * g.sz, tmp[si].hb + g.off, (size_t)s.B * g.per * g.sz);
-        }
-    release();
+    for (size_t si = 0; si < h->shards.size(); ++si) {
+        const Shard& s = h->shards[si];
+        Tmp& t = tmp[si];
+        if (!err && t.hb) stage_unpack(s, t.sg.data(), t.sg.size(), t.hb);
+        pool_free(s.dev, t.bytes, t.d, false);
+        pool_free(s.dev, t.bytes, t.hb, true);
+    }
     return err;
 }
 
 // The solution record (mpcqp.h): what k_adjoint reads of a finished solve -- x~ by variable, z~, y~,
 // the status -- out of the workspace and back into it.  Both move a handle on an eliminated plan to
 // the plain plan first, as the adjoint does, so a record is the same whichever plan the solve ran on.
-int mpcqp_save_solution_device(mpcqp_handle* h, double* drecord, void* stream) {
-    const char* what = "mpcqp_save_solution_device";
+static int record_enter(mpcqp_handle* h, const double* drecord, bool need_solved, const char* what) {
     if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
     if (!drecord) return fail(MPCQP_EINVAL, "%s: NULL record", what);
-    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    if (int e = need_state(h, what)) return e;
-    if (!h->solved) return fail(MPCQP_EINVAL, "%s: no solve has run on this handle's setup yet", what);
-    if (h->plan->ne > 0)
-        if (int e = replan_plain(h)) return e;
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    HIPCHK(launch_save_solution(s.kp, s.B, drecord, st));
-    return stream_leave(s, st);
+    if (int e = single_device(h)) return e;
+    return need_plain_state(h, need_solved, what);
+}
+
+int mpcqp_save_solution_device(mpcqp_handle* h, double* drecord, void* stream) {
+    if (int e = record_enter(h, drecord, true, "mpcqp_save_solution_device")) return e;
+    return on_caller_stream(h, stream, [&](Shard& s, hipStream_t st) -> int {
+        HIPCHK(launch_save_solution(s.kp, s.B, drecord, st));
+        return 0;
+    });
 }
 
 int mpcqp_load_solution_device(mpcqp_handle* h, const double* drecord, void* stream) {
-    const char* what = "mpcqp_load_solution_device";
-    if (!h) return fail(MPCQP_EINVAL, "%s: NULL handle", what);
-    if (!drecord) return fail(MPCQP_EINVAL, "%s: NULL record", what);
-    if (h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
-    if (int e = need_state(h, what)) return e;
-    if (!h->has_setup) return fail(MPCQP_EINVAL, "%s: no setup has run on this handle yet", what);
-    if (h->plan->ne > 0)
-        if (int e = replan_plain(h)) return e;
+    if (int e = record_enter(h, drecord, false, "mpcqp_load_solution_device")) return e;
     h->staged = false;  // (device work: the staged results of the last solve are stale)
-    Shard& s = h->shards[0];
-    hipStream_t st = pick(s, stream);
-    HIPCHK(hipSetDevice(s.dev));
-    if (int e = stream_enter(s, st)) return e;
-    HIPCHK(launch_load_solution(s.kp, s.B, drecord, st));
-    h->solved = true;
-    return stream_leave(s, st);
+    return on_caller_stream(h, stream, [&](Shard& s, hipStream_t st) -> int {
+        HIPCHK(launch_load_solution(s.kp, s.B, drecord, st));
+        h->solved = true;
+        return 0;
+    });
 }
 
 void* mpcqp_get_stream(const mpcqp_handle* h) {
@@ -1698,7 +1659,7 @@ void* mpcqp_get_stream(const mpcqp_handle* h) {
 }
 
 int mpcqp_set_one_shot(mpcqp_handle* h, int32_t on) {
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    if (int e = single_device(h)) return e;
     h->one_shot = on != 0;
     return 0;
 }
@@ -1708,7 +1669,7 @@ int mpcqp_one_shot_applies(const mpcqp_handle* h) {
 }
 
 int mpcqp_set_shared_matrices(mpcqp_handle* h, int32_t shared) {
-    if (!h || h->shards.size() != 1) return fail(MPCQP_EINVAL, "device entry points need a single-device handle");
+    if (int e = single_device(h)) return e;
     h->staged = false;  // (device work: the staged results of the last solve are stale)
     h->shards[0].kp.mat_shared = shared ? 1 : 0;
     return 0;
@@ -1769,17 +1730,8 @@ int mpcqp_timing_read(mpcqp_handle* h, double* setup_ms, int32_t* n_setup, doubl
 
 int mpcqp_get_plan_info(const mpcqp_handle* h, mpcqp_plan_info* info) {
     if (!h || !info) return fail(MPCQP_EINVAL, "NULL argument");
-    info->n = h->n; info->m = h->m; info->nb = h->plan->nb; info->block = kS;
-    info->npad = h->plan->npad; info->max_level = h->plan->max_level;
+    fill_plan_info(info, h->n, h->m, *h->plan, h->shards.empty() ? nullptr : &h->shards[0].kp);
     info->batch = h->B; info->n_devices = (int)h->shards.size();
-    info->lds_bytes_solve = h->shards.empty() ? 0 : (int64_t)lds_kernel_bytes(h->shards[0].kp);
-    info->bytes_per_instance = (int64_t)(workspace_bytes(*h->plan, 1, false));
-    info->amax = h->plan->amax;
-    info->gather_k = h->plan->gather_k;
-    info->variant = h->shards.empty() ? -1 : h->shards[0].kp.variant;
-    info->threads_per_qp = h->shards.empty() ? 0 : solve_threads(h->shards[0].kp.variant);
-    info->n_eliminated = h->plan->ne;
-    info->plan_choice = h->plan->choice;
     return 0;
 }
 
@@ -1797,21 +1749,9 @@ int mpcqp_plan_preview(int32_t n, int32_t m, const int32_t* Pp, const int32_t* P
     if (!err.empty()) return fail(err.rfind("unsupported", 0) == 0 ? MPCQP_EUNSUPPORTED : MPCQP_EINVAL, "%s", err.c_str());
     KParams k{};
     shape_params(pl, k);
-    k.variant = solve_variant(k);
-    if (const char* ev = getenv("MPCQP_VARIANT"); ev && *ev) {  // the override alloc_shard applies
-        const int v = atoi(ev);
-        if (!variant_fits(k, v)) return fail(MPCQP_EUNSUPPORTED, "MPCQP_VARIANT=%d does not fit this plan", v);
-        k.variant = v;
-    }
-    k.mode = k.variant >= 0 ? solve_mode(k.variant) : 0;
+    if (int e = pick_variant(k)) return e;
     *info = mpcqp_plan_info{};
-    info->n = n; info->m = m; info->nb = pl.nb; info->block = kS; info->npad = pl.npad;
-    info->max_level = pl.max_level;
-    info->lds_bytes_solve = k.variant >= 0 ? (int64_t)lds_kernel_bytes(k) : 0;
-    info->bytes_per_instance = (int64_t)workspace_bytes(pl, 1, false);
-    info->amax = pl.amax; info->gather_k = pl.gather_k; info->variant = k.variant;
-    info->threads_per_qp = k.variant >= 0 ? solve_threads(k.variant) : 0;
-    info->n_eliminated = pl.ne; info->plan_choice = pl.choice;
+    fill_plan_info(info, n, m, pl, &k);
     return 0;
 }
 

@@ -214,21 +214,30 @@ def test_cfg2_workspace_carries_no_dense_inverse_rows():
     """The production library carves no dense-inverse rows (KParams::Kd, 256 x 54 doubles per
     instance) for cfg 2's four-block plan: that form is compiled into the experimental build
     only.  About 121 kB per instance (231 kB with the rows' 110,592 B), with and
-    without MPCQP_DENSE_W4=1 (read once per process: children)."""
+    without MPCQP_DENSE_W4=1 (read once per process: children).
+
+    The workspace's size is pinned to the byte for configs 1-5: the resource pool keys blocks by
+    their exact size and bytes_per_instance is reported to callers, so the one listing of the
+    regions (api.hip::workspace_regions) must keep every region, its alignment and the tail."""
     code = r"""
 import json
 import osqp_amd
 from osqp_amd import mpc
-b = mpc.make_batch(2, B=2, seed=3)
-P, _ = osqp_amd._drop_common_zeros(b["P"], b["Px"])
-A, _ = osqp_amd._drop_common_zeros(b["A"], b["Ax"])
-print(json.dumps(osqp_amd.plan_preview(P, A, **b["settings"])["bytes_per_instance"]))
+out = {}
+for cfg in (1, 2, 3, 4, 5):
+    b = mpc.make_batch(cfg, B=2, seed=3)
+    P, _ = osqp_amd._drop_common_zeros(b["P"], b["Px"])
+    A, _ = osqp_amd._drop_common_zeros(b["A"], b["Ax"])
+    out[cfg] = osqp_amd.plan_preview(P, A, **b["settings"])["bytes_per_instance"]
+print(json.dumps(out))
 """
+    pins = {"1": 131368, "2": 121640, "3": 131368, "4": 131368, "5": 510504}
     for dk in ("0", "1"):
         env = dict(os.environ, MPCQP_DENSE_W4=dk, MPCQP_BUILD="", PYTHONPATH=os.path.join(ROOT, "python-mpc_amd"))
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True)
         bpi = json.loads(out.stdout.strip().splitlines()[-1])
-        assert 115_000 < bpi < 125_000, bpi
+        assert 115_000 < bpi["2"] < 125_000, bpi
+        assert bpi == pins, bpi
 
 
 def test_plan_preview_reports_a_rejected_elimination():
