@@ -56,6 +56,44 @@ __device__ __forceinline__ long instance_of(const KParams& p) {
     return p.order ? (long)__builtin_amdgcn_readfirstlane(p.order[blockIdx.x]) : (long)blockIdx.x;
 }
 
+// Optional in-kernel phase timers (the prof build, MPCQP_PHASE_PROF): thread 0's shader clock,
+// accumulated per phase in the LDS slots L.pacc[16] and written to KParams::prof at the end
+// (kProfSlots per instance).  Every phase ends at a barrier.  A solve kernel declares the state
+// with PROF_START (in scope: p, L), stamps the phase that just ended with PH(k) and ends with
+// prof_flush; a factorisation does the same on its own clock with FPROF_START / FPH(k).  All
+// of it is empty in the other builds.
+#ifdef MPCQP_PHASE_PROF
+#define PROF_START                                                                                     \
+    long long tph = 0, t0c = 0, t0w = 0;                                                               \
+    const bool prof = p.prof != nullptr;                                                               \
+    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (threadIdx.x < 16) L.pacc[threadIdx.x] = 0; }
+#define PH(k) if (prof && threadIdx.x == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
+#define FPROF_START long long tf = clock64();
+#define FPH(k) if (threadIdx.x == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
+// the slots every solve kernel writes the same way (thread 0): the phases 0-5 and 8-last, the
+// total in cycles (6) and 100 MHz ticks (7), the absolute start (15: dispatch order / residency)
+template <class KP, class LDS>
+__device__ __forceinline__ void prof_flush(const KP& p, long b, const LDS& L, long long t0c, long long t0w, int last) {
+    for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
+    for (int k = 8; k <= last; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
+    p.prof[b * kProfSlots + 6] = clock64() - t0c;
+    p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
+    p.prof[b * kProfSlots + 15] = t0w;
+}
+#else
+#define PROF_START
+#define PH(k)
+#define FPROF_START
+#define FPH(k)
+#endif
+#ifdef MPCQP_CHECK_PROF  // diagnostic: slots 12-14 time the run end / reductions / certificates of a check
+#define PHL(k) PH(2)
+#define PHC(k) PH(k)
+#else
+#define PHL(k) PH(k)
+#define PHC(k)
+#endif
+
 __device__ __forceinline__ double cmax(double a, double b) { return a > b ? a : b; }
 __device__ __forceinline__ double cmin(double a, double b) { return a < b ? a : b; }
 __device__ __forceinline__ double limit_scaling(double d) {

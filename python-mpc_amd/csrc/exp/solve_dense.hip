@@ -76,20 +76,11 @@ __global__ __launch_bounds__(TD, 2) void k_solve_d(KParams p, double* __restrict
     constexpr int PBL = 2 * R + 2;
 
     if (p.err[b]) {  // invalid data (flagged by setup/update): NaN outputs
-        for (int j = tid; j < n; j += TD) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += TD) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
+        reject_instance<TD>(p, b, xo, yo);
         return;
     }
 
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START
 
     const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
     double rho = p.scal[b * 4 + 2];
@@ -241,9 +232,7 @@ __global__ __launch_bounds__(TD, 2) void k_solve_d(KParams p, double* __restrict
             PH(10)
             if (!ok) {
                 if (iter == 0) {
-                    for (int j = tid; j < n; j += TD) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = tid; i < m; i += TD) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (tid == 0) fail_status(p, b);
+                    reject_instance<TD>(p, b, xo, yo);
                     return;
                 }
                 status = MPCQP_NON_CVX_;
@@ -284,9 +273,7 @@ __global__ __launch_bounds__(TD, 2) void k_solve_d(KParams p, double* __restrict
         __syncthreads();  // every ys / Z read before w is written
 #pragma unroll
         for (int s = 0; s < RS; ++s) L.w[ri[s]] = rv[s] * Z[s] - y[s];  // w = rho z_prev - y (rho may be new)
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+        const int stop_at = run_stop(p, iter);
         __syncthreads();
         PH(5)
         while (iter < stop_at) {
@@ -529,49 +516,22 @@ __global__ __launch_bounds__(TD, 2) void k_solve_d(KParams p, double* __restrict
         if (!stop && do_rho) {
             Res R_;
             R_.restore(L.res);
-            const double pr = R_.rpri / (cmax(R_.rz, R_.rax) + DIVISION_TOL);
-            const double du = R_.rdua / (cmax(cmax(R_.rq, R_.raty), R_.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
+            adapt_rho(p, R_, rho, rho_updates, need_factor);
         }
         __syncthreads();
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<TD>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<TD>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<TD>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<TD>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<TD>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<TD>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
         if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 12; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
+            prof_flush(p, b, L, t0c, t0w, 11);
         }
     }
 #endif
-#undef PH
 }
 
 // The dense kernel's LDS: the base carve, then bc, v2p and the pivot buffers.

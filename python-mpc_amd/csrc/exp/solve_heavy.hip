@@ -167,7 +167,7 @@ template <int K, int KC, int KPK, int QR>
 __device__ __forceinline__ void solve_h_body(const KParams& p, double* __restrict__ xo, double* __restrict__ yo) {
     const int tid = threadIdx.x;
     const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
+    const int m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
     extern __shared__ __attribute__((aligned(16))) double smh[];
@@ -177,42 +177,17 @@ __device__ __forceinline__ void solve_h_body(const KParams& p, double* __restric
     const double* Hg = p.H + b * (long)p.nb * SS;
 
     if (p.err[b]) {
-        for (int j = tid; j < n; j += TH) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += TH) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
+        reject_instance<TH>(p, b, xo, yo);
         return;
     }
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START
     auto cscal = [&](int k) __attribute__((always_inline)) { return opaque_gptr(p.scal + b * 4)[k]; };
     double rho = p.scal[b * 4 + 2];
     const double sigma = p.sigma, alpha = p.alpha;
     const bool warm = p.warm_start != 0;
-    for (int e = tid; e < nnzA; e += TH) L.Acsc[e] = p.Ax[b * nnzA + e];
-    if (tid == 0) L.Acsc[nnzA] = 0.0;
-    for (int v = tid; v < nnzP; v += TH) L.Pv[v] = p.Px[b * nnzP + v];
-    if (tid == 0) L.Pv[nnzP] = 0.0;
     const int mp = solve_mpad(m);
-    for (int i = tid; i < mp; i += TH) {
-        const bool in = i < m;
-        L.lo[i] = in ? p.l[b * m + i] : 0.0;
-        L.up[i] = in ? p.u[b * m + i] : 0.0;
-        L.ct[i] = in ? p.ct[b * m + i] : 0;
-        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
-    }
-    for (int pc = tid; pc < npad; pc += TH) {
-        L.qv[pc] = p.q[b * npad + pc];
-        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
-    }
+    load_instance<TH>(p, b, C, warm);
     for (int e = tid; e < 8 * HSTR; e += TH) rbs[e] = 0.0;
-    if (tid < 16) L.res[tid] = 0.0;
-    if (tid < 4) L.flag[tid] = 0;
 
     int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
     bool can_check = false, need_factor = true;
@@ -250,9 +225,7 @@ __device__ __forceinline__ void solve_h_body(const KParams& p, double* __restric
             if (tid == 0) p.ffresh[b] = 0;  // (the workspace Si tiles are not this factor's)
             if (!ok) {
                 if (iter == 0) {
-                    if (xo) for (int j = tid; j < n; j += TH) opaque_ptr(xo + b * n)[j] = __builtin_nan("");
-                    if (yo) for (int i = tid; i < m; i += TH) opaque_ptr(yo + b * m)[i] = __builtin_nan("");
-                    if (tid == 0) fail_status(p, b);
+                    reject_instance<TH>(p, b, xo, yo);
                     return;
                 }
                 status = MPCQP_NON_CVX_;
@@ -307,9 +280,7 @@ __device__ __forceinline__ void solve_h_body(const KParams& p, double* __restric
         const double rvi = cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho);
         const bool rows_wave = tid < mp;
         if (rows_wave) L.w[ri] = rv * Z - y;
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+        const int stop_at = run_stop(p, iter);
         bool pend = false;  // xt holds an x~ whose x update the rhs has not applied yet
         // the loop's scalar constants in VGPRs (through an empty asm): held in SGPRs, the
         // compiler spilled them to VGPR lanes and read all sixteen back (v_readlane) at every
@@ -551,51 +522,23 @@ __device__ __forceinline__ void solve_h_body(const KParams& p, double* __restric
         if (!stop && do_rho) {
             Res R;
             R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
+            adapt_rho(p, R, rho, rho_updates, need_factor);
         }
         __syncthreads();
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
     const double cval = cscal(0), cinv = cscal(1);
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<TH>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<TH>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<TH>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<TH>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<TH>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<TH>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
         if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-            p.prof[b * kProfSlots + 15] = t0w;
+            prof_flush(p, b, L, t0c, t0w, 14);
         }
     }
 #endif
-#undef PH
 }
 
 template <int K, int KC, int KPK, int QR>

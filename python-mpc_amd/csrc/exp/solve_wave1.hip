@@ -61,51 +61,26 @@ __global__ __launch_bounds__(TW, 1) void k_solve_w(KParams p, double* __restrict
     const int kb0 = h, kb1 = 3 - h;
     constexpr int NB = 4, NP = NB * (NB - 1) / 2;  // exactly four blocks (solve.hip::variant_fits)
     const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
+    const int m = p.m, npad = p.npad, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
     const double* Hg = p.H + b * (long)p.nb * SS;
     const double* Sg = p.Si + b * (long)p.nb * SS;
 
     if (p.err[b]) {  // invalid data (flagged by setup/update): NaN outputs
-        for (int j = lane; j < n; j += TW) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = lane; i < m; i += TW) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (lane == 0) fail_status(p, b);
+        reject_instance<TW>(p, b, xo, yo);
         return;
     }
 
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (lane < 16) L.pacc[lane] = 0; }
-#define PH(k) if (prof && lane == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START
 
     const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
     double rho = p.scal[b * 4 + 2];
     const double sigma = p.sigma, alpha = p.alpha;
     const bool warm = p.warm_start != 0;
-    for (int e = lane; e < nnzA; e += TW) L.Acsc[e] = p.Ax[b * nnzA + e];
-    if (lane == 0) L.Acsc[nnzA] = 0.0;  // the gather lists' padding slot
-    for (int v = lane; v < nnzP; v += TW) L.Pv[v] = p.Px[b * nnzP + v];
-    if (lane == 0) L.Pv[nnzP] = 0.0;
     const int mp = solve_mpad(m);
-    for (int i = lane; i < mp; i += TW) {  // rows >= m: inert padding (l = u = 0, z = 0)
-        const bool in = i < m;
-        L.lo[i] = in ? p.l[b * m + i] : 0.0;
-        L.up[i] = in ? p.u[b * m + i] : 0.0;
-        L.ct[i] = in ? p.ct[b * m + i] : 0;
-        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
-    }
-    for (int pc = lane; pc < npad; pc += TW) {
-        L.qv[pc] = p.q[b * npad + pc];
-        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
-    }
+    load_instance<TW>(p, b, C, warm);
     if (lane < S) L.cor[lane] = 0.0;  // block 0 has no phase-A correction
-    if (lane < 16) L.res[lane] = 0.0;
-    if (lane < 4) L.flag[lane] = 0;
 
     int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
     bool can_check = false, need_factor = true;
@@ -125,9 +100,7 @@ __global__ __launch_bounds__(TW, 1) void k_solve_w(KParams p, double* __restrict
             const bool ok = factorize_nl<TW>(p.self, b, rho);
             if (!ok) {
                 if (iter == 0) {
-                    for (int j = lane; j < n; j += TW) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = lane; i < m; i += TW) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (lane == 0) fail_status(p, b);
+                    reject_instance<TW>(p, b, xo, yo);
                     return;
                 }
                 status = MPCQP_NON_CVX_;
@@ -180,9 +153,7 @@ __global__ __launch_bounds__(TW, 1) void k_solve_w(KParams p, double* __restrict
             rvi[s] = cl < 0 ? 1.0 / RHO_MIN : (cl > 0 ? 1.0 / r_hi : 1.0 / rho);
             L.w[i] = rv[s] * Z[s] - y[s];  // w = rho z_prev - y (rho may be new)
         }
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+        const int stop_at = run_stop(p, iter);
         __syncthreads();
         PH(5)
         while (iter < stop_at) {
@@ -345,59 +316,23 @@ __global__ __launch_bounds__(TW, 1) void k_solve_w(KParams p, double* __restrict
         can_check = p.check_term && (iter % p.check_term == 0);
         const bool do_rho = p.adaptive_rho && p.rho_interval && (iter % p.rho_interval == 0);
         if (!can_check && !do_rho) break;  // max_iter reached
-        update_info_nl<TW>(p.self, b, cinv);
         info_iter = iter;
-        bool stop = false;
-        if (can_check) {
-            status = check_termination_nl<TW>(p.self, b, cval, cinv, 0);
-            stop = status != MPCQP_UNSOLVED_;
-        }
-        if (!stop && do_rho) {
-            Res R;
-            R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
-        }
+        const bool stop = check_and_adapt<TW>(p, b, L, cval, cinv, can_check, do_rho, status, rho, rho_updates,
+                                                need_factor);
         __syncthreads();
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<TW>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<TW>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<TW>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<TW>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<TW>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<TW>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
         if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 12; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
+            prof_flush(p, b, L, t0c, t0w, 11);
         }
     }
 #endif
-#undef PH
 }
 
 template <int K, int RS>

@@ -65,7 +65,8 @@ struct KParams {
     int apart;  // k_solve_b's bottom chain may update the middle block in place (solve_big.hip::middle_apart;
                 // MPCQP_MIDDLE_APART=0: never, A/B)
     int *ostat, *oiter;  // per-call copies of status / iter (mpcqp_solve_device's outputs), or null
-    const struct KParams* self;  // device copy of this block (read by the out-of-line device functions)
+    const struct KParams* self;  // device copy of this block (read by the out-of-line device functions: the _nl
+                                 // phases of solve_phases.h, called from its shared shell -- check_and_adapt, conclude)
     long long* prof;  // optional per-instance phase timers (MPCQP_PHASE_PROF=1), kProfSlots each
     // settings
     double sigma, alpha, eps_abs, eps_rel, eps_pinf, eps_dinf, rho0, rho_tol, delta;

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
                                                 int factor_only) {
     const int tid = threadIdx.x;
     const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
+    const int m = p.m, npad = p.npad, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
     double* X = C.X;
@@ -271,26 +271,18 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
     double* const DX = TRI ? L.xt : L.rb;
 
     if (p.err[b]) {  // invalid data (flagged by setup/update): NaN outputs
-        for (int j = tid; j < n; j += T) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += T) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
+        reject_instance<T>(p, b, xo, yo);
         return;
     }
-
-    // optional phase timers (thread 0's shader clock; every phase ends at a barrier)
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START  // optional phase timers (device_common.h)
 
     const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
     double rho = p.scal[b * 4 + 2];
     const double sigma = p.sigma, alpha = p.alpha;
     const bool warm = p.warm_start != 0;
+    // the instance into LDS (the wave kernels' load_instance with unpadded rows, and delta y in
+    // LDS; spelled out here: as a function it cost variant 6 four more spilled SGPRs)
+    const int nnzP = p.nnzP;
     for (int e = tid; e < nnzA; e += T) L.Acsc[e] = p.Ax[b * nnzA + e];
     if (tid == 0) L.Acsc[nnzA] = 0.0;  // the gather lists' padding slot
     for (int v = tid; v < nnzP; v += T) L.Pv[v] = p.Px[b * nnzP + v];
@@ -322,7 +314,7 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
     PH(5)
     // The solve alternates "runs" of ADMM iterations up to the next termination /
     // rho-adaptation point (no calls, everything in registers and LDS) with the
-    // out-of-line phases.  The per-thread run state (factor tiles, gather lists)
+    // out-of-line phases (solve_phases.h: check_and_adapt between runs, conclude at the end).  The per-thread run state (factor tiles, gather lists)
     // is re-derived at the start of every run, so it is not live across a call
     // (the calling convention would otherwise spill it to scratch).
     for (;;) {
@@ -332,9 +324,7 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
             const bool ok = factorize_nl<T>(p.self, b, rho);
             if (!ok) {
                 if (iter == 0) {
-                    for (int j = tid; j < n; j += T) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = tid; i < m; i += T) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (tid == 0) fail_status(p, b);
+                    reject_instance<T>(p, b, xo, yo);
                     return;
                 }
                 status = MPCQP_NON_CVX_;
@@ -369,6 +359,7 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
             }
         }
         // the run ends at the next termination check / rho adaptation / max_iter
+        // (solve_phases.h::run_stop, spelled out: the call moved the loop's spill reloads)
         int stop_at = p.max_iter;
         if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
         if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
@@ -429,64 +420,27 @@ __global__ __launch_bounds__(T, W) void k_solve(KParams p, double* __restrict__ 
 #pragma unroll
         for (int s = 0; s < RS; ++s) { const int i = tid + s * T; if (i < m) L.ys[i] = y[s]; }
         __syncthreads();
-        // ---- out-of-line phases (only scalars live across these calls) ----
+        // ---- out-of-line phases (solve_phases.h::check_and_adapt; only scalars live across
+        // these calls) ----
         can_check = p.check_term && (iter % p.check_term == 0);
         const bool do_rho = p.adaptive_rho && p.rho_interval && (iter % p.rho_interval == 0);
         if (!can_check && !do_rho) break;  // max_iter reached
-        update_info_nl<T>(p.self, b, cinv);
         info_iter = iter;
-        bool stop = false;
-        if (can_check) {
-            status = check_termination_nl<T>(p.self, b, cval, cinv, 0);
-            stop = status != MPCQP_UNSOLVED_;
-        }
-        if (!stop && do_rho) {
-            Res R;
-            R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
-        }
+        const bool stop = check_and_adapt<T>(p, b, L, cval, cinv, can_check, do_rho, status, rho, rho_updates,
+                                             need_factor);
         __syncthreads();  // red / res reused
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
     // ys holds y here
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<T>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<T>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<T>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<T>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<T>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<T>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 12; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-        }
+        if (tid == 0) prof_flush(p, b, L, t0c, t0w, 11);
     }
 #endif
-#undef PH
 }
 
 // ------------------------------------------------------------------ polish --

@@ -70,12 +70,7 @@ __device__ __forceinline__ bool factorize2(const KP& p, SLds& L, double* __restr
     double *SP = L.SP, *DK = L.DK, *EK = L.EK;                                   // top chain
     double *SP2 = X2, *DK2 = X2 + SS, *EK2 = X2 + 2 * SS, *EKp = X2 + 3 * SS;   // bottom chain
     bool ok = true;
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     auto init = [&](int k, double* D, double* E, int t0, int stride) {
         for (int e = t0; e < SS; e += stride) {
             const int r = e >> 5;
@@ -234,7 +229,6 @@ __device__ __forceinline__ bool factorize2(const KP& p, SLds& L, double* __restr
         if (!(okslot[0] > 0.5)) ok = false;
         FPH(10)
     }
-#undef FPH
     return ok;
 }
 
@@ -534,12 +528,7 @@ __device__ __forceinline__ bool factorize2s(const KP& p, SLds& L, double rho, do
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     auto rows = [&](int a, int n) -> unsigned { return n <= 0 ? 0u : (((n >= 32 ? ~0u : ((1u << n) - 1u))) << a); };
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     bool okw = true;
     // stage 1
 #pragma unroll 1
@@ -659,7 +648,6 @@ __device__ __forceinline__ bool factorize2s(const KP& p, SLds& L, double rho, do
         FPH(11)
     }
     }
-#undef FPH
     if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
     __syncthreads();
     bool ok = true;

@@ -3,6 +3,12 @@
 // stand-alone kernel's, instruction for instruction) and into solve_b_body, which the persistent
 // form loops over.  In scope at the include: p (the parameter block), b (the instance), tid, xo,
 // yo, factor_only and the template parameters TTK, NS, K, CS, RS, IF.
+// The shell around the ADMM loop (invalid-data exits, staging, the run's stop, the between-run
+// block, the conclusion) is k_solve's, but spelled out here, not taken from solve_phases.h's
+// shared functions (reject_instance ... conclude): with any of them -- adapt_rho and
+// has_solution alone included -- the compiler allocates this kernel's scalar registers
+// differently (4 to 6 fewer spilled SGPRs, other lanes read back inside the sweep-step loops
+// that tests/test_isa_shape.py pins).  A change to the shell has to be repeated here.
     const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA, nb = p.nb, amax = p.amax;
     SL2 C = carve(p);
     SLds& L = C.L;
@@ -23,14 +29,7 @@
         return;
     }
 
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START
 
     const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
     double rho = p.scal[b * 4 + 2];
@@ -274,13 +273,7 @@
         __syncthreads();
         PH(5)
         if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-            p.prof[b * kProfSlots + 15] = t0w;  // (the start, for the dispatch timeline)
+            prof_flush(p, b, L, t0c, t0w, 14);
             if constexpr (!IF) {  // the CU: HW_REG_HW_ID, HW_REG_XCC_ID (tools/dispatch_timeline.py)
                 p.prof[b * kProfSlots + 22] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
                 p.prof[b * kProfSlots + 23] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (15 << 11));
@@ -298,4 +291,3 @@
         }
     }
 #endif
-#undef PH

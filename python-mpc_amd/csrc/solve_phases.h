@@ -2,8 +2,9 @@
 // (solve.hip: one 256-thread workgroup per QP; solve_wave.hip: one 64-lane wave per
 // QP): the LDS carve, the in-kernel factorisation of K, the packed gather lists
 // and the out-of-line phases (update_info, check_termination with the
-// infeasibility certificates, objective, store_solution).  Everything is templated
-// on TT, the number of threads working on one QP.
+// infeasibility certificates, objective, store_solution), and the shell every solve
+// kernel puts around its own ADMM loop (reject_instance ... conclude, at the end).
+// Everything is templated on TT, the number of threads working on one QP.
 //
 // Reference semantics: OSQP 0.6 as called at vehicle_lateral_mpc_slack_increment.py:248
 // and Control/MPC/mpc_dynamics.py:396; oracle/osqp_oracle.c restates the same
@@ -550,12 +551,7 @@ __device__ __forceinline__ bool factorize_w2(const KP& p, SLds& L, const double 
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     bool okw = true;
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
@@ -618,7 +614,6 @@ __device__ __forceinline__ bool factorize_w2(const KP& p, SLds& L, const double 
     if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
     __syncthreads();
     FPH(9)
-#undef FPH
     return okf[0] > 0.5 && okf[1] > 0.5;
 }
 
@@ -653,12 +648,7 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     const bool sw = TT == 256 || w < 4;  // a stage-1 wave (wave w: block w)
     constexpr bool PR = __is_base_of(KParamsPR, KP);  // the pivot in registers (gj_seg SEG 3 / 4)
     // an eliminated column's pivot K_jj is a pivot of the full KKT factorisation too: a
@@ -755,7 +745,6 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
     if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
     __syncthreads();
     FPH(9)
-#undef FPH
     return okf[0] > 0.5 && okf[1] > 0.5 && okf[2] > 0.5 && okf[3] > 0.5;
 }
 
@@ -885,12 +874,7 @@ __device__ __forceinline__ bool factorize_w8(const KP& p, SLds& L, const double 
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     assemble_block<false, true>(p, L, rho, w, Sg + (long)w * SS, Ek(w), lane, 64, wave_sync);
     wave_sync();
     FPH(8)
@@ -945,7 +929,6 @@ __device__ __forceinline__ bool factorize_w8(const KP& p, SLds& L, const double 
     if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
     __syncthreads();
     FPH(9)
-#undef FPH
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < NB; ++k) ok = ok && okf[k] > 0.5;
@@ -980,12 +963,7 @@ __device__ __forceinline__ bool factorize_g(const KP& p, SLds& L, const double r
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     bool okw = true;
 #pragma unroll 1
     for (int k = w; k < nb; k += 4) {
@@ -1040,7 +1018,6 @@ __device__ __forceinline__ bool factorize_g(const KP& p, SLds& L, const double r
     if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
     __syncthreads();
     FPH(9)
-#undef FPH
     return okf[0] > 0.5 && okf[1] > 0.5 && okf[2] > 0.5 && okf[3] > 0.5;
 }
 
@@ -1083,12 +1060,7 @@ __device__ __forceinline__ bool factorize(const KP& p, SLds& L, double rho, doub
     double* SP = L.SP;
     double* DK = L.DK;
     double* EK = L.EK;
-#ifdef MPCQP_PHASE_PROF
-    long long tf = clock64();
-#define FPH(k) if (tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tf; tf = t_; }
-#else
-#define FPH(k)
-#endif
+    FPROF_START
     auto assemble = [&](const int k, double* __restrict__ D, double* __restrict__ E, const int t0, const int nt,
                         auto sync) __attribute__((always_inline)) {
         assemble_block<POL, false>(p, L, rho, k, D, E, t0, nt, sync);
@@ -1195,7 +1167,6 @@ __device__ __forceinline__ bool factorize(const KP& p, SLds& L, double rho, doub
         if (!OVL) __syncthreads();
         FPH(11)
     }
-#undef FPH
     return ok;
 }
 
@@ -1661,6 +1632,13 @@ __device__ __noinline__ void objective_nl(const KParams* gp, double cinv) {
     objective_ph<TT>(gp, cinv);
 }
 
+// the statuses that come with a point (x, y): every one but the certificates and "non convex"
+__device__ __forceinline__ bool has_solution(int status) {
+    return !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
+             status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
+             status == MPCQP_NON_CVX_);
+}
+
 // store_solution + info (y is in ys).  ONE (the one-shot fused setup + solve, mpcqp_set_one_shot):
 // no later call reads the workspace, so the warm-start iterates x, z, y and the infeasibility
 // certificates are not stored -- the outputs, the status / iteration count (the next dispatch
@@ -1682,9 +1660,7 @@ __device__ __forceinline__ void finalize_ph(const KParams* gp, long b, double* _
         const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
         rho_est = cmin(cmax(rho * sqrt(pr / (du + DIVISION_TOL)), RHO_MIN), RHO_MAX);
     }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
+    const bool has_sol = has_solution(status);
     const bool pinf = status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_;
     const bool dinf = status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_;
     // the objective: computed (objective_nl) when there is a solution, else the value the
@@ -1745,6 +1721,119 @@ __device__ __noinline__ void finalize_nl(const KParams* gp, long b, double* __re
                                          double* __restrict__ yo, double cinv, double rho, int status,
                                          int info_iter, int rho_updates, int* ostat, int* oiter) {
     finalize_ph<TT, ONE, EDL>(gp, b, xo, yo, cinv, rho, status, info_iter, rho_updates, ostat, oiter);
+}
+
+// ---- the ADMM shell: what every solve kernel does around its own hot loop (k_solve, the two-,
+// four- and eight-wave kernels and the other experimental kernels of exp/).  All inline.  A site
+// that keeps its own text says why: the shipped ADMM loops must not move (tools/isa_diff.py
+// against the previous build), and k_solve_b's do with any of these (solve_big_body.inc keeps
+// the whole shell spelled out) ----
+
+// Invalid data (flagged by setup / update) or a first factorisation that failed: NaN outputs,
+// status "non convex", no iteration.  The caller returns.
+template <int TT, class KP>
+__device__ __forceinline__ void reject_instance(const KP& p, long b, double* __restrict__ xo,
+                                                double* __restrict__ yo) {
+    const int tid = threadIdx.x, n = p.n, m = p.m;
+    for (int j = tid; j < n; j += TT) if (xo) xo[b * n + j] = __builtin_nan("");
+    for (int i = tid; i < m; i += TT) if (yo) yo[b * m + i] = __builtin_nan("");
+    if (tid == 0) fail_status(p, b);
+}
+
+// Stage one instance in LDS, for the kernels with one row per lane (rows padded to whole waves,
+// solve_mpad): A, P (with their gather-padding zeros), the bounds and row classes -- rows >= m
+// are inert (l = u = 0, z = 0) --, q, the warm-start (or zero) x and z, and the phases' shared
+// slots.  k_solve and k_solve_b (unpadded rows, delta y in LDS) and the four-wave kernel keep
+// their own loops: through a function their register allocation moved (their comments say how).
+template <int TT, class KP>
+__device__ __forceinline__ void load_instance(const KP& p, long b, const SL2& C, bool warm) {
+    const int tid = threadIdx.x, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
+    const SLds& L = C.L;
+    for (int e = tid; e < nnzA; e += TT) L.Acsc[e] = p.Ax[b * nnzA + e];
+    if (tid == 0) L.Acsc[nnzA] = 0.0;  // the gather lists' padding slot
+    for (int v = tid; v < nnzP; v += TT) L.Pv[v] = p.Px[b * nnzP + v];
+    if (tid == 0) L.Pv[nnzP] = 0.0;
+    const int mp = solve_mpad(m);
+    for (int i = tid; i < mp; i += TT) {
+        const bool in = i < m;
+        L.lo[i] = in ? p.l[b * m + i] : 0.0;
+        L.up[i] = in ? p.u[b * m + i] : 0.0;
+        L.ct[i] = in ? p.ct[b * m + i] : 0;
+        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
+    }
+    for (int pc = tid; pc < npad; pc += TT) {
+        L.qv[pc] = p.q[b * npad + pc];
+        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
+    }
+    if (tid < 16) L.res[tid] = 0.0;
+    if (tid < 4) L.flag[tid] = 0;
+}
+
+// the iteration a run stops at: the next termination check / rho adaptation / max_iter
+// (k_solve and k_solve_b spell it out: this call in front of their loops changed the loops)
+template <class KP>
+__device__ __forceinline__ int run_stop(const KP& p, int iter) {
+    int stop_at = p.max_iter;
+    if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
+    if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+    return stop_at;
+}
+
+// OSQP 0.6 adapt_rho (compute_rho_estimate on the residuals R of the last update_info): the
+// new rho is taken, and a refactorisation asked for, outside the rho_tol window only
+template <class KP>
+__device__ __forceinline__ void adapt_rho(const KP& p, const Res& R, double& rho, int& rho_updates,
+                                          bool& need_factor) {
+    const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
+    const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
+    double rn = rho * sqrt(pr / (du + DIVISION_TOL));
+    rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
+    if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
+        rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
+        rho_updates++;
+        need_factor = true;
+    }
+}
+
+// Between two runs, for the kernels whose checks are the out-of-line phases (ys holds y):
+// update_info, the termination check where one is due, else / then the rho step.  Returns
+// whether the solve stops.
+template <int TT, class KP>
+__device__ __forceinline__ bool check_and_adapt(const KP& p, long b, const SLds& L, double cval, double cinv,
+                                                bool can_check, bool do_rho, int& status, double& rho,
+                                                int& rho_updates, bool& need_factor) {
+    update_info_nl<TT>(p.self, b, cinv);
+    bool stop = false;
+    if (can_check) {
+        status = check_termination_nl<TT>(p.self, b, cval, cinv, 0);
+        stop = status != MPCQP_UNSOLVED_;
+    }
+    if (!stop && do_rho) {
+        Res R;
+        R.restore(L.res);
+        adapt_rho(p, R, rho, rho_updates, need_factor);
+    }
+    return stop;
+}
+
+// The end of every solve (ys holds y): the check the last run did not have, the objective, the
+// approximate check of an unsolved instance ("max iterations reached" if that fails too), and
+// the outputs (finalize_nl)
+template <int TT, bool ONE = false, bool EDL = false, class KP>
+__device__ __forceinline__ void conclude(const KP& p, long b, double* __restrict__ xo, double* __restrict__ yo,
+                                         double cval, double cinv, double rho, int& status, bool can_check,
+                                         int iter, int info_iter, int rho_updates) {
+    if (!can_check && status == MPCQP_UNSOLVED_) {
+        update_info_nl<TT, EDL>(p.self, b, cinv);
+        info_iter = iter;
+        status = check_termination_nl<TT, EDL>(p.self, b, cval, cinv, 0);
+    }
+    if (has_solution(status)) objective_nl<TT>(p.self, cinv);
+    if (status == MPCQP_UNSOLVED_) {
+        status = check_termination_nl<TT, EDL>(p.self, b, cval, cinv, 1);
+        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
+    }
+    finalize_nl<TT, ONE, EDL>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
 }
 
 template <int TT>

@@ -41,60 +41,27 @@ __device__ __forceinline__ void solve_w2_body(const KParams& p, double* __restri
     const int rq = r >> 2, cq = r & 3;         // recomputed row / column chunk
     constexpr int NB = 4, NP = NB * (NB - 1) / 2;  // exactly four blocks (solve.hip::variant_fits)
     const long b = instance_of(p);
-    const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
+    const int m = p.m, npad = p.npad, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
     const double* Hg = p.H + b * (long)p.nb * SS;
     // S_k^{-1} stays in LDS after the carve (lds_w2_bytes): at one wave per SIMD two
     // workgroups share a CU, so the LDS is there; nothing goes to / comes from the workspace
-    double* const Sg = C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16);
+    double* const Sg = w4_tiles(p, C);
 
     if (p.err[b]) {  // invalid data (flagged by setup/update): NaN outputs
-        for (int j = tid; j < n; j += T2) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += T2) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
+        reject_instance<T2>(p, b, xo, yo);
         return;
     }
-
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
-#ifdef MPCQP_CHECK_PROF  // diagnostic: slots 12-14 time the run end / reductions / certificates of a check
-#define PHL(k) PH(2)
-#define PHC(k) PH(k)
-#else
-#define PHL(k) PH(k)
-#define PHC(k)
-#endif
+    PROF_START
 
     const double cval = p.scal[b * 4 + 0], cinv = p.scal[b * 4 + 1];
     double rho = p.scal[b * 4 + 2];
     const double sigma = p.sigma, alpha = p.alpha;
     const bool warm = p.warm_start != 0;
-    for (int e = tid; e < nnzA; e += T2) L.Acsc[e] = p.Ax[b * nnzA + e];
-    if (tid == 0) L.Acsc[nnzA] = 0.0;  // the gather lists' padding slot
-    for (int v = tid; v < nnzP; v += T2) L.Pv[v] = p.Px[b * nnzP + v];
-    if (tid == 0) L.Pv[nnzP] = 0.0;
     const int mp = solve_mpad(m);
-    for (int i = tid; i < mp; i += T2) {  // rows >= m: inert padding (l = u = 0, z = 0)
-        const bool in = i < m;
-        L.lo[i] = in ? p.l[b * m + i] : 0.0;
-        L.up[i] = in ? p.u[b * m + i] : 0.0;
-        L.ct[i] = in ? p.ct[b * m + i] : 0;
-        C.Z[i] = (in && warm) ? p.z[b * m + i] : 0.0;
-    }
-    for (int pc = tid; pc < npad; pc += T2) {
-        L.qv[pc] = p.q[b * npad + pc];
-        C.X[pc] = warm ? p.x[b * npad + pc] : 0.0;
-    }
+    load_instance<T2>(p, b, C, warm);
     if (tid < 16) L.cor[(tid >> 3) * 32 + (tid & 7)] = 0.0;  // cw[w][0][*]: block 0 has no correction
-    if (tid < 16) L.res[tid] = 0.0;
-    if (tid < 4) L.flag[tid] = 0;
 
     int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
     bool can_check = false, need_factor = true;
@@ -126,9 +93,7 @@ __device__ __forceinline__ void solve_w2_body(const KParams& p, double* __restri
             const bool ok = factorize_nl<T2>(p.self, b, rho, Sg);
             if (!ok) {
                 if (iter == 0) {
-                    for (int j = tid; j < n; j += T2) if (xo) xo[b * n + j] = __builtin_nan("");
-                    for (int i = tid; i < m; i += T2) if (yo) yo[b * m + i] = __builtin_nan("");
-                    if (tid == 0) fail_status(p, b);
+                    reject_instance<T2>(p, b, xo, yo);
                     return;
                 }
                 status = MPCQP_NON_CVX_;
@@ -209,9 +174,7 @@ __device__ __forceinline__ void solve_w2_body(const KParams& p, double* __restri
         __syncthreads();  // every ys / Z read before w is written
 #pragma unroll
         for (int s = 0; s < RS; ++s) L.w[ri[s]] = rv[s] * Z[s] - y[s];  // w = rho z_prev - y (rho may be new)
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+        const int stop_at = run_stop(p, iter);
         __syncthreads();
         PH(5)
         double* const cw = L.cor + w * 32;  // this wave's c_k rows < 8
@@ -543,55 +506,25 @@ __device__ __forceinline__ void solve_w2_body(const KParams& p, double* __restri
         if (!stop && do_rho) {
             Res R;
             R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
+            adapt_rho(p, R, rho, rho_updates, need_factor);
         }
         __syncthreads();
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<T2>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<T2>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<T2>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<T2>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<T2>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<T2>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
         if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
+            prof_flush(p, b, L, t0c, t0w, 14);
 #ifndef MPCQP_CHECK_PROF
             p.prof[b * kProfSlots + 2] = L.pacc[12] + L.pacc[13] + L.pacc[14];
 #endif
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-            p.prof[b * kProfSlots + 15] = t0w;  // absolute start (100 MHz): dispatch order / residency
         }
     }
 #endif
-#undef PH
-#undef PHL
-#undef PHC
 }
 
 // the kernel: the solve, then (last workgroup only) the dispatch order of the next launch
@@ -811,9 +744,8 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     constexpr bool WV = GL == 3;             // ... with the loop's phase A / B reads issued earlier
     // GL 1: the G blocks (amax x S per pair) go to LDS after the S_k^{-1} tiles; GL 2: straight
     // into gl (factorize_w4_gl), no copy
-    const double* Hg = G1 ? C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16) + (long)NB * SS
-                           : p.H + b * (long)p.nb * SS;
-    double* const Sg = C.L.Acsc + 2 * ((lds_base_bytes(p) + 15) / 16);  // S_k^{-1} tiles in LDS (lds_w2_bytes)
+    const double* Hg = G1 ? w4_tiles(p, C) + (long)NB * SS : p.H + b * (long)p.nb * SS;
+    double* const Sg = w4_tiles(p, C);  // S_k^{-1} tiles in LDS (lds_w2_bytes)
     // SWZ: the tiles in tile_at<true>'s layout (solve_phases.h) -- the one-shot form 2 without
     // eliminated columns and amax <= 5, the headline's instantiation.  Its tiles never leave LDS
     // (no RU / factor_only copy, no dense rows); the other instantiations' stay row-major
@@ -827,19 +759,10 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     constexpr bool LEAN = SWZ;
 
     if (p.err[b]) {
-        for (int j = tid; j < n; j += T4) if (xo) xo[b * n + j] = __builtin_nan("");
-        for (int i = tid; i < m; i += T4) if (yo) yo[b * m + i] = __builtin_nan("");
-        if (tid == 0) fail_status(p, b);
+        reject_instance<T4>(p, b, xo, yo);
         return;
     }
-#ifdef MPCQP_PHASE_PROF
-    long long tph = 0, t0c = 0, t0w = 0;
-    const bool prof = p.prof != nullptr;
-    if (prof) { t0w = wall_clock64(); t0c = tph = clock64(); if (tid < 16) L.pacc[tid] = 0; }
-#define PH(k) if (prof && tid == 0) { const long long t_ = clock64(); L.pacc[k] += t_ - tph; tph = t_; }
-#else
-#define PH(k)
-#endif
+    PROF_START
     // OPQ: the instantiations whose solve loop leaves no register for values used only at run
     // starts, refactorisations and checks (the eliminated-column and QR = 8 ones); they form
     // those values where used (see the lane identity at the top of the outer loop)
@@ -853,6 +776,8 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     const bool warm = !ONE && p.warm_start != 0;
     const int mp = solve_mpad(m);
     if constexpr (!ONE) {
+        // (load_instance's text: the call cost k_solve_w4 two spilled SGPRs without eliminated
+        // columns and moved four with them)
         for (int e = tid; e < nnzA; e += T4) L.Acsc[e] = p.Ax[b * nnzA + e];
         if (tid == 0) L.Acsc[nnzA] = 0.0;
         for (int v = tid; v < nnzP; v += T4) L.Pv[v] = p.Px[b * nnzP + v];
@@ -962,6 +887,8 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             }
             if (!ok) {
                 if (iter == 0) {
+                    // (reject_instance's stores through opaque_ptr, on purpose: with the plain
+                    // ones the eliminated-column instantiations' ADMM loop changes)
                     if (xo) for (int j = tid; j < n; j += T4) opaque_ptr(xo + b * n)[j] = __builtin_nan("");
                     if (yo) for (int i = tid; i < m; i += T4) opaque_ptr(yo + b * m)[i] = __builtin_nan("");
                     if (tid == 0) fail_status(p, b);
@@ -1139,9 +1066,7 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 for (int q = 0; q < QR; ++q) gc[s][q] = s < nsw ? lds_at(gslot[s] + q * S * 8) : 0.0;
         }
         if (rows_wave) L.w[ri] = rv * Z - y;  // (lanes past the padded rows may hold a stale y)
-        int stop_at = p.max_iter;
-        if (p.check_term) stop_at = min(stop_at, (iter / p.check_term + 1) * p.check_term);
-        if (p.adaptive_rho && p.rho_interval) stop_at = min(stop_at, (iter / p.rho_interval + 1) * p.rho_interval);
+        const int stop_at = run_stop(p, iter);
         __syncthreads();
         PH(15)  // (the run starts; slot 5 keeps the kernel's start and finalize)
         double* const cw = L.cor + w * 8;                 // c_w rows < 8
@@ -1579,44 +1504,20 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             Res R;
             if constexpr (LEAN) R = Rk;  // (every thread formed the same Res from the reduced maxima)
             else R.restore(L.res);
-            const double pr = R.rpri / (cmax(R.rz, R.rax) + DIVISION_TOL);
-            const double du = R.rdua / (cmax(cmax(R.rq, R.raty), R.rpx) + DIVISION_TOL);
-            double rn = rho * sqrt(pr / (du + DIVISION_TOL));
-            rn = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-            if (rn > rho * p.rho_tol || rn < rho / p.rho_tol) {
-                rho = cmin(cmax(rn, RHO_MIN), RHO_MAX);
-                rho_updates++;
-                need_factor = true;
-            }
+            adapt_rho(p, R, rho, rho_updates, need_factor);
         }
         __syncthreads();
         PH(4)
         if (stop || iter >= p.max_iter) break;
     }
     const double cval = cscal(0), cinv = cscal(1);
-    if (!can_check && status == MPCQP_UNSOLVED_) {
-        update_info_nl<T4, G1>(p.self, b, cinv);
-        info_iter = iter;
-        status = check_termination_nl<T4, G1>(p.self, b, cval, cinv, 0);
-    }
-    const bool has_sol = !(status == MPCQP_PRIMAL_INFEASIBLE_ || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_DUAL_INFEASIBLE_ || status == MPCQP_DUAL_INFEASIBLE_INACCURATE_ ||
-                           status == MPCQP_NON_CVX_);
-    if (has_sol) objective_nl<T4>(p.self, cinv);
-    if (status == MPCQP_UNSOLVED_) {
-        status = check_termination_nl<T4, G1>(p.self, b, cval, cinv, 1);
-        if (status == MPCQP_UNSOLVED_) status = MPCQP_MAX_ITER_REACHED_;
-    }
-    finalize_nl<T4, ONE, G1>(p.self, b, xo, yo, cinv, rho, status, info_iter, rho_updates, p.ostat, p.oiter);
+    conclude<T4, ONE, G1>(p, b, xo, yo, cval, cinv, rho, status, can_check, iter, info_iter, rho_updates);
 #ifdef MPCQP_PHASE_PROF
     if (prof) {
         __syncthreads();
         PH(5)
         if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
-#pragma unroll
-            for (int k = 8; k < 15; ++k) p.prof[b * kProfSlots + k] = L.pacc[k];
+            prof_flush(p, b, L, t0c, t0w, 14);
             p.prof[b * kProfSlots + 2] = L.pacc[12] + L.pacc[13] + L.pacc[14];
             // the check's and the tail's splits: slots 16-18 (a check up to its reduction, the
             // reduction, the run starts); 4 and 5 keep their totals
@@ -1625,13 +1526,9 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
             p.prof[b * kProfSlots + 16] = L.pacc[6];
             p.prof[b * kProfSlots + 17] = L.pacc[7];
             p.prof[b * kProfSlots + 18] = L.pacc[15];
-            p.prof[b * kProfSlots + 6] = clock64() - t0c;
-            p.prof[b * kProfSlots + 7] = wall_clock64() - t0w;
-            p.prof[b * kProfSlots + 15] = t0w;
         }
     }
 #endif
-#undef PH
 }
 
 // FO: the factor-only instantiation (api.hip::check_convex), so that the solve's own code
@@ -1710,50 +1607,65 @@ int one_shot_form(const KParams& p, size_t* lds) {
     return form;
 }
 
+// The four-wave kernel's instantiations, one shape per kind of plan (solve.hip's table gives the
+// preconditions): K / KC the row / column gather-list lengths, KPK the P terms per column, QR the
+// rows of the G blocks phase C sums (the nonzero ones: amax), SK / SAS the fused setup's list
+// length and A values per thread, EL eliminated columns (the slack layouts)
+template <int K_, int KPK_, int QR_, int SK_, int SAS_, bool EL_, int KC_>
+struct W4Shape {
+    static constexpr int K = K_, KPK = KPK_, QR = QR_, SK = SK_, SAS = SAS_, KC = KC_;
+    static constexpr bool EL = EL_;
+    template <bool FO = false, bool DK = false>
+    static constexpr auto solve() { return k_solve_w4<K, KPK, QR, EL, KC, FO, DK>; }
+    template <bool ONE = false, int GL = 0, bool DK = false>
+    static constexpr auto setup_solve() { return k_setup_solve_w4<K, KPK, QR, SK, SAS, EL, KC, DK, ONE, GL>; }
+    // the plan's lists fit the instantiation's (a shorter list would silently drop A entries)
+    static hipError_t fits(const KParams& p) { return lists_fit(p, K, KC, KPK, QR); }
+};
+using W4Elim = W4Shape<6, 4, 8, 8, 3, true, 8>;    // eliminated columns
+using W4Five = W4Shape<6, 4, 5, 6, 2, false, 6>;   // amax <= 5 (cfg 2, the headline)
+using W4Rest = W4Shape<6, 4, 8, 6, 2, false, 6>;
+// f(shape) for the plan's shape
+template <class F>
+static auto with_w4_shape(const KParams& p, F f) {
+    if (p.ne) return f(W4Elim{});
+    if (p.amax <= 5) return f(W4Five{});
+    return f(W4Rest{});
+}
+
 // the four-wave kernel's fused launch (variant_fits covers its preconditions: list lengths,
 // pk <= 4, nnzA <= 2 or 3 x T4)
 hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                  const double* l, const double* u, double* xo, double* yo, hipStream_t st,
                                  int one_shot) {
-    size_t lds1 = 0;
-    const int form = one_shot ? one_shot_form(p, &lds1) : 0;
-    if (form) {
-        decltype(&k_setup_solve_w4<6, 4, 5, 6, 2>) k4;
-        if (form == 2)
-            k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8, false, true, 1>
-                      : (p.amax <= 5 ? (one_shot == 2 ? k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 1>
-                                                      : k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 3>)
-                                     : k_setup_solve_w4<6, 4, 8, 6, 2, false, 6, false, true, 1>);
-        else if (form == 3)
-            k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8, false, true, 2>
-                      : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true, 2>
-                                     : k_setup_solve_w4<6, 4, 8, 6, 2, false, 6, false, true, 2>);
-        else
-            k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8, false, true>
-                      : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, false, true>
-                                     : k_setup_solve_w4<6, 4, 8, 6, 2, false, 6, false, true>);
-        hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k4, dim3((unsigned)B), dim3(T4), lds1, st, p, Px, Ax, q, l, u, xo, yo);
-        return hipGetLastError();
-    }
-    const size_t lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
-    // QR: rows of the G blocks phase C sums (the nonzero ones: amax)
-    // EL (eliminated columns, the slack layouts): three A values per setup thread
-    auto k4 = p.ne ? k_setup_solve_w4<6, 4, 8, 8, 3, true, 8>
-                   : (p.amax <= 5 ? k_setup_solve_w4<6, 4, 5, 6, 2> : k_setup_solve_w4<6, 4, 8, 6, 2>);
+    size_t lds = 0;
+    const int form = one_shot ? one_shot_form(p, &lds) : 0;
+    if (!form) lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
+    using Kernel = decltype(W4Five::setup_solve());
+    // one-shot form 2 is GL 1 (GL 3 on the headline's shape, unless one_shot == 2 asks for the
+    // A/B baseline), form 3 is GL 2, form 1 is the persisting loop on the one-shot setup
+    const Kernel k4 = with_w4_shape(p, [&](auto sh) -> Kernel {
+        using Sh = decltype(sh);
+        if (form == 2) {
+            if constexpr (!Sh::EL && Sh::QR <= 5)
+                if (one_shot != 2) return Sh::template setup_solve<true, 3>();
+            return Sh::template setup_solve<true, 1>();
+        }
+        if (form == 3) return Sh::template setup_solve<true, 2>();
+        if (form == 1) return Sh::template setup_solve<true>();
 #ifdef MPCQP_EXPERIMENTAL
-    if (!p.ne && p.amax <= 5 && dense_w4(p)) k4 = k_setup_solve_w4<6, 4, 5, 6, 2, false, 6, true>;
+        if constexpr (!Sh::EL && Sh::QR <= 5)
+            if (dense_w4(p)) return Sh::template setup_solve<false, 0, true>();
 #endif
-    hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
+        return Sh::setup_solve();
+    });
+    hipError_t e = with_w4_shape(p, [&](auto sh) { return decltype(sh)::fits(p); });
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k4, dim3((unsigned)B), dim3(T4), lds, st, p, Px, Ax, q, l, u, xo, yo);
     e = hipGetLastError();
-    if (e != hipSuccess || !p.polish) return e;
+    if (e != hipSuccess || !p.polish) return e;  // (a one-shot form implies no polish: one_shot_form)
     return launch_polish(p, B, xo, yo, st);
 }
 
@@ -1796,19 +1708,21 @@ size_t lds_w2_bytes(const KParams& p) {
     return 16 * ((lds_base_bytes(p) + 15) / 16) + sizeof(double) * (size_t)p.nb * SS;
 }
 
-// The four-wave kernel's instantiations (solve.hip's table gives the preconditions).
+// the four-wave kernel's solve (FO: setup()'s convexity check)
 hipError_t launch_solve_w4(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
                            KernelRef* ref) {
-    auto k = factor_only
-                 ? (p.ne ? k_solve_w4<6, 4, 8, true, 8, true>
-                         : (p.amax <= 5 ? k_solve_w4<6, 4, 5, false, 6, true> : k_solve_w4<6, 4, 8, false, 6, true>))
-                 : (p.ne ? k_solve_w4<6, 4, 8, true, 8>
-                         : (p.amax <= 5 ? k_solve_w4<6, 4, 5> : k_solve_w4<6, 4, 8>));
+    using Kernel = decltype(W4Five::solve());
+    const Kernel k = with_w4_shape(p, [&](auto sh) -> Kernel {
+        using Sh = decltype(sh);
+        if (factor_only) return Sh::template solve<true>();
 #ifdef MPCQP_EXPERIMENTAL
-    if (!factor_only && !p.ne && p.amax <= 5 && dense_w4(p)) k = k_solve_w4<6, 4, 5, false, 6, false, true>;
+        if constexpr (!Sh::EL && Sh::QR <= 5)
+            if (dense_w4(p)) return Sh::template solve<false, true>();
 #endif
+        return Sh::solve();
+    });
     const size_t lds = lds_w2_bytes(p);
-    hipError_t e = lists_fit(p, 6, p.ne ? 8 : 6, 4, p.ne || p.amax > 5 ? 8 : 5);
+    hipError_t e = with_w4_shape(p, [&](auto sh) { return decltype(sh)::fits(p); });
     if (e != hipSuccess) return e;
     if (ref) { *ref = {(const void*)k, T4, lds}; return hipSuccess; }
     e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
