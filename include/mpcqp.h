@@ -146,7 +146,10 @@ int mpcqp_update_batch(mpcqp_handle *h, const double *q, const double *l, const 
  * mentions at vehicle_lateral_mpc_slack_increment.py:236 (commented out). */
 int mpcqp_update_matrices_batch(mpcqp_handle *h, const double *Px, const int32_t *Px_idx, int32_t nPx,
                                 const double *Ax, const int32_t *Ax_idx, int32_t nAx);
-/* x, y may each be NULL (keeps the current iterate of that part). */
+/* osqp_warm_start / osqp_warm_start_x / osqp_warm_start_y (OSQP 0.6): x, y may each be NULL
+ * (keeps the current iterate of that part).  With x: x = D^-1 x0 and z = A x.  With y alone:
+ * y = c E^-1 y0, and x and z stay as the last solve (or setup) left them -- after a solve z is
+ * not A x, and OSQP keeps it too.  Turns the warm_start setting on. */
 int mpcqp_warm_start_batch(mpcqp_handle *h, const double *x, const double *y);
 /* osqp_update_settings / osqp_update_rho (OSQP 0.6; osqp-python's update_settings): max_iter,
  * eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho (with set_rho != 0 only, as osqp-python
@@ -159,7 +162,12 @@ int mpcqp_warm_start_batch(mpcqp_handle *h, const double *x, const double *y);
  * data, scaling, iterates, rho and row classes are kept, so the next solve continues exactly
  * as on a handle set up with polish on. */
 int mpcqp_update_settings(mpcqp_handle *h, const mpcqp_settings *s, int32_t set_rho);
-/* any output may be NULL */
+/* any output may be NULL.  Every solve starts from the status "unsolved" and reports its own
+ * conclusion.  (OSQP 0.6's osqp_solve keeps info.status_val of the previous solve when no
+ * osqp_update_* call came in between -- only those reset it -- and then skips the approximate
+ * check at the iteration cap: solve, warm_start, solve can report the first solve's "solved
+ * inaccurate" for a second one that is not.  With an update call between two solves, as the
+ * reference's loops make, the two agree.) */
 int mpcqp_solve_batch(mpcqp_handle *h, double *x, double *y, int32_t *status, int32_t *iters);
 /* info of the last solve; any output may be NULL */
 int mpcqp_get_info_batch(mpcqp_handle *h, double *obj_val, double *pri_res, double *dua_res,
@@ -186,7 +194,8 @@ int mpcqp_solve_device(mpcqp_handle *h, double *dx, double *dy, int32_t *dstatus
                        void *stream);
 /* setup + warm start of the same call: mpcqp_setup_device(dPx..du) followed by
  * mpcqp_warm_start_device(dx0, dy0), with identical results (either may be null, as there).
- * Where the wide batch setup applies (the long-horizon plans: setup_wide.h) both run as ONE
+ * Where mpcqp_setup_device takes the wide batch setup (the long-horizon plans: setup_wide.h;
+ * not the plans of up to 256 columns and rows, which set up through setup_r.h) both run as ONE
  * kernel -- each workgroup scales its instance and forms x = D^-1 x0, y = E^-1 y0 c, z = A x
  * from the values still on chip -- so the warm-start kernel's pass over the workspace goes.
  * The reference's warm-started step prob.setup(...); prob.warm_start(x=, y=); prob.solve()

@@ -626,6 +626,23 @@ int orc_warm_start(orc_work *w, const double *x, const double *y) {
     mat_vec(w->n, w->Ap, w->Ai, w->Ax, w->m, w->x, w->z, 0);
     return 0;
 }
+/* osqp_warm_start_x: x <- Dinv x0, z <- A x; y stays */
+int orc_warm_start_x(orc_work *w, const double *x) {
+    w->set.warm_start = 1;
+    memcpy(w->x, x, sizeof(double) * w->n);
+    if (w->set.scaling)
+        for (int j = 0; j < w->n; ++j) w->x[j] *= w->Dinv[j];
+    mat_vec(w->n, w->Ap, w->Ai, w->Ax, w->m, w->x, w->z, 0);
+    return 0;
+}
+/* osqp_warm_start_y: y <- c Einv y0; x and z stay (z is not A x after a solve) */
+int orc_warm_start_y(orc_work *w, const double *y) {
+    w->set.warm_start = 1;
+    memcpy(w->y, y, sizeof(double) * w->m);
+    if (w->set.scaling)
+        for (int i = 0; i < w->m; ++i) { w->y[i] *= w->Einv[i]; w->y[i] *= w->c; }  /* vec_ew_prod, vec_mult_scalar */
+    return 0;
+}
 
 /* ---- scaling.c: unscale_data (OSQP 0.6), used by the matrix updates ----
  * P <- cinv Dinv P Dinv (mat_mult_scalar, mat_premult_diag, mat_postmult_diag),

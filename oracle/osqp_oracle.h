@@ -93,7 +93,12 @@ int orc_update_P_A(orc_work *w, const double *Px, const int *Px_idx, int nP, con
                    const int *Ax_idx, int nA);
 /* osqp_update_settings (the settings OSQP lets change after setup; rho via osqp_update_rho) */
 int orc_update_settings(orc_work *w, const orc_settings *s, int set_rho);
+/* osqp_warm_start: x <- Dinv x0, y <- c Einv y0, z <- A x.  osqp_warm_start_x: x and z only
+ * (y stays).  osqp_warm_start_y: y only -- x and z stay, and after a solve z is not A x.
+ * All three turn the warm_start setting on. */
 int orc_warm_start(orc_work *w, const double *x, const double *y);
+int orc_warm_start_x(orc_work *w, const double *x);
+int orc_warm_start_y(orc_work *w, const double *y);
 int orc_solve(orc_work *w);
 /* x (n), y (m); certificates may be NULL */
 void orc_get_solution(const orc_work *w, double *x, double *y,

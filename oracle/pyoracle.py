@@ -84,6 +84,8 @@ def lib():
         L.orc_update_P_A.argtypes = [C.c_void_p, P(C.c_double), P(C.c_int), C.c_int,
                                      P(C.c_double), P(C.c_int), C.c_int]
         L.orc_warm_start.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double)]
+        L.orc_warm_start_x.argtypes = [C.c_void_p, P(C.c_double)]
+        L.orc_warm_start_y.argtypes = [C.c_void_p, P(C.c_double)]
         L.orc_solve.argtypes = [C.c_void_p]
         L.orc_get_solution.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double),
                                        P(C.c_double), P(C.c_double)]
@@ -207,9 +209,25 @@ class OSQP:
         self._settings = new
 
     def warm_start(self, x=None, y=None):
-        x = np.ascontiguousarray(x, np.float64); y = np.ascontiguousarray(y, np.float64)
-        lib().orc_warm_start(self._w, _dp(x), _dp(y))
-        self._settings["warm_start"] = True  # (osqp_warm_start turns the setting on)
+        """osqp.OSQP.warm_start: both (osqp_warm_start), x alone (osqp_warm_start_x: z = A x, y
+        kept) or y alone (osqp_warm_start_y: x and z kept)."""
+        if x is None and y is None:
+            raise ValueError("Unrecognized fields")
+        if x is not None:
+            x = np.ascontiguousarray(x, np.float64)
+            if x.size != self.n:
+                raise ValueError("Wrong dimension for variable x")
+        if y is not None:
+            y = np.ascontiguousarray(y, np.float64)
+            if y.size != self.m:
+                raise ValueError("Wrong dimension for variable y")
+        if x is not None and y is not None:
+            lib().orc_warm_start(self._w, _dp(x), _dp(y))
+        elif x is not None:
+            lib().orc_warm_start_x(self._w, _dp(x))
+        else:
+            lib().orc_warm_start_y(self._w, _dp(y))
+        self._settings["warm_start"] = True  # (osqp_warm_start* turn the setting on)
 
     def solve(self):
         L = lib()

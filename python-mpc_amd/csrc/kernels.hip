@@ -8,7 +8,7 @@
 //   k_setup  : osqp_setup -> scale_data (Ruiz, 10 passes + cost scaling),
 //              set_rho_vec (loose / equality / inequality classes)
 //   k_update : osqp_update_lin_cost / osqp_update_bounds (+ update_rho_vec)
-//   k_warm   : osqp_warm_start
+//   k_warm   : osqp_warm_start, osqp_warm_start_x, osqp_warm_start_y
 //   k_solve  : osqp_solve -> ADMM (update_xz_tilde, update_x, update_z,
 //              update_y), update_info / check_termination every
 //              check_termination iterations, adapt_rho + refactorisation,
@@ -347,6 +347,8 @@ __global__ __launch_bounds__(T) void k_warm(KParams p, const double* __restrict_
         }
     if (y_in)
         for (int i = tid; i < m; i += T) p.y[b * m + i] = ((1.0 / p.E[b * m + i]) * y_in[b * m + i]) * c;
+    // y alone (osqp_warm_start_y) keeps x and z: after a solve z is not A x
+    if (!x_in) return;
     __syncthreads();
     // z = A x (scaled)
     const double* Ax = p.Ax + b * p.nnzA;
@@ -436,7 +438,11 @@ hipError_t launch_warm(const KParams& p, long B, const double* x, const double* 
     hipLaunchKernelGGL(k_warm, dim3((unsigned)B), dim3(T), 0, st, p, x, y);
     return hipGetLastError();
 }
-bool setup_warm_fused(const KParams& p) { return setup_rw_fits(p) && !getenv_flag("MPCQP_SETUP_STAGED"); }
+// exactly where launch_setup takes the wide kernel: a plan it sets up through k_setup_r
+// (another summation order of the cost scale) runs launch_setup + launch_warm
+bool setup_warm_fused(const KParams& p) {
+    return !setup_r_variant(p) && setup_rw_fits(p) && !getenv_flag("MPCQP_SETUP_STAGED");
+}
 hipError_t launch_setup_warm(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                              const double* l, const double* u, const double* x0, const double* y0, hipStream_t st) {
     if (!setup_warm_fused(p)) {

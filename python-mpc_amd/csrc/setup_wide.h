@@ -16,7 +16,8 @@
 // WARM (mpcqp_setup_warm_device): the warm start of the same call follows in the workgroup, as
 // kernels.hip::k_warm computes it from the workspace -- x = D^-1 x0, y = E^-1 y0 c, z = A x over
 // each row's entries in CSR order -- from the values still on chip, in place of the zeros
-// setup writes (x0 / y0 null: those stay zero, as k_warm leaves them).
+// setup writes (x0 / y0 null: those stay zero, as k_warm leaves them; without x0
+// k_warm keeps z, the setup's zero, and z = A 0 here is that zero).
 //
 // TT = 1024, CS = 1: one instance per CU (the register lists need ~90 VGPRs), the latency
 // form for a few QPs.  TT = 512, CS = 2: two instances per CU (<= 128 VGPRs), for batches --

@@ -697,8 +697,8 @@ class DeviceBatch:
         _check(lib().mpcqp_warm_start_device(self._h.ptr, self._ptr(x), self._ptr(y), stream), "warm_start_device")
 
     def setup_warm(self, Px, Ax, q, l, u, x=None, y=None, stream=None):
-        """setup(Px, Ax, q, l, u) then warm_start(x, y) -- one fused kernel where the wide batch
-        setup applies (mpcqp_setup_warm_device; setup_warm_fused()), identical results."""
+        """setup(Px, Ax, q, l, u) then warm_start(x, y) -- one fused kernel where setup() takes the
+        wide batch setup (mpcqp_setup_warm_device; setup_warm_fused()), identical results."""
         self._shared(Px, Ax)
         _check(lib().mpcqp_setup_warm_device(self._h.ptr, self._ptr(Px), self._ptr(Ax), self._ptr(q), self._ptr(l),
                                              self._ptr(u), self._ptr(x), self._ptr(y), stream), "setup_warm_device")

@@ -123,6 +123,19 @@ class OSQP:
             up = self.u / self.E if u is None else u
             self._bounds(lo, up)
 
+    def warm_start(self, x=None, y=None):
+        """osqp.OSQP.warm_start (OSQP 0.6): x given: x = x0 / D and z = A x; y given: y = c y0 / E.
+        With y alone x and z stay (osqp_warm_start_y) -- after a solve z is not A x.  Turns the
+        warm_start setting on."""
+        if x is None and y is None:
+            raise ValueError("Unrecognized fields")
+        if x is not None:
+            self.x = np.asarray(x, float) / self.D
+            self.z = self.A @ self.x
+        if y is not None:
+            self.y = np.asarray(y, float) / self.E * self.c
+        self.warm = True
+
     def solve(self):
         from types import SimpleNamespace
         A, Pful, q, D, E, c = self.A, self.Pful, self.q, self.D, self.E, self.c

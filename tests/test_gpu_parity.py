@@ -1574,7 +1574,8 @@ def test_wide_setup_forms_and_fused_warm_start_agree(monkeypatch):
     """The wide batch setup (setup_wide.h): its 512-thread form (two instances per CU, batches of
     512 or more) and its 1024-thread form (MPCQP_SETUP_FULL=1), each as setup() + warm_start()
     and fused as setup_warm() (mpcqp_setup_warm_device: one kernel), give the same cfg-5 solve
-    bit for bit -- with x0 and y0, and with x0 alone (y stays zero as warm_start leaves it)."""
+    bit for bit -- with x0 and y0, with x0 alone (y stays zero as warm_start leaves it) and with y0
+    alone (x and z stay zero)."""
     import torch
     from osqp_amd import DeviceBatch, _drop_common_zeros
     from osqp_amd.mpc_device import warm_shift
@@ -1599,7 +1600,7 @@ def test_wide_setup_forms_and_fused_warm_start_agree(monkeypatch):
     h0.synchronize()
     xs, ys = warm_shift(b["N"], 8, 2, o[0], o[1])
     torch.cuda.synchronize()
-    for y0 in (ys, None):
+    for x0, y0 in ((xs, ys), (xs, None), (None, ys)):
         runs = []
         for full in ("0", "1"):
             monkeypatch.setenv("MPCQP_SETUP_FULL", full)
@@ -1608,10 +1609,10 @@ def test_wide_setup_forms_and_fused_warm_start_agree(monkeypatch):
                 assert h.setup_warm_fused() == 1
                 o = outs()
                 if fused:
-                    h.setup_warm(dPx, dAx, dq, dl, du, xs, y0)
+                    h.setup_warm(dPx, dAx, dq, dl, du, x0, y0)
                 else:
                     h.setup(dPx, dAx, dq, dl, du)
-                    h.warm_start(xs, y0)
+                    h.warm_start(x0, y0)
                 h.solve(*o)
                 h.synchronize()
                 runs.append([v.cpu().numpy() for v in o])

@@ -86,6 +86,40 @@ def test_oracle_matches_dense_restatement(golden, name):
         assert np.abs(r.y - y).max() < 1e-6 * max(1, np.abs(y).max())
 
 
+@pytest.mark.parametrize("part", ["x", "y", "xy"])
+@pytest.mark.parametrize("name", ["vanilla_n20.npz", "slack_n20.npz"])
+def test_oracle_warm_start_parts_match_dense_restatement(golden, name, part):
+    """OSQP 0.6's three warm starts (osqp_warm_start, _x, _y) on a used workspace, where
+    z != A x: five iterations, the warm start from half of their result, five more -- the
+    oracle against the dense restatement.  The y-only form must keep z: the premise holds it
+    apart from the both-form given the x of the first solve (which sets z = A x)."""
+    import osqp_dense_ref
+    for P, q, A, l, u, s in instances(golden, name):
+        def run(mod, start):
+            o = mod.OSQP()
+            o.setup(P, q, A, l, u, warm_start=True, max_iter=5, adaptive_rho_interval=100)
+            r0 = o.solve()
+            assert r0.info.iter == 5 and r0.info.status == "maximum iterations reached"
+            o.warm_start(**start(r0))
+            r = o.solve()
+            assert r.info.iter == 5 and r.info.status == "maximum iterations reached"
+            return r
+
+        half = lambda r0: {k: 0.5 * getattr(r0, k) for k in part}  # noqa: E731
+        ro, rd = run(pyoracle, half), run(osqp_dense_ref, half)
+        ro_both = run(pyoracle, lambda r0: dict(x=r0.x, y=0.5 * r0.y))
+        assert np.abs(ro.x - rd.x).max() < 1e-8 * max(1, np.abs(rd.x).max())
+        assert np.abs(ro.y - rd.y).max() < 1e-6 * max(1, np.abs(rd.y).max())
+        if part == "y":  # (keeping z is what the comparison above sees)
+            assert np.abs(ro.x - ro_both.x).max() > 1e-4 * max(1, np.abs(ro.x).max())
+    o = pyoracle.OSQP()
+    o.setup(P, q, A, l, u)
+    with pytest.raises(ValueError):
+        o.warm_start()
+    with pytest.raises(ValueError):
+        osqp_dense_ref.OSQP().warm_start()
+
+
 def test_oracle_update_and_warm_start(golden):
     """update(q,l,u) rescales with the setup-time scaling; warm start keeps iterates
     (slack script :237,248,269)."""

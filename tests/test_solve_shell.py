@@ -21,22 +21,12 @@ import pytest
 
 import isa_shape
 import pyoracle
-from osqp_amd import mpc
 from parity import check_agreement
+from solve_families import FAMILIES, batch as _batch, env as _env, handle as _handle, run as _run, \
+    out_of as _out_of, settings as _settings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "python-mpc_amd", "osqp_amd", "libmpcqp.so")
-B = 3
-SEED = {2: 337, 3: 6, 5: 75}
-
-FAMILIES = {  # name: (config, MPCQP_VARIANT, MPCQP_ELIM, plan_info()["variant"])
-    "w4": (2, None, None, 17),
-    "w4_elim": (3, None, None, 17),
-    "w2": (2, "10", None, 10),
-    "tri256": (2, "0", None, 0),
-    "sweep256": (3, "2", "0", 2),
-    "big": (5, "12", None, 12),
-}
 
 
 def _capped(cfg):
@@ -48,24 +38,6 @@ def _capped(cfg):
     }
 
 
-def _env(monkeypatch, variant, elim):
-    for k, v in (("MPCQP_VARIANT", variant), ("MPCQP_ELIM", elim)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, v)
-
-
-@functools.lru_cache(maxsize=None)
-def _batch(cfg):
-    return mpc.make_batch(cfg, B=B, seed=SEED[cfg])
-
-
-def _settings(cfg, **kw):
-    s = {k: v for k, v in _batch(cfg)["settings"].items() if k != "verbose"}
-    return dict(s, polish=False, warm_start=False, **kw)
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(cfg, setting):
     b = _batch(cfg)
@@ -74,41 +46,6 @@ def _oracle(cfg, setting):
     cap = _capped(cfg)[setting]["max_iter"]
     assert (bo.iter == cap).all() and (bo.status_val != 1).all(), (bo.iter, bo.status_val)  # (the seeds' premise)
     return bo
-
-
-def _handle(cfg, one_shot=False, **kw):
-    """DeviceBatch over _batch(cfg), its inputs on the device, and fresh outputs."""
-    import torch
-    from osqp_amd import DeviceBatch, _drop_common_zeros
-    b = _batch(cfg)
-    dev = torch.device("cuda", 0)
-    P, Px = _drop_common_zeros(b["P"], b["Px"])
-    A, Ax = _drop_common_zeros(b["A"], b["Ax"])
-    X = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (Px, Ax, b["q"], b["l"], b["u"])]
-    torch.cuda.synchronize()  # (the handle's stream is not ordered with torch's)
-    h = DeviceBatch(P, A, B, device=0, **_settings(cfg, **kw))
-    if one_shot:
-        assert h.one_shot(True) == {2: 2, 3: 3}[cfg]
-    return h, X
-
-
-def _run(h, X, fused):
-    """One cold solve of the inputs X: (x, y, status, iter) as numpy arrays."""
-    o = _out_of(h)
-    if fused:
-        h.setup_solve(*X, *o)
-    else:
-        h.setup(*X)
-        h.solve(*o)
-    h.synchronize()
-    return [t.cpu().numpy() for t in o]
-
-
-def _out_of(h):
-    import torch
-    dev = torch.device("cuda", 0)
-    return (torch.empty((B, h.n), dtype=torch.float64, device=dev), torch.empty((B, h.m), dtype=torch.float64, device=dev),
-            torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
 
 
 def _check_capped(label, cfg, setting, x, y, st, it):
