@@ -514,6 +514,7 @@ __global__ __launch_bounds__(TD, 2) void k_solve_d(KParams p, double* __restrict
             }
         }
         if (!stop && do_rho) {
+            if (!can_check) __syncthreads();  // (no check at this iteration: thread 0's save, solve_wave.hip)
             Res R_;
             R_.restore(L.res);
             adapt_rho(p, R_, rho, rho_updates, need_factor);

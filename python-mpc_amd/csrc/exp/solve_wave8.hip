@@ -418,6 +418,7 @@ __device__ __forceinline__ void solve_w8_body(const KParams& p, double* __restri
             }
         }
         if (!stop && do_rho) {
+            if (!can_check) __syncthreads();  // (no check at this iteration: thread 0's save, solve_wave.hip)
             Res R;
             R.restore(L.res);
             adapt_rho(p, R, rho, rho_updates, need_factor);

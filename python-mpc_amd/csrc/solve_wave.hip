@@ -504,6 +504,10 @@ __device__ __forceinline__ void solve_w2_body(const KParams& p, double* __restri
         }
         PHC(14)
         if (!stop && do_rho) {
+            // (a rho step with no termination check at this iteration -- check_termination 0, or
+            // an interval that is no multiple of it: the check's barriers are the only ones
+            // between thread 0's save and this read)
+            if (!can_check) __syncthreads();
             Res R;
             R.restore(L.res);
             adapt_rho(p, R, rho, rho_updates, need_factor);
@@ -1502,8 +1506,13 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         }
         if (!stop && do_rho) {
             Res R;
-            if constexpr (LEAN) R = Rk;  // (every thread formed the same Res from the reduced maxima)
-            else R.restore(L.res);
+            if constexpr (LEAN) {
+                R = Rk;  // (every thread formed the same Res from the reduced maxima)
+            } else {
+                // (without a check at this iteration nothing else orders thread 0's save before this read)
+                if (!can_check) __syncthreads();
+                R.restore(L.res);
+            }
             adapt_rho(p, R, rho, rho_updates, need_factor);
         }
         __syncthreads();

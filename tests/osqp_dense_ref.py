@@ -41,13 +41,21 @@ def solve(P,q,A,l,u,rho=0.1,sigma=1e-6,alpha=1.6,eps_abs=1e-3,eps_rel=1e-3,max_i
     if x0 is not None:  # osqp_warm_start: x / D, y / E * c, z = A x (scaled)
         x=np.asarray(x0,float)/D; y=np.asarray(y0,float)/E*c if y0 is not None else y; z=A@x
     status='max_iter'; nref=0
+    def resid(x,z,y):
+        Ax=A@x; Px=Pful@x; Aty=A.T@y
+        return Ax,Px,Aty,np.abs((Ax-z)/E).max(),np.abs((Px+q+Aty)/D).max()/c
+    def within(x,z,y,f):  # the "solved" test at f times eps (f = 10: osqp_solve's approximate check)
+        Ax,Px,Aty,pr,dr=resid(x,z,y)
+        ep=f*eps_abs+f*eps_rel*max(np.abs(z/E).max(),np.abs(Ax/E).max())
+        ed=f*eps_abs+f*eps_rel*max(np.abs(q/D).max(),np.abs(Aty/D).max(),np.abs(Px/D).max())/c
+        return pr<ep and dr<ed
     for k in range(1,max_iter+1):
         xp=x; zp=z
         xt=Kinv@(sigma*xp-q+A.T@(rv*zp-y)); zt=A@xt
         x=alpha*xt+(1-alpha)*xp
         z=np.clip(alpha*zt+(1-alpha)*zp+y/rv,l,u)
         dy=rv*(alpha*zt+(1-alpha)*zp-z); y=y+dy
-        chk=(k%check==0); ad=(k%interval==0)
+        chk=bool(check) and k%check==0; ad=(k%interval==0)
         if chk or ad:
             Ax=A@x; Px=Pful@x; Aty=A.T@y
             pr=np.abs((Ax-z)/E).max(); dr=np.abs((Px+q+Aty)/D).max()/c
@@ -61,6 +69,9 @@ def solve(P,q,A,l,u,rho=0.1,sigma=1e-6,alpha=1.6,eps_abs=1e-3,eps_rel=1e-3,max_i
                 rn=rho*np.sqrt(prs/(drs+1e-30)); rn=min(max(rn,RHO_MIN),RHO_MAX)
                 if rn>rho*tol or rn<rho/tol:
                     rho=rn; rv=rhovec(rho); Kinv=factor(rv); nref+=1
+    else:  # the cap (osqp_solve's conclusion): the check the last iteration did not make, then the approximate one
+        if not chk and within(x,z,y,1): status='solved'
+        elif within(x,z,y,10): status='solved inaccurate'
     return D*x, E*y/c, status, k, nref
 
 
