@@ -129,7 +129,9 @@ struct mpcqp_handle {
     std::pair<hipEvent_t, hipEvent_t> last_pair{nullptr, nullptr};  // events of the last device solve
     bool staged = false;  // every shard's hstage holds the last mpcqp_solve_batch's results
     bool one_shot = false;    // mpcqp_set_one_shot: setup_solve_device persists no workspace state
-    bool one_shot_lds = false;  // MPCQP_ONE_SHOT_LOOP=lds at creation: the one-shot cfg-2 kernel's GL 1 form (A/B)
+    // launch_setup_solve's one_shot value; MPCQP_ONE_SHOT_LOOP=lds / wave at creation: 2 / 3 (the
+    // one-shot cfg-2 kernel's GL 1 / GL 3 forms, the A/B baselines of its GL 4 default)
+    int one_shot_loop = 1;
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
     bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
     bool has_setup = false;   // some setup has written the workspace (mpcqp_load_solution_device needs one)
@@ -671,7 +673,8 @@ int make_handle(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, cons
     if (settings) h->set = *settings;
     else mpcqp_default_settings(&h->set);
     if (int e = validate_settings(h->set)) return e;
-    if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP"); ev && !strcmp(ev, "lds")) h->one_shot_lds = true;
+    if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP"))
+        h->one_shot_loop = !strcmp(ev, "lds") ? 2 : (!strcmp(ev, "wave") ? 3 : 1);
     strace().mark("(enter)");
     std::string err = cached_plan(n, m, Pp, Pi, Ap, Ai, h->set, h->plan);
     strace().mark("plan");
@@ -1536,7 +1539,7 @@ int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* d
         const bool one = h->one_shot && one_shot_form(k) > 0;
         h->state_gone = one;
         if (int e = timed_launch(h->collect, h->ev_solve, st, &h->last_pair, [&]() -> int {
-                HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? (h->one_shot_lds ? 2 : 1) : 0));
+                HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? h->one_shot_loop : 0));
                 return 0;
             }))
             return e;

@@ -195,8 +195,9 @@ bool variant_fits(const KParams& p, int variant);
 hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st);
 // setup + solve of the same inputs (solve_wave.hip): one fused kernel where the variant
 // allows it, else launch_setup then launch_solve.  one_shot: 0 the persisting form, 1 the one-shot
-// form (one_shot_form), 2 the same with the headline plan's earlier instantiation (GL 1 instead of
-// GL 3: MPCQP_ONE_SHOT_LOOP=lds, the A/B baseline)
+// form (one_shot_form; on the headline's plan GL 4, the loop compiled per wave role), 2 and 3 the
+// same with that plan's earlier instantiations, the A/B baselines (2: GL 1, MPCQP_ONE_SHOT_LOOP=lds;
+// 3: GL 3, MPCQP_ONE_SHOT_LOOP=wave)
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
                               int one_shot = 0);

@@ -265,7 +265,7 @@ __device__ __forceinline__ bool gj_wave(double* __restrict__ T, double* __restri
 }
 
 // KParams for factorize_w4 with the Gauss-Jordan pivot taken in registers (gj_seg's SEG 3 / 4):
-// the one-shot cfg-2 kernel's GL 3 instantiation (solve_wave.hip, factorize_gp_nl).  The same
+// the one-shot cfg-2 kernel's GL 3 and GL 4 instantiations (solve_wave.hip, factorize_gp_nl).  The same
 // data; the type alone selects the form, so that the other kernels' factorisation keeps its code
 struct KParamsPR : KParams {};
 typedef __attribute__((address_space(4))) const KParamsPR KPcPR;
@@ -1925,7 +1925,7 @@ __device__ __noinline__ bool factorize_g_nl(const KParams* gp, long b, double rh
     return factorize<TT, KPc, false, ROT, SWZ>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
 }
 // factorize_g_nl with the Gauss-Jordan pivot taken in registers (KPcPR): the one-shot cfg-2
-// kernel's GL 3 instantiation only, so that factorize_g_nl keeps its code for the others
+// kernel's GL 3 and GL 4 instantiations only, so that factorize_g_nl keeps its code for the others
 template <int TT, bool ROT = false, bool SWZ = false>
 __device__ __noinline__ bool factorize_gp_nl(const KParams* gp, long b, double rho) {
     static_assert(SWZ && TT == 256, "factorize_w4's swizzled form");

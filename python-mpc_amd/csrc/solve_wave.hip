@@ -727,7 +727,10 @@ __device__ __forceinline__ void form_dense_rows(__attribute__((address_space(1))
 // straight into gl (factorize_w4_gl); GL 3 (form 2 without eliminated columns and amax <= 5, the
 // headline's plan): GL 1 with the loop's phase A and B reads issued earlier (WV below) and the
 // Gauss-Jordan pivot's reciprocal taken off its LDS round trip (factorize_gp_nl) -- the same sums
-// and operands; GL 1 stays as the A/B baseline (MPCQP_ONE_SHOT_LOOP=lds) and keeps its code
+// and operands; GL 4 (the same plan, the default there): GL 3 with the run's loop compiled once
+// per wave role (admm_run<W>, solve_w4_run.inc) -- what serves the other waves' roles leaves each
+// wave's path, the arithmetic stays operand for operand; GL 1 and GL 3 stay as the A/B baselines
+// (MPCQP_ONE_SHOT_LOOP=lds / wave) and keep their code
 template <int K, int KPK, int QR, bool EL = false, int KC = K, bool DK = false, bool RU = false, bool ONE = false,
           int GL = 0>
 __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restrict__ xo, double* __restrict__ yo,
@@ -743,9 +746,10 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
-    static_assert(GL >= 0 && GL <= 3 && (GL != 3 || (ONE && !EL && !DK && QR <= 5)), "GL 3: the headline's plan only");
-    constexpr bool G1 = GL == 1 || GL == 3;  // the one-shot form 2 (G blocks, y, E and D on chip)
-    constexpr bool WV = GL == 3;             // ... with the loop's phase A / B reads issued earlier
+    static_assert(GL >= 0 && GL <= 4 && (GL < 3 || (ONE && !EL && !DK && QR <= 5)), "GL 3, 4: the headline's plan");
+    constexpr bool G1 = GL == 1 || GL >= 3;  // the one-shot form 2 (G blocks, y, E and D on chip)
+    constexpr bool WV = GL >= 3;             // ... with the loop's phase A / B reads issued earlier
+    constexpr bool ROLES = GL == 4;          // ... and the run's loop compiled once per wave (admm_run)
     // GL 1: the G blocks (amax x S per pair) go to LDS after the S_k^{-1} tiles; GL 2: straight
     // into gl (factorize_w4_gl), no copy
     const double* Hg = G1 ? w4_tiles(p, C) + (long)NB * SS : p.H + b * (long)p.nb * SS;
@@ -772,7 +776,10 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     // those values where used (see the lane identity at the top of the outer loop)
     constexpr bool OPQ = EL || QR > 5;
     // c and 1 / c of the cost scaling, from the instance's scal slots where used
+    // (ROLES: from the copy in L.cor made below -- a check reads them without a global round trip)
+    constexpr int kCorScal = 40;  // the copy's slots: L.cor[40], L.cor[41]
     auto cscal = [&](int k) __attribute__((always_inline)) {
+        if constexpr (ROLES) return L.cor[kCorScal + k];
         return OPQ ? opaque_gptr(p.scal + b * 4)[k] : p.scal[b * 4 + k];
     };
     double rho = p.scal[b * 4 + 2];
@@ -807,12 +814,23 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     if (tid < 8) L.cor[32 + tid] = 0.0;   // the upper half's zero correction row (phase B)
     if (tid < 16) L.res[tid] = 0.0;
     if (tid < 4) L.flag[tid] = 0;
+    // ROLES: c and 1 / c of the cost scaling, which every check took from global memory, kept on
+    // chip from here on in two slots of L.cor that the four-wave kernel leaves unused (it holds
+    // nb S doubles; the loop uses [0, 40): c_w and the zero row).  The first pass's opening
+    // barrier orders them before any read
+    if constexpr (ROLES) {
+        static_assert(kCorScal + 2 <= NB * S, "the carve's unused L.cor slots");
+        if (tid < 2) L.cor[kCorScal + tid] = p.scal[b * 4 + tid];
+    }
 
     int status = MPCQP_UNSOLVED_, rho_updates = 0, iter = 0, info_iter = 0;
     bool can_check = false, need_factor = true;
     const bool low = h == 0;
     const int pe0 = (EL && !low) ? p.eown[w * S + r] : -1;  // the upper lane's eliminated column, or -1
     const bool colv = low && p.pad_var[w * S + r] >= 0;     // a real block column (padding: rb = 0)
+    // (ROLES: the check's "column tid is a real one", held from here instead of loaded per check;
+    // kept per column in LDS instead it spilled two VGPRs)
+    [[maybe_unused]] const bool padme = ROLES && tid < npad && p.pad_var[ROLES ? tid : 0] >= 0;
     double* const Fo = p.F + b * (long)p.nb * SS;    // ec, ed of the eliminated columns (factorize_w4)
     double ec = 0.0, ed = 0.0;
     const unsigned abase = lds_addr(L.Acsc), wbase = lds_addr(L.w), xbase = lds_addr(L.xt);
@@ -1073,234 +1091,33 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
         const int stop_at = run_stop(p, iter);
         __syncthreads();
         PH(15)  // (the run starts; slot 5 keeps the kernel's start and finalize)
-        double* const cw = L.cor + w * 8;                 // c_w rows < 8
-        const double* const cwh = L.cor + (h ? 32 : w * 8);  // the half's correction (upper half: zeros)
-        while (iter < stop_at) {
-            ++iter;
-            // rhs = sigma x_prev - q + A' (rho z_prev - y), column pc: the lower half sums
-            // the list's first KH entries, the upper half the rest, one permlane32 swap
-            {
-                double wv[KH];
-#pragma unroll
-                for (int k = 0; k < KH; ++k) wv[k] = lds_at(ch2.e[k] >> 16);
-                double v;
-                if constexpr (EL) {
-                    // sigma x - q of the lane's column (upper: the eliminated one, whose list it
-                    // adds; zero entries on the other lanes), then the upper half's b_p share
-                    // carries -ec b_pe
-                    double we[LE];
-#pragma unroll
-                    for (int k = 0; k < LE; ++k) we[k] = lds_at(el.e[k] >> 16);
-                    bj = sigma * X - Q;
-#pragma unroll
-                    for (int k = 0; k < LE; ++k) bj += ea[k] * we[k];
-                    v = low ? bj : -(ec * bj);
-                } else {
-                    v = low ? sigma * X - Q : 0.0;
-                }
-#pragma unroll
-                for (int k = 0; k < KH; ++k) v += ca[k] * wv[k];
-                const unsigned vlo = (unsigned)__double2loint(v), vhi = (unsigned)__double2hiint(v);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(vlo, vlo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(vhi, vhi, false, false);
-                const double v0 = __hiloint2double((int)h2[0], (int)l2[0]);
-                const double v1 = __hiloint2double((int)h2[1], (int)l2[1]);
-                if (low) L.rb[pc] = colv ? v0 + v1 : 0.0;
+        // The run's loop (solve_w4_run.inc: the text between here and the write-back).  ROLES
+        // compiles it once per wave role: admm_run<W> re-forms the wave's index and what follows
+        // from it alone (nsw, the wave's column) from the compile-time W and is reached once per
+        // run through a switch on w.  With W a constant the tests that are uniform within a
+        // wave fold: the selects, zero-fills and moves that serve the other roles leave the
+        // wave's path, and so does arithmetic whose result the role never stores (wave 0's
+        // reduce8).  No operation that reaches x, y, z, w, rb, tv or xt is removed or reordered
+        // by hand: what folds is control flow on compile-time constants.  Every
+        // other instantiation takes the same text with the run-time w, in place and not through
+        // the lambda: going through it with "W = -1" moved the code of all seventeen
+        if constexpr (ROLES) {
+            auto admm_run = [&](auto wc) __attribute__((always_inline)) {
+                constexpr int W = decltype(wc)::value;
+                // (rows_wave stays the body's: it depends on the run-time mp, and one copy per
+                // role, each live across the kernel, spilled one role's mask: two v_readlane in
+                // that role's loop)
+                const int w = W, nsw = (NB - W) >> 1, pc = W * S + r;
+#include "solve_w4_run.inc"
+            };
+            switch (w) {
+                case 0: admm_run(std::integral_constant<int, 0>{}); break;
+                case 1: admm_run(std::integral_constant<int, 1>{}); break;
+                case 2: admm_run(std::integral_constant<int, 2>{}); break;
+                default: admm_run(std::integral_constant<int, 3>{}); break;
             }
-            __syncthreads();
-            PH(1)
-            if constexpr (DK) {
-                // x~[pc] = M^{-1}[pc] b: the half's NB0 + NB1 columns (broadcast reads, one address
-                // per half-wave), four FMA chains, one permlane32 swap
-                const double* const rbh = L.rb + S * h;
-                double a[4] = {0.0, 0.0, 0.0, 0.0};
-                // software-pipelined in windows of DKW values: window k + 1's reads are issued
-                // before window k's FMAs (two windows in flight; all 27 reads at once spill)
-                constexpr int NE = NB0 + NB1, NWIN = (NE + DKW - 1) / DKW;
-                double v[2][DKW];
-                auto issue = [&](int k, double (&dst)[DKW]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int c = 0; c < DKW; c += 2) {
-                        const int e = k * DKW + c;  // block h column e, or block 2 + h column e - NB0
-                        if (e < NE) ld2(rbh + (e < NB0 ? e : 2 * S + e - NB0), dst[c], dst[c + 1]);
-                    }
-                };
-                issue(0, v[0]);
-#pragma unroll
-                for (int k = 0; k < NWIN; ++k) {
-                    if (k + 1 < NWIN) issue(k + 1, v[(k + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int c = 0; c < DKW; ++c)
-                        if (k * DKW + c < NE) a[c & 3] += Kr[k * DKW + c] * v[k & 1][c];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                const double th = (a[0] + a[1]) + (a[2] + a[3]);
-                const unsigned lo = (unsigned)__double2loint(th), hi = (unsigned)__double2hiint(th);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                const double xn = __hiloint2double((int)h2[0], (int)l2[0]) + __hiloint2double((int)h2[1], (int)l2[1]);
-                if (low) L.xt[pc] = xn;
-                const double xnew = alpha * xn + (1.0 - alpha) * X;
-                DX = xnew - X;
-                X = xnew;
-            } else {
-            // WV: every pair's b_j is read at once (blocks j >= w too: read and not used), so
-            // that wave 3 waits for LDS once and not once per branch of the pair nest, and
-            // phase B's b_w reads are issued ahead of the reduction (they depend on nothing of
-            // phase A): they return while its DPP steps and the c_w round trip run.  c_w still
-            // goes through L.cor: taking it from the reduction's lanes by v_readlane was
-            // measured slower in three forms
-            double vb[WV ? 16 : 1];
-            if constexpr (WV) {
-                double sa = 0.0;
-                if (w > 0) {
-                    double bj[NB - 1][4];
-#pragma unroll
-                    for (int j = 0; j < NB - 1; ++j) {
-                        ld2(L.rb + j * S + 4 * ch, bj[j][0], bj[j][1]);
-                        ld2(L.rb + j * S + 4 * ch + 2, bj[j][2], bj[j][3]);
-                    }
-                    double acc[NB - 1] = {0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int j = 0; j < NB - 1; ++j) {
-                        if (j < w) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[j] += ga[j][e] * bj[j][e];
-                        }
-                    }
-                    sa = (acc[0] + acc[1]) + acc[2];
-                }
-#pragma unroll
-                for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, vb[c], vb[c + 1]);
-                const double cs = reduce8(sa);
-                if (w > 0) cw[rr] = cs;
-            } else {
-            // A: c_w = sum_{j<w} G_wj b_j (rows < 8), wave w only
-            if (w > 0) {
-                // one accumulator per pair (wave 3: three 4-deep FMA chains instead of one 12-deep)
-                double acc[NB - 1] = {0.0, 0.0, 0.0};
-#pragma unroll
-                for (int j = 0; j < NB - 1; ++j) {
-                    if (j < w) {
-                        double bj[4];
-                        ld2(L.rb + j * S + 4 * ch, bj[0], bj[1]);
-                        ld2(L.rb + j * S + 4 * ch + 2, bj[2], bj[3]);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[j] += ga[j][e] * bj[e];
-                    }
-                }
-                cw[rr] = reduce8((acc[0] + acc[1]) + acc[2]);
-            }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            PH(12)
-            // B: t_w[r] = S_w^{-1}[r] (b_w + c_w): half-row sums, permlane32 swap
-            double t;
-            {
-                constexpr int QE = (QR + 1) & ~1;  // c_w's nonzero rows (< amax), read in pairs
-                double v[16], cc[QE];
-                if constexpr (WV) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) v[c] = vb[c];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 16; c += 2) ld2(L.rb + w * S + 16 * h + c, v[c], v[c + 1]);
-                }
-#pragma unroll
-                for (int c = 0; c < QE; c += 2) ld2(cwh + c, cc[c], cc[c + 1]);
-#pragma unroll
-                for (int c = 0; c < QR; ++c) v[c] += cc[c];
-                double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int c = 0; c < 16; ++c) a[c & 3] += SB[c] * v[c];
-                const double th = (a[0] + a[1]) + (a[2] + a[3]);
-                const unsigned lo = (unsigned)__double2loint(th), hi = (unsigned)__double2hiint(th);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                const double t0 = __hiloint2double((int)h2[0], (int)l2[0]);  // lower half's
-                const double t1 = __hiloint2double((int)h2[1], (int)l2[1]);  // upper half's
-                t = t0 + t1;
-                if (low && r < 8) L.tv[w * 8 + r] = t;
-            }
-            __syncthreads();
-            PH(13)
-            // C: x~_w[r] = t + sum_s G_{pair_s}[q][r] t_{j_s}[q]  (slots split over the halves;
-            // rows q < QR: the G blocks are zero from row amax on)
-            {
-                constexpr int QE = (QR + 1) & ~1;  // t rows read in pairs
-                // the wave's slot count (wave 0: 2, waves 1-2: 1, wave 3: 0): slots no half
-                // of the wave has a pair for are skipped, not read as the zero pair (LDS
-                // return bandwidth is shared with the CU's other workgroup)
-                double gv[2][QE], tq[2][QE];
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    if (s < nsw) {
-#pragma unroll
-                        for (int q = 0; q < QE; ++q) gv[s][q] = q < QR ? gc[s][q] : 0.0;
-#pragma unroll
-                        for (int q = 0; q < QE; q += 2) lds_at2(tslot[s] + q * 8, tq[s][q], tq[s][q + 1]);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < QE; ++q) gv[s][q] = tq[s][q] = 0.0;
-                    }
-                }
-                double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int q = 0; q < QR; q += 2) {
-                        a0 += gv[s][q] * tq[s][q];
-                        if (q + 1 < QR) a1 += gv[s][q + 1] * tq[s][q + 1];
-                    }
-                const double d = a0 + a1;
-                const unsigned lo = (unsigned)__double2loint(d), hi = (unsigned)__double2hiint(d);
-                const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-                const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-                const double d0 = __hiloint2double((int)h2[0], (int)l2[0]);
-                const double d1 = __hiloint2double((int)h2[1], (int)l2[1]);
-                const double xn = t + (d0 + d1);
-                if (low) L.xt[pc] = xn;
-                double xl = xn;  // x~ of the lane's column
-                if constexpr (EL) {
-                    if (!low) {
-                        xl = ed * bj - ec * xn;
-                        if (pe >= 0) L.xt[pe] = xl;
-                    }
-                }
-                const double xnew = alpha * xl + (1.0 - alpha) * X;
-                DX = xnew - X;
-                X = xnew;
-            }
-            }  // !DK
-            __syncthreads();
-            PH(14)
-            // rows: z~ = A x~ ; relaxed + projected z ; y ; next w (waves wholly past the
-            // padded rows skip it: their lanes would only repeat the inert last row)
-            if (rows_wave) {
-                double xv[K], ar[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) xv[k] = lds_at(rg.e[k] >> 16);
-                // DK: the row's A values read with x~ (the dense rows leave no registers to
-                // keep them across the run)
-#pragma unroll
-                for (int k = 0; k < K; ++k) ar[k] = DK ? lds_at(rg.e[k] & 0xFFFFu) : av[k];
-                const double lo = rlo, up = rup;
-                double zt = ar[0] * xv[0];
-#pragma unroll
-                for (int k = 1; k < K; ++k) zt += ar[k] * xv[k];
-                const double zr = alpha * zt + (1.0 - alpha) * Z;
-                const double zn = __builtin_fmin(__builtin_fmax(zr + rvi * y, lo), up);
-                const double dd = rv * (zr - zn);
-                Z = zn;
-                dy = dd;
-                y += dd;
-                L.w[ri] = rv * zn - y;
-            }
-            __syncthreads();
-            PH(3)
+        } else {
+#include "solve_w4_run.inc"
         }
         // run state back to LDS (lds_put: the addresses are formed here, not held across the
         // loop)
@@ -1412,7 +1229,11 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                     mx[16] = fabs(unscale ? pdx * di : pdx);
                 }
             }
+            if constexpr (ROLES) {
+                if (padme) sm[1] = L.qv[tid + oz] * L.dx[tid + oz];
+            } else {
             if (tid < npad && opaque_gptr(p.pad_var)[tid] >= 0) sm[1] = L.qv[tid + oz] * L.dx[tid + oz];
+            }
             PH(6)  // (a check up to its reduction: write-back, operands, gathers)
             if (do_rho || !unscale) {
                 block_max_sum_tr<T4, 17, 2, LEAN>(mx, sm, L.red);
@@ -1561,7 +1382,7 @@ __global__ __launch_bounds__(T4, 2) void k_setup_solve_w4(KParams p, const doubl
                                                           const double* __restrict__ u_in, double* __restrict__ xo,
                                                           double* __restrict__ yo) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    setup_r_body<T4, SK, 4, 1, SAS, 1, false, ONE, GL == 1 || GL == 3>(p, instance_of(p), Px_in, Ax_in, q_in, l_in, u_in, sm);
+    setup_r_body<T4, SK, 4, 1, SAS, 1, false, ONE, GL == 1 || GL >= 3>(p, instance_of(p), Px_in, Ax_in, q_in, l_in, u_in, sm);
     __syncthreads();
     solve_w4_body<K, KPK, QR, EL, KC, DK, false, ONE, GL>(p, xo, yo);
     order_epilogue<T4>(p, (int*)sm);
@@ -1651,13 +1472,16 @@ hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, con
     const int form = one_shot ? one_shot_form(p, &lds) : 0;
     if (!form) lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
     using Kernel = decltype(W4Five::setup_solve());
-    // one-shot form 2 is GL 1 (GL 3 on the headline's shape, unless one_shot == 2 asks for the
-    // A/B baseline), form 3 is GL 2, form 1 is the persisting loop on the one-shot setup
+    // one-shot form 2 is GL 1 (GL 4 on the headline's shape, unless one_shot == 2 or 3 asks for
+    // the A/B baselines GL 1 or GL 3), form 3 is GL 2, form 1 is the persisting loop on the
+    // one-shot setup
     const Kernel k4 = with_w4_shape(p, [&](auto sh) -> Kernel {
         using Sh = decltype(sh);
         if (form == 2) {
-            if constexpr (!Sh::EL && Sh::QR <= 5)
-                if (one_shot != 2) return Sh::template setup_solve<true, 3>();
+            if constexpr (!Sh::EL && Sh::QR <= 5) {
+                if (one_shot == 3) return Sh::template setup_solve<true, 3>();
+                if (one_shot != 2) return Sh::template setup_solve<true, 4>();
+            }
             return Sh::template setup_solve<true, 1>();
         }
         if (form == 3) return Sh::template setup_solve<true, 2>();

@@ -75,6 +75,12 @@ __device__ __forceinline__ int opaque_v(int x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// A per-lane double through an empty asm: a product passed through it stays a rounded value of
+// its own -- the add that takes it is not contracted with the multiply into an fma.
+__device__ __forceinline__ double rounded(double x) {
+    asm("" : "+v"(x));
+    return x;
+}
 // arr[idx] = v in LDS with arr's address through an empty asm: the element address is
 // formed at the store (a run's write-back) instead of being kept across the solve loop.
 __device__ __forceinline__ void lds_put(const double* arr, int idx, double v) {
