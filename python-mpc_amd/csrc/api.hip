@@ -129,8 +129,9 @@ struct mpcqp_handle {
     std::pair<hipEvent_t, hipEvent_t> last_pair{nullptr, nullptr};  // events of the last device solve
     bool staged = false;  // every shard's hstage holds the last mpcqp_solve_batch's results
     bool one_shot = false;    // mpcqp_set_one_shot: setup_solve_device persists no workspace state
-    // launch_setup_solve's one_shot value; MPCQP_ONE_SHOT_LOOP=lds / wave at creation: 2 / 3 (the
-    // one-shot cfg-2 kernel's GL 1 / GL 3 forms, the A/B baselines of its GL 4 default)
+    // launch_setup_solve's one_shot value; MPCQP_ONE_SHOT_LOOP=lds / wave / roles at creation:
+    // 2 / 3 / 4 (the one-shot cfg-2 kernel's GL 1 / GL 3 / GL 4 forms, the A/B baselines of its
+    // GL 5 default)
     int one_shot_loop = 1;
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
     bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
@@ -674,7 +675,7 @@ int make_handle(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, cons
     else mpcqp_default_settings(&h->set);
     if (int e = validate_settings(h->set)) return e;
     if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP"))
-        h->one_shot_loop = !strcmp(ev, "lds") ? 2 : (!strcmp(ev, "wave") ? 3 : 1);
+        h->one_shot_loop = !strcmp(ev, "lds") ? 2 : (!strcmp(ev, "wave") ? 3 : (!strcmp(ev, "roles") ? 4 : 1));
     strace().mark("(enter)");
     std::string err = cached_plan(n, m, Pp, Pi, Ap, Ai, h->set, h->plan);
     strace().mark("plan");

@@ -195,9 +195,10 @@ bool variant_fits(const KParams& p, int variant);
 hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st);
 // setup + solve of the same inputs (solve_wave.hip): one fused kernel where the variant
 // allows it, else launch_setup then launch_solve.  one_shot: 0 the persisting form, 1 the one-shot
-// form (one_shot_form; on the headline's plan GL 4, the loop compiled per wave role), 2 and 3 the
-// same with that plan's earlier instantiations, the A/B baselines (2: GL 1, MPCQP_ONE_SHOT_LOOP=lds;
-// 3: GL 3, MPCQP_ONE_SHOT_LOOP=wave)
+// form (one_shot_form; on the headline's plan GL 4, the loop compiled per wave role, and with
+// amax = bmax = 5 GL 5, the factorisation compiled for those constants too), 2, 3 and 4 the same
+// with that plan's earlier instantiations, the A/B baselines (2: GL 1, MPCQP_ONE_SHOT_LOOP=lds;
+// 3: GL 3, MPCQP_ONE_SHOT_LOOP=wave; 4: GL 4, MPCQP_ONE_SHOT_LOOP=roles)
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
                               int one_shot = 0);

@@ -748,6 +748,197 @@ __device__ __forceinline__ bool factorize_w4(const KP& p, SLds& L, const double 
     return okf[0] > 0.5 && okf[1] > 0.5 && okf[2] > 0.5 && okf[3] > 0.5;
 }
 
+// gj_seg<SEG 3 / 4, false, false, true> (the unrolled step on swizzled tiles with the pivot taken
+// in registers) for factorize_w4q: the first pivot row A is a compile-time constant and npiv is
+// wave-uniform (a scalar), so the guard around each unrolled step is a compile-time test and one
+// scalar branch, and SG 2's A steps have no guard.  Every floating-point operation, operand and
+// order is gj_seg's.
+template <int SG, int A>
+__device__ __forceinline__ bool gj_q(double* __restrict__ T, double* __restrict__ buf, const int npiv,
+                                     const double* __restrict__ dl) {
+    static_assert((SG == 1 || SG == 2) && A >= 0 && A <= 8, "gj_seg's segments; a <= 8 for the unrolled SEG 2");
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    double v[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; jj += 2) {
+        const double2 t2 = *(const double2*)(T + tile_at<true>(i, 16 * h + jj));
+        v[jj] = t2.x;
+        v[jj + 1] = t2.y;
+    }
+    if (SG == 2 && h == 0 && i < A) {
+#pragma unroll
+        for (int jj = 0; jj < A; ++jj) v[jj] += dl[i * 16 + jj];
+    }
+    bool ok = true;
+    double sc = 1.0, iv = 1.0;
+    auto step = [&](const int p, const bool pv) __attribute__((always_inline)) {
+        const int pj = p & 15, ph = p >> 4;
+        double* rb = buf + (pj & 1) * S;
+        // lane p of half ph publishes rb[p] = vp unflipped (pv is false for i == p): the same
+        // value by v_readlane, and its reciprocal while the column's LDS round trip is in flight
+        const double vp = sc * v[pj];
+        if (h == ph) rb[i] = pv ? -vp : vp;  // row p = +-column p
+        const int sl = p + 32 * ph;
+        const double piv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(vp), sl),
+                                            __builtin_amdgcn_readlane(__double2loint(vp), sl));
+        double d = __builtin_amdgcn_rcp(piv);
+        d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+        d = __builtin_fma(d, __builtin_fma(-piv, d, 1.0), d);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const double mi = rb[i];
+        double rowv[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; jj += 2) {
+            const double2 r2 = *(const double2*)(rb + 16 * h + jj);
+            rowv[jj] = r2.x;
+            rowv[jj + 1] = r2.y;
+        }
+        const double colv = pv ? -mi : mi;
+        ok = ok && piv > 0.0;  // (the pivot is wave-uniform: a scalar mask, not gj_seg's minpiv select)
+        const double cd = (colv * d) * iv;
+        const bool self = i == p;
+        if (!self) {
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) v[jj] = __builtin_fma(-cd, rowv[jj], v[jj]);
+        } else {
+            sc = d;
+            iv = piv;
+        }
+        if (h == ph) v[pj] = self ? 1.0 : -cd;
+    };
+    if constexpr (SG == 1) {
+        // (the padding pivots p >= npiv: one scalar branch around each unrolled step)
+#pragma unroll
+        for (int p = A; p < S; ++p)
+            if (p < npiv) step(p, i >= A && i < p);
+    } else {
+        const bool done = i >= A && i < npiv;  // pivoted in SG 1
+#pragma unroll
+        for (int p = 0; p < A; ++p) step(p, done || i < p);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 16; jj += 2)
+        *(double2*)(T + tile_at<true>(i, 16 * h + jj)) = make_double2(sc * v[jj], sc * v[jj + 1]);
+    return ok;
+}
+
+// factorize_w4<false, 256, true> on KPcPR for the headline's plan (the one-shot cfg-2 kernel's GL 5
+// instantiation, factorize_gq_nl): no eliminated columns, amax = AMAX and bmax = BMAX compile-time
+// constants.  The same sums on the same operands in the same order; what changes is control flow
+// and address formation:
+//   - the wave index, bsize[w] and toff[k] are scalars, so the stage-1 pivots are compiled once
+//     for wave 0 (a = 0) and once for waves 1-3 (a = AMAX), each step behind one scalar branch
+//     (gj_q), and the corner's AMAX pivots are straight-line;
+//   - F_k, the corner and the G blocks are one output per thread (AMAX S <= 192): all operand
+//     loads first, then the one FMA chain l = l0 .. l0 + BMAX - 1 (G: l < AMAX, no predicated
+//     rows).
+template <int AMAX, int BMAX>
+__device__ __forceinline__ bool factorize_w4q(KPcPR& p, SLds& L, const double rho, double* __restrict__ Hg,
+                                              double* __restrict__ Sg) {
+    constexpr int TT = 256, as = AMAX * S;
+    static_assert(as <= TT - 64 && AMAX * AMAX <= 64 && AMAX <= 8, "one output per thread; gj_q's SG 2");
+    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    constexpr long gstride = as;
+    double* const V = L.SP;
+    double* const G20 = V + 7 * as;
+    double* const dl = V + 8 * as;              // amax x amax, row stride 16
+    double* const bufw = dl + 256 + w * 2 * S;  // the wave's Gauss-Jordan publish buffers
+    double* const okf = dl + 256 + 8 * S;
+    auto Ek = [&](int k) __attribute__((always_inline)) { return V + k * as; };
+    auto Fk = [&](int k) __attribute__((always_inline)) { return V + (3 + k) * as; };
+    auto wave_sync = []() __attribute__((always_inline)) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    FPROF_START
+    assemble_block<false, true, true>(p, L, rho, w, Sg + (long)w * SS, Ek(w), lane, 64, wave_sync);
+    wave_sync();
+    FPH(8)
+    bool okw;
+    {
+        const int np = __builtin_amdgcn_readfirstlane(p.bsize[w]);
+        if (w == 0) okw = gj_q<1, 0>(Sg, bufw, np, nullptr);
+        else okw = gj_q<1, AMAX>(Sg + (long)w * SS, bufw, np, nullptr);
+    }
+    FPH(10)
+    __syncthreads();
+    FPH(11)
+#pragma unroll 1
+    for (int k = 1; k < 4; ++k) {
+        const double* Sp = Sg + (long)(k - 1) * SS;
+        const double* E = Ek(k);
+        double* F = Fk(k);
+        const int l0 = __builtin_amdgcn_readfirstlane(p.toff[k - 1]);
+        if (tid < as) {
+            const int r = tid >> 5, j = tid & (S - 1);
+            double e[BMAX], s[BMAX];
+#pragma unroll
+            for (int l = 0; l < BMAX; ++l) {
+                e[l] = E[r * S + l0 + l];
+                s[l] = Sp[tile_at<true>(l0 + l, j)];
+            }
+            double sacc = 0.0;
+#pragma unroll
+            for (int l = 0; l < BMAX; ++l) sacc += e[l] * s[l];
+            F[tid] = sacc;
+            Hg[(long)(k * (k - 1) / 2 + k - 1) * gstride + tid] = -sacc;
+        }
+        __syncthreads();
+        FPH(9)
+        if (w == 0) {
+            // wave 0: the corner S_k = D_k - F_k E_k' and its pivots right away
+            if (lane < AMAX * AMAX) {
+                const int r = lane / AMAX, c = lane - r * AMAX;
+                double f[BMAX], e[BMAX];
+#pragma unroll
+                for (int l = 0; l < BMAX; ++l) {
+                    f[l] = F[r * S + l0 + l];
+                    e[l] = E[c * S + l0 + l];
+                }
+                double sacc = 0.0;
+#pragma unroll
+                for (int l = 0; l < BMAX; ++l) sacc += f[l] * e[l];
+                dl[r * 16 + c] = -sacc;
+            }
+            wave_sync();
+            okw = gj_q<2, AMAX>(Sg + (long)k * SS, bufw, __builtin_amdgcn_readfirstlane(p.bsize[k]), dl) && okw;
+        } else {
+            // waves 1-3 meanwhile: G_kj = -F_k G_{k-1,j} (j < k-1), off the chain's path
+#pragma unroll 1
+            for (int j = 0; j < k - 1; ++j) {
+                const bool adj = j == k - 2;
+                const double* Gp = adj ? Fk(k - 1) : G20;
+                const double sg = adj ? 1.0 : -1.0;
+                const int o = tid - 64;
+                if (o < as) {
+                    const int r = o >> 5, c = o & (S - 1);
+                    double f[AMAX], g5[AMAX];
+#pragma unroll
+                    for (int l = 0; l < AMAX; ++l) {
+                        f[l] = F[r * S + l];
+                        g5[l] = Gp[l * S + c];
+                    }
+                    double sacc = 0.0;
+#pragma unroll
+                    for (int l = 0; l < AMAX; ++l) sacc += f[l] * g5[l];
+                    const double g = sg * sacc;
+                    Hg[(long)(k * (k - 1) / 2 + j) * gstride + o] = g;
+                    if (k == 2) G20[o] = g;
+                }
+            }
+        }
+        __syncthreads();
+        FPH(11)
+    }
+    if (lane == 0) okf[w] = okw ? 1.0 : 0.0;
+    __syncthreads();
+    FPH(9)
+    return okf[0] > 0.5 && okf[1] > 0.5 && okf[2] > 0.5 && okf[3] > 0.5;
+}
+
 // factorize_w4's form for the one-shot kernel on plans whose G blocks have no LDS region of
 // their own (one_shot_form 3, the slack layouts): the G blocks go straight into the solve's
 // copy gl (pair q at q 8 S, rows < amax; rows amax..7 and pair NP are zero from the kernel's
@@ -1933,6 +2124,51 @@ __device__ __noinline__ bool factorize_gp_nl(const KParams* gp, long b, double r
     SL2 c = carve(p);
     double* const sg = w4_tiles(p, c);
     return factorize<TT, KPcPR, false, ROT, SWZ>(p, c.L, rho, p.F + b * (long)p.nb * SS, sg + (long)p.nb * SS, sg);
+}
+// factorize_gp_nl for plans with amax = AMAX and bmax = BMAX (factorize_w4q): the one-shot cfg-2
+// kernel's GL 5 instantiation only, so that factorize_gp_nl keeps its code for GL 3 and GL 4
+template <int TT, bool SWZ, int AMAX, int BMAX>
+__device__ __noinline__ bool factorize_gq_nl(const KParams* gp, long b, double rho) {
+    static_assert(SWZ && TT == 256, "factorize_w4's swizzled form");
+    // The kernel body around the call is compiled with what its callee does to the registers:
+    // the scalar registers the callee writes count as changed (the ones it saves and restores
+    // too), and so do the vector registers it keeps its saved scalars in.  factorize_gp_nl writes
+    // s0-s29 and s34-s99 and needs two such vector registers (v40, v41: 75 lanes, 8 bytes of
+    // stack).  This function needs fewer of each, and with any other set the body's register
+    // allocation moves (measured: role loops of 175-184 instructions with 16 v_readlane each, or
+    // two spilled VGPRs and 24-28 bytes of scratch, instead of GL 4's 160-169 with none and 12;
+    // DESIGN.md §22).  So it presents factorize_gp_nl's set: 56 scalar values are defined, every
+    // scalar register factorize_gp_nl writes is named as changed, and the values are used after
+    // it -- they pass through lanes of v40 and v41 once per call, about 170 scalar-to-lane moves
+    // per factorisation.  tests/test_isa_shape_one_shot_factor.py holds the body to GL 4's shape
+    int d[56];
+    asm volatile("" : "=s"(d[0]), "=s"(d[1]), "=s"(d[2]), "=s"(d[3]), "=s"(d[4]), "=s"(d[5]), "=s"(d[6]), "=s"(d[7]),
+                 "=s"(d[8]), "=s"(d[9]), "=s"(d[10]), "=s"(d[11]), "=s"(d[12]), "=s"(d[13]), "=s"(d[14]),
+                 "=s"(d[15]), "=s"(d[16]), "=s"(d[17]), "=s"(d[18]), "=s"(d[19]), "=s"(d[20]), "=s"(d[21]),
+                 "=s"(d[22]), "=s"(d[23]), "=s"(d[24]), "=s"(d[25]), "=s"(d[26]), "=s"(d[27]));
+    asm volatile("" : "=s"(d[28]), "=s"(d[29]), "=s"(d[30]), "=s"(d[31]), "=s"(d[32]), "=s"(d[33]), "=s"(d[34]),
+                 "=s"(d[35]), "=s"(d[36]), "=s"(d[37]), "=s"(d[38]), "=s"(d[39]), "=s"(d[40]), "=s"(d[41]),
+                 "=s"(d[42]), "=s"(d[43]), "=s"(d[44]), "=s"(d[45]), "=s"(d[46]), "=s"(d[47]), "=s"(d[48]),
+                 "=s"(d[49]), "=s"(d[50]), "=s"(d[51]), "=s"(d[52]), "=s"(d[53]), "=s"(d[54]), "=s"(d[55]));
+    asm volatile("" ::: "s0", "s1", "s2", "s3", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "s12", "s13", "s14",
+                 "s15", "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28",
+                 "s29", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46",
+                 "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60",
+                 "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74",
+                 "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88",
+                 "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99");
+    asm volatile("" :: "s"(d[0]), "s"(d[1]), "s"(d[2]), "s"(d[3]), "s"(d[4]), "s"(d[5]), "s"(d[6]), "s"(d[7]), "s"(d[8]),
+                 "s"(d[9]), "s"(d[10]), "s"(d[11]), "s"(d[12]), "s"(d[13]), "s"(d[14]), "s"(d[15]), "s"(d[16]),
+                 "s"(d[17]), "s"(d[18]), "s"(d[19]), "s"(d[20]), "s"(d[21]), "s"(d[22]), "s"(d[23]), "s"(d[24]),
+                 "s"(d[25]), "s"(d[26]), "s"(d[27]));
+    asm volatile("" :: "s"(d[28]), "s"(d[29]), "s"(d[30]), "s"(d[31]), "s"(d[32]), "s"(d[33]), "s"(d[34]), "s"(d[35]),
+                 "s"(d[36]), "s"(d[37]), "s"(d[38]), "s"(d[39]), "s"(d[40]), "s"(d[41]), "s"(d[42]), "s"(d[43]),
+                 "s"(d[44]), "s"(d[45]), "s"(d[46]), "s"(d[47]), "s"(d[48]), "s"(d[49]), "s"(d[50]), "s"(d[51]),
+                 "s"(d[52]), "s"(d[53]), "s"(d[54]), "s"(d[55]));
+    KPcPR& p = static_cast<KPcPR&>(kconst(gp));
+    SL2 c = carve(p);
+    double* const sg = w4_tiles(p, c);
+    return factorize_w4q<AMAX, BMAX>(p, c.L, rho, sg + (long)p.nb * SS, sg);
 }
 
 

@@ -729,8 +729,10 @@ __device__ __forceinline__ void form_dense_rows(__attribute__((address_space(1))
 // Gauss-Jordan pivot's reciprocal taken off its LDS round trip (factorize_gp_nl) -- the same sums
 // and operands; GL 4 (the same plan, the default there): GL 3 with the run's loop compiled once
 // per wave role (admm_run<W>, solve_w4_run.inc) -- what serves the other waves' roles leaves each
-// wave's path, the arithmetic stays operand for operand; GL 1 and GL 3 stay as the A/B baselines
-// (MPCQP_ONE_SHOT_LOOP=lds / wave) and keep their code
+// wave's path, the arithmetic stays operand for operand; GL 5 (that plan with amax = bmax = 5, the
+// default there): GL 4 with the factorisation compiled for those constants and per wave role
+// (factorize_gq_nl) -- the same sums; GL 1, GL 3 and GL 4 stay as the A/B baselines
+// (MPCQP_ONE_SHOT_LOOP=lds / wave / roles) and keep their code
 template <int K, int KPK, int QR, bool EL = false, int KC = K, bool DK = false, bool RU = false, bool ONE = false,
           int GL = 0>
 __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restrict__ xo, double* __restrict__ yo,
@@ -746,10 +748,10 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
     const int n = p.n, m = p.m, npad = p.npad, nnzP = p.nnzP, nnzA = p.nnzA;
     SL2 C = carve(p);
     SLds& L = C.L;
-    static_assert(GL >= 0 && GL <= 4 && (GL < 3 || (ONE && !EL && !DK && QR <= 5)), "GL 3, 4: the headline's plan");
+    static_assert(GL >= 0 && GL <= 5 && (GL < 3 || (ONE && !EL && !DK && QR <= 5)), "GL 3, 4, 5: the headline's plan");
     constexpr bool G1 = GL == 1 || GL >= 3;  // the one-shot form 2 (G blocks, y, E and D on chip)
     constexpr bool WV = GL >= 3;             // ... with the loop's phase A / B reads issued earlier
-    constexpr bool ROLES = GL == 4;          // ... and the run's loop compiled once per wave (admm_run)
+    constexpr bool ROLES = GL >= 4;          // ... and the run's loop compiled once per wave (admm_run)
     // GL 1: the G blocks (amax x S per pair) go to LDS after the S_k^{-1} tiles; GL 2: straight
     // into gl (factorize_w4_gl), no copy
     const double* Hg = G1 ? w4_tiles(p, C) + (long)NB * SS : p.H + b * (long)p.nb * SS;
@@ -894,6 +896,8 @@ __device__ __forceinline__ void solve_w4_body(const KParams& p, double* __restri
                 }
                 __syncthreads();
                 if (tid == 0) p.ffresh[b] = 0;
+            } else if constexpr (GL == 5) {  // (amax = bmax = 5: factorize_w4q)
+                ok = factorize_gq_nl<T4, SWZ, 5, 5>(p.self, b, rho);
             } else if constexpr (WV) {  // (the Gauss-Jordan pivot in registers: gj_seg SEG 3 / 4)
                 ok = factorize_gp_nl<T4, EL, SWZ>(p.self, b, rho);
             } else if constexpr (G1) {
@@ -1472,14 +1476,15 @@ hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, con
     const int form = one_shot ? one_shot_form(p, &lds) : 0;
     if (!form) lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
     using Kernel = decltype(W4Five::setup_solve());
-    // one-shot form 2 is GL 1 (GL 4 on the headline's shape, unless one_shot == 2 or 3 asks for
-    // the A/B baselines GL 1 or GL 3), form 3 is GL 2, form 1 is the persisting loop on the
-    // one-shot setup
+    // one-shot form 2 is GL 1 (on the headline's shape GL 4, GL 5 with amax = bmax = 5, unless
+    // one_shot == 2, 3 or 4 asks for the A/B baselines GL 1, GL 3 or GL 4), form 3 is GL 2, form 1
+    // is the persisting loop on the one-shot setup
     const Kernel k4 = with_w4_shape(p, [&](auto sh) -> Kernel {
         using Sh = decltype(sh);
         if (form == 2) {
             if constexpr (!Sh::EL && Sh::QR <= 5) {
                 if (one_shot == 3) return Sh::template setup_solve<true, 3>();
+                if (one_shot != 2 && one_shot != 4 && p.amax == 5 && p.bmax == 5) return Sh::template setup_solve<true, 5>();
                 if (one_shot != 2) return Sh::template setup_solve<true, 4>();
             }
             return Sh::template setup_solve<true, 1>();
