@@ -294,10 +294,14 @@ int mpcqp_set_shared_matrices(mpcqp_handle *h, int32_t shared);
  * updates, certificates) fail with MPCQP_EINVAL until a setup.  mpcqp_one_shot_applies: 0 the
  * handle's kernel has no one-shot form (not the fused four-wave kernel, or polish: the call runs
  * as usual), 1 the form with the G blocks in the workspace, 2 with the G blocks in an LDS region
- * of their own, 3 with the G blocks written straight into the solve's LDS copy.  The osqp API
- * never turns it on. */
+ * of their own, 3 with the G blocks written straight into the solve's LDS copy.
+ * mpcqp_one_shot_kernel: which instantiation of the fused four-wave kernel a setup_solve on the
+ * handle launches as currently set, as its GL number 0..5 (the form, the plan's
+ * shape and MPCQP_ONE_SHOT_LOOP decide); -1 while one-shot mode is off, where no form applies,
+ * for a NULL handle and for a sharded one.  The osqp API never turns one-shot mode on. */
 int mpcqp_set_one_shot(mpcqp_handle *h, int32_t on);
 int mpcqp_one_shot_applies(const mpcqp_handle *h);
+int mpcqp_one_shot_kernel(const mpcqp_handle *h);
 /* The handle's own hipStream_t (the one a NULL `stream` selects; first shard), so that a
  * caller's kernels (e.g. mpcqp_affine_apply_device) can be ordered with the handle's calls. */
 void *mpcqp_get_stream(const mpcqp_handle *h);

@@ -129,10 +129,7 @@ struct mpcqp_handle {
     std::pair<hipEvent_t, hipEvent_t> last_pair{nullptr, nullptr};  // events of the last device solve
     bool staged = false;  // every shard's hstage holds the last mpcqp_solve_batch's results
     bool one_shot = false;    // mpcqp_set_one_shot: setup_solve_device persists no workspace state
-    // launch_setup_solve's one_shot value; MPCQP_ONE_SHOT_LOOP=lds / wave / roles at creation:
-    // 2 / 3 / 4 (the one-shot cfg-2 kernel's GL 1 / GL 3 / GL 4 forms, the A/B baselines of its
-    // GL 5 default)
-    int one_shot_loop = 1;
+    OneShot one_shot_loop = OneShot::dflt;  // MPCQP_ONE_SHOT_LOOP at creation (make_handle; one_shot_gl)
     bool state_gone = false;  // the last setup was one-shot: calls that read the workspace refuse
     bool solved = false;      // a solve has run on the current setup (mpcqp_adjoint_* needs its solution)
     bool has_setup = false;   // some setup has written the workspace (mpcqp_load_solution_device needs one)
@@ -674,8 +671,15 @@ int make_handle(int32_t n, int32_t m, const int32_t* Pp, const int32_t* Pi, cons
     if (settings) h->set = *settings;
     else mpcqp_default_settings(&h->set);
     if (int e = validate_settings(h->set)) return e;
-    if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP"))
-        h->one_shot_loop = !strcmp(ev, "lds") ? 2 : (!strcmp(ev, "wave") ? 3 : (!strcmp(ev, "roles") ? 4 : 1));
+    if (const char* ev = getenv("MPCQP_ONE_SHOT_LOOP")) {  // (before any device call; an unknown name is refused)
+        constexpr struct { const char* name; OneShot loop; } names[] = {
+            {"", OneShot::dflt}, {"lds", OneShot::lds}, {"wave", OneShot::wave}, {"roles", OneShot::roles}};
+        h->one_shot_loop = OneShot::off;
+        for (const auto& e : names)
+            if (!strcmp(ev, e.name)) h->one_shot_loop = e.loop;
+        if (h->one_shot_loop == OneShot::off)
+            return fail(MPCQP_EINVAL, "MPCQP_ONE_SHOT_LOOP=%s: not one of lds, wave, roles (or empty: the default)", ev);
+    }
     strace().mark("(enter)");
     std::string err = cached_plan(n, m, Pp, Pi, Ap, Ai, h->set, h->plan);
     strace().mark("plan");
@@ -1540,7 +1544,8 @@ int mpcqp_setup_solve_device(mpcqp_handle* h, const double* dPx, const double* d
         const bool one = h->one_shot && one_shot_form(k) > 0;
         h->state_gone = one;
         if (int e = timed_launch(h->collect, h->ev_solve, st, &h->last_pair, [&]() -> int {
-                HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st, one ? h->one_shot_loop : 0));
+                HIPCHK(launch_setup_solve(k, s.B, dPx, dAx, dq, dl, du, dx, dy, st,
+                                          one ? h->one_shot_loop : OneShot::off));
                 return 0;
             }))
             return e;
@@ -1670,6 +1675,10 @@ int mpcqp_set_one_shot(mpcqp_handle* h, int32_t on) {
 
 int mpcqp_one_shot_applies(const mpcqp_handle* h) {
     return (h && h->shards.size() == 1) ? one_shot_form(h->shards[0].kp) : 0;
+}
+
+int mpcqp_one_shot_kernel(const mpcqp_handle* h) {
+    return (h && h->shards.size() == 1 && h->one_shot) ? one_shot_kernel(h->shards[0].kp, h->one_shot_loop) : -1;
 }
 
 int mpcqp_set_shared_matrices(mpcqp_handle* h, int32_t shared) {

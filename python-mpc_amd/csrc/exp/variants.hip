@@ -46,7 +46,7 @@ static hipError_t launch19(const KParams& p, long B, double* xo, double* yo, int
 }
 static hipError_t setup_solve19(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                 const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                                int /*one_shot*/) {
+                                OneShot /*one_shot*/) {
     hipError_t e = launch_setup_solve_heavy(p, B, Px, Ax, q, l, u, xo, yo, st);
     return (e != hipSuccess || !p.polish) ? e : launch_polish(p, B, xo, yo, st);
 }

@@ -160,6 +160,9 @@ hipError_t launch_copy16(const double* src, double* dst, long n, hipStream_t st,
 constexpr long kDenseRowDoubles = 256L * 54;
 bool dense_w4_on();  // solve_wave.hip: experimental build and MPCQP_DENSE_W4=1
 inline long dense_rows_doubles(int nb, int ne) { return nb == 4 && ne == 0 && dense_w4_on() ? kDenseRowDoubles : 0; }
+// launch_setup_solve's mode: the persisting form, the one-shot form, or the one-shot form held to
+// an earlier loop of the headline's plan (the A/B baselines; solve_wave.hip::one_shot_gl)
+enum class OneShot { off, dflt, lds, wave, roles };
 // What a solve launch runs: the variant's kernel, workgroup size and dynamic LDS.  A launch
 // function given a non-null ref only fills it in (no launch).
 struct KernelRef {
@@ -182,7 +185,8 @@ struct Variant {
                          KernelRef* ref);
     // setup + solve of the same inputs where the variant owns a fused launch (polish included), or null
     hipError_t (*setup_solve)(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
-                              const double* l, const double* u, double* xo, double* yo, hipStream_t st, int one_shot);
+                              const double* l, const double* u, double* xo, double* yo, hipStream_t st,
+                              OneShot one_shot);
 };
 constexpr int kVariantIds = 20;
 const Variant* variant_of(int id);  // null: this build has no such variant
@@ -194,19 +198,19 @@ int solve_threads(int variant);  // workgroup size of the variant's kernel
 bool variant_fits(const KParams& p, int variant);
 hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st);
 // setup + solve of the same inputs (solve_wave.hip): one fused kernel where the variant
-// allows it, else launch_setup then launch_solve.  one_shot: 0 the persisting form, 1 the one-shot
-// form (one_shot_form; on the headline's plan GL 4, the loop compiled per wave role, and with
-// amax = bmax = 5 GL 5, the factorisation compiled for those constants too), 2, 3 and 4 the same
-// with that plan's earlier instantiations, the A/B baselines (2: GL 1, MPCQP_ONE_SHOT_LOOP=lds;
-// 3: GL 3, MPCQP_ONE_SHOT_LOOP=wave; 4: GL 4, MPCQP_ONE_SHOT_LOOP=roles)
+// allows it, else launch_setup then launch_solve.  one_shot: the persisting form (off) or the
+// one-shot form, whose instantiation solve_wave.hip::one_shot_gl picks
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                              int one_shot = 0);
+                              OneShot one_shot = OneShot::off);
 // the one-shot fused kernel's form for the plan (solve_wave.hip): 0 none (not the fused four-wave
 // kernel, or polish), 1 the G blocks in the workspace, 2 the G blocks in an LDS region of their
 // own (two workgroups per CU still fit), 3 the G blocks straight into the solve's LDS copy
 // (factorize_w4_gl); *lds = its dynamic LDS bytes
 int one_shot_form(const KParams& p, size_t* lds = nullptr);
+// the GL number (0..5) of the fused four-wave kernel that launch_setup_solve(p, ..., loop) runs
+// (solve_wave.hip::one_shot_gl of one_shot_form; *lds as there), -1: not a one-shot one (off, or no form)
+int one_shot_kernel(const KParams& p, OneShot loop, size_t* lds = nullptr);
 // resident workgroups of the variant's kernel per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 int solve_blocks_per_cu(const KParams& p);
 size_t lds_w2_bytes(const KParams& p);  // solve_wave.hip: the two- and four-wave kernels
@@ -238,10 +242,10 @@ hipError_t launch_solve_w4(const KParams& p, long B, double* xo, double* yo, int
                            KernelRef* ref = nullptr);
 hipError_t launch_setup_solve_w2(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                  const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                                 int one_shot);
+                                 OneShot one_shot);
 hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                  const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                                 int one_shot);
+                                 OneShot one_shot);
 // 512-thread long-horizon kernel (solve_big.hip): the instantiations for nb <= 12, 18, 24
 hipError_t launch_solve_big12(const KParams& p, long B, double* xo, double* yo, int factor_only, hipStream_t st,
                               KernelRef* ref = nullptr);

@@ -731,7 +731,7 @@ hipError_t launch_solve(const KParams& p, long B, double* xo, double* yo, int fa
 // setup + solve of the same inputs: the variant's fused launch, else the two kernels
 hipError_t launch_setup_solve(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                               const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                              int one_shot) {
+                              OneShot one_shot) {
     const Variant* d = variant_of(p.variant);
     if (d && d->setup_solve) return d->setup_solve(p, B, Px, Ax, q, l, u, xo, yo, st, one_shot);
     hipError_t e = launch_setup(p, B, Px, Ax, q, l, u, st);

@@ -1467,32 +1467,48 @@ static auto with_w4_shape(const KParams& p, F f) {
     return f(W4Rest{});
 }
 
+// the one-shot fused kernel's GL (solve_w4_body) for one_shot_form `form` > 0
+constexpr int one_shot_gl(int form, bool el, bool qr5, bool ab5, OneShot loop) {
+    if (form != 2) return form == 3 ? 2 : 0;
+    if (el || !qr5) return 1;
+    const int best = ab5 ? 5 : 4;
+    const int cap = loop == OneShot::lds ? 1 : loop == OneShot::wave ? 3 : loop == OneShot::roles ? 4 : 5;
+    return cap < best ? cap : best;
+}
+static_assert(one_shot_gl(2, false, true, true, OneShot::dflt) == 5 && one_shot_gl(2, false, true, false, OneShot::dflt) == 4);
+static_assert(one_shot_gl(2, false, true, true, OneShot::roles) == 4 && one_shot_gl(2, false, true, false, OneShot::roles) == 4);
+static_assert(one_shot_gl(2, false, true, true, OneShot::wave) == 3 && one_shot_gl(2, false, true, false, OneShot::wave) == 3);
+static_assert(one_shot_gl(2, false, true, true, OneShot::lds) == 1 && one_shot_gl(2, false, true, false, OneShot::lds) == 1);
+static_assert(one_shot_gl(1, false, true, true, OneShot::dflt) == 0 && one_shot_gl(3, false, true, true, OneShot::dflt) == 2);
+static_assert(one_shot_gl(2, true, false, true, OneShot::dflt) == 1 && one_shot_gl(2, false, false, true, OneShot::dflt) == 1);
+
+int one_shot_kernel(const KParams& p, OneShot loop, size_t* lds) {
+    const int form = loop == OneShot::off ? 0 : one_shot_form(p, lds);
+    return form ? one_shot_gl(form, p.ne != 0, p.amax <= 5, p.amax == 5 && p.bmax == 5, loop) : -1;
+}
+
 // the four-wave kernel's fused launch (variant_fits covers its preconditions: list lengths,
-// pk <= 4, nnzA <= 2 or 3 x T4)
+// pk <= 4, nnzA <= 2 or 3 x T4); one-shot: the instantiation one_shot_kernel names
 hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                  const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                                 int one_shot) {
+                                 OneShot one_shot) {
     size_t lds = 0;
-    const int form = one_shot ? one_shot_form(p, &lds) : 0;
-    if (!form) lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
+    const int gl = one_shot_kernel(p, one_shot, &lds);
+    if (gl < 0) lds = std::max(lds_w2_bytes(p), lds_setup_r_bytes(p.nnzP, p.nnzA, p.npad, p.m));
     using Kernel = decltype(W4Five::setup_solve());
-    // one-shot form 2 is GL 1 (on the headline's shape GL 4, GL 5 with amax = bmax = 5, unless
-    // one_shot == 2, 3 or 4 asks for the A/B baselines GL 1, GL 3 or GL 4), form 3 is GL 2, form 1
-    // is the persisting loop on the one-shot setup
     const Kernel k4 = with_w4_shape(p, [&](auto sh) -> Kernel {
         using Sh = decltype(sh);
-        if (form == 2) {
-            if constexpr (!Sh::EL && Sh::QR <= 5) {
-                if (one_shot == 3) return Sh::template setup_solve<true, 3>();
-                if (one_shot != 2 && one_shot != 4 && p.amax == 5 && p.bmax == 5) return Sh::template setup_solve<true, 5>();
-                if (one_shot != 2) return Sh::template setup_solve<true, 4>();
-            }
-            return Sh::template setup_solve<true, 1>();
+        constexpr bool five = !Sh::EL && Sh::QR <= 5;  // (one_shot_gl gives 3, 4, 5 on this shape only)
+        switch (gl) {  // (the cases' order is the kernels' order in the code object: tools/codeobj.py's hash)
+            case 3: if constexpr (five) return Sh::template setup_solve<true, 3>(); break;
+            case 5: if constexpr (five) return Sh::template setup_solve<true, 5>(); break;
+            case 4: if constexpr (five) return Sh::template setup_solve<true, 4>(); break;
+            case 1: return Sh::template setup_solve<true, 1>();
+            case 2: return Sh::template setup_solve<true, 2>();
+            case 0: return Sh::template setup_solve<true>();
         }
-        if (form == 3) return Sh::template setup_solve<true, 2>();
-        if (form == 1) return Sh::template setup_solve<true>();
 #ifdef MPCQP_EXPERIMENTAL
-        if constexpr (!Sh::EL && Sh::QR <= 5)
+        if constexpr (five)
             if (dense_w4(p)) return Sh::template setup_solve<false, 0, true>();
 #endif
         return Sh::setup_solve();
@@ -1511,7 +1527,7 @@ hipError_t launch_setup_solve_w4(const KParams& p, long B, const double* Px, con
 // padded column per thread, two rows, four A values), else the two kernels
 hipError_t launch_setup_solve_w2(const KParams& p, long B, const double* Px, const double* Ax, const double* q,
                                  const double* l, const double* u, double* xo, double* yo, hipStream_t st,
-                                 int /*one_shot*/) {
+                                 OneShot /*one_shot*/) {
     if (!(p.npad <= T2 && p.m <= 2 * T2 && p.gk <= 6 && p.pk <= 4 && p.nnzA <= 4 * T2 && p.nnzP <= 2 * T2)) {
         hipError_t e = launch_setup(p, B, Px, Ax, q, l, u, st);
         return e != hipSuccess ? e : launch_solve(p, B, xo, yo, 0, st);

@@ -145,6 +145,7 @@ def lib():
     L.mpcqp_set_shared_matrices.argtypes = [vp, C.c_int32]
     L.mpcqp_set_one_shot.argtypes = [vp, C.c_int32]
     L.mpcqp_one_shot_applies.argtypes = [vp]
+    L.mpcqp_one_shot_kernel.argtypes = [vp]
     L.mpcqp_get_stream.argtypes = [vp]
     L.mpcqp_get_stream.restype = vp
     L.mpcqp_last_kernel_ms.argtypes = [vp]
@@ -817,6 +818,11 @@ class DeviceBatch:
         (mpcqp_one_shot_applies)."""
         _check(lib().mpcqp_set_one_shot(self._h.ptr, int(on)), "set_one_shot")
         return int(lib().mpcqp_one_shot_applies(self._h.ptr))
+
+    def one_shot_kernel(self):
+        """mpcqp_one_shot_kernel: the GL number (0..5) of the fused four-wave kernel a setup_solve
+        on this handle launches as currently set; -1 with one-shot mode off or no form applying."""
+        return int(lib().mpcqp_one_shot_kernel(self._h.ptr))
 
     def synchronize(self):
         _check(lib().mpcqp_synchronize(self._h.ptr), "synchronize")

@@ -1,7 +1,9 @@
 """Code-object shape of the production library's hot kernels (test helper, CPU only): what
 actually ships, read by tools/codeobj.py from libmpcqp.so's bundled gfx950 code objects."""
+import collections
 import os
 import re
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -69,6 +71,104 @@ def report(lib, kernels):
                 out[key] = r
                 break
         return out
+
+
+def role_loops(ins, labels):
+    """{header: [census of each back edge, shortest first]} of the call-free loops with exactly
+    four workgroup barriers."""
+    out = {}
+    for lo, hi in loops(ins, labels):
+        if count(ins, lo, hi, "s_swappc") == 0 and count(ins, lo, hi, "s_barrier") == 4:
+            out.setdefault(lo, []).append(census(ins, lo, hi))
+    for v in out.values():
+        v.sort(key=lambda c: c["instructions"])
+    return out
+
+
+def shape_of(cos, symbol):
+    """Of the kernel whose name contains `symbol` in the code objects `cos` (code_objects): its
+    metadata, "roles": per header (in code order) the census of its back edges (role_loops), and
+    "loop": the shortest of them (report's form "w4").  None: no such kernel."""
+    for co in cos:
+        md = metadata(co)
+        hit = [k for k in md if symbol in k]
+        if hit:
+            ins, labels = instructions(co, hit[0])
+            r = dict(md[hit[0]], symbol=hit[0])
+            r["roles"] = [v for _, v in sorted(role_loops(ins, labels).items())]
+            r["loop"] = min((c for v in r["roles"] for c in v), key=lambda c: c["instructions"])
+            return r
+    return None
+
+
+def _is_scratch(s):
+    return s.startswith(("scratch_", "buffer_store", "buffer_load"))
+
+
+def step_paths(ins, labels):
+    """Per v_rcp_f64 that reaches another one: the instructions on the shortest executed path to
+    the next reciprocal -- every divergent branch entered (s_cbranch_execz never taken,
+    s_cbranch_execnz always), scalar branches either way --, as a list of instruction indices."""
+    rcp = {i for i, s in enumerate(ins) if s.startswith("v_rcp_f64")}
+
+    def succ(i):
+        s = ins[i]
+        op, _, arg = s.partition(" ")
+        tgt = labels.get(arg.strip())
+        if op == "s_branch":
+            return [tgt]
+        if op == "s_cbranch_execz":
+            return [i + 1]
+        if op == "s_cbranch_execnz":
+            return [tgt]
+        if op.startswith("s_cbranch"):
+            return [i + 1, tgt]
+        if op in ("s_setpc_b64", "s_endpgm"):
+            return []
+        return [i + 1]
+
+    out = {}
+    for r in sorted(rcp):
+        prev = {r: None}
+        q = collections.deque([r])
+        hit = None
+        while q and hit is None:
+            i = q.popleft()
+            for j in succ(i):
+                if j is None or j >= len(ins) or j in prev:
+                    continue
+                prev[j] = i
+                if j in rcp:
+                    hit = j
+                    break
+                q.append(j)
+        if hit is not None:
+            path = []
+            while hit is not None:
+                path.append(hit)
+                hit = prev[hit]
+            out[r] = path[::-1][1:]  # (from the instruction after this reciprocal to the next one)
+    return out
+
+
+def callee_census(cos, name):
+    """The out-of-line function `name` in the code objects `cos`: its pivot steps (step_paths) and
+    where it touches scratch."""
+    for co in cos:
+        txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-s", "-W", co], check=True, capture_output=True,
+                             text=True).stdout
+        if any(ln.split()[-1:] == [name] for ln in txt.splitlines()):
+            break
+    else:
+        raise KeyError(name)
+    ins, labels = instructions(co, name)
+    paths = step_paths(ins, labels)
+    lens = sorted(len(p) for p in paths.values())
+    on_path = sorted({i for p in paths.values() for i in p})
+    return dict(symbol=name, instructions=len(ins), steps=sum(s.startswith("v_rcp_f64") for s in ins),
+                step_median=statistics.median(lens), step_min=lens[0], step_max=lens[-1],
+                step_scratch=sum(_is_scratch(ins[i]) for i in on_path),
+                scratch_at=[i for i, s in enumerate(ins) if _is_scratch(s)])
 
 
 HOT = {

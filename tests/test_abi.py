@@ -309,10 +309,31 @@ def test_null_handle_is_einval():
     for c in calls:
         assert c() == 1  # MPCQP_EINVAL (include/mpcqp.h)
     assert L.mpcqp_one_shot_applies(null) == 0
+    assert L.mpcqp_one_shot_kernel(null) == -1
+    assert callable(osqp_amd.DeviceBatch.one_shot_kernel)
     with pytest.raises(ValueError, match="not initialized"):
         osqp_amd.OSQP().update_settings(eps_abs=1e-4)
     with pytest.raises(ValueError, match="not initialized"):
         osqp_amd.OSQPBatch().update(Px=np.ones((1, 3)))
+
+
+@pytest.mark.parametrize("value", ["LDS", "wave ", "1", "default"])
+def test_unknown_one_shot_loop_is_refused(monkeypatch, value):
+    """MPCQP_ONE_SHOT_LOOP is read when a handle is created, before any device call: a value that
+    is no rung's name fails the creation with MPCQP_EINVAL and the accepted names (a bit-identity
+    test whose baseline handle silently became the default would compare a kernel with itself)."""
+    monkeypatch.setenv("MPCQP_ONE_SHOT_LOOP", value)
+    with pytest.raises(ValueError, match="MPCQP_ONE_SHOT_LOOP.*lds, wave, roles"):
+        osqp_amd.OSQP().setup(*_tiny())
+
+
+@pytest.mark.parametrize("value", ["", "lds", "wave", "roles"])
+def test_known_one_shot_loop_is_accepted(monkeypatch, value):
+    monkeypatch.setenv("MPCQP_ONE_SHOT_LOOP", value)
+    try:
+        osqp_amd.OSQP().setup(*_tiny(), verbose=False)
+    except RuntimeError as e:  # (without a GPU the creation goes on to the device count and stops there)
+        assert "no HIP device" in str(e), e
 
 
 def test_matrix_update_index_mapping_on_host():

@@ -1,132 +1,30 @@
-"""The one-shot cfg-2 kernel against the persisting kernel on every path of the outer pass.
-
-The one-shot form-2 instantiation of the fused four-wave kernel (no eliminated columns, amax <= 5)
-has its own code between the ADMM runs: the check's column list comes from the run's registers,
-its maxima are combined a lane each, the rho step keeps the residuals in registers, and the run
-start reads the G blocks where the factorisation left them (solve_wave.hip::solve_w4_body, LEAN).
-The persisting kernel keeps the general code.  Each settings variant below reaches another path of the pass; the
-table says which, and what the oracle (run here, on the host) must itself show on the batch before
-the device is touched:
-
-  defaults                          rho steps and refactorisations on the slow instances
-  max_iter=110                      runs ended by the iteration cap; the post-loop termination path
-  scaled_termination=True           the 17-maxima reduction at every check
-  check_termination=10              runs of 10 iterations, checks off the rho grid
-  adaptive_rho=False, max_iter=500  a single factorisation, 20 check passes
-
-The batch is tests/test_one_shot_small.py's: 32 instances cut from mpc.make_batch(2, B=1024,
-seed=2000), the 8 with the highest oracle iteration counts and the first 24 others.  Per variant:
-two setup_solve calls (the second with moved bounds) on a persisting and on a one-shot handle; x,
-y, status and iteration counts are bit-identical in both calls, and the first call agrees with the
-oracle (tests/parity.py::check_agreement).
-
-Not here: a pass that adapts rho without a check (adaptive_rho_interval=40; check_termination=0
-with max_iter=120).  On that pass the persisting kernel's rho step reads the residuals that
-thread 0 has just stored with no barrier in between, and its results are not reproducible (measured:
-non-convex statuses and 4000-iteration runs where the oracle solves in 125-225), so it cannot
-serve as the reference for those settings.
-"""
-import numpy as np
+"""Earlier ids of five rows of tests/test_one_shot_ladder.py's matrix (the paths of the outer pass):
+each is that row's ladder case, all five handles, which runs once per process."""
 import pytest
 
-import pyoracle
-from parity import check_agreement
-from test_one_shot_small import _batch, _out, _same_bits
-
-SOLVED = 1
-CAPPED = (-2, 2)  # ended by the iteration cap: max iterations reached, or solved inaccurate at the cap
-
-
-@pytest.fixture(scope="module")
-def cut():
-    bs, s, idx, full = _batch()  # (the 1024-instance oracle: once per module)
-    assert idx.size == 32
-    rng = np.random.default_rng(2001)  # the second call's bounds (test_one_shot_small.py)
-    l2, u2 = bs["l"].copy(), bs["u"].copy()
-    fin = np.isfinite(l2) & np.isfinite(u2) & (l2 == u2)
-    shift = rng.normal(scale=0.05, size=l2.shape)
-    l2[fin] += shift[fin]
-    u2[fin] += shift[fin]
-    return bs, s, (l2, u2)
-
-
-def _oracle(cut, **kw):
-    bs, s, _ = cut
-    bo = pyoracle.solve_batch(bs["P"], bs["A"], bs["Px"], bs["q"], bs["Ax"], bs["l"], bs["u"], nthreads=4,
-                              **dict(s, **kw))
-    print(f"oracle, {kw}: iterations {bo.iter.tolist()}, "
-          f"status {dict(zip(*(v.tolist() for v in np.unique(bo.status_val, return_counts=True))))}")
-    return bo
-
-
-def _hold(cut, bo, label, **kw):
-    import torch
-    from osqp_amd import DeviceBatch
-    bs, s, (l2, u2) = cut
-    s = dict(s, **kw)
-    B = 32
-    dev = torch.device("cuda", 0)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    dPx, dAx, dq = t(bs["Px"]), t(bs["Ax"]), t(bs["q"])
-    bounds = [(t(bs["l"]), t(bs["u"])), (t(l2), t(u2))]
-    torch.cuda.synchronize()
-    keep, one = DeviceBatch(bs["P"], bs["A"], B, device=0, **s), DeviceBatch(bs["P"], bs["A"], B, device=0, **s)
-    assert one.one_shot(True) == 2
-    pi = one.plan_info()
-    assert pi["variant"] == 17 and pi["amax"] <= 5, pi
-    first = None
-    for call, (l, u) in enumerate(bounds):
-        o1, o2 = _out(B, bs["n"], bs["m"], dev), _out(B, bs["n"], bs["m"], dev)
-        keep.setup_solve(dPx, dAx, dq, l, u, *o1)
-        one.setup_solve(dPx, dAx, dq, l, u, *o2)
-        torch.cuda.synchronize()
-        st = o1[2].cpu().numpy()
-        print(f"{label}, call {call}: status counts {dict(zip(*np.unique(st, return_counts=True)))}, "
-              f"iterations {o1[3].cpu().tolist()}")
-        for a, c in zip(o1, o2):
-            assert _same_bits(a, c), (label, call)
-        if call == 0:
-            first = [v.cpu().numpy() for v in o2]
-    check_agreement(f"cfg2 one-shot passes, {label}", bs, first[0], first[1], first[2], first[3], bo)
+from test_one_shot_ladder import cut_case
 
 
 @pytest.mark.gpu
-def test_passes_defaults(cut):
-    bo = _oracle(cut)
-    assert bo.iter[:8].tolist() == [350, 325, 325, 300, 275, 250, 250, 250], bo.iter[:8]
-    assert bo.iter[8:].min() >= 25 and bo.iter[8:].max() <= 125, bo.iter[8:]
-    assert (bo.status_val == SOLVED).all()
-    _hold(cut, bo, "defaults")
+def test_passes_defaults():
+    cut_case("defaults")
 
 
 @pytest.mark.gpu
-def test_passes_iteration_cap(cut):
-    bo = _oracle(cut, max_iter=110)
-    capped = bo.iter == 110
-    assert capped.sum() == 9 and np.isin(bo.status_val[capped], CAPPED).all(), (bo.iter, bo.status_val)
-    assert (bo.status_val[~capped] == SOLVED).all() and (~capped).sum() == 23
-    _hold(cut, bo, "max_iter=110", max_iter=110)
+def test_passes_iteration_cap():
+    cut_case("max_iter=110")
 
 
 @pytest.mark.gpu
-def test_passes_scaled_termination(cut):
-    bo = _oracle(cut, scaled_termination=True)
-    assert bo.iter[:3].tolist() == [350, 325, 350], bo.iter[:8]
-    assert (bo.status_val == SOLVED).all()
-    _hold(cut, bo, "scaled_termination", scaled_termination=True)
+def test_passes_scaled_termination():
+    cut_case("scaled_termination")
 
 
 @pytest.mark.gpu
-def test_passes_check_every_10(cut):
-    bo = _oracle(cut, check_termination=10)
-    assert bo.iter[:8].min() >= 120 and bo.iter[:8].max() <= 220, bo.iter[:8]
-    assert (bo.iter % 10 == 0).all() and (bo.iter % 25 != 0).any(), bo.iter
-    _hold(cut, bo, "check_termination=10", check_termination=10)
+def test_passes_check_every_10():
+    cut_case("check_termination=10")
 
 
 @pytest.mark.gpu
-def test_passes_single_factorisation(cut):
-    bo = _oracle(cut, adaptive_rho=False, max_iter=500)
-    capped = bo.iter == 500
-    assert capped.sum() == 8 and np.isin(bo.status_val[capped], CAPPED).all(), (bo.iter, bo.status_val)
-    _hold(cut, bo, "adaptive_rho=False max_iter=500", adaptive_rho=False, max_iter=500)
+def test_passes_single_factorisation():
+    cut_case("adaptive_rho=False max_iter=500")

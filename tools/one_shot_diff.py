@@ -8,7 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "python-mpc_amd"))
-from test_one_shot import _inputs, _out  # noqa: E402
+from one_shot_cut import _inputs, out  # noqa: E402
 from osqp_amd import DeviceBatch  # noqa: E402
 
 cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 2
@@ -20,7 +20,7 @@ print("one-shot applies:", hs[2].one_shot(True), hs[3].one_shot(True))
 l, u = bounds[0]
 outs = []
 for h in hs:
-    o = _out(B, b["n"], b["m"], dev)
+    o = out(B, b["n"], b["m"], dev)
     h.setup_solve(Px, Ax, q, l, u, *o)
     torch.cuda.synchronize()
     outs.append([t.cpu().numpy() for t in o])
