@@ -842,6 +842,85 @@ int mpcqp_linearise_vjp_device(const mpcqp_vehicle *veh, int64_t B, int32_t N, c
                                const double *dgBd, const double *dggd, double *dgx, double *dgu, int32_t device,
                                void *stream);
 
+/* ======================================================================
+ * Fleets: a batch of DIFFERENT vehicles.  Every entry point above that takes a
+ * vehicle struct applies it to all B vehicles; its `_fleet` twin below takes a table of B
+ * structs' constants instead and vehicle b uses entry b.
+ * ====================================================================== */
+
+/* veh is a HOST array of B structs.  Creation validates them and derives each vehicle's model
+ * constants on the host with the formulas the uniform entry points use (the dynamic bicycle's
+ * Iz, roll and drag terms and Pacejka coefficients; the kinematic bicycle has none derived), so
+ * vehicle b of a fleet carries exactly the constants a uniform call with veh[b] passes.  It
+ * makes no device call: the table is uploaded to `device` by the first device call that takes
+ * the fleet.  MPCQP_EINVAL with a "fleet_create: ..." message for a NULL veh or out, B < 1, a
+ * non-finite field, m, l_f, l_r or dt <= 0, width^2 + length^2 = 0, or a dt that is not the same
+ * double in every entry (the reference search and the QP's horizon have one dt). */
+typedef struct mpcqp_fleet mpcqp_fleet;         /* dynamic bicycle   */
+typedef struct mpcqp_kin_fleet mpcqp_kin_fleet; /* kinematic bicycle */
+int mpcqp_fleet_create(int64_t B, const mpcqp_vehicle *veh, int32_t device, mpcqp_fleet **out);
+int mpcqp_kin_fleet_create(int64_t B, const mpcqp_kin_vehicle *veh, int32_t device, mpcqp_kin_fleet **out);
+/* Host only: vehicle b's thirteen derived doubles, (m, l_f, l_r, Iz, dt, roh C_d A_f,
+ * C_roll m 9.81, B_f, C_f, D_f, B_r, C_r, D_r). */
+int mpcqp_fleet_constants(const mpcqp_fleet *f, int64_t b, double *out13);
+void mpcqp_fleet_free(mpcqp_fleet *f);
+void mpcqp_kin_fleet_free(mpcqp_kin_fleet *f);
+
+/* The twelve twins: the signature of the entry point named without `_fleet`, the fleet in place of
+ * the vehicle, and that entry point's semantics and argument checks; a B-vehicle call returns the
+ * bits of the B uniform calls with veh[b] on vehicle b alone.  Added, as MPCQP_EINVAL before any
+ * device call: a NULL fleet, a B that is not the fleet's size, a call on another device than the
+ * fleet's (the `device` argument, or the layout's). */
+int mpcqp_linearise_fleet_device(const mpcqp_fleet *f, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                                 int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, double *dAd, double *dBd,
+                                 double *dgd, int32_t device, void *stream);
+int mpcqp_linearise_vjp_fleet_device(const mpcqp_fleet *f, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                                     int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, const double *dgAd,
+                                     const double *dgBd, const double *dggd, double *dgx, double *dgu, int32_t device,
+                                     void *stream);
+int mpcqp_incr_shift_fleet_device(const mpcqp_incr_layout *L, const mpcqp_fleet *f, int64_t B, const double *dsol,
+                                  const double *dAd, const double *dBd, const double *dgd, double *dxt, double *dpred,
+                                  double *dpdu, void *stream);
+int mpcqp_incr_shift_vjp_fleet_device(const mpcqp_incr_layout *L, const mpcqp_fleet *f, int64_t B, const double *dsol,
+                                      const double *dAd, const double *dBd, const double *dgd,
+                                      const double *dxt_before, const double *dgxt, const double *dgpred,
+                                      const double *dgpdu, double *dgsol, double *dgAd0, double *dgBd0, double *dggd0,
+                                      double *dgxt_before, void *stream);
+int mpcqp_kin_linearise_fleet_device(const mpcqp_kin_fleet *f, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                                     int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, double *dAd,
+                                     double *dBd, double *dgd, int32_t device, void *stream);
+int mpcqp_kin_linearise_vjp_fleet_device(const mpcqp_kin_fleet *f, int64_t B, int32_t N, const double *dx,
+                                         int64_t x_sb, int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk,
+                                         const double *dgAd, const double *dgBd, const double *dggd, double *dgx,
+                                         double *dgu, int32_t device, void *stream);
+int mpcqp_kin_shift_fleet_device(const mpcqp_incr_layout *L, const mpcqp_kin_fleet *f, int64_t B, const double *dsol,
+                                 const double *dAd, const double *dBd, const double *dgd, const double *dXr,
+                                 double *dxt, double *dpred, double *dpdu, int32_t *dfinish_cnt, int32_t *ddone,
+                                 double *dtraj, int32_t traj_cap, int32_t *dtraj_len, void *stream);
+int mpcqp_kin_shift_vjp_fleet_device(const mpcqp_incr_layout *L, const mpcqp_kin_fleet *f, int64_t B,
+                                     const double *dsol, const double *dAd, const double *dBd, const double *dgd,
+                                     const double *dxt_before, const int32_t *dmode, const double *dgxt,
+                                     const double *dgpred, const double *dgpdu, double *dgsol, double *dgAd0,
+                                     double *dgBd0, double *dggd0, double *dgxt_before, void *stream);
+int mpcqp_kin_rollout_fleet_device(const mpcqp_kin_fleet *f, int64_t B, int32_t N, const double *dx0,
+                                   const double *du0, double *dpred_x, double *dpred_u, int32_t device, void *stream);
+int mpcqp_kin_ltv_shift_fleet_device(const mpcqp_ltv_layout *L, const mpcqp_kin_fleet *f, int64_t B,
+                                     const double *dsol, const int32_t *dstatus, const double *dAd, const double *dBd,
+                                     const double *dgd, double *dx, double *du, double *dpred_x, double *dpred_u,
+                                     int32_t *dskipped, int32_t *dsteps_taken, double *dtraj, int32_t traj_cap,
+                                     int32_t *dtraj_len, void *stream);
+int mpcqp_kin_ltv_shift_vjp_fleet_device(const mpcqp_ltv_layout *L, const mpcqp_kin_fleet *f, int64_t B,
+                                         const double *dsol, const double *dAd, const double *dBd,
+                                         const double *dx_before, const int32_t *dmode, const double *dgx,
+                                         const double *dgu, const double *dgpred_x, const double *dgpred_u,
+                                         double *dgsol, double *dgAd0, double *dgBd0, double *dggd0,
+                                         double *dgx_before, void *stream);
+int mpcqp_lane_tail_fleet_device(const mpcqp_incr_layout *L, const mpcqp_kin_fleet *f, int64_t B, const double *dsol,
+                                 const double *dAd, const double *dBd, const double *dgd, double *dxt, double *dpred,
+                                 double *dpdu, int32_t nsw, const int32_t *switch_steps, const int32_t *paths_of,
+                                 int32_t *dstep, int32_t *dpath_id, double *dtraj, int32_t traj_cap,
+                                 int32_t *dtraj_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

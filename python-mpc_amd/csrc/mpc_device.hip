@@ -38,6 +38,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mpcqp.h"
@@ -77,6 +78,24 @@ static VehicleK vehicle_constants(const mpcqp_vehicle& v) {
     return k;
 }
 static const mpcqp_kin_vehicle& vehicle_constants(const mpcqp_kin_vehicle& v) { return v; }  // nothing derived
+
+// Where a kernel's constants come from: the struct itself, by value, one car for
+// the whole batch (uniform; it stays in SGPRs), or a fleet's table, one K per vehicle in batch
+// order (array of structs), which thread (b, .) reads through the reference at the point of use.
+template <class K>
+struct TableK {
+    const K* k;
+};
+template <class K>
+__device__ __forceinline__ const K& constants(const K& k, long) { return k; }
+template <class K>
+__device__ __forceinline__ const K& constants(const TableK<K>& t, long b) { return t.k[b]; }
+// A model or a Tail (below) over a fleet: the kernels that are templates over one take M::K by
+// value, so the table goes where the struct went; everything else of M is M's.
+template <class M>
+struct OverFleet : M {
+    using K = TableK<typename M::K>;
+};
 
 __device__ __forceinline__ double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
 
@@ -400,8 +419,8 @@ __global__ __launch_bounds__(256) void k_linearise(typename M::K k, long B, int 
     if (t >= B * N) return;
     const long b = t / N, s = t - b * N;
     constexpr int nx = M::NX, nu = 2;
-    linearise_one(k, x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * (nx * nx), Bd + t * (nx * nu),
-                  gd + t * nx);  // the overload of M::K
+    linearise_one(constants(k, b), x + b * x_sb + s * x_sk, u + b * u_sb + s * u_sk, Ad + t * (nx * nx),
+                  Bd + t * (nx * nu), gd + t * nx);  // the overload of the model's constants
 }
 
 // ------------------------------------------------------- incremental QP layout --
@@ -639,16 +658,19 @@ __global__ __launch_bounds__(256) void k_weights(int nx, int nnzP, int tr, const
 
 // VJP of linearise_one(const mpcqp_kin_vehicle&, ...) per (vehicle, stage): only v, yaw and steer
 // carry derivative; the outputs are dense (B, N, 4) / (B, N, 2) whatever the input strides.
-__global__ __launch_bounds__(256) void k_kin_linearise_vjp(mpcqp_kin_vehicle k, long B, int N,
-                                                           const double* __restrict__ x, long x_sb, long x_sk,
-                                                           const double* __restrict__ u, long u_sb, long u_sk,
-                                                           const double* __restrict__ gAd,
+// A template over the constants' source KS (the struct, or a fleet's TableK), as every kernel of
+// this file that takes a vehicle and is not a template over its model or Tail already.
+template <class KS>
+__global__ __launch_bounds__(256) void k_kin_linearise_vjp(KS ks, long B, int N, const double* __restrict__ x,
+                                                           long x_sb, long x_sk, const double* __restrict__ u,
+                                                           long u_sb, long u_sk, const double* __restrict__ gAd,
                                                            const double* __restrict__ gBd,
                                                            const double* __restrict__ ggd, double* __restrict__ gx,
                                                            double* __restrict__ gu) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * N) return;
     const long b = t / N, s = t - b * N;
+    const mpcqp_kin_vehicle& k = constants(ks, b);
     const double* xs = x + b * x_sb + s * x_sk;
     const double v = xs[2], yaw = xs[3], st = u[b * u_sb + s * u_sk];
     const double dt = k.dt, wb = k.l_f + k.l_r;
@@ -701,14 +723,19 @@ struct VjpFold {
 // written: the low-speed guard first (what it replaces by a constant carries no derivative), then
 // continuous_model over forward-mode duals in (yaw, vx, vy, r, steer, accel), each output's
 // tangent contracted with its cotangent as soon as it exists.  Outputs dense (B, N, 6) / (B, N, 2).
-__global__ __launch_bounds__(256) void k_linearise_vjp(VehicleK k, long B, int N, const double* __restrict__ x,
-                                                       long x_sb, long x_sk, const double* __restrict__ u, long u_sb,
-                                                       long u_sk, const double* __restrict__ gAd,
-                                                       const double* __restrict__ gBd, const double* __restrict__ ggd,
-                                                       double* __restrict__ gx, double* __restrict__ gu) {
+template <class KS>
+__global__ __launch_bounds__(256) void k_linearise_vjp(KS ks, long B, int N, const double* __restrict__ x, long x_sb,
+                                                       long x_sk, const double* __restrict__ u, long u_sb, long u_sk,
+                                                       const double* __restrict__ gAd, const double* __restrict__ gBd,
+                                                       const double* __restrict__ ggd, double* __restrict__ gx,
+                                                       double* __restrict__ gu) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * N) return;
     const long b = t / N, s = t - b * N;
+    // By value: read through the table's pointer, the constants are loaded again at every use over
+    // these six thousand instructions, 1 / m and 1 / Iz are formed again with them, and the
+    // products contract with other sums than in the uniform form -- other bits.
+    const VehicleK k = constants(ks, b);
     const double* xin = x + b * x_sb + s * x_sk;
     const double* uin = u + b * u_sb + s * u_sk;
     double xg[6], ug[2];
@@ -875,7 +902,8 @@ __global__ __launch_bounds__(256) void k_stage_shift(long total, int len, int N,
 //   u = u_past + du_0;  x_next = Ad_0 x + Bd_0 u + gd_0;  x~ = (x_next, u)
 //   shift pred_x~ / du one stage; terminal state by one nonlinear Euler step from
 //   (pred_x~[:nx, N], pred_x~[nx:, N-1]) (update_dynamics_model)
-__global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B, const double* __restrict__ sol,
+template <class KS>
+__global__ __launch_bounds__(128) void k_incr_shift(KS ks, IncrK L, long B, const double* __restrict__ sol,
                                                     const double* __restrict__ Ad, const double* __restrict__ Bd,
                                                     const double* __restrict__ gd, double* __restrict__ xt,
                                                     double* __restrict__ pred, double* __restrict__ pdu) {
@@ -905,7 +933,7 @@ __global__ __launch_bounds__(128) void k_incr_shift(VehicleK vk, IncrK L, long B
     double xN[6], uN[2], xe[6];
     for (int i = 0; i < 6; ++i) xN[i] = s[N * nxa + i];
     for (int j = 0; j < 2; ++j) uN[j] = s[(N - 1) * nxa + nx + j];
-    euler_step_guarded(vk, xN, uN, xe);
+    euler_step_guarded(constants(ks, b), xN, uN, xe);
     for (int i = 0; i < nx; ++i) pb[N * nxa + i] = xe[i];
     for (int j = 0; j < nu; ++j) pb[N * nxa + nx + j] = pb[(N - 1) * nxa + nx + j];
     for (int j = 0; j < nu; ++j) db[N * nu + j] = db[(N - 1) * nu + j];
@@ -977,13 +1005,13 @@ __device__ __forceinline__ void kin_incr_step_shift(const mpcqp_kin_vehicle& vk,
 // control of the terminal Euler step is the solution's stage-N control, not stage N-1's;
 // update_kinematics_model (vehicle_models.py:877-880) then advances v before yaw uses it.
 // A vehicle whose done flag is set is skipped whole.
-__global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L, long B,
-                                                   const double* __restrict__ sol, const double* __restrict__ Ad,
-                                                   const double* __restrict__ Bd, const double* __restrict__ gd,
-                                                   const double* __restrict__ Xr, double* __restrict__ xt,
-                                                   double* __restrict__ pred, double* __restrict__ pdu,
-                                                   int* __restrict__ finish_cnt, int* __restrict__ done,
-                                                   double* __restrict__ traj, int traj_cap,
+template <class KS>
+__global__ __launch_bounds__(128) void k_kin_shift(KS ks, IncrK L, long B, const double* __restrict__ sol,
+                                                   const double* __restrict__ Ad, const double* __restrict__ Bd,
+                                                   const double* __restrict__ gd, const double* __restrict__ Xr,
+                                                   double* __restrict__ xt, double* __restrict__ pred,
+                                                   double* __restrict__ pdu, int* __restrict__ finish_cnt,
+                                                   int* __restrict__ done, double* __restrict__ traj, int traj_cap,
                                                    int* __restrict__ traj_len) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -1012,8 +1040,8 @@ __global__ __launch_bounds__(128) void k_kin_shift(mpcqp_kin_vehicle vk, IncrK L
             return;
         }
     }
-    kin_incr_step_shift(vk, N, s, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu, gd + b * (long)N * nx, xb, pb,
-                        db);
+    kin_incr_step_shift(constants(ks, b), N, s, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu,
+                        gd + b * (long)N * nx, xb, pb, db);
 }
 
 // A step schedule by value: value = val[#{j < nsw : step > sw[j]}] (k_lti_step's convention).
@@ -1033,13 +1061,14 @@ struct StepSchedule {
 // kin_incr_step_shift), then the step counter and the path the NEXT step's reference search
 // runs on (the double lane change of :380-391).  No skip rule: mpc_increment uses the solution
 // whatever its status (:248-252).
-__global__ __launch_bounds__(128) void k_lane_tail(mpcqp_kin_vehicle vk, IncrK L, StepSchedule sched, long B,
+template <class KS>
+__global__ __launch_bounds__(128) void k_lane_tail(KS ks, IncrK L, StepSchedule sched, long B,
                                                    const double* __restrict__ sol, const double* __restrict__ Ad,
                                                    const double* __restrict__ Bd, const double* __restrict__ gd,
                                                    double* __restrict__ xt, double* __restrict__ pred,
                                                    double* __restrict__ pdu, int* __restrict__ step,
-                                                   int* __restrict__ path_id, double* __restrict__ traj,
-                                                   int traj_cap, int* __restrict__ traj_len) {
+                                                   int* __restrict__ path_id, double* __restrict__ traj, int traj_cap,
+                                                   int* __restrict__ traj_len) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     constexpr int nx = 4, nu = 2, nxa = 6;
@@ -1047,7 +1076,7 @@ __global__ __launch_bounds__(128) void k_lane_tail(mpcqp_kin_vehicle vk, IncrK L
     double* xb = xt + b * nxa;
     if (double* tr = traj_append(traj, traj_cap, traj_len, b, nxa))
         for (int i = 0; i < nxa; ++i) tr[i] = xb[i];
-    kin_incr_step_shift(vk, N, sol + b * L.n, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu,
+    kin_incr_step_shift(constants(ks, b), N, sol + b * L.n, Ad + b * (long)N * nx * nx, Bd + b * (long)N * nx * nu,
                         gd + b * (long)N * nx, xb, pred + b * (long)(N + 1) * nxa, pdu + b * (long)(N + 1) * nu);
     const int k = step[b] + 1;
     step[b] = k;
@@ -1056,11 +1085,13 @@ __global__ __launch_bounds__(128) void k_lane_tail(mpcqp_kin_vehicle vk, IncrK L
 
 // Initial horizon of mpc_kinematics_pred_matrix.main (:405-419): u0 in every stage, the
 // nonlinear model rolled forward from x0.  pred_x (B, N+1, 4), pred_u (B, N+1, 2).
-__global__ __launch_bounds__(128) void k_kin_rollout(mpcqp_kin_vehicle vk, long B, int N,
-                                                     const double* __restrict__ x0, const double* __restrict__ u0,
-                                                     double* __restrict__ pred_x, double* __restrict__ pred_u) {
+template <class KS>
+__global__ __launch_bounds__(128) void k_kin_rollout(KS ks, long B, int N, const double* __restrict__ x0,
+                                                     const double* __restrict__ u0, double* __restrict__ pred_x,
+                                                     double* __restrict__ pred_u) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const mpcqp_kin_vehicle& vk = constants(ks, b);
     double* px = pred_x + b * (long)(N + 1) * 4;
     double* pu = pred_u + b * (long)(N + 1) * 2;
     const double uu[2] = {u0[b * 2], u0[b * 2 + 1]};
@@ -1078,15 +1109,15 @@ __global__ __launch_bounds__(128) void k_kin_rollout(mpcqp_kin_vehicle vk, long 
 // U_0..U_{N-1}) the result is: pred_x = (x_next, S_2..S_N, update(S_N, U_{N-1})),
 // pred_u = (U_1..U_{N-1}, U_{N-1}, U_{N-1}) -- the terminal control is stage N-1, unlike
 // k_kin_shift.  A vehicle whose status is not `solved` is skipped whole (:480-484).
-__global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int N, int n, long B,
-                                                       const double* __restrict__ sol,
-                                                       const int* __restrict__ status,
-                                                       const double* __restrict__ Ad, const double* __restrict__ Bd,
-                                                       const double* __restrict__ gd, double* __restrict__ x,
-                                                       double* __restrict__ u, double* __restrict__ pred_x,
-                                                       double* __restrict__ pred_u, int* __restrict__ skipped,
-                                                       int* __restrict__ steps_taken, double* __restrict__ traj,
-                                                       int traj_cap, int* __restrict__ traj_len) {
+template <class KS>
+__global__ __launch_bounds__(128) void k_kin_ltv_shift(KS ks, int N, int n, long B, const double* __restrict__ sol,
+                                                       const int* __restrict__ status, const double* __restrict__ Ad,
+                                                       const double* __restrict__ Bd, const double* __restrict__ gd,
+                                                       double* __restrict__ x, double* __restrict__ u,
+                                                       double* __restrict__ pred_x, double* __restrict__ pred_u,
+                                                       int* __restrict__ skipped, int* __restrict__ steps_taken,
+                                                       double* __restrict__ traj, int traj_cap,
+                                                       int* __restrict__ traj_len) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     if (status && status[b] != 1) {
@@ -1113,7 +1144,7 @@ __global__ __launch_bounds__(128) void k_kin_ltv_shift(mpcqp_kin_vehicle vk, int
     // shift (:543-563), from the solution
     for (int k = 1; k <= N - 1; ++k)
         for (int i = 0; i < nx; ++i) px[k * nx + i] = S[(k + 1) * nx + i];
-    kin_update(vk, S + N * nx, U + (N - 1) * nu, px + N * nx);
+    kin_update(constants(ks, b), S + N * nx, U + (N - 1) * nu, px + N * nx);
     for (int k = 0; k <= N - 2; ++k)
         for (int j = 0; j < nu; ++j) pu[k * nu + j] = U[(k + 1) * nu + j];
     for (int j = 0; j < nu; ++j) pu[(N - 1) * nu + j] = pu[N * nu + j] = U[(N - 1) * nu + j];
@@ -1234,7 +1265,7 @@ __global__ __launch_bounds__(256) void k_tail_vjp(typename Tail::K vk, int N, in
             if constexpr (Tail::incremental)
                 if (k == N && gp)
                     for (int j = 0; j < nu; ++j) g[nx + j] = g[nx + j] + gp[N * nxa + nx + j];
-            if (gp) Tail::terminal(vk, N, s, gp + N * nxa, row, g);
+            if (gp) Tail::terminal(constants(vk, b), N, s, gp + N * nxa, row, g);
         }
         for (int i = 0; i < nxa; ++i) gsol[b * n + k * nxa + i] = g[i];
         return;
@@ -1285,7 +1316,7 @@ __global__ __launch_bounds__(256) void k_tail_vjp(typename Tail::K vk, int N, in
             else g[j] = gd ? gd[(k - 1) * nu + j] : 0.0;
             if (k == N - 1 && gd) g[j] = (g[j] + gd[(N - 1) * nu + j]) + gd[N * nu + j];
         }
-        if (gp) Tail::terminal(vk, N, s, gp + N * nxa, row, g);
+        if (gp) Tail::terminal(constants(vk, b), N, s, gp + N * nxa, row, g);
         for (int j = 0; j < nu; ++j) gsol[b * n + (N + 1) * nxa + k * nu + j] = g[j];
         return;
     }
@@ -1503,9 +1534,23 @@ struct mpcqp_affine {
     double* d_pcoef = nullptr;
 };
 
+// A fleet: the B structs as given, each vehicle's constants (vehicle_constants, on the host, at
+// creation) and their device table, uploaded by the first call that needs it.
+template <class V, class KT>
+struct Fleet {
+    using Vehicle = V;
+    using K = KT;
+    int dev = 0;
+    std::vector<V> veh;
+    std::vector<KT> k;
+    KT* d_k = nullptr;
+};
+struct mpcqp_fleet : Fleet<mpcqp_vehicle, VehicleK> {};
+struct mpcqp_kin_fleet : Fleet<mpcqp_kin_vehicle, mpcqp_kin_vehicle> {};
+
 namespace {
 
-#define MHIPCHK(expr)                                                                         \
+#define MHIPCHK(expr)                                                                        \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess)                                                                 \
@@ -1716,15 +1761,197 @@ int launch(int device, void* stream, long count, int block, void (*kernel)(P...)
     return 0;
 }
 
+// The constants' source of a call, V: a vehicle struct (one car for the batch, by value) or a fleet
+// (its table, entry b for vehicle b).  Every host function below that takes one is written once
+// over V: source_check after its own argument checks and before any device call, then launch_from.
+template <class V>
+constexpr bool kIsFleet = std::is_same<V, mpcqp_fleet>::value || std::is_same<V, mpcqp_kin_fleet>::value;
+
+// a fleet serves batches of its own size on its own device; a vehicle struct any
+template <class V>
+int source_check(const char* what, const V* veh, int64_t B, int device) {
+    if constexpr (kIsFleet<V>) {
+        if ((int64_t)veh->k.size() != B)
+            return set_error(MPCQP_EINVAL, "%s: B = %lld is not the fleet's size %lld", what, (long long)B,
+                             (long long)veh->k.size());
+        if (veh->dev != device)
+            return set_error(MPCQP_EINVAL, "%s: the fleet was created for device %d, the call is on device %d", what,
+                             veh->dev, device);
+    }
+    return 0;
+}
+
+// launch(): `uniform` with the struct's constants, or `table` with the fleet's device table
+// (uploaded here on first use), first among the kernel's arguments
+#define BOTH_FORMS(kernel, K) kernel<K>, kernel<TableK<K>>  // `uniform`, `table` of a kernel template over KS
+template <class V, class KU, class KT, class... A>
+int launch_from(const V* veh, int device, void* stream, long count, int block, KU uniform, KT table, A... args) {
+    if constexpr (kIsFleet<V>) {
+        V& f = *const_cast<V*>(veh);
+        if (!f.d_k) {
+            MHIPCHK(hipSetDevice(f.dev));
+            if (int e = upload(f.k, &f.d_k)) return e;
+        }
+        return launch(device, stream, count, block, table, TableK<typename V::K>{f.d_k}, args...);
+    } else {
+        return launch(device, stream, count, block, uniform, vehicle_constants(*veh), args...);
+    }
+}
+
 template <class M, class V>
 int linearise_device(const char* what, const V* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
                      int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
                      double* dgd, int32_t device, void* stream) {
     if (!veh || !dx || !du || !dAd || !dBd || !dgd || B < 0 || N < 1)
         return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (int e = source_check(what, veh, B, device)) return e;
     if (B == 0) return 0;
-    return launch(device, stream, B * N, 256, k_linearise<M>, vehicle_constants(*veh), B, N, dx, x_sb, x_sk, du, u_sb,
-                  u_sk, dAd, dBd, dgd);
+    return launch_from(veh, device, stream, B * N, 256, k_linearise<M>, k_linearise<OverFleet<M>>, B, N, dx, x_sb,
+                       x_sk, du, u_sb, u_sk, dAd, dBd, dgd);
+}
+
+// M: the model, which selects the kernel pair (the dynamic bicycle's duals, the kinematic closed form)
+template <class M, class V>
+int linearise_vjp_device(const char* what, const V* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                         int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                         const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
+                         void* stream) {
+    if (!veh || !dx || !du || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (int e = source_check(what, veh, B, device)) return e;
+    if (B == 0 || (!dgx && !dgu)) return 0;
+    if constexpr (M::NX == 6)
+        return launch_from(veh, device, stream, B * N, 256, BOTH_FORMS(k_linearise_vjp, VehicleK), B, N, dx, x_sb,
+                           x_sk, du, u_sb, u_sk, dgAd, dgBd, dggd, dgx, dgu);
+    else
+        return launch_from(veh, device, stream, B * N, 256, BOTH_FORMS(k_kin_linearise_vjp, mpcqp_kin_vehicle), B, N, dx,
+                           x_sb, x_sk, du, u_sb, u_sk, dgAd, dgBd, dggd, dgx, dgu);
+}
+
+template <class V>
+int incr_shift_device(const mpcqp_incr_layout* L, const V* veh, int64_t B, const double* dsol, const double* dAd,
+                      const double* dBd, const double* dgd, double* dxt, double* dpred, double* dpdu, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dxt || !dpred || !dpdu || B < 0)
+        return set_error(MPCQP_EINVAL, "incr_shift: bad arguments");
+    if (L->nx != 6 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED, "incr_shift: the plant model is the 6-state dynamic bicycle (nx 6, nu 2)");
+    if (int e = source_check("incr_shift", veh, B, L->dev)) return e;
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    return launch_from(veh, L->dev, stream, B, 128, BOTH_FORMS(k_incr_shift, VehicleK), incr_k(*L), B, dsol, dAd, dBd,
+                       dgd, dxt, dpred, dpdu);
+}
+
+template <class V>
+int kin_shift_device(const mpcqp_incr_layout* L, const V* veh, int64_t B, const double* dsol, const double* dAd,
+                     const double* dBd, const double* dgd, const double* dXr, double* dxt, double* dpred,
+                     double* dpdu, int32_t* dfinish_cnt, int32_t* ddone, double* dtraj, int32_t traj_cap,
+                     int32_t* dtraj_len, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dXr || !dxt || !dpred || !dpdu || !dfinish_cnt || !ddone ||
+        B < 0 || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_shift: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED, "kin_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (int e = source_check("kin_shift", veh, B, L->dev)) return e;
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    return launch_from(veh, L->dev, stream, B, 128, BOTH_FORMS(k_kin_shift, mpcqp_kin_vehicle), incr_k(*L), B, dsol, dAd, dBd, dgd,
+                       dXr, dxt, dpred, dpdu, dfinish_cnt, ddone, dtraj, traj_cap, dtraj_len);
+}
+
+template <class V>
+int kin_rollout_device(const V* veh, int64_t B, int32_t N, const double* dx0, const double* du0, double* dpred_x,
+                       double* dpred_u, int32_t device, void* stream) {
+    if (!veh || !dx0 || !du0 || !dpred_x || !dpred_u || B < 0 || N < 1)
+        return set_error(MPCQP_EINVAL, "kin_rollout: bad arguments");
+    if (int e = source_check("kin_rollout", veh, B, device)) return e;
+    if (B == 0) return 0;
+    return launch_from(veh, device, stream, B, 128, BOTH_FORMS(k_kin_rollout, mpcqp_kin_vehicle), B, N, dx0, du0, dpred_x,
+                       dpred_u);
+}
+
+template <class V>
+int kin_ltv_shift_device(const mpcqp_ltv_layout* L, const V* veh, int64_t B, const double* dsol,
+                         const int32_t* dstatus, const double* dAd, const double* dBd, const double* dgd, double* dx,
+                         double* du, double* dpred_x, double* dpred_u, int32_t* dskipped, int32_t* dsteps_taken,
+                         double* dtraj, int32_t traj_cap, int32_t* dtraj_len, void* stream) {
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dpred_u || !dskipped || B < 0 ||
+        traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "kin_ltv_shift: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "kin_ltv_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (int e = source_check("kin_ltv_shift", veh, B, L->dev)) return e;
+    if (B == 0) return 0;
+    return launch_from(veh, L->dev, stream, B, 128, BOTH_FORMS(k_kin_ltv_shift, mpcqp_kin_vehicle), L->N, L->n, B, dsol,
+                       dstatus, dAd, dBd, dgd, dx, du, dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap,
+                       dtraj_len);
+}
+
+template <class V>
+int lane_tail_device(const mpcqp_incr_layout* L, const V* veh, int64_t B, const double* dsol, const double* dAd,
+                     const double* dBd, const double* dgd, double* dxt, double* dpred, double* dpdu, int32_t nsw,
+                     const int32_t* switch_steps, const int32_t* paths_of, int32_t* dstep, int32_t* dpath_id,
+                     double* dtraj, int32_t traj_cap, int32_t* dtraj_len, void* stream) {
+    if (nsw > 8) return set_error(MPCQP_EUNSUPPORTED, "lane_tail: need nsw <= 8");
+    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dxt || !dpred || !dpdu || !paths_of || !dstep || !dpath_id ||
+        B < 0 || nsw < 0 || (nsw > 0 && !switch_steps) || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
+        return set_error(MPCQP_EINVAL, "lane_tail: bad arguments");
+    if (L->nx != 4 || L->nu != 2)
+        return set_error(MPCQP_EUNSUPPORTED,
+                         "lane_tail: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
+    if (int e = source_check("lane_tail", veh, B, L->dev)) return e;
+    if (B == 0) return 0;
+    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
+    StepSchedule sched = {};
+    sched.nsw = nsw;
+    std::copy(switch_steps, switch_steps + nsw, sched.sw);
+    std::copy(paths_of, paths_of + nsw + 1, sched.val);
+    return launch_from(veh, L->dev, stream, B, 128, BOTH_FORMS(k_lane_tail, mpcqp_kin_vehicle), incr_k(*L), sched, B, dsol, dAd,
+                       dBd, dgd, dxt, dpred, dpdu, dstep, dpath_id, dtraj, traj_cap, dtraj_len);
+}
+
+// mpcqp_fleet_create / mpcqp_kin_fleet_create: the refusals, then every vehicle's constants
+inline const double* fields_of(const mpcqp_vehicle& v, int* n) { *n = 9; return &v.m; }
+inline const double* fields_of(const mpcqp_kin_vehicle& v, int* n) { *n = 3; return &v.l_f; }
+inline bool inertia_ok(const mpcqp_vehicle& v) { return v.m > 0.0 && v.width * v.width + v.length * v.length != 0.0; }
+inline bool inertia_ok(const mpcqp_kin_vehicle&) { return true; }  // the kinematic model has none
+
+template <class F, class V>
+int fleet_create(int64_t B, const V* veh, int32_t device, F** out) {
+    if (!veh || !out) return set_error(MPCQP_EINVAL, "fleet_create: NULL argument");
+    *out = nullptr;
+    if (B < 1) return set_error(MPCQP_EINVAL, "fleet_create: need B >= 1");
+    for (int64_t b = 0; b < B; ++b) {
+        int nf = 0;
+        const double* f = fields_of(veh[b], &nf);
+        for (int i = 0; i < nf; ++i)
+            if (!std::isfinite(f[i]))
+                return set_error(MPCQP_EINVAL, "fleet_create: vehicle %lld has a non-finite field", (long long)b);
+        if (!(veh[b].l_f > 0.0) || !(veh[b].l_r > 0.0) || !(veh[b].dt > 0.0) || !inertia_ok(veh[b]))
+            return set_error(MPCQP_EINVAL,
+                             "fleet_create: vehicle %lld needs m, l_f, l_r, dt > 0 and width^2 + length^2 > 0",
+                             (long long)b);
+        if (veh[b].dt != veh[0].dt)
+            return set_error(MPCQP_EINVAL, "fleet_create: vehicle %lld has dt %.17g, vehicle 0 has %.17g: one dt per fleet",
+                             (long long)b, veh[b].dt, veh[0].dt);
+    }
+    auto f = std::make_unique<F>();
+    f->dev = device;
+    f->veh.assign(veh, veh + B);
+    f->k.reserve(B);
+    for (int64_t b = 0; b < B; ++b) f->k.push_back(vehicle_constants(veh[b]));
+    *out = f.release();  // the table is uploaded by the first device call that takes the fleet
+    return 0;
+}
+
+template <class F>
+void fleet_free(F* f) {
+    if (!f) return;
+    if (f->d_k) {
+        (void)hipSetDevice(f->dev);
+        (void)hipFree(f->d_k);
+    }
+    delete f;
 }
 
 // dmode: null where the Tail has no modes; dgu: the direct-input Tail's, else null.  Every
@@ -1739,9 +1966,11 @@ int tail_vjp_device(const char* what, const IncrLayout* L, const V* veh, int64_t
     if (L->nx != Tail::nx || L->nu != Tail::nu)
         return set_error(MPCQP_EUNSUPPORTED, "%s: the plant model is the %s bicycle (nx %d, nu %d)", what, Tail::model,
                          Tail::nx, Tail::nu);
+    if (int e = source_check(what, veh, B, L->dev)) return e;
     if (B == 0 || (!dgsol && !dgAd0 && !dgBd0 && !dggd0 && !dgx_before)) return 0;
-    return launch(L->dev, stream, B * (2 * L->N + 2), 256, k_tail_vjp<Tail>, vehicle_constants(*veh), L->N, L->n, B,
-                  dsol, dAd, dBd, dx_before, dmode, dgx, dgu, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgx_before);
+    return launch_from(veh, L->dev, stream, B * (2 * L->N + 2), 256, k_tail_vjp<Tail>, k_tail_vjp<OverFleet<Tail>>,
+                       L->N, L->n, B, dsol, dAd, dBd, dx_before, dmode, dgx, dgu, dgpred, dgpdu, dgsol, dgAd0, dgBd0,
+                       dggd0, dgx_before);
 }
 
 // dpath_yaw, dset_speed: the kinematic reference's (its entry point checks them), else null
@@ -1983,20 +2212,16 @@ int mpcqp_kin_linearise_vjp_device(const mpcqp_kin_vehicle* veh, int64_t B, int3
                                    int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
                                    const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
                                    void* stream) {
-    if (!veh || !dx || !du || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "kin_linearise_vjp: bad arguments");
-    if (B == 0 || (!dgx && !dgu)) return 0;
-    return launch(device, stream, B * N, 256, k_kin_linearise_vjp, *veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd,
-                  dgBd, dggd, dgx, dgu);
+    return linearise_vjp_device<KinematicBicycle>("kin_linearise_vjp", veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd,
+                                                  dgBd, dggd, dgx, dgu, device, stream);
 }
 
 int mpcqp_linearise_vjp_device(const mpcqp_vehicle* veh, int64_t B, int32_t N, const double* dx, int64_t x_sb,
                                int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
                                const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
                                void* stream) {
-    if (!veh || !dx || !du || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "linearise_vjp: bad arguments");
-    if (B == 0 || (!dgx && !dgu)) return 0;
-    return launch(device, stream, B * N, 256, k_linearise_vjp, vehicle_constants(*veh), B, N, dx, x_sb, x_sk, du, u_sb,
-                  u_sk, dgAd, dgBd, dggd, dgx, dgu);
+    return linearise_vjp_device<DynamicBicycle>("linearise_vjp", veh, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd, dgBd,
+                                                dggd, dgx, dgu, device, stream);
 }
 
 void mpcqp_incr_layout_free(mpcqp_incr_layout* L) {
@@ -2014,14 +2239,7 @@ void mpcqp_ltv_layout_free(mpcqp_ltv_layout* L) {
 int mpcqp_incr_shift_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh, int64_t B, const double* dsol,
                             const double* dAd, const double* dBd, const double* dgd, double* dxt, double* dpred,
                             double* dpdu, void* stream) {
-    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dxt || !dpred || !dpdu || B < 0)
-        return set_error(MPCQP_EINVAL, "incr_shift: bad arguments");
-    if (L->nx != 6 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED, "incr_shift: the plant model is the 6-state dynamic bicycle (nx 6, nu 2)");
-    if (B == 0) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    return launch(L->dev, stream, B, 128, k_incr_shift, vehicle_constants(*veh), incr_k(*L), B, dsol, dAd, dBd, dgd,
-                  dxt, dpred, dpdu);
+    return incr_shift_device(L, veh, B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu, stream);
 }
 
 int mpcqp_incr_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_vehicle* veh, int64_t B, const double* dsol,
@@ -2037,23 +2255,13 @@ int mpcqp_kin_shift_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* 
                            const double* dAd, const double* dBd, const double* dgd, const double* dXr, double* dxt,
                            double* dpred, double* dpdu, int32_t* dfinish_cnt, int32_t* ddone, double* dtraj,
                            int32_t traj_cap, int32_t* dtraj_len, void* stream) {
-    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dXr || !dxt || !dpred || !dpdu || !dfinish_cnt || !ddone ||
-        B < 0 || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
-        return set_error(MPCQP_EINVAL, "kin_shift: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED, "kin_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    return launch(L->dev, stream, B, 128, k_kin_shift, *veh, incr_k(*L), B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu,
-                  dfinish_cnt, ddone, dtraj, traj_cap, dtraj_len);
+    return kin_shift_device(L, veh, B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu, dfinish_cnt, ddone, dtraj, traj_cap,
+                            dtraj_len, stream);
 }
 
 int mpcqp_kin_rollout_device(const mpcqp_kin_vehicle* veh, int64_t B, int32_t N, const double* dx0,
                              const double* du0, double* dpred_x, double* dpred_u, int32_t device, void* stream) {
-    if (!veh || !dx0 || !du0 || !dpred_x || !dpred_u || B < 0 || N < 1)
-        return set_error(MPCQP_EINVAL, "kin_rollout: bad arguments");
-    if (B == 0) return 0;
-    return launch(device, stream, B, 128, k_kin_rollout, *veh, B, N, dx0, du0, dpred_x, dpred_u);
+    return kin_rollout_device(veh, B, N, dx0, du0, dpred_x, dpred_u, device, stream);
 }
 
 int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicle* veh, int64_t B,
@@ -2061,15 +2269,8 @@ int mpcqp_kin_ltv_shift_device(const mpcqp_ltv_layout* L, const mpcqp_kin_vehicl
                                const double* dgd, double* dx, double* du, double* dpred_x, double* dpred_u,
                                int32_t* dskipped, int32_t* dsteps_taken, double* dtraj, int32_t traj_cap,
                                int32_t* dtraj_len, void* stream) {
-    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dx || !du || !dpred_x || !dpred_u || !dskipped || B < 0 ||
-        traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
-        return set_error(MPCQP_EINVAL, "kin_ltv_shift: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "kin_ltv_shift: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0) return 0;
-    return launch(L->dev, stream, B, 128, k_kin_ltv_shift, *veh, L->N, L->n, B, dsol, dstatus, dAd, dBd, dgd, dx, du,
-                  dpred_x, dpred_u, dskipped, dsteps_taken, dtraj, traj_cap, dtraj_len);
+    return kin_ltv_shift_device(L, veh, B, dsol, dstatus, dAd, dBd, dgd, dx, du, dpred_x, dpred_u, dskipped,
+                                dsteps_taken, dtraj, traj_cap, dtraj_len, stream);
 }
 
 int mpcqp_kin_shift_vjp_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* veh, int64_t B, const double* dsol,
@@ -2108,21 +2309,8 @@ int mpcqp_lane_tail_device(const mpcqp_incr_layout* L, const mpcqp_kin_vehicle* 
                            double* dpdu, int32_t nsw, const int32_t* switch_steps, const int32_t* paths_of,
                            int32_t* dstep, int32_t* dpath_id, double* dtraj, int32_t traj_cap, int32_t* dtraj_len,
                            void* stream) {
-    if (nsw > 8) return set_error(MPCQP_EUNSUPPORTED, "lane_tail: need nsw <= 8");
-    if (!L || !veh || !dsol || !dAd || !dBd || !dgd || !dxt || !dpred || !dpdu || !paths_of || !dstep || !dpath_id ||
-        B < 0 || nsw < 0 || (nsw > 0 && !switch_steps) || traj_cap < 0 || (traj_cap > 0 && (!dtraj || !dtraj_len)))
-        return set_error(MPCQP_EINVAL, "lane_tail: bad arguments");
-    if (L->nx != 4 || L->nu != 2)
-        return set_error(MPCQP_EUNSUPPORTED,
-                         "lane_tail: the plant model is the 4-state kinematic bicycle (nx 4, nu 2)");
-    if (B == 0) return 0;
-    if (int e = ensure_device(*const_cast<mpcqp_incr_layout*>(L))) return e;
-    StepSchedule sched = {};
-    sched.nsw = nsw;
-    std::copy(switch_steps, switch_steps + nsw, sched.sw);
-    std::copy(paths_of, paths_of + nsw + 1, sched.val);
-    return launch(L->dev, stream, B, 128, k_lane_tail, *veh, incr_k(*L), sched, B, dsol, dAd, dBd, dgd, dxt, dpred,
-                  dpdu, dstep, dpath_id, dtraj, traj_cap, dtraj_len);
+    return lane_tail_device(L, veh, B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu, nsw, switch_steps, paths_of, dstep,
+                            dpath_id, dtraj, traj_cap, dtraj_len, stream);
 }
 
 int mpcqp_kin_frozen_tail_device(const mpcqp_ltv_layout* L, int64_t B, const double* dsol, const int32_t* dstatus,
@@ -2264,6 +2452,127 @@ void mpcqp_affine_free(mpcqp_affine* a) {
                     (void*)a->d_pcoef})
         if (p) (void)hipFree(p);
     delete a;
+}
+
+// ---- fleets: one table of constants per batch, and the twin of every entry point above that
+// takes a vehicle (the same host code over the constants' source) ----
+
+int mpcqp_fleet_create(int64_t B, const mpcqp_vehicle* veh, int32_t device, mpcqp_fleet** out) {
+    return fleet_create(B, veh, device, out);
+}
+
+int mpcqp_kin_fleet_create(int64_t B, const mpcqp_kin_vehicle* veh, int32_t device, mpcqp_kin_fleet** out) {
+    return fleet_create(B, veh, device, out);
+}
+
+int mpcqp_fleet_constants(const mpcqp_fleet* f, int64_t b, double* out13) {
+    if (!f || !out13) return set_error(MPCQP_EINVAL, "fleet_constants: NULL argument");
+    if (b < 0 || b >= (int64_t)f->k.size())
+        return set_error(MPCQP_EINVAL, "fleet_constants: vehicle %lld of a fleet of %lld", (long long)b,
+                         (long long)f->k.size());
+    static_assert(sizeof(VehicleK) == 13 * sizeof(double), "VehicleK is thirteen doubles");
+    std::memcpy(out13, &f->k[b], sizeof(VehicleK));
+    return 0;
+}
+
+void mpcqp_fleet_free(mpcqp_fleet* f) { fleet_free(f); }
+void mpcqp_kin_fleet_free(mpcqp_kin_fleet* f) { fleet_free(f); }
+
+int mpcqp_linearise_fleet_device(const mpcqp_fleet* f, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                                 int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd, double* dBd,
+                                 double* dgd, int32_t device, void* stream) {
+    return linearise_device<DynamicBicycle>("linearise_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dAd, dBd, dgd,
+                                            device, stream);
+}
+
+int mpcqp_kin_linearise_fleet_device(const mpcqp_kin_fleet* f, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                                     int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, double* dAd,
+                                     double* dBd, double* dgd, int32_t device, void* stream) {
+    return linearise_device<KinematicBicycle>("kin_linearise_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dAd, dBd,
+                                              dgd, device, stream);
+}
+
+int mpcqp_linearise_vjp_fleet_device(const mpcqp_fleet* f, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                                     int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                                     const double* dgBd, const double* dggd, double* dgx, double* dgu, int32_t device,
+                                     void* stream) {
+    return linearise_vjp_device<DynamicBicycle>("linearise_vjp_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd,
+                                                dgBd, dggd, dgx, dgu, device, stream);
+}
+
+int mpcqp_kin_linearise_vjp_fleet_device(const mpcqp_kin_fleet* f, int64_t B, int32_t N, const double* dx,
+                                         int64_t x_sb, int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk,
+                                         const double* dgAd, const double* dgBd, const double* dggd, double* dgx,
+                                         double* dgu, int32_t device, void* stream) {
+    return linearise_vjp_device<KinematicBicycle>("kin_linearise_vjp_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk,
+                                                  dgAd, dgBd, dggd, dgx, dgu, device, stream);
+}
+
+int mpcqp_incr_shift_fleet_device(const mpcqp_incr_layout* L, const mpcqp_fleet* f, int64_t B, const double* dsol,
+                                  const double* dAd, const double* dBd, const double* dgd, double* dxt, double* dpred,
+                                  double* dpdu, void* stream) {
+    return incr_shift_device(L, f, B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu, stream);
+}
+
+int mpcqp_incr_shift_vjp_fleet_device(const mpcqp_incr_layout* L, const mpcqp_fleet* f, int64_t B, const double* dsol,
+                                      const double* dAd, const double* dBd, const double* dgd,
+                                      const double* dxt_before, const double* dgxt, const double* dgpred,
+                                      const double* dgpdu, double* dgsol, double* dgAd0, double* dgBd0, double* dggd0,
+                                      double* dgxt_before, void* stream) {
+    (void)dgd;
+    return tail_vjp_device<DynamicIncrTail>("incr_shift_vjp_fleet", L, f, B, dsol, dAd, dBd, dxt_before, nullptr, dgxt,
+                                            nullptr, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before, stream);
+}
+
+int mpcqp_kin_shift_fleet_device(const mpcqp_incr_layout* L, const mpcqp_kin_fleet* f, int64_t B, const double* dsol,
+                                 const double* dAd, const double* dBd, const double* dgd, const double* dXr,
+                                 double* dxt, double* dpred, double* dpdu, int32_t* dfinish_cnt, int32_t* ddone,
+                                 double* dtraj, int32_t traj_cap, int32_t* dtraj_len, void* stream) {
+    return kin_shift_device(L, f, B, dsol, dAd, dBd, dgd, dXr, dxt, dpred, dpdu, dfinish_cnt, ddone, dtraj, traj_cap,
+                            dtraj_len, stream);
+}
+
+int mpcqp_kin_shift_vjp_fleet_device(const mpcqp_incr_layout* L, const mpcqp_kin_fleet* f, int64_t B,
+                                     const double* dsol, const double* dAd, const double* dBd, const double* dgd,
+                                     const double* dxt_before, const int32_t* dmode, const double* dgxt,
+                                     const double* dgpred, const double* dgpdu, double* dgsol, double* dgAd0,
+                                     double* dgBd0, double* dggd0, double* dgxt_before, void* stream) {
+    (void)dgd;
+    return tail_vjp_device<KinIncrTail>("kin_shift_vjp_fleet", L, f, B, dsol, dAd, dBd, dxt_before, dmode, dgxt,
+                                        nullptr, dgpred, dgpdu, dgsol, dgAd0, dgBd0, dggd0, dgxt_before, stream);
+}
+
+int mpcqp_kin_rollout_fleet_device(const mpcqp_kin_fleet* f, int64_t B, int32_t N, const double* dx0,
+                                   const double* du0, double* dpred_x, double* dpred_u, int32_t device, void* stream) {
+    return kin_rollout_device(f, B, N, dx0, du0, dpred_x, dpred_u, device, stream);
+}
+
+int mpcqp_kin_ltv_shift_fleet_device(const mpcqp_ltv_layout* L, const mpcqp_kin_fleet* f, int64_t B,
+                                     const double* dsol, const int32_t* dstatus, const double* dAd, const double* dBd,
+                                     const double* dgd, double* dx, double* du, double* dpred_x, double* dpred_u,
+                                     int32_t* dskipped, int32_t* dsteps_taken, double* dtraj, int32_t traj_cap,
+                                     int32_t* dtraj_len, void* stream) {
+    return kin_ltv_shift_device(L, f, B, dsol, dstatus, dAd, dBd, dgd, dx, du, dpred_x, dpred_u, dskipped,
+                                dsteps_taken, dtraj, traj_cap, dtraj_len, stream);
+}
+
+int mpcqp_kin_ltv_shift_vjp_fleet_device(const mpcqp_ltv_layout* L, const mpcqp_kin_fleet* f, int64_t B,
+                                         const double* dsol, const double* dAd, const double* dBd,
+                                         const double* dx_before, const int32_t* dmode, const double* dgx,
+                                         const double* dgu, const double* dgpred_x, const double* dgpred_u,
+                                         double* dgsol, double* dgAd0, double* dgBd0, double* dggd0,
+                                         double* dgx_before, void* stream) {
+    return tail_vjp_device<KinLtvTail>("kin_ltv_shift_vjp_fleet", L, f, B, dsol, dAd, dBd, dx_before, dmode, dgx, dgu,
+                                       dgpred_x, dgpred_u, dgsol, dgAd0, dgBd0, dggd0, dgx_before, stream);
+}
+
+int mpcqp_lane_tail_fleet_device(const mpcqp_incr_layout* L, const mpcqp_kin_fleet* f, int64_t B, const double* dsol,
+                                 const double* dAd, const double* dBd, const double* dgd, double* dxt, double* dpred,
+                                 double* dpdu, int32_t nsw, const int32_t* switch_steps, const int32_t* paths_of,
+                                 int32_t* dstep, int32_t* dpath_id, double* dtraj, int32_t traj_cap,
+                                 int32_t* dtraj_len, void* stream) {
+    return lane_tail_device(L, f, B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu, nsw, switch_steps, paths_of, dstep,
+                            dpath_id, dtraj, traj_cap, dtraj_len, stream);
 }
 
 }  // extern "C"

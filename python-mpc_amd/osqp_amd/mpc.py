@@ -356,6 +356,21 @@ def kin_update(l_f, l_r, dt, x, u):
                      yaw + v1 / (l_f + l_r) * np.tan(u[..., 0]) * dt], axis=-1)
 
 
+def per_vehicle(statement, vehicles, *batched, **common):
+    """A statement of this module that takes ONE vehicle, over a fleet: vehicles[b] is the
+    statement's leading argument(s) for vehicle b (a tuple is unpacked: (l_f, l_r, dt)); each of
+    `batched` has the batch on axis 0 (None passes through) and vehicle b's call gets the slice
+    [b:b+1], so the statement runs in its batch form on one vehicle; `common` goes to every call.
+    Returns the statement's result(s) concatenated along axis 0: what B calls would give, stacked."""
+    outs = []
+    for b, v in enumerate(vehicles):
+        lead = v if isinstance(v, tuple) else (v,)
+        outs.append(statement(*lead, *(None if a is None else np.asarray(a)[b:b + 1] for a in batched), **common))
+    if isinstance(outs[0], tuple):
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+    return np.concatenate(outs)
+
+
 # ------------------------------------------- the MPC step differentiated (host) --
 def _slots(M, rows, cols):
     """Positions in M.data (sorted CSC) of the entries (rows[i], cols[i]); -1 where not stored."""

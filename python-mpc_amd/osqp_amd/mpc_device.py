@@ -30,6 +30,11 @@ step on every stage (mpcqp_kin_frozen_tail_device).
 LateralMPC is the closed loop of vehicle_lateral_mpc_slack_increment.py (:123-269), the one loop
 that keeps a problem alive: one setup, then per step LateralAssembler -> DeviceBatch.update ->
 warm-started DeviceBatch.solve -> mpcqp_lti_step_device.
+
+Wherever a function or a class here takes ``veh`` (a Vehicle or KinVehicle struct: one car for the
+whole batch) it also takes a Fleet / KinFleet: a table with one car per vehicle of the batch
+(mpcqp_fleet_create and the `_fleet` twins of the entry points).  LateralMPC, whose
+model is fixed at setup, takes neither.
 """
 from __future__ import annotations
 
@@ -60,6 +65,88 @@ class KinVehicle(C.Structure):
 
     def __init__(self, l_f=1.25, l_r=1.40, dt=0.02):
         super().__init__(l_f, l_r, dt)
+
+
+class _FleetBase:
+    """A batch of different vehicles: one table of model constants, entry b for vehicle b
+    (mpcqp_fleet / mpcqp_kin_fleet).  Accepted wherever this module takes ``veh``; the batch must then
+    have the fleet's size.  Every vehicle of a fleet has the same dt (``dt``)."""
+    _struct = _create = _free = None
+
+    def __init__(self, vehicles, device=0):
+        vehicles = list(vehicles)
+        if not all(isinstance(v, self._struct) for v in vehicles):
+            raise TypeError(f"{type(self).__name__} takes a sequence of {self._struct.__name__}")
+        self._h = None
+        self._vehicles = (self._struct * max(len(vehicles), 1))(*vehicles)
+        self._n = len(vehicles)
+        self.device = int(device)
+        L = _bind()
+        self._release = getattr(L, self._free)  # bound now: __del__ may run while the interpreter shuts down
+        h = vp()
+        _check(getattr(L, self._create)(self._n, self._vehicles, self.device, C.byref(h)), "fleet_create")
+        self._h = h
+
+    @classmethod
+    def from_arrays(cls, device=0, **fields):
+        """One array or scalar per constructor argument of the vehicle struct, broadcast to the
+        fleet's size B (the longest array's); an argument not given takes the struct's default."""
+        names = [k for k, _ in cls._struct._fields_]
+        bad = sorted(set(fields) - set(names))
+        if bad:
+            raise TypeError(f"unknown field(s) {', '.join(bad)}; {cls._struct.__name__} has {', '.join(names)}")
+        cols = np.broadcast_arrays(*(np.asarray(v, np.float64) for v in fields.values()), np.zeros(1))[:-1]
+        if any(c.ndim != 1 for c in cols):
+            raise ValueError("every field must be a scalar or a 1-D array")
+        return cls([cls._struct(**{k: float(c[b]) for k, c in zip(fields, cols)}) for b in range(cols[0].shape[0])]
+                   if cols else [cls._struct()], device=device)
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, b):
+        if not -self._n <= b < self._n:
+            raise IndexError(b)
+        v = self._vehicles[b % self._n]
+        return self._struct(*(getattr(v, k) for k, _ in self._struct._fields_))
+
+    @property
+    def dt(self):
+        return self._vehicles[0].dt
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._release(h)
+
+
+class Fleet(_FleetBase):
+    """B dynamic bicycles (Vehicle structs)."""
+    _struct, _create, _free = Vehicle, "mpcqp_fleet_create", "mpcqp_fleet_free"
+
+    def constants(self):
+        """(B, 13): each vehicle's derived constants as the kernels read them, in the order
+        (m, l_f, l_r, Iz, dt, roh C_d A_f, C_roll m 9.81, B_f, C_f, D_f, B_r, C_r, D_r)."""
+        out = np.empty((self._n, 13))
+        for b in range(self._n):
+            _check(_bind().mpcqp_fleet_constants(self._h, b, _np_ptr(out[b])), "fleet_constants")
+        return out
+
+
+class KinFleet(_FleetBase):
+    """B kinematic bicycles (KinVehicle structs)."""
+    _struct, _create, _free = KinVehicle, "mpcqp_kin_fleet_create", "mpcqp_kin_fleet_free"
+
+
+def _entry(name, veh, B):
+    """The entry point mpcqp_<name>_device and its vehicle argument; for a fleet the `_fleet` twin
+    and the fleet's handle, once its size is known to be the batch's."""
+    L = _bind()
+    if isinstance(veh, _FleetBase):
+        if len(veh) != B:
+            raise ValueError(f"{name}: a fleet of {len(veh)} vehicles was given a batch of {B}")
+        return getattr(L, f"mpcqp_{name}_fleet_device"), veh._h
+    return getattr(L, f"mpcqp_{name}_device"), C.byref(veh)
 
 
 # structural nonzeros of get_dynamics_model's Ad and Bd (kept under these names here too)
@@ -117,6 +204,16 @@ def _bind():
                                                  vp, i32, vp]
     L.mpcqp_linearise_vjp_device.argtypes = [_P(Vehicle), i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32,
                                              vp]
+    # fleets: every twin has its entry point's argument types with the fleet's handle for the struct
+    L.mpcqp_fleet_create.argtypes = L.mpcqp_kin_fleet_create.argtypes = [i64, vp, i32, _P(vp)]
+    L.mpcqp_fleet_constants.argtypes = [vp, i64, vp]
+    for free in (L.mpcqp_fleet_free, L.mpcqp_kin_fleet_free):
+        free.argtypes, free.restype = [vp], None
+    for name in ("linearise", "linearise_vjp", "incr_shift", "incr_shift_vjp", "kin_linearise", "kin_linearise_vjp",
+                 "kin_shift", "kin_shift_vjp", "kin_rollout", "kin_ltv_shift", "kin_ltv_shift_vjp", "lane_tail"):
+        twin = getattr(L, f"mpcqp_{name}_device").argtypes
+        getattr(L, f"mpcqp_{name}_fleet_device").argtypes = [
+            vp if t in (_P(Vehicle), _P(KinVehicle)) else t for t in twin]
     L._mpc_bound = True
     return L
 
@@ -151,10 +248,10 @@ def _linearise(symbol, veh, x, u, nx):
     if x.stride(2) != 1 or u.stride(2) != 1:
         raise ValueError("the state / input axis must be contiguous")
     kw = dict(dtype=torch.float64, device=x.device)
+    fn, v = _entry(symbol, veh, B)
     Ad = torch.empty((B, N, nx, nx), **kw); Bd = torch.empty((B, N, nx, 2), **kw); gd = torch.empty((B, N, nx), **kw)
-    _check(getattr(L, f"mpcqp_{symbol}_device")(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u),
-                                                u.stride(0), u.stride(1), _p(Ad), _p(Bd), _p(gd), x.device.index or 0,
-                                                _stream(torch, x.device)), symbol)
+    _check(fn(v, B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0), u.stride(1), _p(Ad), _p(Bd), _p(gd),
+              x.device.index or 0, _stream(torch, x.device)), symbol)
     if squeeze:
         return Ad[:, 0], Bd[:, 0], gd[:, 0]
     return Ad, Bd, gd
@@ -197,9 +294,9 @@ def _linearise_vjp(symbol, veh, x, u, gAd, gBd, ggd, nx, out=None):
         for t, w in ((gx, nx), (gu, 2)):
             if tuple(t.shape) != (B, N, w) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != x.device:
                 raise ValueError(f"out must be contiguous float64 (B, N, {nx}) and (B, N, 2) tensors on x's device")
-    _check(getattr(L, f"mpcqp_{symbol}_device")(C.byref(veh), B, N, _p(x), x.stride(0), x.stride(1), _p(u),
-                                                u.stride(0), u.stride(1), _po(gAd), _po(gBd), _po(ggd), _p(gx), _p(gu),
-                                                x.device.index or 0, _stream(torch, x.device)), symbol)
+    fn, v = _entry(symbol, veh, B)
+    _check(fn(v, B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0), u.stride(1), _po(gAd), _po(gBd),
+              _po(ggd), _p(gx), _p(gu), x.device.index or 0, _stream(torch, x.device)), symbol)
     if squeeze:
         return gx[:, 0], gu[:, 0]
     return gx, gu
@@ -603,8 +700,9 @@ def incr_shift(layout, veh: Vehicle, sol, Ad, Bd, gd, xt):
     xt1 = _shift_in(xt, (B, 8), "xt").clone()
     pred = torch.empty((B, N + 1, 8), dtype=torch.float64, device=sol.device)
     pdu = torch.empty((B, N + 1, 2), dtype=torch.float64, device=sol.device)
-    _check(_bind().mpcqp_incr_shift_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(xt1),
-                                           _p(pred), _p(pdu), _stream(torch, sol.device)), "incr_shift")
+    fn, v = _entry("incr_shift", veh, B)
+    _check(fn(layout._h, v, B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(xt1), _p(pred), _p(pdu),
+              _stream(torch, sol.device)), "incr_shift")
     return xt1, pred, pdu
 
 
@@ -630,9 +728,9 @@ def _tail_vjp(name, symbol, layout, veh, B, head, cots, shapes, outputs, want, o
         elif tuple(t.shape) != shapes[k] or t.dtype != torch.float64 or not t.is_contiguous():
             raise ValueError(f"{name}: {k} must be a contiguous float64 tensor of shape {shapes[k]}")
         setattr(o, k, t)
-    _check(getattr(_bind(), symbol)(layout._h, C.byref(veh), B, *(_po(t) for t in head),
-                                    *(_po(t) for _, t, _ in cots), *(_po(getattr(o, k)) for k in outputs),
-                                    _stream(torch, dev)), name)
+    fn, v = _entry(name, veh, B)
+    _check(fn(layout._h, v, B, *(_po(t) for t in head), *(_po(t) for _, t, _ in cots),
+              *(_po(getattr(o, k)) for k in outputs), _stream(torch, dev)), name)
     given = {k: t for k, t, _ in cots}
     for k_out, k_cot in dict(prev).items():
         g = given[k_cot]
@@ -703,6 +801,8 @@ class _ClosedLoop:
         if x0.shape[1] != layout.nx or u0.shape != (x0.shape[0], 2):
             raise ValueError(f"x0 must be (B, {layout.nx}) and u0 (B, 2)")
         self.B = x0.shape[0]
+        if isinstance(veh, _FleetBase) and len(veh) != self.B:
+            raise ValueError(f"a fleet of {len(veh)} vehicles was given a batch of {self.B}")
         P, A, _, _ = layout.pattern()
         settings.pop("verbose", None)
         self.shift_warm = bool(shift_warm)
@@ -836,8 +936,9 @@ class DynamicMPC(_ClosedLoop):
         return self.xt, self.pred[:, :, :6], self.pred[:, :, 6:]
 
     def _shift(self, L, Ad, Bd, gd, Xr, st):
-        _check(L.mpcqp_incr_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
-                                         _p(gd), _p(self.xt), _p(self.pred), _p(self.pdu), st), "incr_shift")
+        fn, v = _entry("incr_shift", self.veh, self.B)
+        _check(fn(self.layout._h, v, self.B, _p(self.sol), _p(Ad), _p(Bd), _p(gd), _p(self.xt), _p(self.pred),
+                  _p(self.pdu), st), "incr_shift")
 
 
 # ------------------------------------------------------------ kinematic bicycle --
@@ -905,9 +1006,9 @@ def kin_shift(layout, veh: KinVehicle, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finis
     cnt1 = torch.zeros(B, **ikw) if finish_cnt is None else finish_cnt.to(**ikw).clone()
     done0 = torch.zeros(B, **ikw) if done is None else done.to(**ikw).contiguous()
     done1 = done0.clone()
-    _check(_bind().mpcqp_kin_shift_device(layout._h, C.byref(veh), B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(Xr), _p(xt1),
-                                          _p(pred1), _p(pdu1), _p(cnt1), _p(done1), None, 0, None,
-                                          _stream(torch, sol.device)), "kin_shift")
+    fn, v = _entry("kin_shift", veh, B)
+    _check(fn(layout._h, v, B, _p(sol), _p(Ad), _p(Bd), _p(gd), _p(Xr), _p(xt1), _p(pred1), _p(pdu1), _p(cnt1),
+              _p(done1), None, 0, None, _stream(torch, sol.device)), "kin_shift")
     mode = torch.where(done0 != 0, 1, torch.where(done1 != 0, 2, 0)).to(torch.int32)
     return xt1, pred1, pdu1, cnt1, done1, mode
 
@@ -932,9 +1033,9 @@ def kin_ltv_shift(layout, veh: KinVehicle, sol, status, Ad, Bd, gd, x, u, pred_x
         status = _mode_in(status, B, "kin_ltv_shift: status")
         mode = (status != 1).to(torch.int32)
     skipped = torch.zeros(B, **ikw)
-    _check(_bind().mpcqp_kin_ltv_shift_device(layout._h, C.byref(veh), B, _p(sol), _po(status), _p(Ad), _p(Bd), _p(gd),
-                                              _p(x1), _p(u1), _p(px1), _p(pu1), _p(skipped), None, None, 0, None,
-                                              _stream(torch, sol.device)), "kin_ltv_shift")
+    fn, v = _entry("kin_ltv_shift", veh, B)
+    _check(fn(layout._h, v, B, _p(sol), _po(status), _p(Ad), _p(Bd), _p(gd), _p(x1), _p(u1), _p(px1), _p(pu1),
+              _p(skipped), None, None, 0, None, _stream(torch, sol.device)), "kin_ltv_shift")
     return x1, u1, px1, pu1, mode
 
 
@@ -1042,10 +1143,10 @@ class KinematicMPC(_ClosedLoop):
         return self.xt, self.pred[:, :, :4], self.pred[:, :, 4:]
 
     def _shift(self, L, Ad, Bd, gd, Xr, st):
-        _check(L.mpcqp_kin_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
-                                        _p(gd), _p(Xr), _p(self.xt), _p(self.pred), _p(self.pdu),
-                                        _p(self.finish_cnt), _p(self.done), _p(self.traj), self.traj_cap,
-                                        _p(self.traj_len), st), "kin_shift")
+        fn, v = _entry("kin_shift", self.veh, self.B)
+        _check(fn(self.layout._h, v, self.B, _p(self.sol), _p(Ad), _p(Bd), _p(gd), _p(Xr), _p(self.xt), _p(self.pred),
+                  _p(self.pdu), _p(self.finish_cnt), _p(self.done), _p(self.traj), self.traj_cap, _p(self.traj_len),
+                  st), "kin_shift")
 
     def run(self, max_steps, check_every=16):
         """step() until every vehicle is done or max_steps steps were taken; returns the number
@@ -1125,8 +1226,9 @@ def rollout_kin(veh: KinVehicle, x0, u0, N):
             raise ValueError("x0 must be (B, 4) and u0 (B, 2), contiguous float64")
     kw = dict(dtype=torch.float64, device=x0.device)
     pred_x = torch.empty((B, N + 1, 4), **kw); pred_u = torch.empty((B, N + 1, 2), **kw)
-    _check(L.mpcqp_kin_rollout_device(C.byref(veh), B, int(N), _p(x0), _p(u0), _p(pred_x), _p(pred_u),
-                                      x0.device.index or 0, _stream(torch, x0.device)), "kin_rollout")
+    fn, v = _entry("kin_rollout", veh, B)
+    _check(fn(v, B, int(N), _p(x0), _p(u0), _p(pred_x), _p(pred_u), x0.device.index or 0,
+              _stream(torch, x0.device)), "kin_rollout")
     return pred_x, pred_u
 
 
@@ -1188,10 +1290,10 @@ class KinematicLTVMPC(_ClosedLoop):
         return self.x, self.pred_x, self.pred_u
 
     def _shift(self, L, Ad, Bd, gd, Xr, st):
-        _check(L.mpcqp_kin_ltv_shift_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(self.status),
-                                            _p(Ad), _p(Bd), _p(gd), _p(self.x), _p(self.u), _p(self.pred_x),
-                                            _p(self.pred_u), _p(self.skipped), _p(self.steps_taken), _p(self.traj),
-                                            self.traj_cap, _p(self.traj_len), st), "kin_ltv_shift")
+        fn, v = _entry("kin_ltv_shift", self.veh, self.B)
+        _check(fn(self.layout._h, v, self.B, _p(self.sol), _p(self.status), _p(Ad), _p(Bd), _p(gd), _p(self.x),
+                  _p(self.u), _p(self.pred_x), _p(self.pred_u), _p(self.skipped), _p(self.steps_taken), _p(self.traj),
+                  self.traj_cap, _p(self.traj_len), st), "kin_ltv_shift")
 
 
 # ------------------------------------- a bank of paths, one selected per vehicle --
@@ -1297,11 +1399,10 @@ class LaneChangeMPC(_ClosedLoop):
         return self.xt, self.pred[:, :, :4], self.pred[:, :, 4:]
 
     def _shift(self, L, Ad, Bd, gd, Xr, st):
-        _check(L.mpcqp_lane_tail_device(self.layout._h, C.byref(self.veh), self.B, _p(self.sol), _p(Ad), _p(Bd),
-                                        _p(gd), _p(self.xt), _p(self.pred), _p(self.pdu), self.switch_steps.size,
-                                        _np_ptr(self.switch_steps), _np_ptr(self.paths_of), _p(self.steps),
-                                        _p(self.path_id), _p(self.traj), self.traj_cap, _p(self.traj_len), st),
-               "lane_tail")
+        fn, v = _entry("lane_tail", self.veh, self.B)
+        _check(fn(self.layout._h, v, self.B, _p(self.sol), _p(Ad), _p(Bd), _p(gd), _p(self.xt), _p(self.pred),
+                  _p(self.pdu), self.switch_steps.size, _np_ptr(self.switch_steps), _np_ptr(self.paths_of),
+                  _p(self.steps), _p(self.path_id), _p(self.traj), self.traj_cap, _p(self.traj_len), st), "lane_tail")
 
 
 class KinematicFrozenMPC(_ClosedLoop):
@@ -1361,7 +1462,12 @@ class KinematicFrozenMPC(_ClosedLoop):
         self.path_yaw = torch.zeros_like(self.path_x)                      # x_ref[3] = deg2rad(0) (:62)
         self.set_speed = torch.full((self.B,), self.SET_SPEED, **kw)
         v = self.veh
-        pred_x, x_start = mpc.kinfrozen_rollout(x0, pred_u0, self.N, v.l_f, v.l_r, v.dt)
+        if isinstance(v, _FleetBase):  # the host statement takes one wheelbase: vehicle by vehicle
+            pred_x, x_start = mpc.per_vehicle(
+                lambda l_f, l_r, dt, x, pu: mpc.kinfrozen_rollout(x, pu, self.N, l_f, l_r, dt),
+                [(k.l_f, k.l_r, k.dt) for k in (v[b] for b in range(self.B))], x0, pred_u0)
+        else:
+            pred_x, x_start = mpc.kinfrozen_rollout(x0, pred_u0, self.N, v.l_f, v.l_r, v.dt)
         self.pred_x = torch.from_numpy(pred_x).to(**kw).contiguous()
         self.x = torch.from_numpy(x_start).to(**kw).contiguous()
         self.u = torch.from_numpy(u0).to(**kw).contiguous()

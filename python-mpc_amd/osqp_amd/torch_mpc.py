@@ -387,6 +387,8 @@ class _Rollout:
             raise ValueError(f"{self._NAME} needs {words} (nx {nx}, nu {nu})")
         self.torch, self.layout, self.veh = torch, layout, veh
         self.B, self.N = int(B), layout.N
+        if isinstance(veh, (md.Fleet, md.KinFleet)) and len(veh) != self.B:  # one table entry per vehicle
+            raise ValueError(f"{self._NAME}: a fleet of {len(veh)} vehicles was given a batch of {self.B}")
         self.dev = torch.device("cuda", int(device))
         self.strict, self.shift_warm = bool(strict), bool(warm_start)
         P, A, _, _ = layout.pattern()

@@ -8,17 +8,20 @@ and after replacing register numbers, labels and the lane index of v_readlane / 
 (the SGPR spill slot) by placeholders ("norm").  The selected loop is the ADMM run where the
 kernel has one: the four-wave kernels' shortest call-free loop with four workgroup barriers,
 the two-wave kernels' shortest with three, else the longest call-free loop (k_solve,
-k_solve_b; tests/isa_shape.py).  Exit status 1 if any kernel differs in metadata or in its
-normalised loop, or is in one library only.
+k_solve_b; tests/isa_shape.py).  A kernel of OLD that became a function template in NEW (another
+symbol, the same name and parameter list) is compared with that instantiation, under its old
+symbol.  Exit status 1 if any kernel differs in metadata or in its normalised loop, or is in one
+library only.
 """
 import os
 import re
+import subprocess
 import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from isa_shape import code_objects, count, instructions, loops, metadata  # noqa: E402
+from isa_shape import LLVM, code_objects, count, instructions, loops, metadata  # noqa: E402
 
 BARRIERS = (("k_solve_w4", 4), ("k_setup_solve_w4", 4), ("k_solve_w2", 3), ("k_setup_solve_w2", 3))
 
@@ -68,11 +71,48 @@ def kernels(lib, workdir):
         return dict(pool.map(one, todo))
 
 
+def signature(symbol):
+    """`name(parameter types)` of a kernel, demangled, without the template arguments of the
+    function itself: what a kernel and the template instantiation it became have in common."""
+    tool = os.path.join(LLVM, "llvm-cxxfilt")
+    txt = subprocess.run([tool if os.path.exists(tool) else "c++filt", symbol], check=True, capture_output=True,
+                         text=True).stdout.strip()
+    depth, at = 0, len(txt)
+    for i, c in enumerate(txt):  # the parameter list opens at the first "(" outside <...>
+        depth += (c == "<") - (c == ">")
+        if c == "(" and depth == 0:
+            at = i
+            break
+    head, params = txt[:at].rstrip(), txt[at:]
+    if head.endswith(">"):  # the function's own template arguments
+        depth = 0
+        for i in range(len(head) - 1, -1, -1):
+            depth += (head[i] == ">") - (head[i] == "<")
+            if depth == 0:
+                head = head[:i]
+                break
+    return head.split()[-1] + params
+
+
+def pair_renamed(a, b):
+    """A kernel of the old library that became a function template keeps its name and its
+    parameter list and changes its symbol: where exactly one kernel of the new library has the
+    signature of a kernel found in the old one only, compare the two under the old symbol."""
+    new_only = {}
+    for name in set(b) - set(a):
+        new_only.setdefault(signature(name), []).append(name)
+    for name in sorted(set(a) - set(b)):
+        hit = new_only.get(signature(name), [])
+        if len(hit) == 1:
+            b[name] = b.pop(hit[0])
+
+
 def diff(old, new):
     """Rows (symbol, metadata equal, old count, new count, loop length, exact, norm) and the
     symbols found in one library only."""
     with tempfile.TemporaryDirectory() as d:
         a, b = kernels(old, os.path.join(d, "a")), kernels(new, os.path.join(d, "b"))
+    pair_renamed(a, b)
     rows = []
     for name in sorted(set(a) & set(b)):
         (ma, na, la), (mb, nb, lb) = a[name], b[name]

@@ -2,6 +2,7 @@
 """First timings of the closed loops on the device (osqp_amd.mpc_device).  No target; numbers to
 compare later work against.
 
+  dyn        DynamicMPC          mpc_dynamics.main
   kin        KinematicMPC        mpc_incre_kine_func.simulate
   ltv        KinematicLTVMPC     mpc_kinematics_pred_matrix.main
   lat        LateralMPC          vehicle_lateral_mpc_slack_increment.py
@@ -26,9 +27,14 @@ that; the pass with mpcqp_timing on gives the solve kernel's own event time.  --
 runs the script's loop through the `import osqp` drop-in on ONE vehicle for K steps
 (tests/test_gpu_parity.py::_slack_script_loop's calls) -> shim_ms_per_step_one_vehicle.
 
+--fleet (every loop but lat, whose model is fixed at setup) runs the same loop with a fleet of B
+distinct vehicles -- masses, axle distances and, for the dynamic bicycle, drag and rolling
+coefficients drawn within +-20 % of the default car's -- in place of B copies of that car.
+
 One JSON line per horizon in --N, every horizon measured by a fresh child process under its own
 time limit; a horizon that fails prints an {"error": ...} line and later ones are not started.
 
+  python tools/loop_time.py dyn       [--N 30]     [--batch 4096] [--steps 20] [--warmup 3] [--warm-start] [--fleet]
   python tools/loop_time.py kin       [--N 40]     [--batch 4096] [--steps 50] [--warmup 5] [--warm-start]
   python tools/loop_time.py ltv       [--N 40 100] [--batch 4096] [--steps 20] [--warmup 3] [--shift-warm]
   python tools/loop_time.py lat       [--N 20 100] [--batch 4096] [--steps 50] [--warmup 5] [--step0-max 1200]
@@ -67,6 +73,29 @@ def _starts(rng, B, y, v_lo=8, yaw_deg=3):
 def _beside(rng, y0, far):
     """1 to `far` m on either side of the path y = y0."""
     return lambda B: y0 + rng.uniform(1.0, far, B) * rng.choice([-1.0, 1.0], B)
+
+
+def dyn_states(B, seed=5):
+    """Starts around mpc_dynamics.main's own: up to 2 m beside the path's start, yaw within 8 deg, vx in [10, 20)."""
+    rng = np.random.default_rng(seed)
+    x0 = np.zeros((B, 6))
+    x0[:, 1] = 5.0 + rng.uniform(-2, 2, B)
+    x0[:, 2] = np.deg2rad(26.57 + rng.uniform(-8, 8, B))
+    x0[:, 3] = rng.uniform(10, 20, B)
+    return x0, np.zeros((B, 2))
+
+
+def fleet_of(a, dynamic, seed=11):
+    """None without --fleet (the loop's default car for everyone); with it a.batch distinct cars within
+    +-20 % of the default's constants."""
+    if not a.fleet:
+        return None
+    from osqp_amd import mpc_device as md
+    rng = np.random.default_rng(seed)
+    base = md.Vehicle() if dynamic else md.KinVehicle()
+    names = ("m", "l_f", "l_r", "C_d", "A_f", "C_roll") if dynamic else ("l_f", "l_r")
+    cls = md.Fleet if dynamic else md.KinFleet
+    return cls.from_arrays(dt=base.dt, **{k: getattr(base, k) * rng.uniform(0.8, 1.2, a.batch) for k in names})
 
 
 def kin_states(B, seed=5):
@@ -111,16 +140,25 @@ def kinfrozen_states(B, N, seed=5):
 
 
 # --------------------------------------------------- controllers from those starts --
+def _dyn(a, N):
+    from osqp_amd.mpc_device import DynamicMPC
+    x0, u0 = dyn_states(a.batch)                        # mpc_dynamics.main's path (:468-469)
+    veh = fleet_of(a, True)
+    return lambda: DynamicMPC(x0, u0, PX, PX * 0.5 + 5, N=N, warm_start=a.warm_start, veh=veh)
+
+
 def _kin(a, N):
     from osqp_amd.mpc_device import KinematicMPC
     x0, u0 = kin_states(a.batch)                        # mpc_incre_kine_func.main's path (:440-442)
-    return lambda: KinematicMPC(x0, u0, PX, PX * 0.0 - 4.0, PX * 0.0, N=N, warm_start=a.warm_start)
+    veh = fleet_of(a, False)
+    return lambda: KinematicMPC(x0, u0, PX, PX * 0.0 - 4.0, PX * 0.0, N=N, warm_start=a.warm_start, veh=veh)
 
 
 def _ltv(a, N):
     from osqp_amd.mpc_device import KinematicLTVMPC
     x0, u0 = ltv_states(a.batch)                        # mpc_kinematics_pred_matrix.main's path (:377-379)
-    return lambda: KinematicLTVMPC(x0, u0, PX, PX * 0.0 - 5.0, N=N, shift_warm=a.shift_warm)
+    veh = fleet_of(a, False)
+    return lambda: KinematicLTVMPC(x0, u0, PX, PX * 0.0 - 5.0, N=N, shift_warm=a.shift_warm, veh=veh)
 
 
 def _lat(a, N):
@@ -133,13 +171,15 @@ def _lane(a, N):
     from osqp_amd.mpc_device import LaneChangeMPC
     x0, u0, step0 = lane_states(a.batch)                # main's path and its second lane (:317-319, :382-383)
     paths_y = np.stack([PX * 0.0, PX * 0.0 + 4])
-    return lambda: LaneChangeMPC(x0, u0, PX, paths_y, N=N, step0=step0, shift_warm=a.shift_warm)
+    veh = fleet_of(a, False)
+    return lambda: LaneChangeMPC(x0, u0, PX, paths_y, N=N, step0=step0, shift_warm=a.shift_warm, veh=veh)
 
 
 def _kinfrozen(a, N):
     from osqp_amd.mpc_device import KinematicFrozenMPC
     x0, u0, pred_u0 = kinfrozen_states(a.batch, N)      # mpc_kinematics.main's path (:290-292)
-    return lambda: KinematicFrozenMPC(x0, u0, PX, PX * 0.0 - 5.0, N=N, pred_u0=pred_u0)
+    veh = fleet_of(a, False)
+    return lambda: KinematicFrozenMPC(x0, u0, PX, PX * 0.0 - 5.0, N=N, pred_u0=pred_u0, veh=veh)
 
 
 # --------------------------------------------------------------------- measurement --
@@ -204,6 +244,7 @@ def measure(loop, a, N):
              "data_path": (dev2_ms - solver_ms) / a.steps, "window": dev2_ms / a.steps,
              "launches": [t["n_setup"], t["n_solve"]]}
     flag = {k: getattr(a, k) for k in loop["flags"]}
+    flag["fleet"] = a.fleet
     return _line(loop, a, N, ctl, wall, dev_ms, split,
                  {"n": ctl.layout.n, "m": ctl.layout.m, **flag, "steps": a.steps, "warmup": a.warmup,
                   **_iters(loop, it), "iters_mean_split_window": float(it2.mean()),
@@ -275,6 +316,10 @@ def measure_lat(loop, a, N):
 # end: ("config" key, controller tensor whose mean it is); lds: report iters_max and lds_bytes_solve
 # (the three newer loops) rather than iters_max_per_step_mean.
 LOOPS = {
+    "dyn": dict(build=_dyn, initial_states=dyn_states, measure=measure, N=[30], steps=20, warmup=3, lds=False,
+                metric="dynamic closed-loop step (DynamicMPC.step, mpc_dynamics.main)",
+                options={"--warm-start": dict(action="store_true")}, flags=("warm_start",),
+                end=("status_mean_end", "status")),
     "kin": dict(build=_kin, initial_states=kin_states, measure=measure, N=[40], steps=50, warmup=5, lds=False,
                 metric="kinematic closed-loop step (KinematicMPC.step, mpc_incre_kine_func.simulate)",
                 options={"--warm-start": dict(action="store_true")}, flags=("warm_start",),
@@ -308,6 +353,8 @@ def main():
         p.add_argument("--warmup", type=int, default=loop["warmup"])
         for opt, kw in loop["options"].items():
             p.add_argument(opt, **kw)
+        if name != "lat":
+            p.add_argument("--fleet", action="store_true", help="B distinct vehicles in place of B copies of one")
         p.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     loop = LOOPS[a.loop]
