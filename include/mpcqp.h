@@ -921,6 +921,55 @@ int mpcqp_lane_tail_fleet_device(const mpcqp_incr_layout *L, const mpcqp_kin_fle
                                  int32_t *dstep, int32_t *dpath_id, double *dtraj, int32_t traj_cap,
                                  int32_t *dtraj_len, void *stream);
 
+/* ======================================================================
+ * Gradients with respect to the vehicle parameters.  Fleet form only: the
+ * cotangent has the table's shape, one row per vehicle; a uniform vehicle is a fleet of copies
+ * whose rows the caller sums.  Coordinates are the ones the kernels read:
+ *   dynamic bicycle    dgK (B, 13): (m, l_f, l_r, Iz, dt, cda, roll, B_f, C_f, D_f, B_r, C_r, D_r),
+ *                      mpcqp_fleet_constants' order
+ *   kinematic bicycle  dgK (B, 3):  (l_f, l_r, dt), the struct's
+ * Each differentiates the forward as it computes, by the rules of mpcqp_linearise_vjp_device: the
+ * low-speed guard first, an input it replaced is a constant, sgn(vx) has derivative 0, Ac as the
+ * reference writes it; dt carries derivative through Ad = I + dt Ac, Bd = dt Bc, gd = dt (...) and
+ * the Euler steps.  Every element of dgK is written (no accumulation into it).  A NULL cotangent
+ * means zero.  MPCQP_EINVAL ("<name>: bad arguments") for a NULL fleet, point or dgK, B < 0, N < 1;
+ * the fleet's own refusals (B, device) as its other entry points; all before any device call.
+ * (B = 0, a no-op where a struct is taken, cannot be a fleet's size: it is that refusal.)
+ * ====================================================================== */
+
+/* The linearisations: x, u, dgAd, dgBd, dggd as mpcqp_linearise_vjp_device /
+ * mpcqp_kin_linearise_vjp_device take them; dgK[b] is the sum over the N stages of vehicle b.
+ * The sum is deterministic: one block holds 256 / N whole vehicles, every (vehicle, stage)
+ * thread leaves its partial on chip, and one thread per output element adds them in stage order,
+ * acc = 0, acc += partial[s] for s = 0 .. N-1; a repeated call returns the same bits.  That shape
+ * needs N <= 256: a larger N returns MPCQP_EUNSUPPORTED before any device call. */
+int mpcqp_linearise_pvjp_fleet_device(const mpcqp_fleet *f, int64_t B, int32_t N, const double *dx, int64_t x_sb,
+                                      int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk, const double *dgAd,
+                                      const double *dgBd, const double *dggd, double *dgK, int32_t device,
+                                      void *stream);
+int mpcqp_kin_linearise_pvjp_fleet_device(const mpcqp_kin_fleet *f, int64_t B, int32_t N, const double *dx,
+                                          int64_t x_sb, int64_t x_sk, const double *du, int64_t u_sb, int64_t u_sk,
+                                          const double *dgAd, const double *dgBd, const double *dggd, double *dgK,
+                                          int32_t device, void *stream);
+/* The terminal steps of the loop tails (the only place the constants enter a tail: its plant step
+ * is affine in stage 0's Ad, Bd, gd): update_dynamics_model's guarded Euler step, x (6) u (2), and
+ * update_kinematics_model, x (4) u (2), each read at a batch stride (x_sb, u_sb doubles between
+ * vehicles) so that views into a taped solution can be passed.  dw (B, 6) / (B, 4) dense: the
+ * cotangent of the new state.  dmode (B) or NULL: a vehicle whose mode is not 0 did not take the
+ * step (the tails' stop and skip masks) and gets a zero row. */
+int mpcqp_euler_step_pvjp_fleet_device(const mpcqp_fleet *f, int64_t B, const double *dx, int64_t x_sb,
+                                       const double *du, int64_t u_sb, const double *dw, const int32_t *dmode,
+                                       double *dgK, int32_t device, void *stream);
+int mpcqp_kin_update_pvjp_fleet_device(const mpcqp_kin_fleet *f, int64_t B, const double *dx, int64_t x_sb,
+                                       const double *du, int64_t u_sb, const double *dw, const int32_t *dmode,
+                                       double *dgK, int32_t device, void *stream);
+/* Host only, no device call: the chain from the thirteen constants back to the constructor
+ * arguments, gveh = J' gk with J the Jacobian at *veh of the derivation mpcqp_fleet_create
+ * applies, formed by running that derivation over dual numbers; gveh in the struct's field order
+ * (m, l_f, l_r, width, length, C_d, A_f, C_roll, dt).  The kinematic struct derives nothing: its
+ * chain is the identity. */
+int mpcqp_vehicle_constants_vjp(const mpcqp_vehicle *veh, const double gk[13], double gveh[9]);
+
 #ifdef __cplusplus
 }
 #endif

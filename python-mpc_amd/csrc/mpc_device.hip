@@ -24,6 +24,9 @@
 // and the one closed loop that keeps its problem alive, vehicle_lateral_mpc_slack_increment.py
 // (setup once, update(q, l, u) + warm-started solve per step; k_affine assembles its vectors):
 //       k_lti_step                    raise rule, record, plant step, schedule :158-172, :252-269
+// and the gradients with respect to the vehicle's constants, in fleet form:
+//       k_linearise_pvjp / k_kin_linearise_pvjp   the linearisations, summed over the stages
+//       k_euler_step_pvjp / k_kin_update_pvjp     the terminal steps of the three loop tails
 // The two bicycles are model structs (DynamicBicycle, KinematicBicycle) over which the
 // linearisation and the reference walk are written once; the three shift kernels share the plant
 // step, the trajectory append and kin_update, and keep their own shift and terminal-state rules.
@@ -56,25 +59,41 @@ struct VehicleK {
     double Bf, Cf, Df, Br, Cr, Dr;
 };
 
-static VehicleK vehicle_constants(const mpcqp_vehicle& v) {
-    VehicleK k;
-    k.m = v.m; k.lf = v.l_f; k.lr = v.l_r; k.dt = v.dt;
-    k.Iz = 1.0 / 12 * v.m * (v.width * v.width + v.length * v.length);
+// Written once over the scalar S of the nine constructor arguments p = (m, l_f, l_r, width, length,
+// C_d, A_f, C_roll, dt), the struct's field order: double for the forward, a 9-wide dual for
+// mpcqp_vehicle_constants_vjp.  k: the thirteen constants in VehicleK's order.
+template <class S>
+static void derive_constants(const S* p, S* k) {
+    using std::atan;
+    using std::sin;
+    const S &m = p[0], &l_f = p[1], &l_r = p[2], &width = p[3], &length = p[4], &C_d = p[5], &A_f = p[6],
+            &C_roll = p[7], &dt = p[8];
+    k[0] = m; k[1] = l_f; k[2] = l_r; k[4] = dt;
+    k[3] = 1.0 / 12 * m * (width * width + length * length);
     const double roh = 1.23;
-    k.cda = roh * v.C_d * v.A_f;
-    k.roll = v.C_roll * v.m * 9.81;
+    k[5] = roh * C_d * A_f;
+    k[6] = C_roll * m * 9.81;
     const double a[8] = {-22.1, 1011, 1078, 1.82, 0.208, 0.000, -0.354, 0.707};
-    const double wheelbase = v.l_f + v.l_r;
+    const S wheelbase = l_f + l_r;
     const double pi = 3.141592653589793;
     for (int axle = 0; axle < 2; ++axle) {
-        const double Fz = 9.81 * (v.m * (axle == 0 ? v.l_r : v.l_f) / wheelbase) * 0.001;
-        const double C = 1.30;
-        const double D = a[0] * Fz * Fz + a[1] * Fz;
-        const double BCD = a[2] * std::sin(a[3] * std::atan(a[4] * Fz));
-        const double B = BCD / (C * D) * 180 / pi;
-        if (axle == 0) { k.Bf = B; k.Cf = C; k.Df = D; }
-        else { k.Br = B; k.Cr = C; k.Dr = D; }
+        const S Fz = 9.81 * (m * (axle == 0 ? l_r : l_f) / wheelbase) * 0.001;
+        const S C = S(1.30);
+        const S D = a[0] * Fz * Fz + a[1] * Fz;
+        const S BCD = a[2] * sin(a[3] * atan(a[4] * Fz));
+        const S B = BCD / (C * D) * 180 / pi;
+        k[7 + 3 * axle] = B; k[8 + 3 * axle] = C; k[9 + 3 * axle] = D;
     }
+}
+
+static VehicleK vehicle_constants(const mpcqp_vehicle& v) {
+    static_assert(sizeof(VehicleK) == 13 * sizeof(double) && sizeof(mpcqp_vehicle) == 9 * sizeof(double),
+                  "thirteen constants of nine arguments");
+    double p[9], kk[13];
+    std::memcpy(p, &v, sizeof(p));
+    derive_constants(p, kk);
+    VehicleK k;
+    std::memcpy(&k, kk, sizeof(k));
     return k;
 }
 static const mpcqp_kin_vehicle& vehicle_constants(const mpcqp_kin_vehicle& v) { return v; }  // nothing derived
@@ -113,90 +132,131 @@ __device__ __forceinline__ void low_speed_guard(double* x, double* u) {
     }
 }
 
-// Forward-mode dual number over the six inputs that carry derivative through linearise_one:
-// d[] = d/d(yaw, vx, vy, r, steer, accel).  The model below is written once over its scalar
-// type: double for the forward kernels, Dual for k_linearise_vjp.
-struct Dual {
-    static constexpr int ND = 6;
+// Forward-mode dual number with W tangent slots.  Dual, the 6-wide instance, carries the six inputs
+// that have derivative through linearise_one: d[] = d/d(yaw, vx, vy, r, steer, accel).  The model
+// below is written once over its scalar types: double for the forward kernels, Dual in the point for
+// k_linearise_vjp, DualN<W> in the constants (VehicleKD<W>) for the parameter kernels.
+template <int W>
+struct DualN {
+    static constexpr int ND = W;
     double v;
     double d[ND];
-    __device__ explicit Dual(double v_ = 0.0) : v(v_) {
+    __host__ __device__ explicit DualN(double v_ = 0.0) : v(v_) {
         for (int j = 0; j < ND; ++j) d[j] = 0.0;
     }
     // the input `slot` at value v_; seed 0 where the low-speed guard replaced it by a constant
-    __device__ Dual(double v_, int slot, bool live) : Dual(v_) { d[slot] = live ? 1.0 : 0.0; }
+    __host__ __device__ DualN(double v_, int slot, bool live) : DualN(v_) { d[slot] = live ? 1.0 : 0.0; }
 };
-__device__ __forceinline__ Dual operator-(const Dual& a) {
-    Dual o(-a.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = -a.d[j];
+using Dual = DualN<6>;
+#define DUAL_FN template <int W> __host__ __device__ __forceinline__
+DUAL_FN DualN<W> operator-(const DualN<W>& a) {
+    DualN<W> o(-a.v);
+    for (int j = 0; j < W; ++j) o.d[j] = -a.d[j];
     return o;
 }
-__device__ __forceinline__ Dual operator+(const Dual& a, const Dual& b) {
-    Dual o(a.v + b.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] + b.d[j];
+DUAL_FN DualN<W> operator+(const DualN<W>& a, const DualN<W>& b) {
+    DualN<W> o(a.v + b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = a.d[j] + b.d[j];
     return o;
 }
-__device__ __forceinline__ Dual operator-(const Dual& a, const Dual& b) {
-    Dual o(a.v - b.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] - b.d[j];
+DUAL_FN DualN<W> operator-(const DualN<W>& a, const DualN<W>& b) {
+    DualN<W> o(a.v - b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = a.d[j] - b.d[j];
     return o;
 }
-__device__ __forceinline__ Dual operator*(const Dual& a, const Dual& b) {
-    Dual o(a.v * b.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] * b.v + a.v * b.d[j];
+DUAL_FN DualN<W> operator*(const DualN<W>& a, const DualN<W>& b) {
+    DualN<W> o(a.v * b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = a.d[j] * b.v + a.v * b.d[j];
     return o;
 }
-__device__ __forceinline__ Dual operator/(const Dual& a, const Dual& b) {
-    Dual o(a.v / b.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = (a.d[j] - o.v * b.d[j]) / b.v;
+DUAL_FN DualN<W> operator/(const DualN<W>& a, const DualN<W>& b) {
+    DualN<W> o(a.v / b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = (a.d[j] - o.v * b.d[j]) / b.v;
     return o;
 }
-__device__ __forceinline__ Dual operator+(const Dual& a, double b) {
-    Dual o = a;
+DUAL_FN DualN<W> operator+(const DualN<W>& a, double b) {
+    DualN<W> o = a;
     o.v = a.v + b;
     return o;
 }
-__device__ __forceinline__ Dual operator+(double a, const Dual& b) {
-    Dual o = b;
+DUAL_FN DualN<W> operator+(double a, const DualN<W>& b) {
+    DualN<W> o = b;
     o.v = a + b.v;
     return o;
 }
-__device__ __forceinline__ Dual operator-(const Dual& a, double b) {
-    Dual o = a;
+DUAL_FN DualN<W> operator-(const DualN<W>& a, double b) {
+    DualN<W> o = a;
     o.v = a.v - b;
     return o;
 }
-__device__ __forceinline__ Dual operator*(const Dual& a, double b) {
-    Dual o(a.v * b);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a.d[j] * b;
+DUAL_FN DualN<W> operator*(const DualN<W>& a, double b) {
+    DualN<W> o(a.v * b);
+    for (int j = 0; j < W; ++j) o.d[j] = a.d[j] * b;
     return o;
 }
-__device__ __forceinline__ Dual operator*(double a, const Dual& b) {
-    Dual o(a * b.v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = a * b.d[j];
+DUAL_FN DualN<W> operator*(double a, const DualN<W>& b) {
+    DualN<W> o(a * b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = a * b.d[j];
     return o;
 }
-// the double overloads stay visible beside Dual's in this namespace
+// a plain value over or under a dual: only the parameter kernels and the host chain meet these
+DUAL_FN DualN<W> operator/(const DualN<W>& a, double b) {
+    DualN<W> o(a.v / b);
+    for (int j = 0; j < W; ++j) o.d[j] = a.d[j] / b;
+    return o;
+}
+DUAL_FN DualN<W> operator/(double a, const DualN<W>& b) {
+    DualN<W> o(a / b.v);
+    for (int j = 0; j < W; ++j) o.d[j] = (-o.v * b.d[j]) / b.v;
+    return o;
+}
+// the double overloads stay visible beside the duals' in this namespace
 using ::atan;
 using ::atan2;
 using ::cos;
 using ::sin;
 // chain rule with the outer derivative dv
-__device__ __forceinline__ Dual chain(double v, double dv, const Dual& a) {
-    Dual o(v);
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = dv * a.d[j];
+DUAL_FN DualN<W> chain(double v, double dv, const DualN<W>& a) {
+    DualN<W> o(v);
+    for (int j = 0; j < W; ++j) o.d[j] = dv * a.d[j];
     return o;
 }
-__device__ __forceinline__ Dual sin(const Dual& a) { return chain(::sin(a.v), ::cos(a.v), a); }
-__device__ __forceinline__ Dual cos(const Dual& a) { return chain(::cos(a.v), -::sin(a.v), a); }
-__device__ __forceinline__ Dual atan(const Dual& a) { return chain(::atan(a.v), 1.0 / (1.0 + a.v * a.v), a); }
-__device__ __forceinline__ Dual atan2(const Dual& y, const Dual& x) {
-    Dual o(::atan2(y.v, x.v));
+DUAL_FN DualN<W> sin(const DualN<W>& a) { return chain(::sin(a.v), ::cos(a.v), a); }
+DUAL_FN DualN<W> cos(const DualN<W>& a) { return chain(::cos(a.v), -::sin(a.v), a); }
+DUAL_FN DualN<W> atan(const DualN<W>& a) { return chain(::atan(a.v), 1.0 / (1.0 + a.v * a.v), a); }
+DUAL_FN DualN<W> atan2(const DualN<W>& y, const DualN<W>& x) {
+    DualN<W> o(::atan2(y.v, x.v));
     const double n = x.v * x.v + y.v * y.v;
-    for (int j = 0; j < Dual::ND; ++j) o.d[j] = (x.v * y.d[j] - y.v * x.d[j]) / n;
+    for (int j = 0; j < W; ++j) o.d[j] = (x.v * y.d[j] - y.v * x.d[j]) / n;
     return o;
 }
-__device__ __forceinline__ double sgn(const Dual& a) { return sgn(a.v); }  // derivative 0, as the reference's Jacobian has it
+DUAL_FN DualN<W> atan2(const DualN<W>& y, double x) {
+    DualN<W> o(::atan2(y.v, x));
+    const double n = x * x + y.v * y.v;
+    for (int j = 0; j < W; ++j) o.d[j] = (x * y.d[j]) / n;
+    return o;
+}
+template <int W>
+__device__ __forceinline__ double sgn(const DualN<W>& a) { return sgn(a.v); }  // derivative 0, as the reference's Jacobian has it
+#undef DUAL_FN
+
+// VehicleK over duals in the constants themselves: what the model functions take where the
+// derivative is wanted with respect to the vehicle (slot q of a field = d field / d constant q).
+template <int W>
+struct VehicleKD {
+    DualN<W> m, lf, lr, Iz, dt, cda, roll, Bf, Cf, Df, Br, Cr, Dr;
+};
+// the scalar a model function computes in: the constants' type times the point's
+template <class KV, class T>
+struct ModelScalarOf {
+    using type = T;  // plain constants: the point's scalar
+};
+template <int W>
+struct ModelScalarOf<VehicleKD<W>, double> {
+    using type = DualN<W>;
+};
+template <class KV, class T>
+using ModelScalar = typename ModelScalarOf<KV, T>::type;
 
 // f(x, u) of the dynamic bicycle model (vehicle_models.py:238-245 / 470-475), plus the
 // tyre quantities the Jacobian needs
@@ -204,26 +264,26 @@ template <class T>
 struct Tyre {
     T af, ar, Fyf, Fyr, Fx;
 };
-template <class T>
-__device__ __forceinline__ Tyre<T> tyre_forces(const VehicleK& k, const T* x, const T* u) {
-    Tyre<T> t;
+template <class T, class KV, class R = ModelScalar<KV, T>>
+__device__ __forceinline__ Tyre<R> tyre_forces(const KV& k, const T* x, const T* u) {
+    Tyre<R> t;
     const T vx = x[3], vy = x[4], r = x[5], st = u[0], acc = u[1];
     t.af = -atan2(k.lf * r + vy, vx) + st;
     t.ar = -atan2(-k.lr * r + vy, vx);
     t.Fyf = k.Df * sin(k.Cf * atan(k.Bf * t.af));
     t.Fyr = k.Dr * sin(k.Cr * atan(k.Br * t.ar));
-    const double R_roll = k.roll * sgn(vx);
-    const T F_aero = 0.5 * k.cda * vx * vx * sgn(vx);
+    const auto R_roll = k.roll * sgn(vx);
+    const R F_aero = 0.5 * k.cda * vx * vx * sgn(vx);
     t.Fx = k.m * acc - F_aero - R_roll;
     return t;
 }
-template <class T>
-__device__ __forceinline__ void dynamics(const VehicleK& k, const T* x, const T* u, const Tyre<T>& t, T* f) {
+template <class T, class KV, class R>
+__device__ __forceinline__ void dynamics(const KV& k, const T* x, const T* u, const Tyre<R>& t, R* f) {
     const T yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
     const T cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
-    f[0] = vx * cy - vy * sy;
-    f[1] = vy * cy + vx * sy;
-    f[2] = r;
+    f[0] = R(vx * cy - vy * sy);
+    f[1] = R(vy * cy + vx * sy);
+    f[2] = R(r);
     f[3] = 1. / k.m * (t.Fx * cs - t.Fyf * ss + k.m * vy * r);
     f[4] = 1. / k.m * (t.Fx * ss + t.Fyr + t.Fyf * cs - k.m * vx * r);
     f[5] = 1. / k.Iz * (t.Fx * k.lf * ss + t.Fyf * k.lf * cs - t.Fyr * k.lr);
@@ -233,29 +293,30 @@ __device__ __forceinline__ void dynamics(const VehicleK& k, const T* x, const T*
 // the reference's Jacobians Ac (6x6) and Bc (6x2; every other entry is the constant 0).  That Ac
 // is not everywhere the derivative of that f (dFx/dvx = -cda vx holds for vx > 0 only).  Each
 // value goes to `out` as soon as it exists: out.F(i, f_i), out.A(i, j, Ac_ij), out.B(i, j, Bc_ij).
-template <class T, class Out>
-__device__ __forceinline__ void continuous_model(const VehicleK& k, const T* x, const T* u, Out& out) {
-    const Tyre<T> t = tyre_forces(k, x, u);
-    T f[6];
+template <class T, class KV, class Out>
+__device__ __forceinline__ void continuous_model(const KV& k, const T* x, const T* u, Out& out) {
+    using R = ModelScalar<KV, T>;
+    const Tyre<R> t = tyre_forces(k, x, u);
+    R f[6];
     dynamics(k, x, u, t, f);
     for (int i = 0; i < 6; ++i) out.F(i, f[i]);
     const T yaw = x[2], vx = x[3], vy = x[4], r = x[5], st = u[0];
-    const double m = k.m, Iz = k.Iz, lf = k.lf, lr = k.lr;
+    const auto m = k.m, Iz = k.Iz, lf = k.lf, lr = k.lr;
     const T cy = cos(yaw), sy = sin(yaw), cs = cos(st), ss = sin(st);
     // :251-270 tyre-force derivatives
-    const T dFxf_dvx = -k.cda * vx;
-    const double dFxf_daccel = m;
-    const T kf = (k.Bf * k.Cf * k.Df * cos(k.Cf * atan(k.Bf * t.af))) / (1 + k.Bf * k.Bf * t.af * t.af);
-    const T kr = (k.Br * k.Cr * k.Dr * cos(k.Cr * atan(k.Br * t.ar))) / (1 + k.Br * k.Br * t.ar * t.ar);
-    const T af_num = lf * r + vy, ar_num = -lr * r + vy;
-    const T nf = af_num * af_num + vx * vx, nr = ar_num * ar_num + vx * vx;
-    const T dFyf_dvx = kf * af_num / nf;
-    const T dFyf_dvy = kf * (-vx / nf);
-    const T dFyf_dr = kf * (-lf * vx) / nf;
-    const T dFyf_dst = kf;
-    const T dFyr_dvx = kr * ar_num / nr;
-    const T dFyr_dvy = kr * (-vx) / nr;
-    const T dFyr_dr = kr * (lr * vx) / nr;
+    const R dFxf_dvx = -k.cda * vx;
+    const auto dFxf_daccel = m;
+    const R kf = (k.Bf * k.Cf * k.Df * cos(k.Cf * atan(k.Bf * t.af))) / (1 + k.Bf * k.Bf * t.af * t.af);
+    const R kr = (k.Br * k.Cr * k.Dr * cos(k.Cr * atan(k.Br * t.ar))) / (1 + k.Br * k.Br * t.ar * t.ar);
+    const R af_num = lf * r + vy, ar_num = -lr * r + vy;
+    const R nf = af_num * af_num + vx * vx, nr = ar_num * ar_num + vx * vx;
+    const R dFyf_dvx = kf * af_num / nf;
+    const R dFyf_dvy = kf * (-vx / nf);
+    const R dFyf_dr = kf * (-lf * vx) / nf;
+    const R dFyf_dst = kf;
+    const R dFyr_dvx = kr * ar_num / nr;
+    const R dFyr_dvy = kr * (-vx) / nr;
+    const R dFyr_dr = kr * (lr * vx) / nr;
     // :273-292 Jacobians
     out.A(0, 2, -vx * sy - vy * cy); out.A(0, 3, cy); out.A(0, 4, -sy);
     out.A(1, 2, -vy * sy + vx * cy); out.A(1, 3, sy); out.A(1, 4, cy);
@@ -307,10 +368,10 @@ __device__ void linearise_one(const VehicleK& k, const double* xin, const double
 // update_dynamics_model (vehicle_models.py:343-477): one explicit-Euler step of the
 // nonlinear model from the guarded state.  euler_step<T> starts at a GUARDED (x, u), as
 // continuous_model does: double for k_incr_shift, Dual for its transpose (euler_step_vjp).
-template <class T>
-__device__ __forceinline__ void euler_step(const VehicleK& k, const T* x, const T* u, T* xn) {
-    const Tyre<T> t = tyre_forces<T>(k, x, u);
-    T f[6];
+template <class T, class KV, class R>
+__device__ __forceinline__ void euler_step(const KV& k, const T* x, const T* u, R* xn) {
+    const Tyre<R> t = tyre_forces<T>(k, x, u);
+    R f[6];
     dynamics(k, x, u, t, f);
     for (int i = 0; i < 6; ++i) xn[i] = x[i] + f[i] * k.dt;
 }
@@ -766,6 +827,224 @@ __global__ __launch_bounds__(256) void k_linearise_vjp(KS ks, long B, int N, con
         gu[t * 2 + 0] = lat ? g[4] : 0.0;
         gu[t * 2 + 1] = g[5];
     }
+}
+
+// ------------------------------------------- gradients of the vehicle's constants --
+// DESIGN.md §25.  The cotangent of a fleet's table has the table's shape: gK (B, 13) in VehicleK's
+// order (m, l_f, l_r, Iz, dt, cda, roll, B_f, C_f, D_f, B_r, C_r, D_r), (B, 3) in
+// mpcqp_kin_vehicle's (l_f, l_r, dt).  Fleet form only: a uniform vehicle is a fleet of copies whose
+// rows the caller sums.  The rules are k_linearise_vjp's: the guard first, what it replaced is a
+// constant (the point carries no tangent here at all), sgn has derivative 0, Ac as written.
+
+// The constants C0 .. C0 + W - 1 of VehicleK's order seeded in slots 0 .. W - 1, the others plain.
+template <int C0, int W>
+__device__ __forceinline__ VehicleKD<W> seed_constants(const VehicleK& k) {
+    const auto sd = [](double v, int c) {
+        return (c >= C0 && c < C0 + W) ? DualN<W>(v, c - C0, true) : DualN<W>(v);
+    };
+    VehicleKD<W> d;
+    d.m = sd(k.m, 0); d.lf = sd(k.lf, 1); d.lr = sd(k.lr, 2); d.Iz = sd(k.Iz, 3); d.dt = sd(k.dt, 4);
+    d.cda = sd(k.cda, 5); d.roll = sd(k.roll, 6);
+    d.Bf = sd(k.Bf, 7); d.Cf = sd(k.Cf, 8); d.Df = sd(k.Df, 9);
+    d.Br = sd(k.Br, 10); d.Cr = sd(k.Cr, 11); d.Dr = sd(k.Dr, 12);
+    return d;
+}
+constexpr int kDtSlot = 4;  // dt's place in VehicleK's order
+
+// VjpFold's twin for the constants.  continuous_model hands it values that are duals in the
+// constants (or plain doubles, where no constant enters); the point (x, u) is plain.  With c the
+// cotangent's weight without dt (gAd_ij, gBd_ij, ggd_i, -ggd_i x_j, -ggd_i u_j):
+//   g[q] += (c dt) d value / d constant q      -- VjpFold's weights
+//   gdt  += c value                            -- Ad = I + dt Ac, Bd = dt Bc, gd = dt (...) in dt itself
+template <int W>
+struct PvjpFold {
+    const double *x, *u;      // the guarded point
+    const double *gAd, *gBd;  // this thread's 36 / 12, or null
+    double ggd[6], dt;
+    double g[W], gdt;
+    __device__ void fold(const DualN<W>& o, double c) {
+        const double cw = c * dt;
+        for (int q = 0; q < W; ++q) g[q] += cw * o.d[q];
+        gdt += c * o.v;
+    }
+    __device__ void fold(double o, double c) { gdt += c * o; }
+    template <class S>
+    __device__ void F(int i, const S& v) { fold(v, ggd[i]); }
+    template <class S>
+    __device__ void A(int i, int j, const S& v) {
+        if (gAd) fold(v, gAd[i * 6 + j]);
+        fold(v * x[j], -ggd[i]);
+    }
+    template <class S>
+    __device__ void B(int i, int j, const S& v) {
+        if (gBd) fold(v, gBd[i * 2 + j]);
+        fold(v * u[j], -ggd[i]);
+    }
+};
+
+// The deterministic stage sum of the two linearisation kernels.  A block of 256 threads holds
+// vpb = 256 / N whole vehicles, thread lv * N + s = (vehicle lv of the block, stage s); its W
+// partials go to LDS as part[q * 256 + thread], and element (lv, q) is summed by ONE thread in stage
+// order, acc = 0, acc += part[s] for s = 0 .. N-1, and written once.  No atomics; N <= 256.
+template <int W, class Write>
+__device__ __forceinline__ void stage_sum(double* part, const double* g, bool live, int N, int vpb, long B,
+                                          Write write) {
+    if (live)
+        for (int q = 0; q < W; ++q) part[q * 256 + threadIdx.x] = g[q];
+    __syncthreads();
+    for (int e = threadIdx.x; e < vpb * W; e += 256) {
+        const int lv = e / W, q = e - lv * W;
+        const long b = (long)blockIdx.x * vpb + lv;
+        if (b >= B) break;
+        double acc = 0.0;
+        for (int s = 0; s < N; ++s) acc += part[q * 256 + lv * N + s];
+        write(b, q, acc);
+    }
+}
+
+// d (Ad, Bd, gd of linearise_one) / d constants C0 .. C0 + W - 1, contracted with (gAd, gBd, ggd)
+// and summed over the N stages: gK[b * 13 + C0 + q].  Two instantiations cover the thirteen,
+// <0, 7> = (m, l_f, l_r, Iz, dt, cda, roll) and <7, 6> = the tyre constants, so that the tangents fit
+// the register file.  Fleet form only; grid = ceil(B / vpb) blocks of 256.
+template <int C0, int W>
+__global__ __launch_bounds__(256) void k_linearise_pvjp(TableK<VehicleK> ks, long B, int N, int vpb,
+                                                        const double* __restrict__ x, long x_sb, long x_sk,
+                                                        const double* __restrict__ u, long u_sb, long u_sk,
+                                                        const double* __restrict__ gAd,
+                                                        const double* __restrict__ gBd,
+                                                        const double* __restrict__ ggd, double* __restrict__ gK) {
+    __shared__ double part[W * 256];
+    const int lv = threadIdx.x / N, s = threadIdx.x - lv * N;
+    const long b = (long)blockIdx.x * vpb + lv;
+    const bool live = lv < vpb && b < B;
+    double g[W];
+    for (int q = 0; q < W; ++q) g[q] = 0.0;
+    if (live) {
+        const long t = b * N + s;
+        const VehicleK k = constants(ks, b);  // by value, as k_linearise_vjp
+        const double* xin = x + b * x_sb + s * x_sk;
+        const double* uin = u + b * u_sb + s * u_sk;
+        double xg[6], ug[2];
+        for (int i = 0; i < 6; ++i) xg[i] = xin[i];
+        ug[0] = uin[0]; ug[1] = uin[1];
+        low_speed_guard(xg, ug);
+        const VehicleKD<W> kd = seed_constants<C0, W>(k);
+        PvjpFold<W> out = {xg, ug, gAd ? gAd + t * 36 : nullptr, gBd ? gBd + t * 12 : nullptr};
+        for (int i = 0; i < 6; ++i) out.ggd[i] = ggd ? ggd[t * 6 + i] : 0.0;
+        out.dt = k.dt;
+        for (int q = 0; q < W; ++q) out.g[q] = 0.0;
+        out.gdt = 0.0;
+        continuous_model(kd, xg, ug, out);
+        for (int q = 0; q < W; ++q) g[q] = out.g[q];
+        if constexpr (kDtSlot >= C0 && kDtSlot < C0 + W) g[kDtSlot - C0] = out.gdt;  // no model value reads dt
+    }
+    stage_sum<W>(part, g, live, N, vpb, B, [&](long bb, int q, double v) { gK[bb * 13 + C0 + q] = v; });
+}
+
+// The same for linearise_one(const mpcqp_kin_vehicle&, ...), in closed form as k_kin_linearise_vjp
+// is: every structural entry is dt times a function of the point and 1 / wb, wb = l_f + l_r, so
+// gK[b] = (g_wb, g_wb, g_dt) summed over the stages.
+__global__ __launch_bounds__(256) void k_kin_linearise_pvjp(TableK<mpcqp_kin_vehicle> ks, long B, int N, int vpb,
+                                                            const double* __restrict__ x, long x_sb, long x_sk,
+                                                            const double* __restrict__ u, long u_sb, long u_sk,
+                                                            const double* __restrict__ gAd,
+                                                            const double* __restrict__ gBd,
+                                                            const double* __restrict__ ggd,
+                                                            double* __restrict__ gK) {
+    __shared__ double part[2 * 256];
+    const int lv = threadIdx.x / N, s = threadIdx.x - lv * N;
+    const long b = (long)blockIdx.x * vpb + lv;
+    const bool live = lv < vpb && b < B;
+    double g[2] = {0.0, 0.0};  // (wb, dt)
+    if (live) {
+        const long t = b * N + s;
+        const mpcqp_kin_vehicle& k = constants(ks, b);
+        const double* xs = x + b * x_sb + s * x_sk;
+        const double v = xs[2], yaw = xs[3], st = u[b * u_sb + s * u_sk];
+        const double dt = k.dt, wb = k.l_f + k.l_r;
+        const double cy = cos(yaw), sy = sin(yaw), cs = cos(st), ts = tan(st);
+        const double sec2 = 1.0 / (cs * cs);
+        const double* A = gAd ? gAd + t * 16 : nullptr;
+        const double a02 = A ? A[0 * 4 + 2] : 0.0, a03 = A ? A[0 * 4 + 3] : 0.0, a12 = A ? A[1 * 4 + 2] : 0.0,
+                     a13 = A ? A[1 * 4 + 3] : 0.0, a32 = A ? A[3 * 4 + 2] : 0.0;
+        const double b21 = gBd ? gBd[t * 8 + 2 * 2 + 1] : 0.0, b30 = gBd ? gBd[t * 8 + 3 * 2 + 0] : 0.0;
+        const double g0 = ggd ? ggd[t * 4 + 0] : 0.0, g1 = ggd ? ggd[t * 4 + 1] : 0.0,
+                     g3 = ggd ? ggd[t * 4 + 3] : 0.0;
+        // what 1 / wb multiplies, without dt
+        const double over_wb = a32 * ts + (b30 - g3 * st) * v * sec2;
+        g[0] = -(dt * over_wb) / (wb * wb);
+        g[1] = ((a02 * cy + a12 * sy) + v * (a13 * cy - a03 * sy)) + b21 + v * yaw * (g0 * sy - g1 * cy) +
+               over_wb / wb;
+    }
+    stage_sum<2>(part, g, live, N, vpb, B, [&](long bb, int q, double v) {
+        if (q == 0) gK[bb * 3 + 0] = gK[bb * 3 + 1] = v;
+        else gK[bb * 3 + 2] = v;
+    });
+}
+
+// d euler_step_guarded / d constants C0 .. C0 + W - 1, contracted with w (6): the Euler step over
+// duals in the constants from the guarded point; dt is one of them (xn = x + f dt).
+template <int C0, int W>
+__device__ __forceinline__ void euler_step_pvjp_group(const VehicleK& k, const double* xg, const double* ug,
+                                                      const double* w, double* gk) {
+    const VehicleKD<W> kd = seed_constants<C0, W>(k);
+    DualN<W> xe[6];
+    euler_step<double>(kd, xg, ug, xe);
+    for (int q = 0; q < W; ++q) {
+        double acc = 0.0;
+        for (int i = 0; i < 6; ++i) acc += w[i] * xe[i].d[q];
+        gk[C0 + q] = acc;
+    }
+}
+
+// The terminal step of k_incr_shift with respect to the constants, one thread per vehicle: x (6)
+// and u (2) at a batch stride (views into the taped solution), w (B, 6) the cotangent of the new
+// state (null = zero), mode (null = 0 everywhere): a vehicle whose mode is not 0 did not take the
+// step and gets a zero row.  gK (B, 13), every element written.
+__global__ __launch_bounds__(128) void k_euler_step_pvjp(TableK<VehicleK> ks, long B, const double* __restrict__ x,
+                                                         long x_sb, const double* __restrict__ u, long u_sb,
+                                                         const double* __restrict__ w,
+                                                         const int* __restrict__ mode, double* __restrict__ gK) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double gk[13];
+    for (int c = 0; c < 13; ++c) gk[c] = 0.0;
+    if (w && !(mode && mode[b] != 0)) {
+        const VehicleK k = constants(ks, b);
+        double xg[6], ug[2], wb[6];
+        for (int i = 0; i < 6; ++i) xg[i] = x[b * x_sb + i];
+        ug[0] = u[b * u_sb + 0]; ug[1] = u[b * u_sb + 1];
+        for (int i = 0; i < 6; ++i) wb[i] = w[b * 6 + i];
+        low_speed_guard(xg, ug);
+        euler_step_pvjp_group<0, 7>(k, xg, ug, wb, gk);
+        euler_step_pvjp_group<7, 6>(k, xg, ug, wb, gk);
+    }
+    for (int c = 0; c < 13; ++c) gK[b * 13 + c] = gk[c];
+}
+
+// The same for kin_update (the terminal step of the three kinematic tails), in closed form:
+// x (4), u (2) at a batch stride, w (B, 4); gK (B, 3) = (g_wb, g_wb, g_dt).
+__global__ __launch_bounds__(128) void k_kin_update_pvjp(TableK<mpcqp_kin_vehicle> ks, long B,
+                                                         const double* __restrict__ x, long x_sb,
+                                                         const double* __restrict__ u, long u_sb,
+                                                         const double* __restrict__ w,
+                                                         const int* __restrict__ mode, double* __restrict__ gK) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double gwb = 0.0, gdt = 0.0;
+    if (w && !(mode && mode[b] != 0)) {
+        const mpcqp_kin_vehicle& k = constants(ks, b);
+        const double v = x[b * x_sb + 2], yaw = x[b * x_sb + 3], st = u[b * u_sb + 0], acc = u[b * u_sb + 1];
+        const double dt = k.dt, wb = k.l_f + k.l_r;
+        const double v1 = v + acc * dt;
+        const double cy = cos(yaw), sy = sin(yaw), ts = tan(st);
+        const double w0 = w[b * 4 + 0], w1 = w[b * 4 + 1], w2 = w[b * 4 + 2], w3 = w[b * 4 + 3];
+        gwb = -(w3 * v1 * ts * dt) / (wb * wb);
+        gdt = (v * (w0 * cy + w1 * sy) + w2 * acc) + w3 * ts * (acc * dt + v1) / wb;
+    }
+    gK[b * 3 + 0] = gwb;
+    gK[b * 3 + 1] = gwb;
+    gK[b * 3 + 2] = gdt;
 }
 
 // ---------------------------------------------------------- receding horizon --
@@ -1827,6 +2106,64 @@ int linearise_vjp_device(const char* what, const V* veh, int64_t B, int32_t N, c
                            x_sb, x_sk, du, u_sb, u_sk, dgAd, dgBd, dggd, dgx, dgu);
 }
 
+// The parameter kernels exist in fleet form only; the fleet's table, uploaded on
+// first use as launch_from does.
+template <class F>
+int fleet_table(const F* fleet, TableK<typename F::K>* out) {
+    F& f = *const_cast<F*>(fleet);
+    if (!f.d_k) {
+        MHIPCHK(hipSetDevice(f.dev));
+        if (int e = upload(f.k, &f.d_k)) return e;
+    }
+    out->k = f.d_k;
+    return 0;
+}
+
+constexpr int kStageSumMax = 256;  // one block holds whole vehicles: N stages of one fit 256 threads
+
+// F: mpcqp_fleet (gK (B, 13), two launches, one per group of constants) or mpcqp_kin_fleet ((B, 3))
+template <class F>
+int linearise_pvjp_device(const char* what, const F* f, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                          int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                          const double* dgBd, const double* dggd, double* dgK, int32_t device, void* stream) {
+    if (!f || !dx || !du || !dgK || B < 0 || N < 1) return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (N > kStageSumMax)
+        return set_error(MPCQP_EUNSUPPORTED, "%s: need N <= %d (the stage sum holds whole vehicles in one block)",
+                         what, kStageSumMax);
+    if (int e = source_check(what, f, B, device)) return e;
+    if (B == 0) return 0;
+    TableK<typename F::K> table;
+    if (int e = fleet_table(f, &table)) return e;
+    const int vpb = kStageSumMax / N;
+    const long threads = (long)grid_of(B, vpb) * 256;
+    if constexpr (std::is_same<F, mpcqp_fleet>::value) {
+        if (int e = launch(device, stream, threads, 256, k_linearise_pvjp<0, 7>, table, B, N, vpb, dx, x_sb, x_sk,
+                           du, u_sb, u_sk, dgAd, dgBd, dggd, dgK))
+            return e;
+        return launch(device, stream, threads, 256, k_linearise_pvjp<7, 6>, table, B, N, vpb, dx, x_sb, x_sk, du,
+                      u_sb, u_sk, dgAd, dgBd, dggd, dgK);
+    } else {
+        return launch(device, stream, threads, 256, k_kin_linearise_pvjp, table, B, N, vpb, dx, x_sb, x_sk, du, u_sb,
+                      u_sk, dgAd, dgBd, dggd, dgK);
+    }
+}
+
+// the terminal step of a tail with respect to the constants: euler_step_guarded / kin_update
+template <class F>
+int step_pvjp_device(const char* what, const F* f, int64_t B, const double* dx, int64_t x_sb, const double* du,
+                     int64_t u_sb, const double* dw, const int32_t* dmode, double* dgK, int32_t device,
+                     void* stream) {
+    if (!f || !dx || !du || !dgK || B < 0) return set_error(MPCQP_EINVAL, "%s: bad arguments", what);
+    if (int e = source_check(what, f, B, device)) return e;
+    if (B == 0) return 0;
+    TableK<typename F::K> table;
+    if (int e = fleet_table(f, &table)) return e;
+    if constexpr (std::is_same<F, mpcqp_fleet>::value)
+        return launch(device, stream, B, 128, k_euler_step_pvjp, table, B, dx, x_sb, du, u_sb, dw, dmode, dgK);
+    else
+        return launch(device, stream, B, 128, k_kin_update_pvjp, table, B, dx, x_sb, du, u_sb, dw, dmode, dgK);
+}
+
 template <class V>
 int incr_shift_device(const mpcqp_incr_layout* L, const V* veh, int64_t B, const double* dsol, const double* dAd,
                       const double* dBd, const double* dgd, double* dxt, double* dpred, double* dpdu, void* stream) {
@@ -2573,6 +2910,52 @@ int mpcqp_lane_tail_fleet_device(const mpcqp_incr_layout* L, const mpcqp_kin_fle
                                  int32_t* dtraj_len, void* stream) {
     return lane_tail_device(L, f, B, dsol, dAd, dBd, dgd, dxt, dpred, dpdu, nsw, switch_steps, paths_of, dstep,
                             dpath_id, dtraj, traj_cap, dtraj_len, stream);
+}
+
+// ---- gradients with respect to a fleet's constants ----
+
+int mpcqp_linearise_pvjp_fleet_device(const mpcqp_fleet* f, int64_t B, int32_t N, const double* dx, int64_t x_sb,
+                                      int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk, const double* dgAd,
+                                      const double* dgBd, const double* dggd, double* dgK, int32_t device,
+                                      void* stream) {
+    return linearise_pvjp_device("linearise_pvjp_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd, dgBd, dggd,
+                                 dgK, device, stream);
+}
+
+int mpcqp_kin_linearise_pvjp_fleet_device(const mpcqp_kin_fleet* f, int64_t B, int32_t N, const double* dx,
+                                          int64_t x_sb, int64_t x_sk, const double* du, int64_t u_sb, int64_t u_sk,
+                                          const double* dgAd, const double* dgBd, const double* dggd, double* dgK,
+                                          int32_t device, void* stream) {
+    return linearise_pvjp_device("kin_linearise_pvjp_fleet", f, B, N, dx, x_sb, x_sk, du, u_sb, u_sk, dgAd, dgBd,
+                                 dggd, dgK, device, stream);
+}
+
+int mpcqp_euler_step_pvjp_fleet_device(const mpcqp_fleet* f, int64_t B, const double* dx, int64_t x_sb,
+                                       const double* du, int64_t u_sb, const double* dw, const int32_t* dmode,
+                                       double* dgK, int32_t device, void* stream) {
+    return step_pvjp_device("euler_step_pvjp_fleet", f, B, dx, x_sb, du, u_sb, dw, dmode, dgK, device, stream);
+}
+
+int mpcqp_kin_update_pvjp_fleet_device(const mpcqp_kin_fleet* f, int64_t B, const double* dx, int64_t x_sb,
+                                       const double* du, int64_t u_sb, const double* dw, const int32_t* dmode,
+                                       double* dgK, int32_t device, void* stream) {
+    return step_pvjp_device("kin_update_pvjp_fleet", f, B, dx, x_sb, du, u_sb, dw, dmode, dgK, device, stream);
+}
+
+int mpcqp_vehicle_constants_vjp(const mpcqp_vehicle* veh, const double gk[13], double gveh[9]) {
+    if (!veh || !gk || !gveh) return set_error(MPCQP_EINVAL, "vehicle_constants_vjp: NULL argument");
+    // derive_constants over duals in the nine arguments: d constant c / d argument a = k[c].d[a]
+    using D9 = DualN<9>;
+    D9 p[9], k[13];
+    const double* v = &veh->m;
+    for (int a = 0; a < 9; ++a) p[a] = D9(v[a], a, true);
+    derive_constants(p, k);
+    for (int a = 0; a < 9; ++a) {
+        double acc = 0.0;
+        for (int c = 0; c < 13; ++c) acc += gk[c] * k[c].d[a];
+        gveh[a] = acc;
+    }
+    return 0;
 }
 
 }  // extern "C"

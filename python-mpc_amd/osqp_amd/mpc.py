@@ -540,8 +540,14 @@ class _Dual:
     __rmul__ = __mul__
 
     def __truediv__(self, o):
+        if not isinstance(o, _Dual):  # a plain value under a dual (the parameter statements only)
+            return _Dual(self.v / o, self.d / (o[..., None] if isinstance(o, np.ndarray) else o))
         q = self.v / o.v
         return _Dual(q, (self.d - q[..., None] * o.d) / o.v[..., None])
+
+    def __rtruediv__(self, o):  # a plain value over a dual
+        q = o / self.v
+        return _Dual(q, (-q[..., None] * self.d) / self.v[..., None])
 
     def chain(self, v, dv):
         return _Dual(v, dv[..., None] * self.d)
@@ -667,6 +673,9 @@ def _fn(name, a):
 
 
 def _atan2(y, x):
+    if isinstance(y, _Dual) and not isinstance(x, _Dual):  # duals in the constants over a plain point
+        n = x * x + y.v * y.v
+        return _Dual(np.arctan2(y.v, x), (x[..., None] * y.d) / n[..., None])
     return _Dual.atan2(y, x) if isinstance(x, _Dual) else np.arctan2(y, x)
 
 
@@ -684,12 +693,24 @@ def _low_speed_guard(x, u):
     return x, u, ~((vx_in > -0.5) & (vx_in < 0.5)), ~((vx_in > -0.3) & (vx_in < 0.3))
 
 
+def model_constants(veh: VehicleParams):
+    """The thirteen constants the kernels read (mpc_device.hip's VehicleK, mpcqp_fleet_constants'
+    order): (m, l_f, l_r, Iz, dt, cda, roll, B_f, C_f, D_f, B_r, C_r, D_r)."""
+    (Bf, Cf, Df), (Br, Cr, Dr) = veh.pacejka()
+    return (veh.m, veh.l_f, veh.l_r, veh.Iz, veh.dt, veh.roh * veh.C_d * veh.A_f, veh.C_roll * veh.m * 9.81,
+            Bf, Cf, Df, Br, Cr, Dr)
+
+
 def _euler_step(veh: VehicleParams, x, u):
     """mpc_device.hip's euler_step<T> from a GUARDED point: x, u lists of six / two ndarrays or
     _Duals -> the six components of x + dt f(x, u) (tyre_forces, dynamics, operation by operation)."""
-    (Bf, Cf, Df), (Br, Cr, Dr) = veh.pacejka()
-    m, Iz, lf, lr, dt = veh.m, veh.Iz, veh.l_f, veh.l_r, veh.dt
-    cda, roll = veh.roh * veh.C_d * veh.A_f, veh.C_roll * m * 9.81
+    return _euler_step_k(model_constants(veh), x, u)
+
+
+def _euler_step_k(k, x, u):
+    """_euler_step over the thirteen constants k themselves: floats, or _Duals in the constants
+    with a plain point (euler_step_pvjp)."""
+    m, lf, lr, Iz, dt, cda, roll, Bf, Cf, Df, Br, Cr, Dr = k
     yaw, vx, vy, r = x[2:]
     st, acc = u
     af = -_atan2(lf * r + vy, vx) + st
@@ -988,6 +1009,221 @@ def kin_ltv_shift_vjp(veh, N, sol, Ad0, Bd0, x, gx=None, gu=None, gpred_x=None, 
     gsol = np.concatenate([gS.reshape(M, -1), gU.reshape(M, -1)], axis=1)
     return (gsol.reshape(lead + (gsol.shape[1],)), gA0.reshape(lead + (4, 4)), gB0.reshape(lead + (4, 2)),
             gg0.reshape(lead + (4,)), gxb.reshape(lead + (4,)))
+
+
+# ----------------------------- gradients with respect to the vehicle's constants --
+# DESIGN.md §25.  The statements of mpc_device.hip's four *_pvjp kernels and of
+# mpcqp_vehicle_constants_vjp, operation by operation.  Coordinates: the thirteen constants the
+# kernels read (model_constants' order) for the dynamic bicycle, (l_f, l_r, dt) for the kinematic
+# one.  Each takes ONE vehicle; per_vehicle applies them to a fleet.
+def _constant_duals(k, shape):
+    """The constants k as _Duals seeded in their own slots: constant c has d[..., c] = 1."""
+    out = []
+    for c, v in enumerate(k):
+        d = np.zeros(shape + (len(k),))
+        d[..., c] = 1.0
+        out.append(_Dual(np.full(shape, float(v)), d))
+    return out
+
+
+def _stage_sum(g):
+    """g (M, N, W) -> (M, W): the device's stage sum, acc = 0, acc += g[:, s] for s = 0 .. N-1."""
+    acc = np.zeros(g.shape[:1] + g.shape[2:])
+    for s in range(g.shape[1]):
+        acc = acc + g[:, s]
+    return acc
+
+
+def linearise_dynamics_pvjp(veh: VehicleParams, x, u, gAd=None, gBd=None, ggd=None):
+    """d (Ad, Bd, gd of linearise_dynamics) / d the thirteen constants, contracted with the
+    cotangents and summed over the stages, in the order of mpc_device.hip's k_linearise_pvjp:
+    x (..., N, 6), u (..., N, 2), gAd (..., N, 6, 6), gBd (..., N, 6, 2), ggd (..., N, 6)
+    (None = zero) -> gK (..., 13).
+
+    linearise_dynamics_vjp's rules with the roles exchanged: the guard first, then f, Ac, Bc over
+    duals in the CONSTANTS at a plain guarded point (an input the guard replaced is a constant
+    either way).  Each value folds with weight c dt into its tangent and with weight c into dt's
+    own slot (Ad = I + dt Ac, Bd = dt Bc, gd = dt (f - Ac x - Bc u)); no model value reads dt."""
+    x, u = np.asarray(x, float), np.asarray(u, float)
+    lead, N = x.shape[:-2], x.shape[-2]
+    x, u = x.reshape(-1, 6), u.reshape(-1, 2)
+    shape = x.shape[:-1]
+    zero = lambda g, tail: np.zeros(shape + tail) if g is None else np.asarray(g, float).reshape(shape + tail)
+    gAd, gBd, ggd = zero(gAd, (6, 6)), zero(gBd, (6, 2)), zero(ggd, (6,))
+    x, u, _, _ = _low_speed_guard(x, u)
+    kv = model_constants(veh)
+    dt = kv[4]
+    m, lf, lr, Iz, _, cda, roll, Bf, Cf, Df, Br, Cr, Dr = _constant_duals(kv, shape)
+    xs, us = [x[:, i] for i in range(6)], [u[:, 0], u[:, 1]]
+    yaw, vx, vy, r = xs[2:]
+    st, acc = us
+    # tyre_forces
+    af = -_atan2(lf * r + vy, vx) + st
+    ar = -_atan2(-lr * r + vy, vx)
+    Fyf = Df * (Cf * (Bf * af).atan()).sin()
+    Fyr = Dr * (Cr * (Br * ar).atan()).sin()
+    sg = np.sign(vx)
+    Fx = m * acc - 0.5 * cda * vx * vx * sg - roll * sg
+    # dynamics
+    cy, sy, cs, ss = np.cos(yaw), np.sin(yaw), np.cos(st), np.sin(st)
+    f = [vx * cy - vy * sy, vy * cy + vx * sy, r,
+         1. / m * (Fx * cs - Fyf * ss + m * vy * r),
+         1. / m * (Fx * ss + Fyr + Fyf * cs - m * vx * r),
+         1. / Iz * (Fx * lf * ss + Fyf * lf * cs - Fyr * lr)]
+    # continuous_model
+    dFx_dvx = -cda * vx
+    dFx_da = m
+    kf = (Bf * Cf * Df * (Cf * (Bf * af).atan()).cos()) / (1 + Bf * Bf * af * af)
+    kr = (Br * Cr * Dr * (Cr * (Br * ar).atan()).cos()) / (1 + Br * Br * ar * ar)
+    af_num, ar_num = lf * r + vy, -lr * r + vy
+    nf, nr = af_num * af_num + vx * vx, ar_num * ar_num + vx * vx
+    dFyf_dvx = kf * af_num / nf
+    dFyf_dvy = kf * (-vx / nf)
+    dFyf_dr = kf * (-lf * vx) / nf
+    dFyf_dst = kf
+    dFyr_dvx = kr * ar_num / nr
+    dFyr_dvy = kr * (-vx) / nr
+    dFyr_dr = kr * (lr * vx) / nr
+    Ac = {(0, 2): -vx * sy - vy * cy, (0, 3): cy, (0, 4): -sy,
+          (1, 2): -vy * sy + vx * cy, (1, 3): sy, (1, 4): cy,
+          (2, 5): np.ones(shape),
+          (3, 3): 1 / m * (dFx_dvx * cs - dFyf_dvx * ss),
+          (3, 4): 1 / m * (-dFyf_dvy * ss + m * r),
+          (3, 5): 1 / m * (-dFyf_dr * ss + m * vy),
+          (4, 3): 1 / m * (dFx_dvx * ss + dFyr_dvx + dFyf_dvx * cs - m * r),
+          (4, 4): 1 / m * (dFyr_dvy + dFyf_dvy * cs),
+          (4, 5): 1 / m * (dFyr_dr + dFyf_dr * cs - m * vx),
+          (5, 3): 1 / Iz * (dFx_dvx * lf * ss + dFyf_dvx * lf * cs - dFyr_dvx * lr),
+          (5, 4): 1 / Iz * (dFyf_dvy * lf * cs - dFyr_dvy * lr),
+          (5, 5): 1 / Iz * (dFyf_dr * lf * cs - dFyr_dr * lr)}
+    Bc = {(3, 0): 1 / m * (-Fx * ss - dFyf_dst * ss - Fyf * cs), (3, 1): 1 / m * (dFx_da * cs),
+          (4, 0): 1 / m * (Fx * cs + dFyf_dst * cs - Fyf * ss), (4, 1): 1 / m * (dFx_da * ss),
+          (5, 0): 1 / Iz * (Fx * lf * cs + dFyf_dst * lf * cs - Fyf * lf * ss), (5, 1): 1 / Iz * (dFx_da * lf * ss)}
+    # PvjpFold: F, then A, then B, as continuous_model emits them
+    g, gdt = np.zeros(shape + (13,)), np.zeros(shape)
+
+    def fold(o, c):
+        nonlocal g, gdt
+        if isinstance(o, _Dual):
+            g = g + (c * dt)[..., None] * o.d
+            gdt = gdt + c * o.v
+        else:
+            gdt = gdt + c * o
+
+    for i in range(6):
+        fold(f[i], ggd[..., i])
+    for (i, j), v in Ac.items():
+        fold(v, gAd[..., i, j])
+        fold(v * xs[j], -ggd[..., i])
+    for (i, j), v in Bc.items():
+        fold(v, gBd[..., i, j])
+        fold(v * us[j], -ggd[..., i])
+    g[..., 4] = gdt
+    return _stage_sum(g.reshape(-1, N, 13)).reshape(lead + (13,))
+
+
+def linearise_kinematics_pvjp(l_f, l_r, dt, x, u, gAd=None, gBd=None, ggd=None):
+    """The same for linearise_kinematics, in closed form as k_kin_linearise_pvjp has it: x (..., N, 4),
+    u (..., N, 2), gAd (..., N, 4, 4), gBd (..., N, 4, 2), ggd (..., N, 4) (None = zero) -> gK (..., 3)
+    in (l_f, l_r, dt).  Every structural entry is dt times a function of the point and 1 / wb,
+    wb = l_f + l_r, so l_f and l_r take the same value."""
+    x, u = np.asarray(x, float), np.asarray(u, float)
+    lead, N = x.shape[:-2], x.shape[-2]
+    shape = x.shape[:-1]
+    zero = lambda g, tail: np.zeros(shape + tail) if g is None else np.asarray(g, float).reshape(shape + tail)
+    gAd, gBd, ggd = zero(gAd, (4, 4)), zero(gBd, (4, 2)), zero(ggd, (4,))
+    wb = l_f + l_r
+    v, yaw, st = x[..., 2], x[..., 3], u[..., 0]
+    cy, sy, cs, ts = np.cos(yaw), np.sin(yaw), np.cos(st), np.tan(st)
+    sec2 = 1.0 / (cs * cs)
+    a02, a03, a12, a13, a32 = gAd[..., 0, 2], gAd[..., 0, 3], gAd[..., 1, 2], gAd[..., 1, 3], gAd[..., 3, 2]
+    b21, b30, g0, g1, g3 = gBd[..., 2, 1], gBd[..., 3, 0], ggd[..., 0], ggd[..., 1], ggd[..., 3]
+    over_wb = a32 * ts + (b30 - g3 * st) * v * sec2  # what 1 / wb multiplies, without dt
+    gwb = -(dt * over_wb) / (wb * wb)
+    gdt = ((a02 * cy + a12 * sy) + v * (a13 * cy - a03 * sy)) + b21 + v * yaw * (g0 * sy - g1 * cy) + over_wb / wb
+    s = _stage_sum(np.stack([gwb, gdt], axis=-1).reshape(-1, N, 2))
+    return np.stack([s[:, 0], s[:, 0], s[:, 1]], axis=-1).reshape(lead + (3,))
+
+
+def euler_step_pvjp(veh: VehicleParams, x, u, w, mode=None):
+    """d (the guarded Euler step _euler_step of x (..., 6), u (..., 2)) / d the thirteen
+    constants, contracted with w (..., 6) -> gK (..., 13) (mpc_device.hip's k_euler_step_pvjp):
+    the step over duals in the constants, dt among them, from the guarded plain point.  mode
+    (...) or None: a vehicle whose mode is not 0 did not take the step and gets a zero row."""
+    x, u, w = np.asarray(x, float), np.asarray(u, float), np.asarray(w, float)
+    lead = x.shape[:-1]
+    x, u, w = x.reshape(-1, 6), u.reshape(-1, 2), w.reshape(-1, 6)
+    xg, ug, _, _ = _low_speed_guard(x, u)
+    k = _constant_duals(model_constants(veh), xg.shape[:1])
+    xe = _euler_step_k(k, [xg[:, i] for i in range(6)], [ug[:, 0], ug[:, 1]])
+    g = np.zeros(xg.shape[:1] + (13,))
+    for i in range(6):
+        g = g + w[:, i, None] * xe[i].d
+    if mode is not None:
+        g[np.asarray(mode).reshape(-1) != 0] = 0.0
+    return g.reshape(lead + (13,))
+
+
+def kin_update_pvjp(l_f, l_r, dt, x, u, w, mode=None):
+    """The same for kin_update in closed form (k_kin_update_pvjp): x (..., 4), u (..., 2), w (..., 4)
+    -> gK (..., 3) in (l_f, l_r, dt)."""
+    x, u, w = np.asarray(x, float), np.asarray(u, float), np.asarray(w, float)
+    v, yaw, st, acc = x[..., 2], x[..., 3], u[..., 0], u[..., 1]
+    wb = l_f + l_r
+    v1 = v + acc * dt
+    cy, sy, ts = np.cos(yaw), np.sin(yaw), np.tan(st)
+    w0, w1, w2, w3 = (w[..., i] for i in range(4))
+    gwb = -(w3 * v1 * ts * dt) / (wb * wb)
+    gdt = (v * (w0 * cy + w1 * sy) + w2 * acc) + w3 * ts * (acc * dt + v1) / wb
+    g = np.stack([gwb, gwb, gdt], axis=-1)
+    if mode is not None:
+        g[np.asarray(mode) != 0] = 0.0
+    return g
+
+
+def vehicle_constants(p):
+    """The thirteen constants of the nine constructor arguments p = (m, l_f, l_r, width, length,
+    C_d, A_f, C_roll, dt) (mpcqp_vehicle's field order), with mpc_device.hip's derivation
+    operation by operation; floats, or _Duals in the arguments."""
+    m, l_f, l_r, width, length, C_d, A_f, C_roll, dt = p
+    Iz = 1.0 / 12 * m * (width * width + length * length)
+    cda = 1.23 * C_d * A_f
+    roll = C_roll * m * 9.81
+    a = [-22.1, 1011, 1078, 1.82, 0.208, 0.000, -0.354, 0.707]
+    wheelbase = l_f + l_r
+    tyre = []
+    for share in (l_r, l_f):
+        Fz = 9.81 * (m * share / wheelbase) * 0.001
+        C = 1.30
+        D = a[0] * Fz * Fz + a[1] * Fz
+        BCD = a[2] * _fn("sin", a[3] * _fn("atan", a[4] * Fz))
+        tyre += [BCD / (C * D) * 180 / np.pi, C, D]
+    return [m, l_f, l_r, Iz, dt, cda, roll] + tyre
+
+
+def vehicle_constants_vjp(params, gk):
+    """mpcqp_vehicle_constants_vjp: params (..., 9) the constructor arguments, gk (..., 13) the
+    cotangent of the constants -> (..., 9), the transpose of vehicle_constants' Jacobian at
+    params, formed by running vehicle_constants over duals in the nine arguments."""
+    params, gk = np.asarray(params, float), np.asarray(gk, float)
+    lead = params.shape[:-1]
+    p = _constant_duals_of(params)
+    k = vehicle_constants(p)
+    g = np.zeros(lead + (9,))
+    for c in range(13):
+        if isinstance(k[c], _Dual):  # C_f, C_r are the number 1.30
+            g = g + gk[..., c, None] * k[c].d
+    return g
+
+
+def _constant_duals_of(params):
+    """params (..., 9) as nine _Duals, argument a seeded in slot a."""
+    out = []
+    for a in range(params.shape[-1]):
+        d = np.zeros(params.shape)
+        d[..., a] = 1.0
+        out.append(_Dual(params[..., a], d))
+    return out
 
 
 # ------------------------------------------------------------ batch generators --

@@ -132,10 +132,31 @@ class Fleet(_FleetBase):
             _check(_bind().mpcqp_fleet_constants(self._h, b, _np_ptr(out[b])), "fleet_constants")
         return out
 
+    def constants_vjp(self, gK):
+        """(B, 13) cotangent of ``constants()`` -> (B, 9) of the constructor arguments, in the
+        struct's field order (m, l_f, l_r, width, length, C_d, A_f, C_roll, dt): the chain through
+        each vehicle's derivation (mpcqp_vehicle_constants_vjp; host only).  gK: an array, or a
+        tensor on any device; the result is a float64 numpy array."""
+        gK = np.ascontiguousarray(gK.detach().cpu().numpy() if hasattr(gK, "detach") else gK, dtype=np.float64)
+        if gK.shape != (self._n, 13):
+            raise ValueError(f"gK must be ({self._n}, 13)")
+        out = np.empty((self._n, 9))
+        for b in range(self._n):
+            _check(_bind().mpcqp_vehicle_constants_vjp(C.byref(self._vehicles[b]), _np_ptr(gK[b]), _np_ptr(out[b])),
+                   "vehicle_constants_vjp")
+        return out
+
 
 class KinFleet(_FleetBase):
     """B kinematic bicycles (KinVehicle structs)."""
     _struct, _create, _free = KinVehicle, "mpcqp_kin_fleet_create", "mpcqp_kin_fleet_free"
+
+    def constants_vjp(self, gK):
+        """The kinematic struct derives nothing: (B, 3) -> (B, 3), the identity."""
+        gK = np.array(gK.detach().cpu().numpy() if hasattr(gK, "detach") else gK, dtype=np.float64)
+        if gK.shape != (self._n, 3):
+            raise ValueError(f"gK must be ({self._n}, 3)")
+        return gK
 
 
 def _entry(name, veh, B):
@@ -214,6 +235,12 @@ def _bind():
         twin = getattr(L, f"mpcqp_{name}_device").argtypes
         getattr(L, f"mpcqp_{name}_fleet_device").argtypes = [
             vp if t in (_P(Vehicle), _P(KinVehicle)) else t for t in twin]
+    # gradients with respect to a fleet's constants (fleet form only)
+    L.mpcqp_linearise_pvjp_fleet_device.argtypes = L.mpcqp_kin_linearise_pvjp_fleet_device.argtypes = [
+        vp, i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, i32, vp]
+    L.mpcqp_euler_step_pvjp_fleet_device.argtypes = L.mpcqp_kin_update_pvjp_fleet_device.argtypes = [
+        vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp]
+    L.mpcqp_vehicle_constants_vjp.argtypes = [_P(Vehicle), vp, vp]
     L._mpc_bound = True
     return L
 
@@ -267,10 +294,10 @@ def linearise(veh: Vehicle, x, u, device=0):
     return _linearise("linearise", veh, x, u, 6)
 
 
-def _linearise_vjp(symbol, veh, x, u, gAd, gBd, ggd, nx, out=None):
-    """linearise_vjp / linearise_kinematics_vjp: the model's C entry point on (B, N, nx) states."""
+def _vjp_point(x, u, gAd, gBd, ggd, nx):
+    """The point and cotangents of a linearisation's VJP, checked: (x, u) as (B, N, ..) views and
+    whether the N axis was added."""
     import torch
-    L = _bind()
     squeeze = x.dim() == 2
     if squeeze:
         x, u = x[:, None, :], u[:, None, :]
@@ -286,6 +313,15 @@ def _linearise_vjp(symbol, veh, x, u, gAd, gBd, ggd, nx, out=None):
                               t.dtype != torch.float64 or not t.is_contiguous()):
             raise ValueError(f"cotangents must be contiguous float64 (B, N, {nx}, {nx}), (B, N, {nx}, 2), "
                              f"(B, N, {nx}) tensors")
+    return x, u, squeeze
+
+
+def _linearise_vjp(symbol, veh, x, u, gAd, gBd, ggd, nx, out=None):
+    """linearise_vjp / linearise_kinematics_vjp: the model's C entry point on (B, N, nx) states."""
+    import torch
+    L = _bind()
+    x, u, squeeze = _vjp_point(x, u, gAd, gBd, ggd, nx)
+    B, N = x.shape[0], x.shape[1]
     kw = dict(dtype=torch.float64, device=x.device)
     if out is None:
         gx = torch.empty((B, N, nx), **kw); gu = torch.empty((B, N, 2), **kw)
@@ -312,6 +348,90 @@ def linearise_vjp(veh: Vehicle, x, u, gAd, gBd, ggd, out=None):
     (include/mpcqp.h).  A caller whose stages share one (x, u) sums over the stage axis.
     ``out`` = (gx, gu): contiguous (B, N, 6) / (B, N, 2) tensors to write into."""
     return _linearise_vjp("linearise_vjp", veh, x, u, gAd, gBd, ggd, 6, out)
+
+
+# ---- gradients with respect to a fleet's constants (DESIGN.md §25) ----
+def _fleet_of(fleet, kind, B, what):
+    if not isinstance(fleet, kind):
+        raise TypeError(f"{what} takes a {kind.__name__}: parameter gradients exist in fleet form only "
+                        "(a uniform vehicle is a fleet of copies whose rows the caller sums)")
+    if len(fleet) != B:
+        raise ValueError(f"{what}: a fleet of {len(fleet)} vehicles was given a batch of {B}")
+    return fleet._h
+
+
+def _gk_out(out, B, nk, device):
+    import torch
+    if out is None:
+        return torch.empty((B, nk), dtype=torch.float64, device=device)
+    if tuple(out.shape) != (B, nk) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous float64 (B, {nk}) tensor on x's device")
+    return out
+
+
+def _linearise_pvjp(symbol, kind, fleet, x, u, gAd, gBd, ggd, nx, nk, out):
+    import torch
+    L = _bind()
+    x, u, _ = _vjp_point(x, u, gAd, gBd, ggd, nx)
+    B, N = x.shape[0], x.shape[1]
+    h = _fleet_of(fleet, kind, B, symbol)
+    gK = _gk_out(out, B, nk, x.device)
+    _check(getattr(L, f"mpcqp_{symbol}_fleet_device")(
+        h, B, N, _p(x), x.stride(0), x.stride(1), _p(u), u.stride(0), u.stride(1), _po(gAd), _po(gBd), _po(ggd),
+        _p(gK), x.device.index or 0, _stream(torch, x.device)), symbol)
+    return gK
+
+
+def linearise_pvjp(fleet: Fleet, x, u, gAd, gBd, ggd, out=None):
+    """d loss / d the fleet's constants through ``linearise`` (mpcqp_linearise_pvjp_fleet_device):
+    x, u and the cotangents as ``linearise_vjp`` takes them -> gK (B, 13), summed over the N stages
+    in stage order (deterministic: a repeated call returns the same bits; N <= 256), in the order of
+    ``Fleet.constants()``.  ``Fleet.constants_vjp`` chains it to the constructor arguments.
+    ``out``: a contiguous float64 (B, 13) tensor to write into."""
+    return _linearise_pvjp("linearise_pvjp", Fleet, fleet, x, u, gAd, gBd, ggd, 6, 13, out)
+
+
+def kin_linearise_pvjp(fleet: KinFleet, x, u, gAd, gBd, ggd, out=None):
+    """The same through ``linearise_kinematics`` (mpcqp_kin_linearise_pvjp_fleet_device): gK (B, 3)
+    in (l_f, l_r, dt)."""
+    return _linearise_pvjp("kin_linearise_pvjp", KinFleet, fleet, x, u, gAd, gBd, ggd, 4, 3, out)
+
+
+def _step_pvjp(symbol, kind, fleet, x, u, w, mode, nx, nk, out):
+    import torch
+    L = _bind()
+    if x.dim() != 2 or u.dim() != 2 or x.shape[1] != nx or u.shape[1] != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"x must be (B, {nx}) and u (B, 2)")
+    if x.dtype != torch.float64 or u.dtype != torch.float64:
+        raise ValueError("x and u must be float64")
+    if x.stride(1) != 1 or u.stride(1) != 1:
+        raise ValueError("the state / input axis must be contiguous")
+    B = x.shape[0]
+    if w is not None and (tuple(w.shape) != (B, nx) or w.dtype != torch.float64 or not w.is_contiguous()):
+        raise ValueError(f"w must be a contiguous float64 (B, {nx}) tensor")
+    if mode is not None:
+        mode = _mode_in(mode, B, symbol)
+    h = _fleet_of(fleet, kind, B, symbol)
+    gK = _gk_out(out, B, nk, x.device)
+    _check(getattr(L, f"mpcqp_{symbol}_fleet_device")(
+        h, B, _p(x), x.stride(0), _p(u), u.stride(0), _po(w), _po(mode), _p(gK), x.device.index or 0,
+        _stream(torch, x.device)), symbol)
+    return gK
+
+
+def euler_step_pvjp(fleet: Fleet, x, u, w, mode=None, out=None):
+    """d loss / d the fleet's constants through the terminal step of ``incr_shift``
+    (update_dynamics_model's guarded Euler step; mpcqp_euler_step_pvjp_fleet_device): x (B, 6),
+    u (B, 2) with any batch stride (views into a taped solution), w (B, 6) the cotangent of the new
+    state (None = zero), mode (B) int32 or None: a vehicle whose mode is not 0 gets a zero row
+    -> gK (B, 13)."""
+    return _step_pvjp("euler_step_pvjp", Fleet, fleet, x, u, w, mode, 6, 13, out)
+
+
+def kin_update_pvjp(fleet: KinFleet, x, u, w, mode=None, out=None):
+    """The same through ``kin_update``, the terminal step of the kinematic tails
+    (mpcqp_kin_update_pvjp_fleet_device): x (B, 4), u (B, 2), w (B, 4) -> gK (B, 3)."""
+    return _step_pvjp("kin_update_pvjp", KinFleet, fleet, x, u, w, mode, 4, 3, out)
 
 
 class _Layout:

@@ -30,6 +30,11 @@ tape of small solution records, the backward sets each step up again, loads its 
 adjoint.  ``KinematicRollout`` and ``KinematicLTVRollout`` are the same body over the
 two kinematic loops (KinematicMPC, KinematicLTVMPC), whose tails carry the stop rule's and the skip
 rule's masks.
+
+``fleet(params)`` makes the vehicle itself an input: a (B, 9) or (B, 3) tensor of constructor
+arguments, one row per vehicle, accepted wherever ``veh`` is; when it requires grad, the backward of
+the linearisations, the three tails and the three rollouts also returns d loss / d params
+(DESIGN.md §25).
 """
 from __future__ import annotations
 
@@ -38,13 +43,76 @@ from .torch_qp import QPLayer
 
 __all__ = ["linearise_kinematics", "linearise_dynamics", "ltv_assemble", "incr_assemble", "affine_assemble",
            "incr_shift", "kin_shift", "kin_ltv_shift", "MPCLayer", "DynamicRollout", "KinematicRollout",
-           "KinematicLTVRollout"]
+           "KinematicLTVRollout", "fleet", "ParamFleet"]
 
 _FN = None
 
 
 def _c(t):
     return None if t is None else t.detach().contiguous()
+
+
+class ParamFleet:
+    """``fleet(params)``: a fleet whose constructor arguments are a tensor.  ``params`` (B, 9) in
+    mpc_device.Vehicle's field order (m, l_f, l_r, width, length, C_d, A_f, C_roll, dt) or (B, 3) in
+    KinVehicle's (l_f, l_r, dt); ``table`` the mpc_device.Fleet / KinFleet made of its values at
+    creation (a snapshot: after changing params, call ``fleet`` again)."""
+
+    def __init__(self, params, device=None):
+        import torch
+        if not isinstance(params, torch.Tensor) or params.dim() != 2 or params.shape[1] not in (9, 3) or \
+                params.dtype != torch.float64:
+            raise ValueError("fleet: params must be a float64 tensor of shape (B, 9) or (B, 3)")
+        if device is None:
+            device = params.device.index or 0 if params.is_cuda else 0
+        kind, struct = (md.Fleet, md.Vehicle) if params.shape[1] == 9 else (md.KinFleet, md.KinVehicle)
+        self.params = params
+        self.table = kind([struct(*row) for row in params.detach().cpu().tolist()], device=int(device))
+
+    def __len__(self):
+        return len(self.table)
+
+    @property
+    def dt(self):
+        return self.table.dt
+
+
+def fleet(params, device=None):
+    """A fleet of B vehicles from a (B, 9) or (B, 3) float64 tensor of constructor arguments, accepted
+    wherever this module takes ``veh``.  When ``params.requires_grad``, the backward of
+    linearise_dynamics / linearise_kinematics, incr_shift / kin_shift / kin_ltv_shift and the three
+    rollouts also returns d loss / d params: the linearisations' part from
+    mpc_device.linearise_pvjp / kin_linearise_pvjp, the tails' from the terminal-step kernels on views
+    of the solution, both chained through ``constants_vjp``.  ``device``: the table's (default: the
+    tensor's, or 0 for a host tensor; the gradient arrives on params' own device)."""
+    return ParamFleet(params, device)
+
+
+def _veh(veh):
+    """(what mpc_device takes, the params tensor or None) of a ``veh`` argument."""
+    return (veh.table, veh.params) if isinstance(veh, ParamFleet) else (veh, None)
+
+
+def _chain(device, table, gK):
+    """d loss / d params, on params' device, from the cotangent of the table's constants (the chain
+    runs on the host: B x 13 doubles)."""
+    import torch
+    return torch.from_numpy(table.constants_vjp(gK)).to(device)
+
+
+def _terminal_pvjp(tail, table, N, sol, gpred, mode):
+    """The terminal step of a tail with respect to the table's constants: the point is a pair of
+    views into the solution (mpc_device.hip's DynamicIncrTail / KinIncrTail / KinLtvTail), the
+    cotangent the state part of gpred[N]."""
+    if tail == "incr":  # euler_step_guarded(x_N, u_{N-1}) of x~ = (x, u), nxa 8
+        x, u, w = sol[:, N * 8:N * 8 + 6], sol[:, (N - 1) * 8 + 6:N * 8], None if gpred is None else gpred[:, N, :6]
+        return md.euler_step_pvjp(table, x, u, None if w is None else w.contiguous(), mode)
+    if tail == "kin":   # kin_update(x_N, u_N) of x~ = (x, u), nxa 6
+        x, u, w = sol[:, N * 6:N * 6 + 4], sol[:, N * 6 + 4:N * 6 + 6], None if gpred is None else gpred[:, N, :4]
+    else:               # kin_update(S_N, U_{N-1}) of sol = (S_0..S_N, U_0..U_{N-1})
+        o = (N + 1) * 4 + (N - 1) * 2
+        x, u, w = sol[:, N * 4:N * 4 + 4], sol[:, o:o + 2], None if gpred is None else gpred[:, N]
+    return md.kin_update_pvjp(table, x, u, None if w is None else w.contiguous(), mode)
 
 
 def _functions():
@@ -55,11 +123,12 @@ def _functions():
     from types import SimpleNamespace
 
     class Linearise(torch.autograd.Function):
-        """inputs (model, veh, x, u); model = (forward, vjp) of mpc_device"""
+        """inputs (model, veh, x, u, params); model = (forward, vjp, pvjp) of mpc_device; params: a
+        ParamFleet's tensor (veh is then its table) or None"""
 
         @staticmethod
-        def forward(ctx, model, veh, x, u):
-            ctx.vjp, ctx.veh = model[1], veh
+        def forward(ctx, model, veh, x, u, params):
+            ctx.vjp, ctx.pvjp, ctx.veh, ctx.pdev = model[1], model[2], veh, getattr(params, "device", None)
             ctx.save_for_backward(x, u)
             ctx.set_materialize_grads(False)
             return model[0](veh, x.detach(), u.detach())
@@ -68,10 +137,14 @@ def _functions():
         def backward(ctx, gAd, gBd, ggd):
             x, u = ctx.saved_tensors
             if gAd is None and gBd is None and ggd is None:
-                return None, None, None, None
-            gx, gu = ctx.vjp(ctx.veh, x.detach(), u.detach(), _c(gAd), _c(gBd), _c(ggd))
+                return None, None, None, None, None
             need = ctx.needs_input_grad
-            return None, None, gx if need[2] else None, gu if need[3] else None
+            gx = gu = gp = None
+            if need[2] or need[3]:
+                gx, gu = ctx.vjp(ctx.veh, x.detach(), u.detach(), _c(gAd), _c(gBd), _c(ggd))
+            if need[4]:
+                gp = _chain(ctx.pdev, ctx.veh,ctx.pvjp(ctx.veh, x.detach(), u.detach(), _c(gAd), _c(gBd), _c(ggd)))
+            return None, None, gx if need[2] else None, gu if need[3] else None, gp
 
     class Assemble(torch.autograd.Function):
         """inputs (layout, Ad, Bd, gd, x0, Xr, xlo, xhi, Q, QN, R, use_w)"""
@@ -137,12 +210,12 @@ def _functions():
         return full
 
     class IncrShift(torch.autograd.Function):
-        """inputs (layout, veh, sol, Ad, Bd, gd, xt)"""
+        """inputs (layout, veh, sol, Ad, Bd, gd, xt, params)"""
 
         @staticmethod
-        def forward(ctx, layout, veh, sol, Ad, Bd, gd, xt):
+        def forward(ctx, layout, veh, sol, Ad, Bd, gd, xt, params):
             sol, Ad, Bd, gd, xt = (_c(t) for t in (sol, Ad, Bd, gd, xt))
-            ctx.layout, ctx.veh = layout, veh
+            ctx.layout, ctx.veh, ctx.pdev = layout, veh, getattr(params, "device", None)
             ctx.save_for_backward(sol, Ad, Bd, xt)
             ctx.set_materialize_grads(False)
             return md.incr_shift(layout, veh, sol, Ad, Bd, gd, xt)
@@ -150,23 +223,25 @@ def _functions():
         @staticmethod
         def backward(ctx, gxt, gpred, gpdu):
             if gxt is None and gpred is None and gpdu is None:
-                return (None,) * 7
+                return (None,) * 8
             sol, Ad, Bd, xt = ctx.saved_tensors
-            need = ctx.needs_input_grad[2:]  # (sol, Ad, Bd, gd, xt)
+            need = ctx.needs_input_grad[2:7]  # (sol, Ad, Bd, gd, xt)
             want = [k for k, n in zip(md.SHIFT_VJP_OUTPUTS, need) if n]
             g = md.incr_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, xt, _c(gxt), _c(gpred), _c(gpdu), want=want)
             N = ctx.layout.N
-            return (None, None, g.gsol, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), g.gxt)
+            gp = _chain(ctx.pdev, ctx.veh,_terminal_pvjp("incr", ctx.veh, N, sol, _c(gpred), None)) \
+                if ctx.needs_input_grad[7] else None
+            return (None, None, g.gsol, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), g.gxt, gp)
 
     class KinShift(torch.autograd.Function):
-        """inputs (layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)"""
+        """inputs (layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done, params)"""
 
         @staticmethod
-        def forward(ctx, layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done):
+        def forward(ctx, layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done, params):
             sol, Ad, Bd, gd, Xr, xt, pred, pdu = (_c(t) for t in (sol, Ad, Bd, gd, Xr, xt, pred, pdu))
             xt1, pred1, pdu1, cnt1, done1, mode = md.kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu,
                                                                finish_cnt, done)
-            ctx.layout, ctx.veh = layout, veh
+            ctx.layout, ctx.veh, ctx.pdev = layout, veh, getattr(params, "device", None)
             ctx.save_for_backward(sol, Ad, Bd, xt, mode)
             ctx.set_materialize_grads(False)
             ctx.mark_non_differentiable(cnt1, done1, mode)
@@ -175,23 +250,24 @@ def _functions():
         @staticmethod
         def backward(ctx, gxt, gpred, gpdu, *_):
             if gxt is None and gpred is None and gpdu is None:
-                return (None,) * 12
+                return (None,) * 13
             sol, Ad, Bd, xt, mode = ctx.saved_tensors
             need = ctx.needs_input_grad
             want = [k for k, n in zip(md.SHIFT_VJP_OUTPUTS, (need[2], need[3], need[4], need[5], need[7])) if n]
             g = md.kin_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, xt, mode, _c(gxt), _c(gpred), _c(gpdu), want=want)
             N = ctx.layout.N
+            gp = _chain(ctx.pdev, ctx.veh,_terminal_pvjp("kin", ctx.veh, N, sol, _c(gpred), mode)) if need[12] else None
             return (None, None, g.gsol, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), None, g.gxt,
-                    g.gpred_prev if need[8] else None, g.gpdu_prev if need[9] else None, None, None)
+                    g.gpred_prev if need[8] else None, g.gpdu_prev if need[9] else None, None, None, gp)
 
     class KinLTVShift(torch.autograd.Function):
-        """inputs (layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)"""
+        """inputs (layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u, params)"""
 
         @staticmethod
-        def forward(ctx, layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
+        def forward(ctx, layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u, params):
             sol, Ad, Bd, gd, x, u, pred_x, pred_u = (_c(t) for t in (sol, Ad, Bd, gd, x, u, pred_x, pred_u))
             x1, u1, px1, pu1, mode = md.kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)
-            ctx.layout, ctx.veh = layout, veh
+            ctx.layout, ctx.veh, ctx.pdev = layout, veh, getattr(params, "device", None)
             ctx.save_for_backward(sol, Ad, Bd, x, mode)
             ctx.set_materialize_grads(False)
             ctx.mark_non_differentiable(mode)
@@ -200,26 +276,28 @@ def _functions():
         @staticmethod
         def backward(ctx, gx, gu, gpx, gpu, *_):
             if gx is None and gu is None and gpx is None and gpu is None:
-                return (None,) * 11
+                return (None,) * 12
             sol, Ad, Bd, x, mode = ctx.saved_tensors
             need = ctx.needs_input_grad
             want = [k for k, n in zip(md.KIN_LTV_SHIFT_VJP_OUTPUTS, (need[2], need[4], need[5], need[6], need[7])) if n]
             g = md.kin_ltv_shift_vjp(ctx.layout, ctx.veh, sol, Ad, Bd, x, mode, _c(gx), _c(gu), _c(gpx), _c(gpu),
                                      want=want)
             N = ctx.layout.N
+            gp = _chain(ctx.pdev, ctx.veh,_terminal_pvjp("ltv", ctx.veh, N, sol, _c(gpx), mode)) if need[11] else None
             return (None, None, g.gsol, None, stage0(g.gAd0, N), stage0(g.gBd0, N), stage0(g.ggd0, N), g.gx,
                     g.gu_prev if need[8] else None, g.gpred_x_prev if need[9] else None,
-                    g.gpred_u_prev if need[10] else None)
+                    g.gpred_u_prev if need[10] else None, gp)
 
     class Rollout(torch.autograd.Function):
-        """inputs (roll, T, path, use_w, *state, *hor, Xr, Q, QN, R), the state and the horizon as many
-        tensors as roll._STATE and roll._HOR say; outputs (*trajectories, [DU0,] *horizon)"""
+        """inputs (roll, T, path, use_w, *state, *hor, Xr, Q, QN, R, params), the state and the horizon
+        as many tensors as roll._STATE and roll._HOR say, params a ParamFleet's tensor or None; outputs
+        (*trajectories, [DU0,] *horizon)"""
 
         @staticmethod
         def forward(ctx, roll, T, path, use_w, *tensors):
             tensors = tuple(_c(t) for t in tensors)
             ns, nh = len(roll._STATE), len(roll._HOR)
-            Xr, Q, QN, R = tensors[ns + nh:]
+            Xr, Q, QN, R = tensors[ns + nh:ns + nh + 4]
             weights = (Q, QN, R) if use_w else None
             ctx.roll, ctx.path, ctx.weights, ctx.Xr = roll, path, weights, Xr
             ctx.set_materialize_grads(False)
@@ -232,14 +310,14 @@ def _functions():
             roll = ctx.roll
             ns, nh = len(roll._STATE), len(roll._HOR)
             if all(g is None for g in cots):
-                return (None,) * (8 + ns + nh)
+                return (None,) * (9 + ns + nh)
             cots = tuple(_c(g) for g in cots)
             n = ctx.needs_input_grad[4:]
-            need = dict(state=n[:ns], hor=n[ns:ns + nh], Xr=n[-4], Q=n[-3], QN=n[-2], R=n[-1])
+            need = dict(state=n[:ns], hor=n[ns:ns + nh], Xr=n[-5], Q=n[-4], QN=n[-3], R=n[-2], params=n[-1])
             gDU0 = cots[ns] if roll._DU0 else None
             g = roll._on_stream(lambda: roll._backward(ctx.tape, ctx.Xr, ctx.path, ctx.weights, cots[:ns], gDU0,
                                                        cots[len(cots) - nh:], need))
-            return (None, None, None, None, *g["state"], *g["hor"], g["Xr"], g["Q"], g["QN"], g["R"])
+            return (None, None, None, None, *g["state"], *g["hor"], g["Xr"], g["Q"], g["QN"], g["R"], g["params"])
 
     _FN = SimpleNamespace(Linearise=Linearise, Assemble=Assemble, Affine=Affine, IncrShift=IncrShift,
                           KinShift=KinShift, KinLTVShift=KinLTVShift, Rollout=Rollout)
@@ -249,7 +327,9 @@ def _functions():
 def linearise_kinematics(veh, x, u):
     """mpc_device.linearise_kinematics, differentiable in x and u (3-D (B, N, 4) / (B, N, 2), any
     strides with a contiguous last axis: an ``expand`` over the stages gets the stage sum)."""
-    return _functions().Linearise.apply((md.linearise_kinematics, md.linearise_kinematics_vjp), veh, x, u)
+    table, params = _veh(veh)
+    return _functions().Linearise.apply((md.linearise_kinematics, md.linearise_kinematics_vjp, md.kin_linearise_pvjp),
+                                        table, x, u, params)
 
 
 def linearise_dynamics(veh, x, u):
@@ -257,7 +337,8 @@ def linearise_dynamics(veh, x, u):
     in x and u (3-D (B, N, 6) / (B, N, 2) or 2-D, any strides with a contiguous last axis: an
     ``expand`` over the stages gets the stage sum).  The gradient is that of the forward as it
     computes (mpc_device.linearise_vjp): zero in X, Y and in what the guard replaced."""
-    return _functions().Linearise.apply((md.linearise, md.linearise_vjp), veh, x, u)
+    table, params = _veh(veh)
+    return _functions().Linearise.apply((md.linearise, md.linearise_vjp, md.linearise_pvjp), table, x, u, params)
 
 
 def _split_weights(weights):
@@ -294,7 +375,8 @@ def incr_shift(layout, veh, sol, Ad, Bd, gd, xt):
     (xt', pred', pdu').  Only stage 0 of Ad, Bd, gd is read, and only it gets a gradient."""
     if layout._kind != "incr":
         raise ValueError("incr_shift needs an IncrementalLayout")
-    return _functions().IncrShift.apply(layout, veh, sol, Ad, Bd, gd, xt)
+    table, params = _veh(veh)
+    return _functions().IncrShift.apply(layout, table, sol, Ad, Bd, gd, xt, params)
 
 
 def kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt=None, done=None):
@@ -305,7 +387,8 @@ def kin_shift(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt=None, 
     done (mode 1: they pass through); Xr only steers the stop rule and gets none."""
     if layout._kind != "incr":
         raise ValueError("kin_shift needs an IncrementalLayout")
-    return _functions().KinShift.apply(layout, veh, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done)
+    table, params = _veh(veh)
+    return _functions().KinShift.apply(layout, table, sol, Ad, Bd, gd, Xr, xt, pred, pdu, finish_cnt, done, params)
 
 
 def kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
@@ -316,7 +399,8 @@ def kin_ltv_shift(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u):
     through)."""
     if layout._kind != "ltv":
         raise ValueError("kin_ltv_shift needs an LTVLayout")
-    return _functions().KinLTVShift.apply(layout, veh, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u)
+    table, params = _veh(veh)
+    return _functions().KinLTVShift.apply(layout, table, sol, status, Ad, Bd, gd, x, u, pred_x, pred_u, params)
 
 
 class MPCLayer:
@@ -375,7 +459,12 @@ class _Rollout:
                                                    did not use, or None
 
     ``_DU0``: the outputs include each step's first input rows of the solution, whose cotangent is
-    added to the adjoint's seed.  ``aux`` is what the tail carries besides state and horizon."""
+    added to the adjoint's seed.  ``aux`` is what the tail carries besides state and horizon.
+
+    ``veh`` may be ``fleet(params)``: its table runs the loop and, when params requires grad, the
+    backward also returns d loss / d params -- per step ``_TAIL``'s terminal step and
+    ``_linearise_pvjp(hor, gAd, gBd, ggd)``, summed in the table's coordinates (``gK`` of the last
+    backward stays on the object) and chained once to the constructor arguments."""
 
     _DU0 = True
 
@@ -385,6 +474,7 @@ class _Rollout:
         kind, nx, nu, words = self._LAYOUT
         if layout._kind != kind or (layout.nx, layout.nu) != (nx, nu):
             raise ValueError(f"{self._NAME} needs {words} (nx {nx}, nu {nu})")
+        veh, self.params = _veh(veh)  # fleet(params): its table runs the loop, its tensor gets the gradient
         self.torch, self.layout, self.veh = torch, layout, veh
         self.B, self.N = int(B), layout.N
         if isinstance(veh, (md.Fleet, md.KinFleet)) and len(veh) != self.B:  # one table entry per vehicle
@@ -396,7 +486,7 @@ class _Rollout:
         self.batch = DeviceBatch(P, A, self.B, device=int(device), **settings)
         self.Px = torch.from_numpy(P.data.copy()).to(self.dev)[None, :].repeat(self.B, 1).contiguous()
         self.stream = torch.cuda.Stream(self.dev)
-        self.status = self.iters = self.astat = self.ares = self.act = self.mode = None
+        self.status = self.iters = self.astat = self.ares = self.act = self.mode = self.gK = None
 
     def tape_doubles_per_instance(self):
         """Doubles the tape holds per step and instance: the state, the horizon, sol and the record
@@ -418,7 +508,7 @@ class _Rollout:
     def _apply(self, T, path, weights, *tensors):
         """The rollout as one autograd node; tensors = (*state, *hor, Xr)."""
         Q, QN, R, use_w = _split_weights(weights)
-        return _functions().Rollout.apply(self, T, path, use_w, *tensors, Q, QN, R)
+        return _functions().Rollout.apply(self, T, path, use_w, *tensors, Q, QN, R, self.params)
 
     def _on_stream(self, fn):
         """fn() on the rollout's stream, ordered after the caller's current stream; the caller's
@@ -485,6 +575,8 @@ class _Rollout:
         want = ["gAd", "gBd", "ggd", "gx0"] + ["gXr"] * (gXr is not None) + ["g" + k for k in wnames]
         g_state = [g[:, T].clone() if g is not None else torch.zeros((B, w), **kw) for g, w in zip(gtraj, self._STATE)]
         g_hor = list(ghor)
+        # d loss / d the table's constants: each step's terminal step and its linearisation (§25)
+        gK = torch.zeros((B, 13 if nx == 6 else 3), **kw) if need["params"] else None
         for t in reversed(range(T)):
             state, hor, sol, rec, mode = steps[t]
             Xr_t, Ad, Bd, gd, Px, (Ax, q, l, u) = self._problem(state, hor, None if Xr is None else Xr[t], path,
@@ -492,6 +584,8 @@ class _Rollout:
             b.setup(Px, Ax, q, l, u, stream=st)
             b.load_solution(rec, stream=st)
             sh, g_before, g_hor_prev = self._shift_vjp(sol, Ad, Bd, state, mode, g_state, g_hor)
+            if gK is not None:
+                gK += _terminal_pvjp(self._TAIL, self.veh, N, sol, g_hor[0], mode)
             if gDU0 is not None:
                 sh.gsol[:, nd:nd + nu] += gDU0[:, t]
             a = b.adjoint(sh.gsol, None, act=act[t], ares=ares[t], astat=astat[t], stream=st)
@@ -506,6 +600,8 @@ class _Rollout:
                 for k in want:
                     g = getattr(v, k)
                     g.masked_fill_(skip.view((-1,) + (1,) * (g.dim() - 1)), 0.0)
+            if gK is not None:
+                gK += self._linearise_pvjp(hor, v.gAd, v.gBd, v.ggd)
             g_hor = self._linearise_vjp(hor, v.gAd, v.gBd, v.ggd)
             if g_hor_prev is not None:
                 g_hor = [g if p is None else g + p for g, p in zip(g_hor, g_hor_prev)]
@@ -531,8 +627,11 @@ class _Rollout:
             gw = {k: zero(g) for k, g in gw.items()}
             if gXr is not None:
                 gXr = torch.where(bad.view(1, -1, 1, 1), 0.0, gXr)
+            gK = zero(gK)
+        self.gK = gK  # the cotangent of the table's constants, before the chain to params
         out = dict(state=[g if n else None for g, n in zip(g_state, need["state"])],
-                   hor=[g if n else None for g, n in zip(g_hor, need["hor"])], Xr=gXr, Q=None, QN=None, R=None)
+                   hor=[g if n else None for g, n in zip(g_hor, need["hor"])], Xr=gXr, Q=None, QN=None, R=None,
+                   params=None if gK is None else _chain(self.params.device, self.veh, gK))
         for k in wnames:
             out[k] = gw[k].sum(0)
         return out
@@ -604,6 +703,12 @@ class DynamicRollout(_Rollout):
         g[:, :N, :6] = gx
         g[:, :N, 6:] = gu
         return [g]
+
+    _TAIL = "incr"
+
+    def _linearise_pvjp(self, hor, gAd, gBd, ggd):
+        N, (pred,) = self.N, hor
+        return md.linearise_pvjp(self.veh, pred[:, :N, :6], pred[:, :N, 6:], gAd, gBd, ggd)
 
 
 def _incr_kin_problem(self, state, hor, Xr_t, path, weights):
@@ -679,6 +784,12 @@ class KinematicRollout(_Rollout):
         g[:, :N, 4:] = gu
         return [g]
 
+    _TAIL = "kin"
+
+    def _linearise_pvjp(self, hor, gAd, gBd, ggd):
+        N, (pred,) = self.N, hor
+        return md.kin_linearise_pvjp(self.veh, pred[:, :N, :4], pred[:, :N, 4:], gAd, gBd, ggd)
+
 
 class KinematicLTVRollout(_Rollout):
     """T steps of the direct-input kinematic closed loop (mpc_device.KinematicLTVMPC's step) as ONE
@@ -730,3 +841,9 @@ class KinematicLTVRollout(_Rollout):
         gpx[:, :N] = gx
         gpu[:, :N] = gu
         return [gpx, gpu]
+
+    _TAIL = "ltv"
+
+    def _linearise_pvjp(self, hor, gAd, gBd, ggd):
+        N, (px, pu) = self.N, hor
+        return md.kin_linearise_pvjp(self.veh, px[:, :N], pu[:, :N], gAd, gBd, ggd)
