@@ -67,7 +67,7 @@ int fail(int code, const char* fmt, ...) {
 
 }  // namespace
 
-// shared with the other translation units of the library (mpc_device.hip)
+// shared with the other translation units of the library (the mpc_*.hip files)
 int mpcqp::set_error(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;

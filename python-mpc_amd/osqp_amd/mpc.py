@@ -390,7 +390,7 @@ def _take(g, slots):
 
 def _assemble_vjp(nxa, P, A, N, nx, nu, Q, QN, Xr, gPx, gAx, gq, gl, gu, xlo, xhi):
     """The transpose of ltv_qp (nxa = nx) / incremental_qp (nxa = nx + nu) in the order of
-    mpc_device.hip's k_assemble_vjp_* (include/mpcqp.h, mpcqp_*_assemble_vjp_device)."""
+    mpc_assembly.hip's k_assemble_vjp_* (include/mpcqp.h, mpcqp_*_assemble_vjp_device)."""
     from types import SimpleNamespace
     A = sparse.csc_matrix(A); A.sort_indices()
     P = sparse.triu(sparse.csc_matrix(P), format="csc"); P.sort_indices()
@@ -488,7 +488,7 @@ def incremental_qp_vjp(P, A, N, nx, nu, Q, QN, Xr=None, gPx=None, gAx=None, gq=N
 
 
 def linearise_kinematics_vjp(l_f, l_r, dt, x, u, gAd, gBd, ggd):
-    """The VJP of linearise_kinematics in the order of mpc_device.hip's k_kin_linearise_vjp:
+    """The VJP of linearise_kinematics in the order of mpc_linearise.hip's k_kin_linearise_vjp:
     x (..., 4), u (..., 2), gAd (..., 4, 4), gBd (..., 4, 2), ggd (..., 4) -> gx (..., 4),
     gu (..., 2); only v, yaw and steer carry derivative."""
     x, u = np.asarray(x, float), np.asarray(u, float)
@@ -508,7 +508,7 @@ def linearise_kinematics_vjp(l_f, l_r, dt, x, u, gAd, gBd, ggd):
 
 
 class _Dual:
-    """mpc_device.hip's Dual in numpy: a value v (...) and its tangent d (..., 6) in
+    """vehicle_model.h's Dual in numpy: a value v (...) and its tangent d (..., 6) in
     (yaw, vx, vy, r, steer, accel), with that struct's rules, operation by operation."""
     __array_ufunc__ = None  # ndarray op _Dual -> _Dual's reflected operator
 
@@ -568,7 +568,7 @@ class _Dual:
 
 
 def linearise_dynamics_vjp(veh: VehicleParams, x, u, gAd=None, gBd=None, ggd=None):
-    """The VJP of linearise_dynamics in the order of mpc_device.hip's k_linearise_vjp: x (..., 6),
+    """The VJP of linearise_dynamics in the order of mpc_linearise.hip's k_linearise_vjp: x (..., 6),
     u (..., 2), cotangents gAd (..., 6, 6), gBd (..., 6, 2), ggd (..., 6) (None = zero) -> gx
     (..., 6), gu (..., 2).
 
@@ -680,7 +680,7 @@ def _atan2(y, x):
 
 
 def _low_speed_guard(x, u):
-    """mpc_device.hip's low_speed_guard on copies of x (M, 6), u (M, 2); also the two regions
+    """vehicle_model.h's low_speed_guard on copies of x (M, 6), u (M, 2); also the two regions
     as k_linearise_vjp names them: lat / lon False where vy, r, steer / vx became constants."""
     x, u = np.array(x, float, copy=True), np.array(u, float, copy=True)
     vx_in = x[:, 3].copy()
@@ -694,7 +694,7 @@ def _low_speed_guard(x, u):
 
 
 def model_constants(veh: VehicleParams):
-    """The thirteen constants the kernels read (mpc_device.hip's VehicleK, mpcqp_fleet_constants'
+    """The thirteen constants the kernels read (vehicle_model.h's VehicleK, mpcqp_fleet_constants'
     order): (m, l_f, l_r, Iz, dt, cda, roll, B_f, C_f, D_f, B_r, C_r, D_r)."""
     (Bf, Cf, Df), (Br, Cr, Dr) = veh.pacejka()
     return (veh.m, veh.l_f, veh.l_r, veh.Iz, veh.dt, veh.roh * veh.C_d * veh.A_f, veh.C_roll * veh.m * 9.81,
@@ -702,7 +702,7 @@ def model_constants(veh: VehicleParams):
 
 
 def _euler_step(veh: VehicleParams, x, u):
-    """mpc_device.hip's euler_step<T> from a GUARDED point: x, u lists of six / two ndarrays or
+    """vehicle_model.h's euler_step<T> from a GUARDED point: x, u lists of six / two ndarrays or
     _Duals -> the six components of x + dt f(x, u) (tyre_forces, dynamics, operation by operation)."""
     return _euler_step_k(model_constants(veh), x, u)
 
@@ -854,7 +854,7 @@ def incr_shift_vjp(veh: VehicleParams, N, sol, Ad0, Bd0, xt, gxt=None, gpred=Non
 
 # ------------------------------------------- the kinematic tails and their VJPs --
 def kin_update_vjp(l_f, l_r, dt, x, u, w):
-    """The transpose of kin_update in closed form (mpc_device.hip::kin_update_vjp): x (.., 4), u
+    """The transpose of kin_update in closed form (vehicle_model.h::kin_update_vjp): x (.., 4), u
     (.., 2) the point, w (.., 4) the cotangent of the new state -> (gx (.., 4), gu (.., 2)).  v
     enters yaw's row through v1 = v + accel dt, which the reference forms first."""
     x, u, w = np.asarray(x, float), np.asarray(u, float), np.asarray(w, float)
@@ -1012,7 +1012,7 @@ def kin_ltv_shift_vjp(veh, N, sol, Ad0, Bd0, x, gx=None, gu=None, gpred_x=None, 
 
 
 # ----------------------------- gradients with respect to the vehicle's constants --
-# DESIGN.md §25.  The statements of mpc_device.hip's four *_pvjp kernels and of
+# DESIGN.md §25.  The statements of mpc_linearise.hip's four *_pvjp kernels and of
 # mpcqp_vehicle_constants_vjp, operation by operation.  Coordinates: the thirteen constants the
 # kernels read (model_constants' order) for the dynamic bicycle, (l_f, l_r, dt) for the kinematic
 # one.  Each takes ONE vehicle; per_vehicle applies them to a fleet.
@@ -1036,7 +1036,7 @@ def _stage_sum(g):
 
 def linearise_dynamics_pvjp(veh: VehicleParams, x, u, gAd=None, gBd=None, ggd=None):
     """d (Ad, Bd, gd of linearise_dynamics) / d the thirteen constants, contracted with the
-    cotangents and summed over the stages, in the order of mpc_device.hip's k_linearise_pvjp:
+    cotangents and summed over the stages, in the order of mpc_linearise.hip's k_linearise_pvjp:
     x (..., N, 6), u (..., N, 2), gAd (..., N, 6, 6), gBd (..., N, 6, 2), ggd (..., N, 6)
     (None = zero) -> gK (..., 13).
 
@@ -1147,7 +1147,7 @@ def linearise_kinematics_pvjp(l_f, l_r, dt, x, u, gAd=None, gBd=None, ggd=None):
 
 def euler_step_pvjp(veh: VehicleParams, x, u, w, mode=None):
     """d (the guarded Euler step _euler_step of x (..., 6), u (..., 2)) / d the thirteen
-    constants, contracted with w (..., 6) -> gK (..., 13) (mpc_device.hip's k_euler_step_pvjp):
+    constants, contracted with w (..., 6) -> gK (..., 13) (mpc_linearise.hip's k_euler_step_pvjp):
     the step over duals in the constants, dt among them, from the guarded plain point.  mode
     (...) or None: a vehicle whose mode is not 0 did not take the step and gets a zero row."""
     x, u, w = np.asarray(x, float), np.asarray(u, float), np.asarray(w, float)
@@ -1183,7 +1183,7 @@ def kin_update_pvjp(l_f, l_r, dt, x, u, w, mode=None):
 
 def vehicle_constants(p):
     """The thirteen constants of the nine constructor arguments p = (m, l_f, l_r, width, length,
-    C_d, A_f, C_roll, dt) (mpcqp_vehicle's field order), with mpc_device.hip's derivation
+    C_d, A_f, C_roll, dt) (mpcqp_vehicle's field order), with vehicle_model.h's derivation
     operation by operation; floats, or _Duals in the arguments."""
     m, l_f, l_r, width, length, C_d, A_f, C_roll, dt = p
     Iz = 1.0 / 12 * m * (width * width + length * length)

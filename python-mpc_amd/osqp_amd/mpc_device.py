@@ -638,7 +638,7 @@ class AffineMap:
         self.nparam, self.nregimes = nparam, nregimes
 
     def evaluate(self, theta, regime=None):
-        """The device kernel's arithmetic (mpc_device.hip::k_affine) in numpy, per instance."""
+        """The device kernel's arithmetic (mpc_assembly.hip::k_affine) in numpy, per instance."""
         theta = np.atleast_2d(theta)
         B = theta.shape[0]
         reg = np.zeros(B, int) if regime is None else np.clip(np.asarray(regime), 0, self.nregimes - 1)
@@ -659,7 +659,7 @@ class AffineMap:
 
     def vjp(self, gq, gl, gu):
         """The transpose of evaluate's linear part in the device kernel's order
-        (mpc_device.hip::k_affine_vjp): gtheta[b, p] = sum of coef[i, t] * g[b, i] over the terms with
+        (mpc_assembly.hip::k_affine_vjp): gtheta[b, p] = sum of coef[i, t] * g[b, i] over the terms with
         idx[i, t] == p, entries ascending, then terms; g = (gq | gl | gu), each (B, seglen) or None."""
         segs = [None if g is None else np.atleast_2d(np.asarray(g, float)) for g in (gq, gl, gu)]
         B = next(g for g in segs if g is not None).shape[0]

@@ -1,5 +1,5 @@
-"""Kinematic-bicycle closed loop on the device (csrc/mpc_device.hip: k_kin_linearise,
-k_kin_reference, k_kin_shift; osqp_amd.mpc_device.KinematicMPC) against host restatements
+"""Kinematic-bicycle closed loop on the device (csrc/mpc_linearise.hip: k_kin_linearise;
+csrc/mpc_device.hip: k_kin_reference, k_kin_shift; osqp_amd.mpc_device.KinematicMPC) against host restatements
 of Control/MPC/mpc_incre_kine_func.py:simulate and the reference's own fixtures
 (tests/golden/make_golden_kin.py):
 

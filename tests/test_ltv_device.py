@@ -1,5 +1,5 @@
-"""The LTV MPC in the inputs themselves on the device (csrc/mpc_device.hip: mpcqp_ltv_layout,
-k_ltv_assemble_vec, k_kin_rollout, k_kin_ltv_shift; osqp_amd.mpc.ltv_qp,
+"""The LTV MPC in the inputs themselves on the device (csrc/mpc_assembly.hip: mpcqp_ltv_layout,
+k_ltv_assemble_vec; csrc/mpc_device.hip: k_kin_rollout, k_kin_ltv_shift; osqp_amd.mpc.ltv_qp,
 osqp_amd.mpc_device.LTVLayout / rollout_kin / KinematicLTVMPC) against host restatements of
 Control/MPC/mpc_kinematics_pred_matrix.py:main and the reference's own fixtures
 (tests/golden/make_golden_ltv.py):

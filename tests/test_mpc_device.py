@@ -1,5 +1,5 @@
-"""Device MPC data path (csrc/mpc_device.hip) against host
-restatements of the reference's steps and the reference's own fixtures.
+"""Device MPC data path (csrc/mpc_assembly.hip, mpc_linearise.hip,
+mpc_device.hip) against host restatements of the reference's steps and the reference's own fixtures.
 
   F2  linearise        vs tests/golden/linearise.npz (Vehicle_Dynamics.get_dynamics_model)
   F1  incr assembly    vs tests/golden/dyn_incr_n50.npz (mpc_increment's P, q, A, l, u)
